@@ -3,14 +3,18 @@ per GPU. A step = one 6-camera frame per stream through backbone+FPN (PyTorch-RO
 decoder hot path (HIP kernels, fp32) including post_process. Inputs are synthetic and resident in
 HBM before the timed region; weights are procedural random-init of the shipped architecture.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job frames/s,
-`roofline` for the 3D deformable-aggregation kernel (HIP events on the launch stream around each of its
-launches in a few instrumented frames run right after the timed region -- event nodes cannot be read back
-from inside a replayed graph; algorithmic bytes per SURVEY.md §8d), `cpu_baseline` = the oracle (CPU restatement
-of the reference) timed on the host cores for a bounded sample (rank 0, N = 1 only).
+Prints ONE JSON line on rank 0: value = whole-job frames/s over the K timed steps, ms_per_step = wall time of one
+timed step. A plain run does only that: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and the line.
+--full adds the secondary legs after the timed region: `reference_protocol_h2d` (the same runner with its frames
+crossing PCIe inside the step), `roofline` / `roofline_msda` for the two sampler kernels (HIP events on the launch
+stream around each of their launches in a few instrumented frames -- event nodes cannot be read back from inside a
+replayed graph; algorithmic bytes per SURVEY.md §8d) and `cpu_baseline` = the oracle (CPU restatement of the
+reference) timed on the host cores for a bounded sample (rank 0, N = 1 only); without --full they are null.
+--dump-outputs DIR writes the detections the last timed step returned as DIR/<name>.npy (float32 / float64); the
+inputs are synthetic and seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -46,7 +50,12 @@ def parse():
     ap.add_argument("--no-split", action="store_true",
                     help="keep the single-frame decoder layer of frame t+1 behind the temporal part of frame t "
                          "(simpb_amd.runner.PipelinedRunner instead of SplitPipelinedRunner)")
-    ap.add_argument("--meter-frames", type=int, default=8, help="instrumented eager frames for the roofline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs after the timed region: the PCIe-inclusive leg (--h2d-steps), the roofline "
+                         "leg (--meter-frames) and the CPU baseline (unless --no-cpu-baseline); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detections the last timed step returned as DIR/<name>.npy (float32, or float64 for integer fields)")
+    ap.add_argument("--meter-frames", type=int, default=8, help="instrumented eager frames for the roofline leg (--full)")
     ap.add_argument("--no-conv-search", action="store_true",
                     help="do not let MIOpen benchmark convolution algorithms during warm-up (cudnn.benchmark off)")
     ap.add_argument("--route", action="append", default=[], metavar="NAME=0|1",
@@ -74,7 +83,7 @@ def parse():
                          "the default workload (ResNet50, 16 blocks) stays as it is")
     ap.add_argument("--h2d-steps", type=int, default=30,
                     help="steps of the secondary leg that repeats the measurement with the frames crossing PCIe (the reference's "
-                         "protocol); reported as reference_protocol_h2d, never as value; 0 = skip")
+                         "protocol); reported as reference_protocol_h2d, never as value; 0 = skip (--full)")
     ap.add_argument("--capacity-by-rank", type=int, nargs="+", default=None, metavar="SLOTS",
                     help="rehearsal only: the static 2D capacity of rank r (so that ONE rank overflows, re-runs and re-captures "
                          "while the others keep submitting: the exchange must stay matched)")
@@ -82,8 +91,13 @@ def parse():
                     help="measurement: load this build of the C-ABI library instead of the in-tree one (a variant built with "
                          "other compiler flags: python -c 'from simpb_amd import build; build.build_extension(extra_flags=[...], out=PATH)')")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-frames", type=int, default=21, help="frames of the CPU baseline leg: 1 cold + the warm frames that are timed")
-    return ap.parse_args()
+    ap.add_argument("--cpu-frames", type=int, default=21,
+                    help="frames of the CPU baseline leg (--full): 1 cold + the warm frames that are timed")
+    args = ap.parse_args()
+    if not args.full:   # a plain run: no secondary leg after the timed region
+        args.h2d_steps = args.meter_frames = 0
+        args.no_cpu_baseline = True
+    return args
 
 
 class KernelMeter:
@@ -286,6 +300,19 @@ def cpu_baseline(args):
                        f"(os.cpu_count()={os.cpu_count()}, affinity mask={share}: the threads are the box's CPU share, capped at 16)")
 
 
+def dump_outputs(results, out_dir, prefix=""):
+    """--dump-outputs: every array of the detections one step returned (the reference's list of {'img_bbox': {...}}, one
+    entry per stream) as out_dir/<prefix>stream<i>_<key>.npy; floating fields as float32, integer fields (labels, instance
+    ids, query_groups as a [cams, 2] table) as float64, which holds them exactly."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for i, r in enumerate(results):
+        for k, v in r["img_bbox"].items():
+            a = np.asarray(v.numpy() if torch.is_tensor(v) else v)
+            a = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+            np.save(os.path.join(out_dir, f"{prefix}stream{i}_{k}.npy"), a)
+
+
 def head_dtype_note():
     """What the decoder computes in, as the route table has it for this run."""
     from simpb_amd.plugin import routes
@@ -424,6 +451,10 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        if results is None:   # a pipelined runner returns frame t-1: with no set-up or warm-up frame, one step has nothing yet
+            raise SystemExit("bench.py --dump-outputs: the last timed step returned no detections (use --warmup >= 1)")
+        dump_outputs(results, args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "")
 
     # secondary figure: the reference's own timing protocol (tools/benchmark.py:90-100 times model(**data) with the scatter
     # of the frame to the device inside). Never `value`: the same runner, the same streams, frames now starting in pinned

@@ -1,15 +1,28 @@
-"""CPU: the boundary. The reference's shipped configs load UNCHANGED through simpb_amd's registry
-(only where /root/reference exists, i.e. the build container), simpb_amd.configs restates their
-`model` dict exactly, and the built head exposes the reference's state_dict keys and shapes."""
+"""CPU: the boundary. The `model` dicts of the reference's shipped configs, as simpb_amd's registry loads those
+files (recorded in tests/golden/ref_configs.json by tools/golden/gen_golden.py --only configs), build UNCHANGED through
+the registry, simpb_amd.configs restates them exactly, and the built head exposes the reference's state_dict keys and
+shapes."""
+import json
 import os
 
 import numpy as np
 import pytest
 
 from simpb_amd import configs, plugin, synth
-from tests.helpers import load_golden
+from tests.helpers import GOLDEN, load_golden
 
-REF_CFG = "/root/reference/projects/configs"
+REF_CONFIGS = os.path.join(GOLDEN, "ref_configs.json")
+
+
+def from_json(x):
+    """Undo tools/golden/gen_golden.py:json_settings (a dict with non-string keys is stored as {"__items__": [[k, v]]})."""
+    if isinstance(x, dict):
+        if set(x) == {"__items__"}:
+            return {k: from_json(v) for k, v in x["__items__"]}
+        return {k: from_json(v) for k, v in x.items()}
+    if isinstance(x, list):
+        return [from_json(v) for v in x]
+    return x
 
 
 def _plain(x):
@@ -20,15 +33,17 @@ def _plain(x):
     return x
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference tree only exists in the build container")
 @pytest.mark.parametrize("name,pretrained", [
     ("simpb_nus_r50_img_704x256.py", "ckpts/resnet50-19c8e357.pth"),
     ("simpb_nus_r50_uimg_704x256.py", None),
 ])
 def test_reference_config_loads_unchanged(name, pretrained):
-    cfg = plugin.Config.fromfile(os.path.join(REF_CFG, name))
+    with open(REF_CONFIGS) as f:
+        cfg = plugin.Config().merge_from_dict({"model": from_json(json.load(f)[name])})
     mine = configs.simpb_plus()
     ref_model = _plain(cfg.model)
+    if pretrained is not None:
+        assert ref_model["img_backbone"]["pretrained"] == pretrained
     my_model = _plain(mine["model"])
     if pretrained is None:  # the nuImages variant differs only in how the backbone is initialised (:79-99,460-463)
         ref_model["img_backbone"] = {k: v for k, v in ref_model["img_backbone"].items() if k not in ("pretrained", "init_cfg")}

@@ -6,7 +6,7 @@ import torch
 
 from oracle import simpb_ref as R
 from simpb_amd import synth
-from tests.helpers import compare_result, compare_trace, golden_params, load_golden, spec_of
+from tests.helpers import _match_rows, compare_result, compare_trace, golden_params, load_golden, spec_of
 
 
 def test_feature_maps_format():
@@ -107,16 +107,41 @@ def test_head_stream(name):
     g = load_golden(name)
     spec = spec_of(g)
     torch.set_num_threads(8)
+    tie_broken = False   # a top-k tie went the other way in an earlier frame: instance order may differ from then on
     for f, trace, outs, res, bank in run_oracle_stream(g):
         pre = f"f{f}."
         assert [x.shape[1] for x in outs["prediction2d"]] == g[pre + "n2#0"].tolist()
         if f in spec["trace_frames"]:
-            compare_trace(trace, g, pre + "trace.")
-        assert np.allclose(bank.cached_anchor.numpy(), g[pre + "bank.cached_anchor#0"], atol=2e-4)
-        assert np.array_equal(bank.instance_id.numpy(), g[pre + "bank.instance_id#0"])
-        assert np.array_equal(outs["instance_id"].numpy(), g[pre + "instance_id#0"])
+            compare_trace(trace, g, pre + "trace.", allow_permutation=tie_broken)
+        same_order = (np.allclose(bank.cached_anchor.numpy(), g[pre + "bank.cached_anchor#0"], atol=2e-4)
+                      and np.array_equal(bank.instance_id.numpy(), g[pre + "bank.instance_id#0"])
+                      and np.array_equal(outs["instance_id"].numpy(), g[pre + "instance_id#0"]))
+        if not same_order:
+            # the golden was captured on one CPU; another CPU's kernels round differently in the last bits, and where
+            # the bank's top-k meets confidences that close, it keeps the same instances in another order
+            assert_same_bank_up_to_ties(bank, outs, g, pre)
+            tie_broken = True
         for b, r in enumerate(res):
             compare_result(r, g, f"{pre}res{b}.")
+
+
+def assert_same_bank_up_to_ties(bank, outs, g, pre, tie=1e-5):
+    """The bank holds the golden's instances (anchor rows as a set within 2e-4, the same confidences), rows sit at
+    other positions only where the golden's confidences there are tied within `tie`, and the track ids keep what a
+    relabelling in slot order keeps (the invariants tests/test_gpu_head.py checks for the HIP head)."""
+    conf = bank.confidence.numpy()
+    for b in range(conf.shape[0]):
+        anchor, want_anchor = bank.cached_anchor[b].numpy(), g[pre + "bank.cached_anchor#0"][b]
+        p = _match_rows(anchor, want_anchor, [2e-4] * anchor.shape[-1])   # anchor[p[i]] ~ want_anchor[i]
+        assert p is not None, "the bank holds other instances than the golden"
+        want_conf = g[pre + "bank.confidence#0"][b]
+        assert np.abs(conf[b][p] - want_conf).max() <= tie, "an instance's confidence differs"
+        moved = np.nonzero(p != np.arange(len(p)))[0]
+        assert np.abs(want_conf[moved] - want_conf[p[moved]]).max(initial=0.0) <= tie, "rows moved without a tie"
+        ids, want_ids = outs["instance_id"][b].numpy(), g[pre + "instance_id#0"][b]
+        assert len(np.unique(ids)) == len(ids) == len(np.unique(want_ids)) and ids.max() == want_ids.max()
+        kept, want_kept = bank.instance_id[b].numpy(), g[pre + "bank.instance_id#0"][b]
+        assert (kept >= 0).sum() == (want_kept >= 0).sum() and len(np.unique(kept[kept >= 0])) == (kept >= 0).sum()
 
 
 def test_c_restatement_of_the_native_kernel():

@@ -1,5 +1,6 @@
 """Generate tests/golden/*.npz by running the reference's own model files (through ref_shim) in
 the build container. Usage: python tools/golden/gen_golden.py [--only NAME]
+(configs: tests/golden/ref_configs.json, the shipped configs' `model` dicts as JSON)
 
 The fixtures hold inputs that are not procedural plus expected outputs; weights and feature maps
 are rebuilt on both sides from simpb_amd.synth. Nothing of the reference's source is stored.
@@ -221,11 +222,41 @@ def run_ops(ns, cfg):
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
 
+def json_settings(x):
+    """JSON form of a config value: tuples become lists, a dict with non-string keys becomes {"__items__": [[k, v], ...]}
+    (tests/test_config_parity.py:from_json undoes it)."""
+    if isinstance(x, dict):
+        if all(isinstance(k, str) for k in x):
+            return {k: json_settings(v) for k, v in x.items()}
+        return {"__items__": [[k, json_settings(v)] for k, v in x.items()]}
+    if isinstance(x, (list, tuple)):
+        return [json_settings(v) for v in x]
+    return x
+
+
+def run_configs():
+    """The `model` dict of each shipped config, as simpb_amd's registry loads the file (settings only, no code)."""
+    import json
+    from simpb_amd import plugin
+    cfg_dir = os.path.join(ref_shim.REF_ROOT, "projects", "configs")
+    data = {name: json_settings(plugin.Config.fromfile(os.path.join(cfg_dir, name)).model)
+            for name in ("simpb_nus_r50_img_704x256.py", "simpb_nus_r50_uimg_704x256.py")}
+    path = os.path.join(OUT, "ref_configs.json")
+    with open(path, "w") as f:
+        json.dump(data, f, indent=1, sort_keys=True, allow_nan=False)
+        f.write("\n")
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default=None, choices=[None, "ops", "small", "r50"])
+    ap.add_argument("--only", default=None, choices=[None, "configs", "ops", "small", "r50"])
     args = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
+    if args.only in (None, "configs"):
+        run_configs()
+        if args.only:
+            return
     torch.set_num_threads(8)
     ns = ref_shim.install()
     cfg = ref_shim.load_config()

@@ -39,7 +39,7 @@ for k, v in agg.items():
     print(k, out[k])
 json.dump(dict(
     command="rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY GRBM_GUI_ACTIVE "
-            "-- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline",
+            "-- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline",
     definition="mfma_busy_fraction = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 * 1024 SIMDs) per dispatch, averaged "
                "(the guide's MfmaUtil): the share of SIMD cycles with a matrix instruction in flight, whatever its flop rate "
                "(v_mfma_f32_4x4x1f32 of mlp_chain_r4 keeps the pipe busy at a quarter of the 16x16x4 flop rate). "

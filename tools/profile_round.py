@@ -1,10 +1,10 @@
 """Summaries of the rocprofv3 passes behind the roofline numbers, written under profiles/ (run AFTER the passes):
 
     cd /tmp && export TMPDIR=/tmp      # on the GPU box, from the repo root:
-    rocprofv3 --kernel-trace --stats -d gpurun_out/prof/stats -- python3 bench.py --steps 40 --warmup 4 --no-cpu-baseline
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/prof/fetch -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/prof/write -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline
-    python3 tools/profile_round.py gpurun_out/prof profiles/r02      # -> profiles/r02_bench_kernel_stats.csv, r02_sampler_traffic.json
+    rocprofv3 --kernel-trace --stats -d prof/stats -- python3 bench.py --full --steps 40 --warmup 4 --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d prof/fetch -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d prof/write -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline
+    python3 tools/profile_round.py prof profiles/r02      # -> profiles/r02_bench_kernel_stats.csv, r02_sampler_traffic.json
 
 (separate --pmc passes, no tracing domains beside --kernel-trace: the counter guide's recipe). The same three passes around
 `python3 tools/bench_daf_hbm.py` (R101 1408x512 feature set, 368 MB, rotated buffers: every launch cold) with the out prefix
@@ -59,7 +59,7 @@ def counter_avg(pass_dir, counter):
 
 def main():
     src, out = sys.argv[1], sys.argv[2]
-    command = sys.argv[3] if len(sys.argv) > 3 else "python3 bench.py --steps N --warmup W --no-cpu-baseline"
+    command = sys.argv[3] if len(sys.argv) > 3 else "python3 bench.py --full --steps N --warmup W --no-cpu-baseline"
     path, rows = kernel_stats(os.path.join(src, "stats"))
     stats = {}
     if rows:

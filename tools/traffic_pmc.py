@@ -31,7 +31,7 @@ for k in sorted(set(fetch) | set(write)):
     out[k] = dict(dispatches=len(fetch[k]), FETCH_SIZE_KB_avg=round(f_kb, 1), WRITE_SIZE_KB_avg=round(w_kb, 1),
                   traffic_MB_per_launch=round((2 * f_kb + w_kb) * 1024 / 1e6, 2))
     print(k, out[k])
-json.dump(dict(command="rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --steps 6 "
+json.dump(dict(command="rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --full --steps 6 "
                        "--warmup 2 --no-cpu-baseline", round=1,
                correction="traffic = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024 (gfx950 FETCH_SIZE half-count for 16 B/lane reads; Infinity-Cache "
                           "hits are included in FETCH_SIZE); averages over all dispatches of a kernel name (all shapes)",
