@@ -145,7 +145,8 @@ int simpb_linear_f32(float* y, const float* x, const float* weight, const float*
 /* Same product on the FP16 matrix cores at fp32-grade accuracy: weight = weight_hi + weight_lo / 2048 with both parts
  * f16 [N, K] (weight_hi = half(weight), weight_lo = half((weight - weight_hi) * 2048), prepared once by the caller);
  * x is split the same way while it is staged; y = x_hi.W_hi^T + (x_hi.W_lo^T + x_lo.W_hi^T) / 2048 + bias in fp32
- * accumulators (the dropped x_lo.W_lo^T term is ~2^-22 relative). Requires |x|, |weight| < 65504. Used for value_proj
+ * accumulators (the dropped x_lo.W_lo^T term is ~2^-22 relative). Any finite x (rows outside [2^-10, 2^15) are staged
+ * with a power-of-two exponent, as simpb_gemm_f32); every weight row's largest |w| must lie in that window or be 0. Used for value_proj
  * (models/group_attn.py:176), where the exact kernel above is compute-bound. K % 32 == 0; 16-byte aligned. */
 int simpb_linear_f16x3(float* y, const float* x, const void* weight_hi, const void* weight_lo, const float* bias, int M,
                        int N, int K, void* stream);
@@ -207,8 +208,10 @@ typedef struct simpb_gemm_job {
   const float* bias2;
   /* optional pre-split weights, f16 [N, K] with dense rows: w_hi = half(w), w_lo = half((w - w_hi) * 2048). When every
    * job of a launch brings them (and its segment widths are multiples of 128) the products run on the FP16 matrix
-   * cores in three passes at fp32-grade accuracy (see simpb_linear_f16x3); `w` stays the reference copy. Needs
-   * |x|, |w| < 65504. Both NULL = exact fp32 path. */
+   * cores in three passes at fp32-grade accuracy (see simpb_linear_f16x3); `w` stays the reference copy. Any finite x:
+   * a row whose largest |x| is outside [2^-10, 2^15) is split as x * 2^-e and the sum scaled by 2^e before the bias (exact;
+   * fp32 denormal rows may be flushed). Weights: the caller passes a split only when every row's largest |w| is in that
+   * window or zero (plugin/dense.py split_in_window). Both NULL = exact fp32 path. */
   const void* w_hi;
   const void* w_lo;
 } simpb_gemm_job;

@@ -64,6 +64,18 @@ __device__ __forceinline__ float out_word(float v, int fmt) {
   return __uint_as_float(bits);
 }
 
+// ---- range of the split operands. x = xh + xl / 2^11 carries 22 bits only while half(x) is a normal half: |x| >= 65520
+// makes xh infinite, and a row whose largest |x| is far below 2^-14 loses its trailing bits to half subnormals. The split
+// kernels therefore stage each row as x * 2^-e with e = 0 while the row's largest |x| lies in [2^-10, 2^15) (or the row
+// is all zeros), and otherwise e = the exponent of that largest |x|; the epilogue multiplies the sum by 2^e before the
+// bias. Scaling by powers of two is exact, so rows inside the window compute exactly what they did without it.
+// The row maxima are collected while the first pass stages x (which splits unscaled, as before); only a workgroup that
+// met a row outside the window makes a second pass with the exponents. The flag is a plain LDS word behind the barrier
+// the epilogue needs anyway. (split_row_outside / split_row_exp: csrc/mfma_f16.h; the window's host-side twin for
+// weights: plugin/dense.py SPLIT_WINDOW.)
+using simpb::split_row_exp;
+using simpb::split_row_outside;
+
 struct GemmLaunch {
   simpb_gemm_args a;
   int tile_start[SIMPB_GEMM_MAX_JOBS + 1];
@@ -251,8 +263,10 @@ __global__ __launch_bounds__(kThreads) void gemm_f32_kernel(GemmLaunch L) {
 using h16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using h16x4 = __attribute__((ext_vector_type(4))) _Float16;
 
+// (four waves per SIMD = two workgroups per CU, as the LDS allows: at most 128 registers, which the row-range bookkeeping
+// below would otherwise push the 32 x 32 form past)
 template <int BN, int DEPTH, int BKT>
-__global__ __launch_bounds__(kThreads) void gemm_f16x3_kernel(GemmLaunch L) {
+__global__ __launch_bounds__(kThreads, 4) void gemm_f16x3_kernel(GemmLaunch L) {
   static_assert(DEPTH % 2 == 0, "LDS buffer index = register set index & 1");
   constexpr int LDH = BKT + 8;            // LDS row stride in halfs: conflict-free 16-lane groups for ds_read_b128
   constexpr int WN = BN / 32, WK = kWaves / WN, KW = BKT / WK;
@@ -264,6 +278,8 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_kernel(GemmLaunch L) {
   constexpr int kStageBytes = 2 * 2 * (BM + BN) * LDH * 2;
   constexpr int kPartBytes = WK * BM * LDP * 4;
   __shared__ __attribute__((aligned(16))) unsigned char smem_raw[kStageBytes > kPartBytes ? kStageBytes : kPartBytes];
+  __shared__ int s_rowexp[BM];                              // row exponents of the second pass (split_row_exp)
+  __shared__ int s_any;                                     // some row of the tile lies outside the window
   _Float16* s_xh = reinterpret_cast<_Float16*>(smem_raw);  // [2][BM][LDH]
   _Float16* s_xl = s_xh + 2 * BM * LDH;
   _Float16* s_wh = s_xl + 2 * BM * LDH;                    // [2][BN][LDH]
@@ -333,18 +349,26 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_kernel(GemmLaunch L) {
       pwl[set][decltype(i)::value] = *reinterpret_cast<const h16x8*>(wl + k0 + wofs[decltype(i)::value]);
     });
   };
-  auto stash = [&](auto set_c) __attribute__((always_inline)) {
+  float xmax[NX4];   // largest |x| this thread staged per row (first pass), then the row's
+  int xe[NX4];       // exponent of the row (second pass)
+#pragma unroll
+  for (int i = 0; i < NX4; ++i) { xmax[i] = 0.f; xe[i] = 0; }
+  auto stash = [&](auto set_c, auto scaled_c) __attribute__((always_inline)) {
     constexpr int set = decltype(set_c)::value;
     constexpr int buf = set & 1;
+    constexpr bool kScaled = decltype(scaled_c)::value;   // second pass: rows staged as x * 2^-e
     static_for<0, NX4>([&](auto i) __attribute__((always_inline)) {
       constexpr int ii = decltype(i)::value;
       const f32x4 v = px[set][ii];
       h16x4 hi, lo;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const _Float16 h = (_Float16)v[e];
+        float s = v[e];
+        if constexpr (kScaled) s = __builtin_amdgcn_ldexpf(s, -xe[ii]);
+        else xmax[ii] = fmaxf(xmax[ii], fabsf(s));
+        const _Float16 h = (_Float16)s;
         hi[e] = h;
-        lo[e] = (_Float16)((v[e] - (float)h) * 2048.f);
+        lo[e] = (_Float16)((s - (float)h) * 2048.f);
       }
       *reinterpret_cast<h16x4*>(&s_xh[(buf * BM + srx + RSX * ii) * LDH + scx * 4]) = hi;
       *reinterpret_cast<h16x4*>(&s_xl[(buf * BM + srx + RSX * ii) * LDH + scx * 4]) = lo;
@@ -361,8 +385,6 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_kernel(GemmLaunch L) {
   // query of the golden R50 stream changed sides of the image border (an N2 of 1129 instead of 1130): the decoder's
   // discrete decisions sit downstream of these products.
   f32x16 acc, acs, act;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acs[r] = 0.f; act[r] = 0.f; }
 
   auto multiply = [&](int buf) __attribute__((always_inline)) {
     const int off = wk * KW + 8 * kb;  // lane (r32, kb) holds k = wk*16 + 8*kb .. +7 of its x row / W row
@@ -376,26 +398,48 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_kernel(GemmLaunch L) {
     acc = simpb::mfma_32x32x16_f16(ah, bh, acc);
   };
 
-  static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) { fetch(d, decltype(d)::value); });
-  const int groups = nchunks / DEPTH;
-  for (int g = 0; g < groups; ++g) {
-    static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) {
-      stash(d);
-      __syncthreads();
-      fetch(d, (g + 1) * DEPTH + decltype(d)::value);
-      multiply(decltype(d)::value & 1);
-    });
-  }
-  const int rem = nchunks - groups * DEPTH;
-  static_for<0, DEPTH - 1>([&](auto d) __attribute__((always_inline)) {
-    if (decltype(d)::value < rem) {
-      stash(d);
-      __syncthreads();
-      multiply(decltype(d)::value & 1);
+  auto kloop = [&](auto scaled_c) __attribute__((always_inline)) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acs[r] = 0.f; act[r] = 0.f; }
+    static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) { fetch(d, decltype(d)::value); });
+    const int groups = nchunks / DEPTH;
+    for (int g = 0; g < groups; ++g) {
+      static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) {
+        stash(d, scaled_c);
+        __syncthreads();
+        fetch(d, (g + 1) * DEPTH + decltype(d)::value);
+        multiply(decltype(d)::value & 1);
+      });
     }
-  });
-
+    const int rem = nchunks - groups * DEPTH;
+    static_for<0, DEPTH - 1>([&](auto d) __attribute__((always_inline)) {
+      if (decltype(d)::value < rem) {
+        stash(d, scaled_c);
+        __syncthreads();
+        multiply(decltype(d)::value & 1);
+      }
+    });
+  };
+  if (tid == 0) s_any = 0;   // (ordered before any write below by the loop's barriers)
+  kloop(std::false_type{});
+  // the C4 lanes that staged a row meet on its largest |x| (consecutive lanes of one wave)
+#pragma unroll
+  for (int i = 0; i < NX4; ++i) {
+#pragma unroll
+    for (int m = 1; m < C4; m <<= 1) xmax[i] = fmaxf(xmax[i], __shfl_xor(xmax[i], m));
+    if (split_row_outside(xmax[i])) s_any = 1;
+  }
   __syncthreads();
+  const bool scaled = s_any != 0;   // workgroup-uniform
+  if (scaled) {
+#pragma unroll
+    for (int i = 0; i < NX4; ++i) {
+      xe[i] = split_row_exp(xmax[i]);
+      if (scx == 0) s_rowexp[srx + RSX * i] = xe[i];
+    }
+    kloop(std::true_type{});
+    __syncthreads();
+  }
   float* part = reinterpret_cast<float*>(smem_raw);  // [WK][BM][LDP]
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -411,6 +455,7 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_kernel(GemmLaunch L) {
       float v = part[r * LDP + c];
 #pragma unroll
       for (int p = 1; p < WK; ++p) v += part[(p * BM + r) * LDP + c];  // fixed order: deterministic
+      if (scaled) v = __builtin_amdgcn_ldexpf(v, s_rowexp[r]);
       if (bias) v += bias[gc];
       if (job.row_flag && job.row_flag[gr]) v += job.bias2[gc];
       if (job.relu) v = fmaxf(v, 0.f);
@@ -439,6 +484,8 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
   __shared__ __attribute__((aligned(16))) _Float16 s_xl[2 * kWM * LDH];
   __shared__ __attribute__((aligned(16))) _Float16 s_wh[2 * kWN * LDH];
   __shared__ __attribute__((aligned(16))) _Float16 s_wl[2 * kWN * LDH];
+  __shared__ int s_rowexp[kWM];   // row exponents of the second pass (split_row_exp)
+  __shared__ int s_any;
 
   const int total = L.tile_start[L.a.num_jobs];
   const int tile = (blockIdx.x & 7) * L.per_xcd + (blockIdx.x >> 3);
@@ -504,18 +551,26 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
       pwl[set][decltype(i)::value] = *reinterpret_cast<const h16x8*>(wl + k0 + wofs[decltype(i)::value]);
     });
   };
-  auto stash = [&](auto set_c) __attribute__((always_inline)) {
+  float xmax[NX4];   // largest |x| this thread staged per row, then the row's (as gemm_f16x3_kernel)
+  int xe[NX4];
+#pragma unroll
+  for (int i = 0; i < NX4; ++i) { xmax[i] = 0.f; xe[i] = 0; }
+  auto stash = [&](auto set_c, auto scaled_c) __attribute__((always_inline)) {
     constexpr int set = decltype(set_c)::value;
     constexpr int buf = set & 1;
+    constexpr bool kScaled = decltype(scaled_c)::value;   // second pass: rows staged as x * 2^-e
     static_for<0, NX4>([&](auto i) __attribute__((always_inline)) {
       constexpr int ii = decltype(i)::value;
       const f32x4 v = px[set][ii];
       h16x4 hi, lo;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const _Float16 h = (_Float16)v[e];
+        float s = v[e];
+        if constexpr (kScaled) s = __builtin_amdgcn_ldexpf(s, -xe[ii]);
+        else xmax[ii] = fmaxf(xmax[ii], fabsf(s));
+        const _Float16 h = (_Float16)s;
         hi[e] = h;
-        lo[e] = (_Float16)((v[e] - (float)h) * 2048.f);
+        lo[e] = (_Float16)((s - (float)h) * 2048.f);
       }
       *reinterpret_cast<h16x4*>(&s_xh[(buf * kWM + srx + RSX * ii) * LDH + scx * 4]) = hi;
       *reinterpret_cast<h16x4*>(&s_xl[(buf * kWM + srx + RSX * ii) * LDH + scx * 4]) = lo;
@@ -528,8 +583,6 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
   };
 
   f32x16 acc, acs, act;   // leading term / cross terms (x 2^11) / trailing term (x 2^22), as gemm_f16x3_kernel
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acs[r] = 0.f; act[r] = 0.f; }
 
   auto multiply = [&](int buf) __attribute__((always_inline)) {
 #pragma unroll
@@ -547,20 +600,42 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
   };
 
   // chunk c lives in register set / LDS buffer c & 1: fetched two chunks ahead, stashed one barrier ahead of its product
-  static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) { fetch(d, decltype(d)::value); });
-  const int pairs = nchunks / 2;
-  for (int g = 0; g < pairs; ++g) {
-    static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) {
-      stash(d);
+  auto kloop = [&](auto scaled_c) __attribute__((always_inline)) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acs[r] = 0.f; act[r] = 0.f; }
+    static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) { fetch(d, decltype(d)::value); });
+    const int pairs = nchunks / 2;
+    for (int g = 0; g < pairs; ++g) {
+      static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) {
+        stash(d, scaled_c);
+        __syncthreads();
+        fetch(d, (g + 1) * DEPTH + decltype(d)::value);
+        multiply(decltype(d)::value & 1);
+      });
+    }
+    if (nchunks & 1) {
+      stash(std::integral_constant<int, 0>{}, scaled_c);
       __syncthreads();
-      fetch(d, (g + 1) * DEPTH + decltype(d)::value);
-      multiply(decltype(d)::value & 1);
-    });
+      multiply(0);
+    }
+  };
+  if (tid == 0) s_any = 0;   // (ordered before any write below by the loop's barriers)
+  kloop(std::false_type{});
+#pragma unroll
+  for (int i = 0; i < NX4; ++i) {
+#pragma unroll
+    for (int m = 1; m < C4; m <<= 1) xmax[i] = fmaxf(xmax[i], __shfl_xor(xmax[i], m));
+    if (split_row_outside(xmax[i])) s_any = 1;
   }
-  if (nchunks & 1) {
-    stash(std::integral_constant<int, 0>{});
-    __syncthreads();
-    multiply(0);
+  __syncthreads();
+  const bool scaled = s_any != 0;   // workgroup-uniform
+  if (scaled) {   // (s_rowexp reaches the epilogue through the second pass's barriers)
+#pragma unroll
+    for (int i = 0; i < NX4; ++i) {
+      xe[i] = split_row_exp(xmax[i]);
+      if (scx == 0) s_rowexp[srx + RSX * i] = xe[i];
+    }
+    kloop(std::true_type{});
   }
 
   // ---- epilogue straight from the accumulators: lane (column r32, row group kb) holds rows (r & 3) + 8 (r >> 2) + 4 kb
@@ -573,7 +648,9 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
     for (int r = 0; r < 16; ++r) {
       const int gr = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kb;
       if (gr < M) {
-        float v = acc[r] + (acs[r] + act[r] * (1.f / 2048.f)) * (1.f / 2048.f) + bcol;
+        float v = acc[r] + (acs[r] + act[r] * (1.f / 2048.f)) * (1.f / 2048.f);
+        if (scaled) v = __builtin_amdgcn_ldexpf(v, s_rowexp[wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kb]);
+        v += bcol;
         if (job.row_flag && job.row_flag[gr]) v += b2;
         if (job.relu) v = fmaxf(v, 0.f);
         y[(size_t)gr * job.ldy + gc] = gr < live ? out_word(v, job.out_fmt) : 0.f;

@@ -42,6 +42,8 @@ __global__ __launch_bounds__(kThreads) void linear_f16x3_kernel(float* __restric
                                                                 const float* __restrict__ bias, int M, int N, int K) {
   __shared__ _Float16 s_xh[BM * LDH], s_xl[BM * LDH];
   __shared__ _Float16 s_wh[BN * LDH], s_wl[BN * LDH];
+  __shared__ int s_rowexp[BM];   // row exponents of the second pass (simpb::split_row_exp, as csrc/gemm.hip)
+  __shared__ int s_any;          // some row of the tile lies outside the split window
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = (tid >> 6) & 3, wm = tid >> 8;  // wave: column group, wm: 64-row group
   const int r32 = lane & 31, kb = lane >> 5;
@@ -67,11 +69,15 @@ __global__ __launch_bounds__(kThreads) void linear_f16x3_kernel(float* __restric
       pwl[i] = *reinterpret_cast<const h16x8*>(wl + wofs[i] + k0);
     }
   };
-  auto stash = [&]() __attribute__((always_inline)) {
+  float xmax = 0.f;   // largest |x| this thread staged (first pass), then its row's
+  int xe = 0;         // the row's exponent (second pass)
+  auto stash = [&](auto scaled_c) __attribute__((always_inline)) {
     h16x8 hi, lo;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float v = e < 4 ? px[0][e] : px[1][e - 4];
+      float v = e < 4 ? px[0][e] : px[1][e - 4];
+      if constexpr (decltype(scaled_c)::value) v = __builtin_amdgcn_ldexpf(v, -xe);
+      else xmax = fmaxf(xmax, fabsf(v));
       const _Float16 h = (_Float16)v;
       hi[e] = h;
       lo[e] = (_Float16)((v - (float)h) * 2048.f);
@@ -86,6 +92,9 @@ __global__ __launch_bounds__(kThreads) void linear_f16x3_kernel(float* __restric
   };
 
   f32x16 acc[2][2], acs[2][2];  // leading term / trailing terms (scaled by 2^11)
+
+  // (a row of x outside the split window: second pass with the row staged as x * 2^-e, as csrc/gemm.hip)
+  auto kloop = [&](auto scaled_c) __attribute__((always_inline)) {
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -96,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void linear_f16x3_kernel(float* __restric
   fetch(0);
   for (int k0 = 0; k0 < K; k0 += BK) {
     __syncthreads();  // everyone is done reading the previous chunk
-    stash();
+    stash(scaled_c);
     __syncthreads();
     fetch(k0 + BK < K ? k0 + BK : k0);  // the last iteration re-requests its own chunk (unconditional loads)
 #pragma unroll
@@ -123,6 +132,19 @@ __global__ __launch_bounds__(kThreads) void linear_f16x3_kernel(float* __restric
         }
     }
   }
+  };
+  if (tid == 0) s_any = 0;   // (ordered before any write below by the loop's barriers)
+  kloop(std::false_type{});
+  xmax = fmaxf(xmax, __shfl_xor(xmax, 1));   // the 4 lanes that staged a row
+  xmax = fmaxf(xmax, __shfl_xor(xmax, 2));
+  if (simpb::split_row_outside(xmax)) s_any = 1;
+  __syncthreads();
+  const bool scaled = s_any != 0;   // workgroup-uniform
+  if (scaled) {   // (s_rowexp reaches the epilogue through the second pass's barriers)
+    xe = simpb::split_row_exp(xmax);
+    if ((tid & 3) == 0) s_rowexp[sr] = xe;
+    kloop(std::true_type{});
+  }
 
   // C/D layout of the 32x32 tile: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
 #pragma unroll
@@ -134,8 +156,12 @@ __global__ __launch_bounds__(kThreads) void linear_f16x3_kernel(float* __restric
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int gr = row0 + wm * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kb;
-        if (gr < M) y[(size_t)gr * N + gc] = acc[m][n][r] + acs[m][n][r] * (1.f / 2048.f) + bv;
+        const int lr = wm * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kb, gr = row0 + lr;
+        if (gr < M) {
+          float v = acc[m][n][r] + acs[m][n][r] * (1.f / 2048.f);
+          if (scaled) v = __builtin_amdgcn_ldexpf(v, s_rowexp[lr]);
+          y[(size_t)gr * N + gc] = v + bv;
+        }
       }
   }
 }

@@ -36,4 +36,14 @@ __device__ __forceinline__ C16 mfma_32x32x16_f16(const A8& a, const A8& b, const
 #endif
 }
 
+// Range window of the split operands x = half(x) + half((x - half(x)) * 2^11) / 2^11 (csrc/gemm.hip, csrc/linear_split.hip):
+// a row whose largest |x| lies in [2^-10, 2^15) (or is 0) splits to 22 bits as it is; any other finite row is staged as
+// x * 2^-e with e = split_row_exp, and its sum multiplied by 2^e. (NaN / inf: nothing to gain, e = 0.)
+__device__ __forceinline__ bool split_row_outside(float m) {   // m = largest |x| of a row
+  return (m >= 32768.f && m <= 3.402823466e38f) || (m > 0.f && m < 0.0009765625f);
+}
+__device__ __forceinline__ int split_row_exp(float m) {
+  return split_row_outside(m) ? __builtin_amdgcn_frexp_expf(m) - 1 : 0;   // m * 2^-e in [1, 2)
+}
+
 }  // namespace simpb

@@ -11,6 +11,7 @@ the module tree and the state_dict are untouched, and the folded copies are rebu
 parameter is replaced or modified in place. GPU only: there is no CPU path behind these calls."""
 import ctypes
 import math
+import warnings
 
 import torch
 
@@ -35,16 +36,42 @@ MAX_SEGS, MAX_JOBS = 4, 4
 from . import routes
 
 
+# Rows of W whose largest |w| lies in this window (or that are all zeros) split into two halfs with 22 bits relative to
+# the row; outside it half(w) overflows (|w| >= 65520) or the row falls into the half subnormals. The GEMM kernels handle
+# rows of x outside it themselves (csrc/gemm.hip split_row_outside: same window).
+SPLIT_WINDOW = (2.0 ** -10, 2.0 ** 15)
+
+
+def split_in_window(w):
+    """True when every row of w [N, K] has its largest |w| inside SPLIT_WINDOW or is all zeros (and nothing is inf / NaN):
+    the weights the split-operand kernels take. One device-to-host read per weight; callers cache the answer."""
+    if w.numel() == 0:
+        return True
+    m = w.detach().abs().amax(dim=-1).double().cpu()
+    ok = bool(torch.isfinite(m).all()) and bool(((m == 0) | ((m >= SPLIT_WINDOW[0]) & (m < SPLIT_WINDOW[1]))).all())
+    if not ok and not getattr(split_in_window, "_warned", False):
+        split_in_window._warned = True
+        warnings.warn("simpb_amd: a weight has rows outside the split-operand window "
+                      f"[{SPLIT_WINDOW[0]:g}, {SPLIT_WINDOW[1]:g}); its launches run on the exact-fp32 kernel")
+    return ok
+
+
 def _split_weights(w):
-    """(w_hi, w_lo) f16 [N, K] of a contiguous f32 weight: w = w_hi + w_lo / 2048 up to ~2^-22 relative. Cached ON
+    """(w_hi, w_lo) f16 [N, K] of a contiguous f32 weight: w = w_hi + w_lo / 2048 up to ~2^-22 relative; (None, None)
+    for a weight outside the split window (split_in_window): its launches take the exact-fp32 kernel. Cached ON
     the tensor object (not in a table keyed by address or id(): both are reused once a model is freed)."""
     tag = (w.data_ptr(), w._version, str(w.device))
     hit = getattr(w, "_simpb_split", None)
     if hit is None or hit[0] != tag:
-        with torch.no_grad():
-            hi = w.detach().half()
-            lo = ((w.detach() - hi.float()) * 2048.0).half()
-        hit = (tag, hi.contiguous(), lo.contiguous())
+        if torch.cuda.is_current_stream_capturing():
+            return None, None   # no host read inside a capture: a weight first seen there takes the exact kernel
+        if split_in_window(w):
+            with torch.no_grad():
+                hi = w.detach().half()
+                lo = ((w.detach() - hi.float()) * 2048.0).half()
+            hit = (tag, hi.contiguous(), lo.contiguous())
+        else:
+            hit = (tag, None, None)
         w._simpb_split = hit
     return hit[1], hit[2]
 
@@ -174,8 +201,9 @@ def gemm(*jobs):
         jb.w, jb.ldw = w.data_ptr(), w.stride(0)
         if routes.R.gemm_split_fp16 and w.is_contiguous() and all(x.shape[-1] % 128 == 0 for x in spec["xs"]):
             w_hi, w_lo = _split_weights(w)
-            jb.w_hi, jb.w_lo = w_hi.data_ptr(), w_lo.data_ptr()
-            keep += [w_hi, w_lo]
+            if w_hi is not None:
+                jb.w_hi, jb.w_lo = w_hi.data_ptr(), w_lo.data_ptr()
+                keep += [w_hi, w_lo]
         jb.bias = bias.data_ptr() if bias is not None else None
         jb.y, jb.ldy = out.data_ptr(), ldo
         jb.relu = 1 if spec["relu"] else 0

@@ -608,8 +608,9 @@ def topk_rows(scores, k):
 def linear_split(x, weight, bias=None):
     """F.linear(x, weight, bias) at fp32-grade accuracy on the FP16 matrix cores (csrc/linear_split.hip):
     both operands split into a leading and a 2^11-scaled trailing half-precision part, three products in
-    fp32 accumulators. |x|, |weight| must be below the half-precision range. x [..., K] f32, or f16 (then its trailing part
-    is zero and two passes give the same result), weight [N, K]."""
+    fp32 accumulators. Any finite x (rows outside the split window are staged with a power-of-two exponent in the kernel);
+    a weight outside the window (dense.split_in_window) runs on the exact-fp32 kernel (linear_f32). x [..., K] f32, or f16
+    (then its trailing part is zero and two passes give the same result), weight [N, K]."""
     _require_gpu(x, weight)
     k = x.shape[-1]
     if weight.shape[1] != k or k % 32:
@@ -617,12 +618,19 @@ def linear_split(x, weight, bias=None):
     tag = (weight.data_ptr(), weight._version, str(weight.device))
     hit = getattr(weight, "_simpb_split_lin", None)  # cached on the tensor object: ids / addresses get reused
     if hit is None or hit[0] != tag:
-        with torch.no_grad():
-            w = weight.detach().float()
-            hi = w.half()
-            lo = ((w - hi.float()) * 2048.0).half()
-        hit = (tag, hi.contiguous(), lo.contiguous())
-        weight._simpb_split_lin = hit
+        from .dense import split_in_window
+        if torch.cuda.is_current_stream_capturing() or not split_in_window(weight):
+            hit = (tag, None, None) if not torch.cuda.is_current_stream_capturing() else None
+        else:
+            with torch.no_grad():
+                w = weight.detach().float()
+                hi = w.half()
+                lo = ((w - hi.float()) * 2048.0).half()
+            hit = (tag, hi.contiguous(), lo.contiguous())
+        if hit is not None:
+            weight._simpb_split_lin = hit
+    if hit is None or hit[1] is None:
+        return linear_f32(x, weight, bias)
     m, n = x.numel() // k, weight.shape[0]
     y = torch.empty(m, n, device=x.device, dtype=torch.float32)
     b = bias.contiguous().float() if bias is not None else None

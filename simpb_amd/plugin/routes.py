@@ -24,6 +24,8 @@ DEFAULTS = dict(
     # streams, oracle, runners), decoder graph 2.06 -> 1.96 ms. Shipped since round 4; False: the v_mfma_f32_32x32x2_f32
     # kernel. (Rounds 1-3 left it off: an earlier three-term form moved one 2D query of the golden R50 stream across an
     # image border -- any re-rounding can; the four-term form does not on any fixture.)
+    # Any finite x: rows outside the half pair's window are staged with a power-of-two exponent (tests/test_split_range.py);
+    # weights outside it take the exact kernel.
     gemm_split_fp16=True,
     # attention core on the FP16 matrix cores with split operands (csrc/attention.hip attention_halfs_kernel): the
     # projections in front of it leave q / k / v as (hi, lo) half pairs in each element's own 32-bit word (csrc/gemm.hip
