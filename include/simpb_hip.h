@@ -172,6 +172,35 @@ int simpb_stem_conv7x7_pool_f16(void* out, const void* img_nhwc4, const void* we
 int simpb_image_to_nhwc4_f16(void* out, const float* img, long long stride_n, long long stride_c, long long stride_h,
                              long long stride_w, int num_images, int channels, int height, int width, void* stream);
 
+/* Camera frame ingest: raw u8 frames as an image decoder delivers them -> the stem's operand, in place of the reference's
+ * host pipeline ResizeCropFlipImage (datasets/pipelines/augment.py:86-106: PIL.Image.resize(resize_dims).crop(crop), optional
+ * left-right flip) + NormalizeMultiviewImage (transform_3d.py:438-466) and of simpb_image_to_nhwc4_f16 behind it.
+ *   src  u8  [num_images, src_height, src_width, 3]  interleaved pixels
+ *   out  f16 [num_images, out_height, out_width, 4]  channel 3 = 0 (what simpb_stem_conv7x7_pool_f16 reads); 16-byte aligned
+ *   mid  u8  scratch of num_images * src_rows * simpb_preprocess_mid_pitch(out_width) bytes, 16-byte aligned: the
+ *        horizontally resampled rows between the two launches
+ * The resize is Pillow's 8-bit resampler (bicubic for RGB), byte for byte: per kept output column j of the RESIZED image
+ * (the crop's columns only, left to right) xn[j] <= taps_x integer coefficients kx[j][0..] with 22 fractional bits over
+ * source columns xlo[j].., and the same per kept output row (ky [out_height][taps_y], ylo, yn) over source ROWS; a pass
+ * computes clamp((2^21 + sum(pixel * k)) >> 22, 0, 255), horizontally first, the result stored as u8, then vertically.
+ * The tables are device pointers (int32) that the caller computes once per (source size, resize, crop), as Pillow's
+ * precompute_coeffs does, in float64; 2^21 + 255 * sum|k| < 2^31 per row is the caller's to assert. src_row0 / src_rows:
+ * the range of source rows the ylo / yn tables touch (min ylo, max (ylo + yn) - min ylo): only those rows are resampled
+ * horizontally. flip: output column j reads kept column out_width - 1 - j. lut f16 [3][256]: out channel c =
+ * lut[c][resampled byte of input channel (swap_rb ? 2 - c : c)], i.e. mean / std / channel order / rounding as a table.
+ * SIMPB_EINVAL, and nothing launched: a null pointer, a non-positive size, src_width > 4096, out_width > 2048, a table
+ * wider than SIMPB_PREPROCESS_MAX_TAPS, a row range outside [0, src_height), more than 65535 images or output rows. The
+ * kernels clamp every table entry into the staged row / the row range, so a wrong table gives wrong pixels, never an
+ * access outside src, mid or out. Two launches on `stream`; no allocation, no synchronisation (graph capture safe). */
+#define SIMPB_PREPROCESS_MAX_TAPS 64
+int simpb_preprocess_u8_nhwc4_f16(void* out, const void* src, void* mid, const int* kx, const int* xlo, const int* xn,
+                                  const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
+                                  int src_height, int src_width, int out_height, int out_width, int taps_x, int taps_y,
+                                  int src_row0, int src_rows, int flip, int swap_rb, void* stream);
+
+/* Bytes of one row of the `mid` scratch above (whole groups of 4 pixels, rounded up to 16); 0 for a width outside 1..2048. */
+int simpb_preprocess_mid_pitch(int out_width);
+
 /* Grouped small GEMM of the decoder: up to 4 independent problems per launch, each
  *   y[M, 0:N] (row stride ldy) = relu?( [x0 | x1 | ...][M, K] . w[N, K]^T (row stride ldw) + bias[N] )
  * where x is given as up to 4 column segments (pointer, row stride, width; widths sum to K). This is

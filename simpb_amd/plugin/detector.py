@@ -146,14 +146,25 @@ class ResNet(BaseModule):
             self.add_module(name, nn.Sequential(*layers))
             self.res_layers.append(name)
 
-    def _stem_kernel_ok(self, x):
+    def _stem_kernel_usable(self):
         c1, mp = self.conv1, self.maxpool
-        return (routes.R.stem_kernel and getattr(self, "fused_epilogue", False) and x.is_cuda and x.dtype == torch.float32
+        return (routes.R.stem_kernel and getattr(self, "fused_epilogue", False)
                 and tuple(c1.weight.shape) == (64, 3, 7, 7) and c1.stride == (2, 2) and c1.padding == (3, 3) and c1.bias is not None
                 and mp.kernel_size == 3 and mp.stride == 2 and mp.padding == 1 and mp.dilation == 1 and not mp.ceil_mode)
 
-    def forward(self, x):
-        if self._stem_kernel_ok(x):
+    def _stem_kernel_ok(self, x):
+        return self._stem_kernel_usable() and x.is_cuda and x.dtype == torch.float32
+
+    def forward(self, x, nhwc4=False):
+        """nhwc4: x is the stem kernel's own operand, f16 [N, H, W, 4] (the camera frame ingest wrote it), not an NCHW image."""
+        if nhwc4:
+            if not (self._stem_kernel_usable() and x.is_cuda and x.dtype == torch.float16):
+                raise RuntimeError("an f16 NHWC4 image (raw camera frame ingest) needs the in-tree stem kernel: routes.stem_kernel on, "
+                                   "a BN-folded fp16 backbone (fuse_conv_bn + half_backbone) with the 7x7 / stride 2 stem and the "
+                                   "3x3 / stride 2 max-pool; there is no second route for it")
+            from .ops import stem_conv_pool_nhwc4
+            x = stem_conv_pool_nhwc4(x, self.conv1.weight, self.conv1.bias)
+        elif self._stem_kernel_ok(x):
             # the whole stem -- cast, 7x7 convolution, bias, ReLU, max-pool -- in two launches of our own (csrc/stem.hip)
             from .ops import stem_conv_pool
             x = stem_conv_pool(x, self.conv1.weight, self.conv1.bias)
@@ -342,17 +353,27 @@ class SimPB(BaseModule):
                     blk.fused_epilogue = True
         return self
 
-    def extract_feat(self, img, return_depth=False, metas=None):
-        """simpb.py:64-91."""
+    def extract_feat(self, img, return_depth=False, metas=None, raw_plan=None):
+        """simpb.py:64-91. A uint8 `img` is the raw form: camera frames [bs, cams, Hs, Ws, 3] (or [N, Hs, Ws, 3]) as decoded,
+        resized / cropped / flipped / normalised on the device by `raw_plan` (simpb_amd.preprocess.ResamplePlan) straight into
+        the stem's operand."""
         bs = img.shape[0]
-        if img.dim() == 5:
+        raw = img.dtype == torch.uint8
+        if raw:
+            if raw_plan is None:
+                raise ValueError("uint8 frames need raw_plan= (simpb_amd.preprocess.ResamplePlan): the resize / crop / normalise to apply")
+            if img.dim() not in (4, 5):
+                raise ValueError(f"raw frames are u8 [bs, cams, Hs, Ws, 3] or [N, Hs, Ws, 3], got {tuple(img.shape)}")
+            num_cams = img.shape[1] if img.dim() == 5 else 1
+            img = raw_plan.run(img)
+        elif img.dim() == 5:
             num_cams = img.shape[1]
             img = img.flatten(end_dim=1)
         else:
             num_cams = 1
-        if self.fp16_enabled and not (img.dtype == torch.float32 and getattr(self.img_backbone, "_stem_kernel_ok", lambda t: False)(img)):
+        if not raw and self.fp16_enabled and not (img.dtype == torch.float32 and getattr(self.img_backbone, "_stem_kernel_ok", lambda t: False)(img)):
             img = img.half().contiguous(memory_format=torch.channels_last)   # (the stem kernel route casts inside its own launch)
-        feature_maps = self.img_backbone(img)
+        feature_maps = self.img_backbone(img, nhwc4=True) if raw else self.img_backbone(img)
         biases = None
         if self.img_neck is not None:
             # fp16 fused path: the four output convolutions of the FPN run without their bias and the bias is added

@@ -578,13 +578,31 @@ def stem_conv_pool(img, weight, bias):
     x4 = torch.empty(n, h, w, 4, device=img.device, dtype=torch.float16)
     _lib.check(lib.simpb_image_to_nhwc4_f16(_ptr(x4), _ptr(img), img.stride(0), img.stride(1), img.stride(2), img.stride(3), n, c, h, w,
                                             _stream()), "simpb_image_to_nhwc4_f16")
+    return stem_conv_pool_nhwc4(x4, weight, bias)
+
+
+def stem_conv_pool_nhwc4(x4, weight, bias):
+    """The stem launch alone, on an operand that is f16 [N, H, W, 4] (RGB + 0) already: what stem_conv_pool's cast pass or
+    the camera frame ingest (preprocess_frames) wrote. -> f16 [N, 64, Hp, Wp] channels_last."""
+    _require_gpu(x4, weight, bias)
+    if (x4.dtype != torch.float16 or x4.dim() != 4 or x4.shape[3] != 4 or not x4.is_contiguous() or tuple(weight.shape) != (64, 3, 7, 7)
+            or bias.numel() != 64 or x4.shape[1] < 8 or x4.shape[2] < 8):
+        raise ValueError("stem_conv_pool_nhwc4: contiguous f16 [N, H, W, 4] image, [64, 3, 7, 7] weight, 64 biases")
+    n, h, w, _ = x4.shape
+    lib = _lib.lib()
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     hp, wp = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
-    out = torch.empty((n, 64, hp, wp), device=img.device, dtype=torch.float16, memory_format=torch.channels_last)
+    out = torch.empty((n, 64, hp, wp), device=x4.device, dtype=torch.float16, memory_format=torch.channels_last)
     b16 = bias if bias.dtype == torch.float16 and bias.is_contiguous() else bias.half().contiguous()
     _lib.check(lib.simpb_stem_conv7x7_pool_f16(_ptr(out), _ptr(x4), _ptr(_stem_weight_packed(weight)), _ptr(b16), n, h, w, 64,
                                                _stream()), "simpb_stem_conv7x7_pool_f16")
     return out
+
+
+def preprocess_frames(frames, plan, out=None):
+    """Camera frame ingest (csrc/preprocess.hip): raw u8 [..., Hs, Ws, 3] frames -> f16 [N, h, w, 4], the reference's
+    resize / crop / flip / normalise of `plan` (simpb_amd.preprocess.ResamplePlan) done on the device, Pillow's bytes."""
+    return plan.run(frames, out=out)
 
 
 def topk_rows(scores, k):

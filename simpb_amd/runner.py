@@ -29,10 +29,15 @@ CAPTURE_MODE = "thread_local"
 
 
 class FrameRunner:
-    def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False):
+    def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
+                 raw_input=None, img_norm_cfg=None):
         """independent_streams: the batch is a set of independent camera streams, each decoded exactly as a batch of one
         would be (`capacity` 2D slots per stream; SimPBHead.independent_streams) -- the throughput form of BASELINE config
-        #3. False: the reference's batch semantics (camera groups padded to the max over the batch)."""
+        #3. False: the reference's batch semantics (camera groups padded to the max over the batch).
+
+        raw_input=(Hs, Ws): frames arrive as the decoder's u8 [bs, cams, Hs, Ws, 3] (device or pinned host memory) and the
+        reference's resize / crop / flip / normalise (img_norm_cfg, default: the shipped configs') runs on the device as the
+        first launches of the frame (csrc/preprocess.hip), keyed by the frame's own aug_config: see _ensure_plan."""
         self.model = model
         self.head = model.head
         self.bs = batch_size
@@ -44,7 +49,14 @@ class FrameRunner:
         h, w = image_hw
         dev = self.device
         cams = self.head.num_cams
-        self.img = torch.zeros(batch_size, cams, 3, h, w, device=dev)
+        self.image_hw = (int(h), int(w))
+        self.raw_input = (int(raw_input[0]), int(raw_input[1])) if raw_input is not None else None
+        self.img_norm_cfg = img_norm_cfg
+        self.plan = None                    # preprocess.ResamplePlan of the stream's aug_config (raw_input mode)
+        if self.raw_input is None:
+            self.img, self.raw = torch.zeros(batch_size, cams, 3, h, w, device=dev), None
+        else:   # (no fp32 staging buffer in this mode)
+            self.img, self.raw = None, torch.zeros(batch_size, cams, *self.raw_input, 3, dtype=torch.uint8, device=dev)
         self.proj = torch.zeros(batch_size, cams, 4, 4, device=dev)
         self.wh = torch.tensor([float(w), float(h)], device=dev).view(1, 1, 2).repeat(batch_size, cams, 1)
         self.wh_host = (int(w), int(h))
@@ -69,9 +81,34 @@ class FrameRunner:
         self.rec_consumed = None
 
     # ------------------------------------------------------------------ per-frame host work
+    def _ensure_plan(self, metas):
+        """raw_input mode: the ingest tables follow the frame's aug_config (metas["img_metas"][0], the dict the decoder reads
+        as well). A frame whose (source size, resize_dims, crop, flip) differ from the resident plan's gets a new plan, and
+        every captured graph is dropped first (they bake the old tables' addresses and the decoder's crop / resize in):
+        a frame never runs on stale tables."""
+        from .preprocess import ResamplePlan, plan_key
+        aug = metas["img_metas"][0]["aug_config"]
+        if self.plan is not None and self.plan.key == plan_key(self.raw_input, aug):
+            return
+        plan = ResamplePlan(self.raw_input, aug, self.img_norm_cfg)
+        if plan.out_hw != self.image_hw:
+            raise ValueError(f"aug_config {aug} turns {self.raw_input} frames into {plan.out_hw} images; this runner was built for "
+                             f"{self.image_hw}")
+        if self.plan is not None:
+            torch.cuda.synchronize(self.device)   # nothing in flight reads the old tables
+            self._drop_all_graphs()
+        self.plan = plan.reserve(self.bs * self.head.num_cams, self.device)
+
+    def _check_frames(self, img):
+        if img.dtype != torch.uint8 or tuple(img.shape) != tuple(self.raw.shape):
+            raise ValueError(f"raw_input runner takes u8 {tuple(self.raw.shape)} frames, got {img.dtype} {tuple(img.shape)}")
+
+    def _extract(self, img, raw):
+        return self.model.extract_feat(raw, raw_plan=self.plan) if raw is not None else self.model.extract_feat(img)
+
     def _stage(self, img, metas):
         """Copy this frame's inputs into the static device buffers (a few small async copies)."""
-        self.img.copy_(img, non_blocking=True)
+        (self.img if self.raw is None else self.raw).copy_(img, non_blocking=True)
         self.pin_proj.copy_(metas["projection_mat"] if not metas["projection_mat"].is_cuda else metas["projection_mat"].cpu())
         self.proj.copy_(self.pin_proj, non_blocking=True)
         if self.prev_metas is not None:
@@ -90,7 +127,7 @@ class FrameRunner:
 
     def _frame(self, dmetas, aug_config):
         """The device part of one frame; every tensor it returns has a fixed shape."""
-        feature_maps = self.model.extract_feat(self.img)
+        feature_maps = self._extract(self.img, self.raw)
         outs = self.head(feature_maps, dmetas)
         alloc = outs["alloc_list"][-1]
         rec3d, rec2d = self.head.decoder.decode_static_device(
@@ -101,6 +138,9 @@ class FrameRunner:
     # ------------------------------------------------------------------ capacity overflow
     def _drop_graphs(self):
         self.graph = self.outputs = None
+
+    def _drop_all_graphs(self):
+        self._drop_graphs()
 
     def _grow(self):
         """A frame's 2D query set did not fit: next capacity (x1.5, multiple of 128, at most anchors x cameras, which
@@ -130,10 +170,13 @@ class FrameRunner:
     # ------------------------------------------------------------------ public
     @torch.no_grad()
     def step(self, img, metas, force_eager=False):
-        """One frame for all streams: img f32 [bs, cams, 3, H, W] (device), metas as the reference's
+        """One frame for all streams: img f32 [bs, cams, 3, H, W] (device; u8 [bs, cams, Hs, Ws, 3] with raw_input), metas as the reference's
         test pipeline collects them (projection_mat, timestamp, img_metas with T_global/T_global_inv/
         aug_config). Returns the reference's list of {'img_bbox': {...}} (simpb_head.py:1089-1123)."""
         aug = metas["img_metas"][0]["aug_config"]
+        if self.raw is not None:
+            self._check_frames(img)
+            self._ensure_plan(metas)
         self._stage(img, metas)
         dmetas = self._device_metas(metas)
         warm = self.prev_metas is not None
@@ -186,12 +229,13 @@ class PipelinedRunner(FrameRunner):
     is chained on the device: a frame's commit also holds back when the flags of the frame enqueued before it are
     set (`overflow_chain`, plugin/head.py), and collect() then re-runs both, in order, on the state frame t-1 found."""
 
-    def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False):
+    def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
+                 raw_input=None, img_norm_cfg=None):
         # two streams side by side from here on: a convolution that misses the in-tree kernels' shape rules must not slip to a
         # vendor kernel silently (plugin/detector.py: STRICT_NO_VENDOR)
         from .plugin import detector
         detector.STRICT_NO_VENDOR = True
-        super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams)
+        super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg)
         dev = self.device
         # the decoder of frame t is the critical path (a chain of ~170 dependent small launches); the
         # backbone of frame t+1 only has to be done by the time that chain ends: decoder stream first
@@ -199,7 +243,10 @@ class PipelinedRunner(FrameRunner):
         self.s_bb = torch.cuda.Stream(device=dev, priority=prio[0])
         self.s_head = torch.cuda.Stream(device=dev, priority=prio[1])
         self.s_rec = self.s_head            # the stream the detection records are written on (for their consumers)
-        self.imgs = [self.img, torch.zeros_like(self.img)]
+        # one input buffer per feature slot: fp32 images, or raw u8 frames (raw_input: the ingest is the first node of the
+        # captured backbone graph and reads the slot's own buffer)
+        self.imgs = [self.img, torch.zeros_like(self.img)] if self.raw is None else [None, None]
+        self.raws = [self.raw, torch.zeros_like(self.raw)] if self.raw is not None else [None, None]
         self.fm = [None, None]              # feature maps of the frame last produced into each slot
         self.bb_graph = [None, None]
         self.bb_out = [None, None]
@@ -237,7 +284,7 @@ class PipelinedRunner(FrameRunner):
     def _features(self, slot):
         """Backbone + FPN + token format, plus everything of the decoder that depends on the features
         alone: the value projections of the three 2D cross-attention layers."""
-        fm = list(self.model.extract_feat(self.imgs[slot]))
+        fm = list(self._extract(self.imgs[slot], self.raws[slot]))
         if hasattr(self.head, "precompute_values") and len(fm) == 3:
             fm.append(self.head.precompute_values(fm))
         return fm
@@ -252,6 +299,10 @@ class PipelinedRunner(FrameRunner):
 
     def _drop_graphs(self):
         self.head_graph, self.head_out, self.head_runs = [None, None], [None, None], [0, 0]
+
+    def _drop_all_graphs(self):
+        self._drop_graphs()
+        self.bb_graph, self.bb_out, self.bb_runs = [None, None], [None, None], [0, 0]
 
     def _run_head(self, slot, dmetas, aug, warm, force_eager):
         """Enqueue the decoder of the frame whose features sit in slot `slot` on s_head."""
@@ -328,11 +379,14 @@ class PipelinedRunner(FrameRunner):
         """Enqueue backbone(t) and decoder(t) without waiting for either (several runners -- several independent
         camera streams on one GPU -- can be launched back to back and collected after)."""
         slot = self.count % 2
+        if self.raw is not None:
+            self._check_frames(img)
+            self._ensure_plan(metas)
         cur = torch.cuda.current_stream()
         self.s_bb.wait_stream(cur)
         self.s_head.wait_stream(cur)
         with torch.cuda.stream(self.s_bb):
-            self.imgs[slot].copy_(img, non_blocking=True)
+            (self.imgs[slot] if self.raw is None else self.raws[slot]).copy_(img, non_blocking=True)
         self._run_backbone(slot, force_eager)
         self.bb_done[slot].record(self.s_bb)
         self.s_head.wait_event(self.bb_done[slot])
@@ -423,8 +477,9 @@ class SplitPipelinedRunner(PipelinedRunner):
         backbone stream, so no tensor of the caching allocator crosses streams.
     """
 
-    def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False):
-        super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams)
+    def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
+                 raw_input=None, img_norm_cfg=None):
+        super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg)
         dev = self.device
         # part A rides on the backbone stream, right behind backbone(t): as fast for one stream as a third stream of its own
         # (350 frames/s either way) and cheaper when several runners share the GPU (8 runners: 368 against 308 frames/s)

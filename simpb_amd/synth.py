@@ -130,6 +130,24 @@ def images(bs, frame_idx, image_wh=(704, 256), seed=0):
     return torch.from_numpy(randn(f"synth.img.f{frame_idx}", (bs, 6, 3, h, w), seed))
 
 
+def raw_frames(bs, frame_idx, src_hw=(900, 1600), num_cams=6, seed=0):
+    """u8 [bs, cams, Hs, Ws, 3] camera frames as an image decoder delivers them (interleaved pixels), a pure function of
+    the arguments: smooth structure (a few low-frequency waves per camera, so a resize has something to interpolate) plus
+    uniform noise that drives the resampler's 0 / 255 clamp. Input of the device ingest (simpb_amd/preprocess.py)."""
+    hs, ws = src_hw
+    r = _rng(f"synth.raw.f{frame_idx}", seed)
+    yy = np.arange(hs, dtype=np.float32)[:, None, None] / hs
+    xx = np.arange(ws, dtype=np.float32)[None, :, None] / ws
+    out = np.empty((bs, num_cams, hs, ws, 3), np.uint8)
+    for b in range(bs):
+        for c in range(num_cams):
+            fx, fy, ph = r.uniform(1.0, 9.0, 3).astype(np.float32), r.uniform(1.0, 9.0, 3).astype(np.float32), r.uniform(0, 6.28, 3).astype(np.float32)
+            wave = 127.5 + 90.0 * np.sin(6.2831853 * (fx * xx + fy * yy) + ph)          # [hs, ws, 3]
+            noise = r.randint(-96, 97, (hs, ws, 3)).astype(np.float32)
+            out[b, c] = np.clip(wave + noise, 0, 255).astype(np.uint8)
+    return torch.from_numpy(out)
+
+
 _DAMPED = re.compile(r"layers\.\d+\.layers\.10\.(weight|bias)$")  # last Linear of the refine MLPs
 
 

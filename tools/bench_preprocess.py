@@ -1,0 +1,193 @@
+"""Measures the camera frame ingest (csrc/preprocess.hip, simpb_amd/preprocess.py) on the GPU; one JSON line out.
+
+  (a) `kernel`: HIP-event time of the two ingest launches alone, warmed, --launches (>= 200) timed launches back to back
+      between one pair of events, for the R50 configuration (1600 x 900 -> 704 x 396 -> crop to 704 x 256) and the derived
+      R101 one (-> 1408 x 792 -> 1408 x 512), bs 1 and 8 (N = 6 and 48 images). Bytes are the ones the algorithm needs,
+      computed from the plan: the needed source rows read once, the u8 intermediate written and read, the output written.
+      Share of the bound = (bytes / HBM peak) / time; the peak is MI355X_MICROARCH.md's 8.0 TB/s spec figure (6.29 TB/s is
+      what a float4 copy reaches there).
+  (b) `runner`: frames/s of SplitPipelinedRunner at bs = 1 with three input forms in one process, alternated in blocks:
+      fp32 frames resident in HBM (what bench.py times), fp32 frames in pinned host memory (bench.py --h2d, 13.0 MB per
+      frame), raw u8 frames in pinned host memory with the device ingest (25.9 MB per frame); plus raw frames resident in
+      HBM, which splits the raw form's cost into launches and copy. Same weights, and the same pictures: the fp32 frames
+      are the ingest's own output widened to fp32, so every form decodes the same operands.
+  (c) `cpu_pillow_ms`: the same preprocessing of one six-camera frame with Pillow + numpy on one CPU thread, if Pillow
+      imports (a CPU number about CPU work).
+
+A run that finds no GPU fails.
+
+    python tools/bench_preprocess.py [--launches 200] [--blocks 5] [--block-steps 40]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_PEAK = 8.0e12       # bytes/s, spec (MI355X_MICROARCH.md, chip-level parameters)
+HBM_COPY = 6.29e12      # bytes/s, measured float4 copy (same table)
+CONFIGS = {"r50_704x256": dict(resize=0.44, crop=(0, 140, 704, 396)), "r101_1408x512": dict(resize=0.88, crop=(0, 280, 1408, 792))}
+
+
+def kernel_leg(torch, args):
+    from simpb_amd import _lib, synth
+    from simpb_amd.preprocess import ResamplePlan
+    six = synth.raw_frames(1, 0).cuda()
+    out = {}
+    for name, aug in CONFIGS.items():
+        plan = ResamplePlan((900, 1600), aug)
+        pitch = int(_lib.lib().simpb_preprocess_mid_pitch(plan.out_hw[1]))
+        per_image = plan.bytes_per_image(pitch)
+        for bs in (1, 8):
+            frames = six.repeat(bs, 1, 1, 1, 1).contiguous()
+            n = bs * 6
+            dst = torch.empty(n, *plan.out_hw, 4, dtype=torch.float16, device="cuda")
+            plan.reserve(n, "cuda")
+            for _ in range(20):
+                plan.run(frames, out=dst)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.launches):
+                plan.run(frames, out=dst)
+            e1.record()
+            e1.synchronize()
+            ms = e0.elapsed_time(e1) / args.launches
+            nbytes = n * sum(per_image.values())
+            floor_ms = nbytes / HBM_PEAK * 1e3
+            out[f"{name}_bs{bs}"] = dict(
+                ms=round(ms, 5), images=n, launches=args.launches, bytes=nbytes, bytes_per_image=per_image,
+                bytes_per_s=round(nbytes / (ms * 1e-3), 1), share_of_hbm_peak=round(floor_ms / ms, 4),
+                share_of_measured_copy_rate=round(nbytes / HBM_COPY * 1e3 / ms, 4),
+                bandwidth_bound=bool(floor_ms / ms >= 0.5),
+                note="bound named bandwidth-bound when the algorithm's bytes at the HBM peak take at least half the measured time")
+    return out
+
+
+def build_model(torch):
+    from simpb_amd import configs, plugin, synth
+    cfg = configs.simpb_plus(anchor=synth.anchors(900))
+    model = plugin.build_detector(cfg["model"]).eval()
+    synth.load_procedural(model)
+    model.cuda()
+    model.fuse_conv_bn()
+    model.half_backbone()
+    return model
+
+
+def runner_leg(torch, args):
+    from simpb_amd import synth
+    from simpb_amd.preprocess import ResamplePlan
+    from simpb_amd.runner import SplitPipelinedRunner
+    ring = 4
+    raws = [synth.raw_frames(1, f) for f in range(ring)]
+    plan = ResamplePlan((900, 1600), CONFIGS["r50_704x256"])
+    # the fp32 form of the same pictures: the ingest's f16 operand widened (exact), as [1, 6, 3, 256, 704]
+    fp32 = [plan.run(r.cuda())[..., :3].permute(0, 3, 1, 2).float().contiguous()[None] for r in raws]
+    forms = {
+        "fp32_hbm": dict(frames=fp32, raw=False, bytes_per_frame=0),
+        "fp32_pinned_host": dict(frames=[x.cpu().pin_memory() for x in fp32], raw=False, bytes_per_frame=fp32[0].numel() * 4),
+        "raw_u8_pinned_host": dict(frames=[r.pin_memory() for r in raws], raw=True, bytes_per_frame=raws[0].numel()),
+        # not a deployment form (a decoder's frames start on the host): raw frames resident in HBM, which splits the raw
+        # form's cost into the ingest launches (this minus fp32_hbm) and the copy (raw_u8_pinned_host minus this)
+        "raw_u8_hbm": dict(frames=[r.cuda() for r in raws], raw=True, bytes_per_frame=0),
+    }
+    if args.profile_raw:   # the run for rocprofv3 --kernel-trace --stats: the raw form alone
+        forms = {"raw_u8_pinned_host": forms["raw_u8_pinned_host"]}
+    dev = torch.device("cuda")
+    runners = {False: None if args.profile_raw else SplitPipelinedRunner(build_model(torch), 1, (256, 704), capacity=1536, device=dev,
+                                                                          use_graph=True),
+               True: SplitPipelinedRunner(build_model(torch), 1, (256, 704), capacity=1536, device=dev, use_graph=True,
+                                          raw_input=(900, 1600))}
+    count = {False: 0, True: 0}
+
+    def run(form, steps):
+        r = runners[form["raw"]]
+        for _ in range(steps):
+            f = count[form["raw"]]
+            r.step(form["frames"][f % ring], synth.frame_metas(1, f))
+            count[form["raw"]] = f + 1
+
+    for form in forms.values():   # cold frame, eager warm frames, graph capture: outside every timed block
+        run(form, 12)
+    torch.cuda.synchronize()
+    blocks = {k: [] for k in forms}
+    for _ in range(args.blocks):
+        for name, form in forms.items():
+            run(form, 4)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(form, args.block_steps)
+            torch.cuda.synchronize()
+            blocks[name].append((time.perf_counter() - t0) / args.block_steps * 1e3)
+    out = {}
+    for name, ms in blocks.items():
+        mean = float(np.mean(ms))
+        out[name] = dict(ms_per_step=round(mean, 4), frames_per_s=round(1e3 / mean, 1), block_ms=[round(v, 4) for v in ms],
+                         spread_ms=round(max(ms) - min(ms), 4), timed_frames=args.blocks * args.block_steps,
+                         host_bytes_per_frame=forms[name]["bytes_per_frame"], replays=runners[forms[name]["raw"]].stats["replay"])
+    if args.profile_raw:
+        return out
+    out["ingest_launches_ms"] = round(out["raw_u8_hbm"]["ms_per_step"] - out["fp32_hbm"]["ms_per_step"], 4)
+    out["raw_copy_ms"] = round(out["raw_u8_pinned_host"]["ms_per_step"] - out["raw_u8_hbm"]["ms_per_step"], 4)
+    out["fp32_copy_ms"] = round(out["fp32_pinned_host"]["ms_per_step"] - out["fp32_hbm"]["ms_per_step"], 4)
+    out["raw_minus_fp32_pinned_ms"] = round(out["raw_u8_pinned_host"]["ms_per_step"] - out["fp32_pinned_host"]["ms_per_step"], 4)
+    out["raw_minus_fp32_hbm_ms"] = round(out["raw_u8_pinned_host"]["ms_per_step"] - out["fp32_hbm"]["ms_per_step"], 4)
+    return out
+
+
+def cpu_leg(frames=3):
+    try:
+        from PIL import Image
+    except ImportError:
+        return None
+    try:
+        import torch
+        torch.set_num_threads(1)
+    except Exception:
+        pass
+    from simpb_amd import synth
+    from simpb_amd.preprocess import IMG_NORM_CFG
+    six = synth.raw_frames(1, 0)[0].numpy()
+    mean = np.asarray(IMG_NORM_CFG["mean"], np.float32)
+    stdinv = (1.0 / np.asarray(IMG_NORM_CFG["std"], np.float64)).astype(np.float32)
+    times = []
+    for _ in range(frames):
+        t0 = time.perf_counter()
+        for cam in six:
+            img = np.asarray(Image.fromarray(cam).resize((704, 396)).crop((0, 140, 704, 396))).astype(np.float32)
+            img = (img[..., ::-1] - mean) * stdinv
+            np.ascontiguousarray(img.transpose(2, 0, 1))
+        times.append((time.perf_counter() - t0) * 1e3)
+    return dict(ms_per_frame=round(float(np.median(times)), 2), frames=frames, threads=1, what="Pillow resize + crop, numpy normalise + "
+                "transpose, six 1600 x 900 cameras; a CPU time of CPU work")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--block-steps", type=int, default=40)
+    ap.add_argument("--skip-runner", action="store_true")
+    ap.add_argument("--profile-raw", action="store_true",
+                    help="only the runner leg's raw form: the program to put behind `rocprofv3 --kernel-trace --stats --`")
+    args = ap.parse_args()
+    if args.launches < 200 or args.blocks * args.block_steps < 200:
+        raise SystemExit("at least 200 timed launches and 200 timed frames per input form")
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/bench_preprocess.py needs a GPU: nothing here is measured on a CPU in its place")
+    with torch.no_grad():
+        result = dict(tool="bench_preprocess", device=torch.cuda.get_device_name(0), hbm_peak_bytes_per_s=HBM_PEAK,
+                      kernel=None if args.profile_raw else kernel_leg(torch, args), runner=None if args.skip_runner else runner_leg(torch, args),
+                      cpu_pillow=None if args.profile_raw else cpu_leg())
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
