@@ -10,7 +10,7 @@
 // FLOPs, so the kernel is organised for latency, not for the matrix cores: one workgroup = R rows,
 // thread t = output column t, weights are read pre-transposed ([in][out], one coalesced 1-KiB
 // wave-load per k, L2-resident and shared by all workgroups), the row tile is broadcast from LDS.
-// Up to 4 independent chains (e.g. the 4 encoder branches) share a launch through blockIdx.y.
+// Up to 8 independent chains (SIMPB_MLP_MAX_CHAINS; e.g. the 4 encoder branches) share a launch through blockIdx.y.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "../../include/simpb_hip.h"
