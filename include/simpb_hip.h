@@ -485,6 +485,28 @@ int simpb_bank_cache_streams(float* confidence, float* cached_feature, float* ca
                              int has_previous, float confidence_decay, int has_threshold, float threshold, const int* hold,
                              int num_hold, int* sticky, unsigned* sync_words, void* stream);
 
+/* A batch of independent streams in which some sit a frame out: `active` u8 [batch_size] (device; NULL = every stream is
+ * active, results identical to the entry point without the suffix). A stream with active = 0:
+ *   simpb_bank_update_merge_active: its instance_id row is not reset even when its mask is 0 (the only persistent write of
+ *     this call does not happen); its output rows are written and unspecified.
+ *   simpb_bank_cache_streams_active (both forms: serial when sync_words is NULL or batch_size is 1): confidence,
+ *     cached_feature, cached_anchor and instance_id rows stay exactly as found, its ids_out row is -1, it takes no fresh ids
+ *     (prev_id advances by the active streams' only, and the streams behind it number theirs as if it were not in the
+ *     batch); its cls / feature / anchor rows are never read and may hold anything. hold / sticky take precedence: a held
+ *     frame writes nothing for anyone. The per-stream form still launches batch_size workgroups and all of them meet. */
+int simpb_bank_update_merge_active(float* feature_out, float* anchor_out, float* embed_out, long long* instance_id,
+                                   const int* index, const float* feature, const float* anchor, const float* embed,
+                                   const float* cached_feature, const float* cached_anchor, const float* cached_embed,
+                                   const unsigned char* mask, const int* hold, int num_hold, const int* sticky, int batch_size,
+                                   int num_anchors, int num_temp, int embed_dims, int pos_embed_dims,
+                                   const unsigned char* active, void* stream);
+int simpb_bank_cache_streams_active(float* confidence, float* cached_feature, float* cached_anchor, long long* instance_id,
+                                    long long* prev_id, long long* ids_out, int* index_scratch, const float* feature,
+                                    const float* anchor, const float* cls, int batch_size, int num_anchors, int num_classes,
+                                    int num_temp, int embed_dims, int has_previous, float confidence_decay, int has_threshold,
+                                    float threshold, const int* hold, int num_hold, int* sticky, unsigned* sync_words,
+                                    const unsigned char* active, void* stream);
+
 /* Fixed-shape detection records of SparseBox3DDecoder.decode_with2d (models/detection3d/decoder.py:124-252).
  * 3D (:133-167 with squeezed classes + decode_box :23-34), one workgroup per sample:
  *   score = max_c sigmoid(cls); the num_output best anchors; re-scored by sigmoid(quality[..., 0]) (quality
@@ -634,6 +656,15 @@ int simpb_alloc_ragged(unsigned char* flag, float* sel_xy, float* depth, int* co
                        int* query_cam, const float* anchor, const float* projection_mat, int batch_size, int num_anchors,
                        int num_cams, int per_stream, float img_w, float img_h, float limit_w, float limit_l, float limit_h,
                        void* stream);
+/* The same with `active` u8 [batch_size] (device; NULL = every stream, identical to simpb_alloc_ragged): a stream with
+ * active = 0 gets no 2D slots -- flag rows 0 (forced: its anchors and matrices are not read and may hold anything), count 0,
+ * empty groups, a2q rows -1 -- and cannot raise overflow. The slot array stays "live slots first": the streams behind it
+ * move down and group_start[bs * cams] shrinks, so a paused stream costs the 2D operators nothing. */
+int simpb_alloc_ragged_active(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order, int* group_start,
+                              int* overflow, float* ref_pts2d, float* ref_depth2d, int* q2a, int* is_center, int* a2q,
+                              int* query_cam, const float* anchor, const float* projection_mat, int batch_size,
+                              int num_anchors, int num_cams, int per_stream, float img_w, float img_h, float limit_w,
+                              float limit_l, float limit_h, const unsigned char* active, void* stream);
 
 /* out[b, s, :] = src[b, q2a[b, s], :], zeros where q2a < 0: replaces
  * torch.matmul(ref_trans_matrix, instance_feature) (models/simpb_head.py:438). channels % 4 == 0. */

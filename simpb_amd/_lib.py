@@ -47,8 +47,10 @@ SIGNATURES = {
     "simpb_bank_update": ([_P] * 10 + [_I] * 5 + [_P], _I),
     "simpb_bank_update_rank": ([_P, _P] + [_I] * 4 + [_P], _I),
     "simpb_bank_update_merge": ([_P] * 13 + [_I, _P] + [_I] * 5 + [_P], _I),
+    "simpb_bank_update_merge_active": ([_P] * 13 + [_I, _P] + [_I] * 5 + [_P, _P], _I),
     "simpb_bank_cache": ([_P] * 10 + [_I] * 6 + [_F, _I, _F, _P, _I, _P, _P], _I),
     "simpb_bank_cache_streams": ([_P] * 10 + [_I] * 6 + [_F, _I, _F, _P, _I, _P, _P, _P], _I),
+    "simpb_bank_cache_streams_active": ([_P] * 10 + [_I] * 6 + [_F, _I, _F, _P, _I, _P, _P, _P, _P], _I),
     "simpb_decode3d_record": ([_P] * 6 + [_I] * 4 + [_P], _I),
     "simpb_decode2d_record": ([_P] * 6 + [_I] * 4 + [_F] * 4 + [_P], _I),
     "simpb_record2d_compact": ([_P, _LL, _P, _LL, _I, _I, _I, _P], _I),
@@ -65,6 +67,7 @@ SIGNATURES = {
     "simpb_alloc_scatter": ([_P] * 12 + [_I] * 4 + [_F] * 2 + [_P], _I),
     "simpb_alloc_static": ([_P] * 15 + [_I] * 4 + [_F] * 5 + [_P], _I),
     "simpb_alloc_ragged": ([_P] * 15 + [_I] * 4 + [_F] * 5 + [_P], _I),
+    "simpb_alloc_ragged_active": ([_P] * 15 + [_I] * 4 + [_F] * 5 + [_P, _P], _I),
     "simpb_gather_rows": ([_P] * 3 + [_I] * 4 + [_P], _I),
     "simpb_aggregate_2d_to_3d": ([_P] * 8 + [_I] * 5 + [_P], _I),
     "simpb_aggregate_2d_to_3d_alpha": ([_P] * 9 + [_I, _I, _P, _P] + [_I] * 5 + [_P], _I),

@@ -14,16 +14,28 @@ namespace {
 
 constexpr int kMaxStaticCams = 8;   // cameras of the static-capacity path (simpb_alloc_static)
 
-// ---- step 1: one thread per (batch, anchor, cam): 9 projected points -> flag, 2D ref, depth
+// ---- step 1: one thread per (batch, anchor, cam): 9 projected points -> flag, 2D ref, depth. `active` (u8 [bs], may be
+// NULL = every stream): a stream that sits this frame out gets flag 0 for every (anchor, cam) without its anchors or
+// matrices being read (they may hold anything), so steps 2-3 give it no slots.
 __global__ void alloc_project_kernel(unsigned char* __restrict__ flag, float* __restrict__ sel_xy,
                                      float* __restrict__ depth, const float* __restrict__ anchor,
                                      const float* __restrict__ proj, int bs, int A, int cams, float img_w, float img_h,
-                                     float lim_w, float lim_l, float lim_h, int* __restrict__ a2q_fill) {
+                                     float lim_w, float lim_l, float lim_h, int* __restrict__ a2q_fill,
+                                     const unsigned char* __restrict__ active) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= bs * A * cams) return;
   const int cam = idx % cams;
   const int a = (idx / cams) % A;
   const int b = idx / (cams * A);
+  if (active && !active[b]) {
+    const size_t o = ((size_t)b * cams + cam) * A + a;
+    flag[o] = 0;
+    sel_xy[2 * o] = 0.f;
+    sel_xy[2 * o + 1] = 0.f;
+    depth[o] = 0.f;
+    if (a2q_fill) a2q_fill[idx] = -1;
+    return;
+  }
   const float* an = anchor + ((size_t)b * A + a) * 11;
   const float* P = proj + ((size_t)b * cams + cam) * 16;
   const float cx = an[0], cy = an[1], cz = an[2];
@@ -353,7 +365,7 @@ extern "C" int simpb_alloc_project(unsigned char* flag, float* sel_xy, float* de
   clear_stale();
   hipLaunchKernelGGL(alloc_project_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), flag,
                      sel_xy, depth, anchor, projection_mat, batch_size, num_anchors, num_cams, img_w, img_h, limit_w,
-                     limit_l, limit_h, static_cast<int*>(nullptr));
+                     limit_l, limit_h, static_cast<int*>(nullptr), static_cast<const unsigned char*>(nullptr));
   return status();
 }
 
@@ -452,7 +464,8 @@ extern "C" int simpb_alloc_static(unsigned char* flag, float* sel_xy, float* dep
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int n = batch_size * num_anchors * num_cams;
   hipLaunchKernelGGL(alloc_project_kernel, dim3((n + 255) / 256), dim3(256), 0, s, flag, sel_xy, depth, anchor, projection_mat,
-                     batch_size, num_anchors, num_cams, img_w, img_h, limit_w, limit_l, limit_h, a2q);
+                     batch_size, num_anchors, num_cams, img_w, img_h, limit_w, limit_l, limit_h, a2q,
+                     static_cast<const unsigned char*>(nullptr));
   hipLaunchKernelGGL(alloc_compact_kernel, dim3(batch_size * num_cams), dim3(256), 0, s, count, order, flag, num_anchors);
   const int ns = batch_size * capacity;
   hipLaunchKernelGGL(alloc_scatter_kernel, dim3((ns + 255) / 256), dim3(256), 0, s, ref_pts2d, ref_depth2d, q2a, is_center, a2q,
@@ -461,11 +474,12 @@ extern "C" int simpb_alloc_static(unsigned char* flag, float* sel_xy, float* dep
   return status();
 }
 
-extern "C" int simpb_alloc_ragged(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order, int* group_start,
-                                  int* overflow, float* ref_pts2d, float* ref_depth2d, int* q2a, int* is_center, int* a2q,
-                                  int* query_cam, const float* anchor, const float* projection_mat, int batch_size,
-                                  int num_anchors, int num_cams, int per_stream, float img_w, float img_h, float limit_w,
-                                  float limit_l, float limit_h, void* stream) {
+extern "C" int simpb_alloc_ragged_active(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order,
+                                         int* group_start, int* overflow, float* ref_pts2d, float* ref_depth2d, int* q2a,
+                                         int* is_center, int* a2q, int* query_cam, const float* anchor,
+                                         const float* projection_mat, int batch_size, int num_anchors, int num_cams,
+                                         int per_stream, float img_w, float img_h, float limit_w, float limit_l, float limit_h,
+                                         const unsigned char* active, void* stream) {
   if (!flag || !sel_xy || !depth || !count || !order || !group_start || !overflow || !ref_pts2d || !ref_depth2d || !q2a ||
       !is_center || !a2q || !query_cam || !anchor || !projection_mat || batch_size <= 0 || num_anchors <= 0 ||
       num_cams <= 0 || batch_size * num_cams > kMaxRaggedGroups || per_stream <= 0 ||
@@ -475,11 +489,21 @@ extern "C" int simpb_alloc_ragged(unsigned char* flag, float* sel_xy, float* dep
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int n = batch_size * num_anchors * num_cams;
   hipLaunchKernelGGL(alloc_project_kernel, dim3((n + 255) / 256), dim3(256), 0, s, flag, sel_xy, depth, anchor, projection_mat,
-                     batch_size, num_anchors, num_cams, img_w, img_h, limit_w, limit_l, limit_h, a2q);
+                     batch_size, num_anchors, num_cams, img_w, img_h, limit_w, limit_l, limit_h, a2q, active);
   hipLaunchKernelGGL(alloc_compact_kernel, dim3(batch_size * num_cams), dim3(256), 0, s, count, order, flag, num_anchors);
   const int ns = batch_size * per_stream;
   hipLaunchKernelGGL(alloc_scatter_ragged_kernel, dim3((ns + 255) / 256), dim3(256), 0, s, ref_pts2d, ref_depth2d, q2a,
                      is_center, a2q, query_cam, count, order, flag, sel_xy, depth, batch_size, num_anchors, num_cams, per_stream,
                      img_w, img_h, group_start, overflow);
   return status();
+}
+
+extern "C" int simpb_alloc_ragged(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order, int* group_start,
+                                  int* overflow, float* ref_pts2d, float* ref_depth2d, int* q2a, int* is_center, int* a2q,
+                                  int* query_cam, const float* anchor, const float* projection_mat, int batch_size,
+                                  int num_anchors, int num_cams, int per_stream, float img_w, float img_h, float limit_w,
+                                  float limit_l, float limit_h, void* stream) {
+  return simpb_alloc_ragged_active(flag, sel_xy, depth, count, order, group_start, overflow, ref_pts2d, ref_depth2d, q2a, is_center,
+                                   a2q, query_cam, anchor, projection_mat, batch_size, num_anchors, num_cams, per_stream, img_w,
+                                   img_h, limit_w, limit_l, limit_h, nullptr, stream);
 }

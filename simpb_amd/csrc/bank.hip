@@ -117,6 +117,10 @@ __device__ __forceinline__ bool held(const int* hold, int num_hold, const int* s
   return h;
 }
 
+// `active` (u8 [bs], may be NULL = every stream): a stream with a zero sits this frame out; the kernels below leave its
+// persistent rows exactly as they found them (runner.py: a camera stream without a frame this step).
+__device__ __forceinline__ bool paused(const unsigned char* active, int b) { return active && active[b] == 0; }
+
 // ---- update (:140-149): rows [0, T) = cached, rows [T, A) = current[index], per stream under its mask; one
 // wave per output row (feature C floats + anchor 11 floats [+ embedding E floats]); the ids of masked-out streams are reset
 // (:147-149) -- unless a `hold` flag is set: then this frame (or the one decoded just before it) is going to be re-run from
@@ -133,7 +137,8 @@ __global__ __launch_bounds__(64) void bank_merge_kernel(float* __restrict__ out_
                                                         int A, int T, int C, float* __restrict__ out_e,
                                                         const float* __restrict__ cur_e, const float* __restrict__ cached_e, int E,
                                                         const int* __restrict__ hold, int num_hold,
-                                                        const int* __restrict__ sticky) {
+                                                        const int* __restrict__ sticky,
+                                                        const unsigned char* __restrict__ active) {
   const int r = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
   const bool use = mask[b] != 0;
   const float* sf;
@@ -160,7 +165,7 @@ __global__ __launch_bounds__(64) void bank_merge_kernel(float* __restrict__ out_
     for (int c = lane * 4; c < E; c += 256) *reinterpret_cast<float4*>(oe + c) = *reinterpret_cast<const float4*>(se + c);
   }
   if (lane < 11) out_a[((size_t)b * A + r) * 11 + lane] = sa[lane];
-  if (!use && instance_id && lane == 0 && !held(hold, num_hold, sticky)) instance_id[(size_t)b * A + r] = -1;
+  if (!use && instance_id && lane == 0 && !paused(active, b) && !held(hold, num_hold, sticky)) instance_id[(size_t)b * A + r] = -1;
 }
 
 // ---- cache (:152-167) + get_instance_id (:169-184) + update_instance_id (:186-196): ONE workgroup walks the
@@ -170,7 +175,8 @@ __global__ __launch_bounds__(512) void bank_cache_kernel(float* __restrict__ con
                                                          long long* __restrict__ prev_id, const float* __restrict__ cls,
                                                          int bs, int A, int C, int T, int has_prev, float decay,
                                                          int has_threshold, float threshold, const int* __restrict__ hold,
-                                                         int num_hold, int* __restrict__ sticky) {
+                                                         int num_hold, int* __restrict__ sticky,
+                                                         const unsigned char* __restrict__ active) {
   __shared__ unsigned long long key[kCap];
   __shared__ long long ids[kCap];
   __shared__ int scan[kCap];
@@ -184,6 +190,11 @@ __global__ __launch_bounds__(512) void bank_cache_kernel(float* __restrict__ con
   if (hold_back) return;  // workgroup-uniform: the frame is re-run by the caller, the state stays as it was
   long long next_id = *prev_id;
   for (int b = 0; b < bs; ++b) {
+    if (paused(active, b)) {   // workgroup-uniform: no fresh ids, nothing of its state rewritten, its cls never read
+      for (int a = tid; a < A; a += 512) ids_out[(size_t)b * A + a] = -1;
+      simpb::stores_retired();   // store_fence.h: the next stream's loads meet no store in flight
+      continue;
+    }
     // scores: sigmoid of the best class; tracked instances keep max(decayed previous, new) (:157-162)
     for (int a = tid; a < kCap; a += 512) {
       unsigned long long kv = 0ull;
@@ -248,7 +259,17 @@ __global__ __launch_bounds__(512) void bank_cache_kernel(float* __restrict__ con
 // workgroup 0 advances behind the meeting). All bs workgroups are resident at once (bs <= 64 workgroups of 512 threads on 256
 // CUs), every one of them arrives before it waits, and the wait is bounded (a launch that could not be co-scheduled would
 // fall through after ~2^22 polls instead of hanging). prev_id is read by everyone in front of the meeting and written by the
-// last stream's workgroup behind it.
+// last stream's workgroup behind it. The workgroup of a paused stream (`active`) takes part in all of that -- it arrives, it
+// writes prev_id when it is the last one, with a total of 0 -- but ranks nothing and rewrites nothing of its own, and the
+// streams behind it do not count its rows (nor read its cls).
+__device__ __forceinline__ void meet_streams(unsigned* sync, unsigned epoch, int bs) {
+  __hip_atomic_fetch_add(&sync[0], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned target = (epoch + 1u) * (unsigned)bs;
+  for (int spin = 0; spin < (1 << 22); ++spin) {
+    if ((int)(__hip_atomic_load(&sync[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0) break;
+    __builtin_amdgcn_s_sleep(2);
+  }
+}
 __global__ __launch_bounds__(512) void bank_cache_streams_kernel(float* __restrict__ conf, int* __restrict__ index,
                                                                  long long* __restrict__ ids_out,
                                                                  long long* __restrict__ instance_id,
@@ -256,7 +277,8 @@ __global__ __launch_bounds__(512) void bank_cache_streams_kernel(float* __restri
                                                                  int bs, int A, int C, int T, int has_prev, float decay,
                                                                  int has_threshold, float threshold,
                                                                  const int* __restrict__ hold, int num_hold,
-                                                                 int* __restrict__ sticky, unsigned* __restrict__ sync) {
+                                                                 int* __restrict__ sticky, unsigned* __restrict__ sync,
+                                                                 const unsigned char* __restrict__ active) {
   __shared__ unsigned long long key[kCap];
   __shared__ long long ids[kCap];
   __shared__ int scan[kCap];
@@ -275,12 +297,25 @@ __global__ __launch_bounds__(512) void bank_cache_streams_kernel(float* __restri
   // fresh instances of the streams in front of this one
   int mine = 0;
   for (int i = tid; i < b * A; i += 512) {
+    if (active && active[i / A] == 0) continue;
     const long long id = instance_id ? instance_id[i] : -1;
     if (id < 0 && (!has_threshold || sigmoidf(row_max(cls + (size_t)i * C, C)) >= threshold)) ++mine;
   }
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) mine += __shfl_xor(mine, m);
   if ((tid & 63) == 0) s_red[tid >> 6] = mine;
+  if (paused(active, b)) {   // workgroup-uniform
+    __syncthreads();
+    if (tid == 0) {
+      int f = 0;
+      for (int w = 0; w < 8; ++w) f += s_red[w];
+      meet_streams(sync, epoch, bs);
+      if (b == bs - 1) *prev_id = first_id + f;
+      if (b == 0) __hip_atomic_store(&sync[1], epoch + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    for (int a = tid; a < A; a += 512) ids_out[(size_t)b * A + a] = -1;
+    return;
+  }
   // this stream's scores and ranking (as the serial kernel)
   for (int a = tid; a < kCap; a += 512) {
     unsigned long long kv = 0ull;
@@ -327,14 +362,7 @@ __global__ __launch_bounds__(512) void bank_cache_streams_kernel(float* __restri
   }
   __syncthreads();
   // ---- the meeting: every stream has read what it needs of the others' instance_id and of prev_id
-  if (tid == 0) {
-    __hip_atomic_fetch_add(&sync[0], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned target = (epoch + 1u) * (unsigned)bs;
-    for (int spin = 0; spin < (1 << 22); ++spin) {
-      if ((int)(__hip_atomic_load(&sync[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0) break;
-      __builtin_amdgcn_s_sleep(2);
-    }
-  }
+  if (tid == 0) meet_streams(sync, epoch, bs);
   __syncthreads();
   for (int r = tid; r < T; r += 512) {
     conf[(size_t)b * T + r] = key_value(key[r]);
@@ -355,8 +383,10 @@ __global__ __launch_bounds__(64) void bank_gather_kernel(float* __restrict__ out
                                                          const float* __restrict__ src_f, const float* __restrict__ src_a,
                                                          const int* __restrict__ index, int A, int T, int C,
                                                          const int* __restrict__ hold, int num_hold,
-                                                         const int* __restrict__ sticky) {
+                                                         const int* __restrict__ sticky,
+                                                         const unsigned char* __restrict__ active) {
   const int r = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  if (paused(active, b)) return;   // its cached rows stay; its index_scratch row was not written
   if (held(hold, num_hold, sticky)) return;   // (sticky: as bank_cache_kernel left it one launch earlier)
   const int src = index[(size_t)b * T + r];
   const float* sf = src_f + ((size_t)b * A + src) * C;
@@ -392,12 +422,12 @@ extern "C" int simpb_bank_update_rank(int* index_scratch, const float* cls, int 
   return simpb_check_launch();
 }
 
-extern "C" int simpb_bank_update_merge(float* feature_out, float* anchor_out, float* embed_out, long long* instance_id,
-                                       const int* index, const float* feature, const float* anchor, const float* embed,
-                                       const float* cached_feature, const float* cached_anchor, const float* cached_embed,
-                                       const unsigned char* mask, const int* hold, int num_hold, const int* sticky,
-                                       int batch_size, int num_anchors, int num_temp, int embed_dims, int pos_embed_dims,
-                                       void* stream) {
+extern "C" int simpb_bank_update_merge_active(float* feature_out, float* anchor_out, float* embed_out, long long* instance_id,
+                                              const int* index, const float* feature, const float* anchor, const float* embed,
+                                              const float* cached_feature, const float* cached_anchor,
+                                              const float* cached_embed, const unsigned char* mask, const int* hold,
+                                              int num_hold, const int* sticky, int batch_size, int num_anchors, int num_temp,
+                                              int embed_dims, int pos_embed_dims, const unsigned char* active, void* stream) {
   if (!feature_out || !anchor_out || !index || !feature || !anchor || !cached_feature || !cached_anchor || !mask ||
       batch_size <= 0 || num_anchors <= 0 || num_anchors > kCap || num_temp <= 0 || num_temp >= num_anchors || embed_dims <= 0 ||
       (embed_dims & 3) || batch_size > 65535 || num_hold < 0 || (num_hold > 0 && !hold))
@@ -406,8 +436,19 @@ extern "C" int simpb_bank_update_merge(float* feature_out, float* anchor_out, fl
   (void)hipGetLastError();
   hipLaunchKernelGGL(bank_merge_kernel, dim3(num_anchors, batch_size), dim3(64), 0, static_cast<hipStream_t>(stream), feature_out,
                      anchor_out, instance_id, feature, anchor, cached_feature, cached_anchor, index, mask, num_anchors, num_temp,
-                     embed_dims, embed_out, embed, cached_embed, pos_embed_dims, hold, num_hold, sticky);
+                     embed_dims, embed_out, embed, cached_embed, pos_embed_dims, hold, num_hold, sticky, active);
   return simpb_check_launch();
+}
+
+extern "C" int simpb_bank_update_merge(float* feature_out, float* anchor_out, float* embed_out, long long* instance_id,
+                                       const int* index, const float* feature, const float* anchor, const float* embed,
+                                       const float* cached_feature, const float* cached_anchor, const float* cached_embed,
+                                       const unsigned char* mask, const int* hold, int num_hold, const int* sticky,
+                                       int batch_size, int num_anchors, int num_temp, int embed_dims, int pos_embed_dims,
+                                       void* stream) {
+  return simpb_bank_update_merge_active(feature_out, anchor_out, embed_out, instance_id, index, feature, anchor, embed,
+                                        cached_feature, cached_anchor, cached_embed, mask, hold, num_hold, sticky, batch_size,
+                                        num_anchors, num_temp, embed_dims, pos_embed_dims, nullptr, stream);
 }
 
 extern "C" int simpb_bank_update(float* feature_out, float* anchor_out, long long* instance_id, int* index_scratch,
@@ -425,7 +466,8 @@ static int bank_cache_launch(float* confidence, float* cached_feature, float* ca
                              long long* prev_id, long long* ids_out, int* index_scratch, const float* feature,
                              const float* anchor, const float* cls, int batch_size, int num_anchors, int num_classes,
                              int num_temp, int embed_dims, int has_previous, float confidence_decay, int has_threshold,
-                             float threshold, const int* hold, int num_hold, int* sticky, unsigned* sync, void* stream) {
+                             float threshold, const int* hold, int num_hold, int* sticky, unsigned* sync,
+                             const unsigned char* active, void* stream) {
   if (!confidence || !cached_feature || !cached_anchor || !prev_id || !ids_out || !index_scratch || !feature || !anchor ||
       !cls || batch_size <= 0 || num_anchors <= 0 || num_anchors > kCap || num_classes <= 0 || num_temp <= 0 ||
       num_temp > num_anchors || embed_dims <= 0 || (embed_dims & 3) || batch_size > 65535 || num_hold < 0 ||
@@ -436,13 +478,13 @@ static int bank_cache_launch(float* confidence, float* cached_feature, float* ca
   if (sync && batch_size > 1 && batch_size <= 64)
     hipLaunchKernelGGL(bank_cache_streams_kernel, dim3(batch_size), dim3(512), 0, s, confidence, index_scratch, ids_out, instance_id,
                        prev_id, cls, batch_size, num_anchors, num_classes, num_temp, has_previous, confidence_decay, has_threshold,
-                       threshold, hold, num_hold, sticky, sync);
+                       threshold, hold, num_hold, sticky, sync, active);
   else
     hipLaunchKernelGGL(bank_cache_kernel, dim3(1), dim3(512), 0, s, confidence, index_scratch, ids_out, instance_id, prev_id, cls,
                        batch_size, num_anchors, num_classes, num_temp, has_previous, confidence_decay, has_threshold, threshold, hold,
-                       num_hold, sticky);
+                       num_hold, sticky, active);
   hipLaunchKernelGGL(bank_gather_kernel, dim3(num_temp, batch_size), dim3(64), 0, s, cached_feature, cached_anchor, feature,
-                     anchor, index_scratch, num_anchors, num_temp, embed_dims, hold, num_hold, sticky);
+                     anchor, index_scratch, num_anchors, num_temp, embed_dims, hold, num_hold, sticky, active);
   return simpb_check_launch();
 }
 
@@ -453,7 +495,7 @@ extern "C" int simpb_bank_cache(float* confidence, float* cached_feature, float*
                                 float threshold, const int* hold, int num_hold, int* sticky, void* stream) {
   return bank_cache_launch(confidence, cached_feature, cached_anchor, instance_id, prev_id, ids_out, index_scratch, feature, anchor,
                            cls, batch_size, num_anchors, num_classes, num_temp, embed_dims, has_previous, confidence_decay,
-                           has_threshold, threshold, hold, num_hold, sticky, nullptr, stream);
+                           has_threshold, threshold, hold, num_hold, sticky, nullptr, nullptr, stream);
 }
 
 extern "C" int simpb_bank_cache_streams(float* confidence, float* cached_feature, float* cached_anchor, long long* instance_id,
@@ -464,5 +506,17 @@ extern "C" int simpb_bank_cache_streams(float* confidence, float* cached_feature
                                         unsigned* sync_words, void* stream) {
   return bank_cache_launch(confidence, cached_feature, cached_anchor, instance_id, prev_id, ids_out, index_scratch, feature, anchor,
                            cls, batch_size, num_anchors, num_classes, num_temp, embed_dims, has_previous, confidence_decay,
-                           has_threshold, threshold, hold, num_hold, sticky, sync_words, stream);
+                           has_threshold, threshold, hold, num_hold, sticky, sync_words, nullptr, stream);
+}
+
+extern "C" int simpb_bank_cache_streams_active(float* confidence, float* cached_feature, float* cached_anchor,
+                                               long long* instance_id, long long* prev_id, long long* ids_out,
+                                               int* index_scratch, const float* feature, const float* anchor, const float* cls,
+                                               int batch_size, int num_anchors, int num_classes, int num_temp, int embed_dims,
+                                               int has_previous, float confidence_decay, int has_threshold, float threshold,
+                                               const int* hold, int num_hold, int* sticky, unsigned* sync_words,
+                                               const unsigned char* active, void* stream) {
+  return bank_cache_launch(confidence, cached_feature, cached_anchor, instance_id, prev_id, ids_out, index_scratch, feature, anchor,
+                           cls, batch_size, num_anchors, num_classes, num_temp, embed_dims, has_previous, confidence_decay,
+                           has_threshold, threshold, hold, num_hold, sticky, sync_words, active, stream);
 }

@@ -54,12 +54,14 @@ class DynamicQueryAllocation(nn.Module):
         self.limit_corners_num = limit_corners_num
         self.last = None
 
-    def forward(self, anchor3d, metas, dense=True, capacity=None, overflow_out=None, independent=False):
+    def forward(self, anchor3d, metas, dense=True, capacity=None, overflow_out=None, independent=False, active=None):
         """Returns the reference's 8-tuple (allocation.py:144). With dense=True the two one-hot
         matrices are materialised from the index form; with dense=False their places hold None
         and callers use `self.last` (an Allocation2D) instead."""
+        if active is not None and not independent:
+            raise ValueError("an activity mask needs the independent-streams layout")
         if independent:
-            alloc, ref_pts2d, ref_depth2d = self.allocate_independent(anchor3d, metas, capacity, overflow_out)
+            alloc, ref_pts2d, ref_depth2d = self.allocate_independent(anchor3d, metas, capacity, overflow_out, active)
             if dense:
                 raise ValueError("independent streams: index form only (dense=False)")
             return ref_pts2d, ref_depth2d, None, None, None, None, None, None
@@ -67,10 +69,11 @@ class DynamicQueryAllocation(nn.Module):
         trans, center = alloc.dense() if dense else (None, None)
         return ref_pts2d, ref_depth2d, trans_mask, trans_shape, trans, center, alloc.query_groups, None
 
-    def allocate_independent(self, anchor3d, metas, capacity, overflow_out=None):
+    def allocate_independent(self, anchor3d, metas, capacity, overflow_out=None, active=None):
         """The batch as `bs` independent camera streams: every stream keeps the 2D set a batch of one gives
         it, at most `capacity` slots each; one flat slot array [1, bs * capacity] over bs * cams groups, live slots first
-        (Allocation2D.streams = bs). Static shapes only."""
+        (Allocation2D.streams = bs). Static shapes only. active (u8 [bs] on the device, or None): a stream with 0 sits the
+        frame out and gets no slots; the streams behind it move down."""
         if self.training:
             raise NotImplementedError("training-time corner sampling (allocation.py:85-87) is not on this path")
         if capacity is None:
@@ -88,6 +91,9 @@ class DynamicQueryAllocation(nn.Module):
             wh = tuple(int(v) for v in metas["image_wh"][0, 0].tolist())
         img_w, img_h = float(wh[0]), float(wh[1])
         dev = anchor3d.device
+        if active is not None and (active.dtype != torch.uint8 or active.numel() != bs or active.device != dev
+                                   or not active.is_contiguous()):
+            raise ValueError("active must be contiguous u8 [bs] on the anchors' device")
         lw, ll, lh = (float(v) for v in self.limit_anchor_size)
         slots = bs * int(capacity)
         flag = torch.empty(bs, cams, num_anchor, dtype=torch.uint8, device=dev)
@@ -110,11 +116,11 @@ class DynamicQueryAllocation(nn.Module):
         out.query_groups = None
         out.num_anchor = num_anchor
         out.overflow = overflow
-        _lib.check(lib.simpb_alloc_ragged(_ptr(flag), _ptr(sel_xy), _ptr(depth), _ptr(out.count), _ptr(order),
-                                          _ptr(out.group_start), _ptr(overflow), _ptr(ref_pts2d), _ptr(ref_depth2d),
-                                          _ptr(out.q2a), _ptr(out.is_center), _ptr(out.a2q), _ptr(out.query_cam), _ptr(anchor3d),
-                                          _ptr(proj), bs, num_anchor, cams, int(capacity), img_w, img_h, lw, ll, lh, _stream()),
-                   "simpb_alloc_ragged")
+        _lib.check(lib.simpb_alloc_ragged_active(
+            _ptr(flag), _ptr(sel_xy), _ptr(depth), _ptr(out.count), _ptr(order), _ptr(out.group_start), _ptr(overflow),
+            _ptr(ref_pts2d), _ptr(ref_depth2d), _ptr(out.q2a), _ptr(out.is_center), _ptr(out.a2q), _ptr(out.query_cam),
+            _ptr(anchor3d), _ptr(proj), bs, num_anchor, cams, int(capacity), img_w, img_h, lw, ll, lh,
+            _ptr(active) if active is not None else None, _stream()), "simpb_alloc_ragged")
         self.last = out
         return out, ref_pts2d, ref_depth2d
 

@@ -254,6 +254,19 @@ class SimPBHead(BaseModule):
         if self.sampler is not None and self.sampler.dn_metas is not None:
             self.sampler.dn_metas = None  # :333-334; never set in eval
 
+        active = metas.get("active")
+        if active is not None:
+            # u8 [bs] on the device (static address): streams with 0 sit this frame out -- no 2D slots, no bank commit, no
+            # track ids (csrc/alloc.hip, csrc/bank.hip `active`). Their rows still run through the 3D side (static shapes).
+            if split:
+                raise NotImplementedError("forward_split is the single-stream form: a paused stream is a step not taken")
+            if not (self.independent_streams and batch_size > 1 and self.static_capacity is not None):
+                raise ValueError("metas['active'] needs independent_streams and a static capacity")
+            if (not torch.is_tensor(active) or active.dtype != torch.uint8 or active.numel() != batch_size
+                    or not active.is_cuda or not active.is_contiguous()):
+                raise ValueError("metas['active'] must be a contiguous u8 [bs] tensor on the device")
+            if not self.instance_bank._fusable(active):
+                raise ValueError("metas['active'] needs the fused bank route (static state, routes.fused_bank)")
         if split:
             if "time_interval" not in metas or self.static_capacity is None:
                 raise ValueError("forward_split needs metas['time_interval'] (f32 [bs]) and a static capacity")
@@ -340,7 +353,7 @@ class SimPBHead(BaseModule):
                 ragged = self.independent_streams and batch_size > 1
                 anchor2d, ref_depth2d, ref_trans_mask, ref_trans_shape, _, _, ref_query_groups, _ = layer(
                     anchor, metas, dense=False, capacity=cap,
-                    overflow_out=overflow[k:k + 1] if overflow is not None else None, independent=ragged)
+                    overflow_out=overflow[k:k + 1] if overflow is not None else None, independent=ragged, active=active)
                 alloc = layer.last
                 if ragged:   # one flat slot array over batch_size * num_cams groups: the 2D operators run as a batch of one
                     groups = batch_size * self.num_cams
@@ -429,9 +442,10 @@ class SimPBHead(BaseModule):
                         temp_anchor_embed = self.anchor_encoder(temp_anchor) if temp_anchor is not None else None
                     if rank is not None:
                         instance_feature, anchor, merged_embed = self.instance_bank.update(
-                            instance_feature, anchor, cls, rank=rank, embed=(cur_embed, temp_anchor_embed), hold=hold, sticky=sticky)
+                            instance_feature, anchor, cls, rank=rank, embed=(cur_embed, temp_anchor_embed), hold=hold, sticky=sticky,
+                            active=active)
                     else:
-                        instance_feature, anchor = self.instance_bank.update(instance_feature, anchor, cls)
+                        instance_feature, anchor = self.instance_bank.update(instance_feature, anchor, cls, active=active)
                 if merged_embed is not None:
                     anchor_embed = dense.report(self.anchor_encoder, merged_embed)
                 elif i != last:
@@ -450,7 +464,7 @@ class SimPBHead(BaseModule):
             "alloc_list": alloc_list, "overflow": overflow,
         }
         ids = self.instance_bank.cache_and_assign_ids(instance_feature, anchor, cls, metas, self.decoder.score_threshold,
-                                                      hold=hold, sticky=sticky)
+                                                      hold=hold, sticky=sticky, active=active)
         if ids is None:
             self.instance_bank.cache(instance_feature, anchor, cls, metas, feature_maps)
             ids = self.instance_bank.get_instance_id(cls, anchor, self.decoder.score_threshold)

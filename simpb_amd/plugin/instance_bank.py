@@ -190,11 +190,12 @@ class InstanceBank(nn.Module):
                                                      _stream()), "simpb_bank_update_rank")
         return index
 
-    def update(self, instance_feature, anchor, confidence, rank=None, embed=None, hold=None, sticky=None):
+    def update(self, instance_feature, anchor, confidence, rank=None, embed=None, hold=None, sticky=None, active=None):
         """Replace the 900 current instances by [cached 600 | best 300 current] for streams whose
         history is valid (instance_bank.py:121-150). rank: rank_current()'s result, if the caller took it early. embed =
         (embedding of `anchor`, embedding of the cached anchors get() returned): the merged set's embedding is then
-        returned as a third value (rows follow their anchors), or None where the fused route does not apply."""
+        returned as a third value (rows follow their anchors), or None where the fused route does not apply. active (u8 [bs]
+        on the device, fused route only): a stream with 0 sits the frame out and keeps its track ids whatever its mask."""
         if self.cached_feature is None:
             return (instance_feature, anchor) if embed is None else (instance_feature, anchor, embed[0])
         if instance_feature.shape[1] > self.num_anchor:
@@ -215,17 +216,19 @@ class InstanceBank(nn.Module):
                 cur_e, cached_e = embed[0].contiguous().float(), embed[1].contiguous().float()
                 e_dim = cur_e.shape[-1]
                 out_e = torch.empty(bs, a, e_dim, device=dev)
-            _lib.check(_lib.lib().simpb_bank_update_merge(
+            _lib.check(_lib.lib().simpb_bank_update_merge_active(
                 _ptr(out_f), _ptr(out_a), _ptr(out_e) if out_e is not None else None, _ptr(ids) if ids is not None else None,
                 _ptr(rank), _ptr(instance_feature.contiguous().float()), _ptr(anchor.contiguous().float()),
                 _ptr(cur_e) if cur_e is not None else None, _ptr(self.cached_feature.contiguous()),
                 _ptr(self.cached_anchor.contiguous()), _ptr(cached_e) if cached_e is not None else None, _ptr(self.mask),
                 _ptr(hold) if hold is not None else None, 0 if hold is None else hold.numel(),
-                _ptr(sticky) if sticky is not None else None, bs, a, t, c, e_dim, _stream()),
-                "simpb_bank_update_merge")
+                _ptr(sticky) if sticky is not None else None, bs, a, t, c, e_dim,
+                _ptr(active) if active is not None else None, _stream()), "simpb_bank_update_merge")
             if ids is None and self.instance_id is not None:
                 self._keep("instance_id", self.instance_id.masked_fill(~self.mask[:, None], -1))
             return (out_f, out_a) if embed is None else (out_f, out_a, out_e)
+        if active is not None:
+            raise ValueError("an activity mask needs the fused bank route (static state, routes.fused_bank)")
         fresh = self.num_anchor - self.num_temp_instances
         _, (best_feature, best_anchor) = topk(confidence.max(dim=-1).values, fresh, instance_feature, anchor)
         merged_feature = torch.cat([self.cached_feature, best_feature], dim=1)
@@ -263,12 +266,16 @@ class InstanceBank(nn.Module):
                 and self.num_anchor <= 1024 and 0 < self.num_temp_instances < self.num_anchor
                 and self.embed_dims % 4 == 0)
 
-    def cache_and_assign_ids(self, instance_feature, anchor, confidence, metas=None, threshold=None, hold=None, sticky=None):
+    def cache_and_assign_ids(self, instance_feature, anchor, confidence, metas=None, threshold=None, hold=None, sticky=None,
+                             active=None):
         """cache() followed by get_instance_id() (simpb_head.py:744-747) on the persistent state, as two
         launches (csrc/bank.hip). Returns the instance ids, or None when the fused route does not apply
         (the caller then runs the two methods). `hold` (i32 flags on the device): when any is set the launches write
-        nothing, i.e. the persistent state stays as the frame found it (an overflowed frame is re-run: runner.py)."""
+        nothing, i.e. the persistent state stays as the frame found it (an overflowed frame is re-run: runner.py). active
+        (u8 [bs] on the device): a stream with 0 keeps its state rows, gets ids -1 and takes no fresh ids."""
         if not self._fusable(instance_feature) or instance_feature.shape[1] != self.num_anchor:
+            if active is not None:
+                raise ValueError("an activity mask needs the fused bank route (static state, routes.fused_bank)")
             return None
         st = self._static
         bs, a, c = instance_feature.shape
@@ -279,13 +286,14 @@ class InstanceBank(nn.Module):
         has_prev = self.confidence is not None
         # a batch of streams: one workgroup per stream (they meet once inside the launch); a batch of one: the serial kernel
         sync = self._sync if (bs > 1 and routes.R.bank_cache_per_stream and getattr(self, "_sync", None) is not None) else None
-        _lib.check(_lib.lib().simpb_bank_cache_streams(
+        _lib.check(_lib.lib().simpb_bank_cache_streams_active(
             _ptr(st["confidence"]), _ptr(st["cached_feature"]), _ptr(st["cached_anchor"]), _ptr(st["instance_id"]),
             _ptr(st["prev_id"]), _ptr(ids_out), _ptr(scratch), _ptr(instance_feature.detach().contiguous().float()),
             _ptr(anchor.detach().contiguous().float()), _ptr(cls), bs, a, cls.shape[-1], t, c, 1 if has_prev else 0,
             float(self.confidence_decay), 0 if threshold is None else 1, 0.0 if threshold is None else float(threshold),
             _ptr(hold) if hold is not None else None, 0 if hold is None else hold.numel(),
-            _ptr(sticky) if sticky is not None else None, _ptr(sync) if sync is not None else None, _stream()), "simpb_bank_cache")
+            _ptr(sticky) if sticky is not None else None, _ptr(sync) if sync is not None else None,
+            _ptr(active) if active is not None else None, _stream()), "simpb_bank_cache")
         self.metas = metas
         self.confidence, self.cached_feature, self.cached_anchor = st["confidence"], st["cached_feature"], st["cached_anchor"]
         self.instance_id, self.prev_id = st["instance_id"], st["prev_id"]

@@ -28,6 +28,36 @@ from .plugin.detection3d import SparseBox3DDecoder
 CAPTURE_MODE = "thread_local"
 
 
+def stream_motion(metas, prev):
+    """Per stream, what the bank needs to bring its cached anchors into this frame (instance_bank.py:90-97): T_temp2cur =
+    inv(T_global of this frame) @ T_global of the stream's previous frame (f32 [bs, 4, 4]) and the time between the two
+    (f32 [bs]). Host metadata only."""
+    t = np.stack([np.asarray(m["T_global_inv"] @ p["T_global"], np.float32)
+                  for m, p in zip(metas["img_metas"], prev["img_metas"])])
+    dt = np.array([float(m["timestamp"] - p["timestamp"]) for m, p in zip(metas["img_metas"], prev["img_metas"])], np.float32)
+    return t, dt
+
+
+def carry_inactive_metas(prev, metas, active):
+    """The metas a frame is staged with when some streams of the batch sit it out. prev: dict(img_metas, projection_mat) as
+    staged for the previous frame, i.e. every stream's LAST ACTIVE entries; metas: this frame's; active: one bool per stream.
+    Returns a copy of `metas` in which an inactive stream's img_metas entry and projection_mat row are prev's. Staged against
+    `prev` (stream_motion) such a stream gets dt = 0 and T_temp2cur = inv(T) @ T, and since the result is the next frame's
+    `prev`, a stream that resumes measures its time step and ego-motion from its own last frame, not from the batch's last
+    step. Pure host function: nothing of `prev` or `metas` is modified."""
+    active = [bool(a) for a in active]
+    if len(active) != len(metas["img_metas"]) or len(active) != len(prev["img_metas"]):
+        raise ValueError(f"active has {len(active)} entries for {len(metas['img_metas'])} streams")
+    out = dict(metas)
+    out["img_metas"] = [m if a else p for a, m, p in zip(active, metas["img_metas"], prev["img_metas"])]
+    proj = metas["projection_mat"].detach().cpu().clone()
+    for i, a in enumerate(active):
+        if not a:
+            proj[i] = prev["projection_mat"][i]
+    out["projection_mat"] = proj
+    return out
+
+
 class FrameRunner:
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
                  raw_input=None, img_norm_cfg=None):
@@ -65,6 +95,12 @@ class FrameRunner:
         self.pin_t = torch.zeros(batch_size, 4, 4).pin_memory()
         self.pin_dt = torch.zeros(batch_size).pin_memory()
         self.pin_proj = torch.zeros(batch_size, cams, 4, 4).pin_memory()
+        # per-stream activity (step(..., active=)): staged like proj / t_buf once a caller has paused a stream; until then
+        # the head is called without it and nothing here is touched (see _activity)
+        self.active_buf = torch.ones(batch_size, dtype=torch.uint8, device=dev)
+        self.pin_active = torch.ones(batch_size, dtype=torch.uint8).pin_memory()
+        self.masked = False                 # True from the first frame with a paused stream on: the graphs read active_buf
+        self.last_active = (True,) * batch_size   # mask of the frame last returned
         self.head.instance_bank.enable_static(batch_size, dev)
         self.head.static_capacity = self.capacity
         self.prev_metas = None
@@ -106,24 +142,74 @@ class FrameRunner:
     def _extract(self, img, raw):
         return self.model.extract_feat(raw, raw_plan=self.plan) if raw is not None else self.model.extract_feat(img)
 
-    def _stage(self, img, metas):
-        """Copy this frame's inputs into the static device buffers (a few small async copies)."""
-        (self.img if self.raw is None else self.raw).copy_(img, non_blocking=True)
+    SUPPORTS_PAUSE = True
+
+    def _activity(self, active, cold):
+        """step / launch's `active` -> None (every stream takes part: today's path) or a tuple of bs bools with a False."""
+        if active is None:
+            return None
+        mask = tuple(bool(a) for a in active)
+        if len(mask) != self.bs:
+            raise ValueError(f"active has {len(mask)} entries for {self.bs} streams")
+        if all(mask):
+            return None
+        if not self.SUPPORTS_PAUSE:
+            raise NotImplementedError(f"{type(self).__name__} is the single-stream form: a paused stream is a step not taken")
+        if not any(mask):
+            raise ValueError("no stream is active: a frame nobody takes part in is a step not taken")
+        if not self.independent:
+            raise ValueError("pausing a stream needs independent_streams=True (the reference's batch pads the camera groups "
+                             "to the max over the batch: its streams are not independent)")
+        if cold:
+            raise ValueError("every stream takes part in the cold frame (a batch-wide dataflow without history)")
+        return mask
+
+    def _carry(self, prev, metas, mask):
+        """This frame's metas with the paused streams' entries held at their last active frame (whose projection matrices
+        are what the pinned staging buffer still holds); the first paused frame also switches the runner to masked graphs."""
+        if not self.masked:
+            torch.cuda.synchronize(self.device)   # nothing in flight replays a graph that does not read the mask
+            self._drop_graphs()
+            self.masked = True
+        return carry_inactive_metas(dict(img_metas=prev["img_metas"], projection_mat=self.pin_proj), metas, mask)
+
+    def _stage_motion(self, metas, prev, mask):
+        """Projection matrices, activity mask, ego-motion and time step into the pinned buffers and on to the device (on the
+        current stream)."""
         self.pin_proj.copy_(metas["projection_mat"] if not metas["projection_mat"].is_cuda else metas["projection_mat"].cpu())
         self.proj.copy_(self.pin_proj, non_blocking=True)
-        if self.prev_metas is not None:
-            for i, m in enumerate(metas["img_metas"]):
-                t = m["T_global_inv"] @ self.prev_metas["img_metas"][i]["T_global"]  # instance_bank.py:90-97
-                self.pin_t[i] = torch.from_numpy(np.asarray(t, np.float32))
-                self.pin_dt[i] = float(m["timestamp"] - self.prev_metas["img_metas"][i]["timestamp"])
+        if self.masked:
+            self.pin_active.copy_(torch.tensor(mask if mask is not None else (True,) * self.bs, dtype=torch.uint8))
+            self.active_buf.copy_(self.pin_active, non_blocking=True)
+        if prev is not None:
+            t, dt = stream_motion(metas, prev)
+            self.pin_t.copy_(torch.from_numpy(t))
+            self.pin_dt.copy_(torch.from_numpy(dt))
             self.t_buf.copy_(self.pin_t, non_blocking=True)
             self.dt_buf.copy_(self.pin_dt, non_blocking=True)
+
+    def _stage(self, img, metas, mask=None):
+        """Copy this frame's inputs into the static device buffers (a few small async copies)."""
+        (self.img if self.raw is None else self.raw).copy_(img, non_blocking=True)
+        self._stage_motion(metas, self.prev_metas, mask)
 
     def _device_metas(self, metas):
         out = dict(projection_mat=self.proj, image_wh=self.wh, image_wh_host=self.wh_host, img_metas=metas["img_metas"])
         if self.prev_metas is not None:
             out["bank_inputs"] = (self.t_buf, self.dt_buf)
+        if self.masked:
+            out["active"] = self.active_buf
         return out
+
+    def _results(self, rec3d, rec2d, mask):
+        self.last_active = mask if mask is not None else (True,) * self.bs
+        rec3d, rec2d = rec3d.numpy(), rec2d.numpy()
+        if mask is None:
+            results = SparseBox3DDecoder.decode_static_host(rec3d, rec2d, self.head.num_cams, self.independent)
+            return [{"img_bbox": r} for r in results]
+        # independent streams: each record is a batch of one; a paused stream's rows are unspecified and are not decoded
+        one = lambda i: SparseBox3DDecoder.decode_static_host(rec3d[i:i + 1], rec2d[i:i + 1], self.head.num_cams)[0]  # noqa: E731
+        return [{"img_bbox": one(i)} if a else None for i, a in enumerate(mask)]
 
     def _frame(self, dmetas, aug_config):
         """The device part of one frame; every tensor it returns has a fixed shape."""
@@ -169,15 +255,23 @@ class FrameRunner:
 
     # ------------------------------------------------------------------ public
     @torch.no_grad()
-    def step(self, img, metas, force_eager=False):
+    def step(self, img, metas, force_eager=False, active=None):
         """One frame for all streams: img f32 [bs, cams, 3, H, W] (device; u8 [bs, cams, Hs, Ws, 3] with raw_input), metas as the reference's
         test pipeline collects them (projection_mat, timestamp, img_metas with T_global/T_global_inv/
-        aug_config). Returns the reference's list of {'img_bbox': {...}} (simpb_head.py:1089-1123)."""
+        aug_config). Returns the reference's list of {'img_bbox': {...}} (simpb_head.py:1089-1123).
+
+        active (independent_streams only): one bool per stream; a stream with False has no frame this step. Its bank, its
+        confidences and its track ids stay as they are, its rows of `img` and `metas` are ignored (they may hold anything),
+        its place in the returned list holds None, and when it resumes its time step and ego-motion are measured from its
+        own last frame. None or all True: every stream takes part."""
+        mask = self._activity(active, self.prev_metas is None)
+        if mask is not None:
+            metas = self._carry(self.prev_metas, metas, mask)
         aug = metas["img_metas"][0]["aug_config"]
         if self.raw is not None:
             self._check_frames(img)
             self._ensure_plan(metas)
-        self._stage(img, metas)
+        self._stage(img, metas, mask)
         dmetas = self._device_metas(metas)
         warm = self.prev_metas is not None
         if warm and self.use_graph and not force_eager and self.graph is None and self.warm_frames >= 1:
@@ -207,8 +301,7 @@ class FrameRunner:
         self.last_rec3d, self.last_rec2d = rec[0], rec[1]
         self.prev_metas = dict(img_metas=metas["img_metas"])
         self.head.instance_bank.metas = self.prev_metas
-        results = SparseBox3DDecoder.decode_static_host(rec3d.numpy(), rec2d.numpy(), self.head.num_cams, self.independent)
-        return [{"img_bbox": r} for r in results]
+        return self._results(rec3d, rec2d, mask)
 
 
 class PipelinedRunner(FrameRunner):
@@ -340,21 +433,13 @@ class PipelinedRunner(FrameRunner):
             done.record(self.s_head)
         return done
 
-    def _stage_head_inputs(self, metas, prev):
-        """Per-frame decoder inputs (projection matrices, ego-motion, time step) of a frame; prev = the metas of the
-        frame before it (None for a cold frame)."""
+    def _stage_head_inputs(self, metas, prev, mask=None):
+        """Per-frame decoder inputs (projection matrices, activity mask, ego-motion, time step) of a frame; prev = the metas
+        of the frame before it (None for a cold frame)."""
         if self.staged is not None:
             self.staged.synchronize()   # the previous frame's copies out of the pinned buffers (long done in practice)
         with torch.cuda.stream(self.s_head):
-            self.pin_proj.copy_(metas["projection_mat"] if not metas["projection_mat"].is_cuda else metas["projection_mat"].cpu())
-            self.proj.copy_(self.pin_proj, non_blocking=True)
-            if prev is not None:
-                for i, m in enumerate(metas["img_metas"]):
-                    t = m["T_global_inv"] @ prev["img_metas"][i]["T_global"]
-                    self.pin_t[i] = torch.from_numpy(np.asarray(t, np.float32))
-                    self.pin_dt[i] = float(m["timestamp"] - prev["img_metas"][i]["timestamp"])
-                self.t_buf.copy_(self.pin_t, non_blocking=True)
-                self.dt_buf.copy_(self.pin_dt, non_blocking=True)
+            self._stage_motion(metas, prev, mask)
             self.staged = torch.cuda.Event()
             self.staged.record(self.s_head)
 
@@ -363,21 +448,27 @@ class PipelinedRunner(FrameRunner):
                    overflow_chain=(self.flags, slot))
         if warm:
             out["bank_inputs"] = (self.t_buf, self.dt_buf)
+        if self.masked:
+            out["active"] = self.active_buf
         return out
 
-    def _enqueue_decoder(self, slot, metas, prev, force_eager):
-        """Stage the inputs of the frame whose features sit in `slot` and enqueue its decoder + read-back on s_head."""
+    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None):
+        """Stage the inputs of the frame whose features sit in `slot` and enqueue its decoder + read-back on s_head. The
+        job keeps the frame's own activity mask: a re-run (_finish) stages it again."""
         warm = prev is not None
         self.prev_metas = prev   # (what the base class's helpers look at)
-        self._stage_head_inputs(metas, prev)
+        self._stage_head_inputs(metas, prev, mask)
         rec = self._run_head(slot, self._head_metas(metas, slot, warm), metas["img_metas"][0]["aug_config"], warm, force_eager)
         done = self._enqueue_readback(slot, rec)
-        return dict(slot=slot, metas=metas, prev=prev, warm=warm, rec=rec, done=done)
+        return dict(slot=slot, metas=metas, prev=prev, warm=warm, rec=rec, done=done, active=mask)
 
     @torch.no_grad()
-    def launch(self, img, metas, force_eager=False):
+    def launch(self, img, metas, force_eager=False, active=None):
         """Enqueue backbone(t) and decoder(t) without waiting for either (several runners -- several independent
-        camera streams on one GPU -- can be launched back to back and collected after)."""
+        camera streams on one GPU -- can be launched back to back and collected after). active: as FrameRunner.step."""
+        mask = self._activity(active, self.last_metas is None)
+        if mask is not None:
+            metas = self._carry(self.last_metas, metas, mask)
         slot = self.count % 2
         if self.raw is not None:
             self._check_frames(img)
@@ -391,7 +482,7 @@ class PipelinedRunner(FrameRunner):
         self.bb_done[slot].record(self.s_bb)
         self.s_head.wait_event(self.bb_done[slot])
         prev = dict(img_metas=self.last_metas["img_metas"]) if self.last_metas is not None else None
-        self.queue.append(self._enqueue_decoder(slot, metas, prev, force_eager))
+        self.queue.append(self._enqueue_decoder(slot, metas, prev, force_eager, mask))
         self.last_metas = metas
         self.count += 1
 
@@ -412,15 +503,14 @@ class PipelinedRunner(FrameRunner):
                 if not job["warm"]:
                     self.head.instance_bank.reset()  # a cold frame starts from an empty bank again
                 self._clear_hold()   # flags left by the overflowed attempt / the speculative decoder behind it
-                job = self._enqueue_decoder(job["slot"], job["metas"], job["prev"], True)
+                job = self._enqueue_decoder(job["slot"], job["metas"], job["prev"], True, job["active"])
                 job["done"].synchronize()
                 h = self.host[job["slot"]]
             for b in behind:
-                self.queue.append(self._enqueue_decoder(b["slot"], b["metas"], b["prev"], True))
+                self.queue.append(self._enqueue_decoder(b["slot"], b["metas"], b["prev"], True, b["active"]))
         self.last_rec3d, self.last_rec2d = job["rec"][0], job["rec"][1]
         self.prev_metas = dict(img_metas=job["metas"]["img_metas"])
-        results = SparseBox3DDecoder.decode_static_host(h[0].numpy(), h[1].numpy(), self.head.num_cams, self.independent)
-        return [{"img_bbox": r} for r in results]
+        return self._results(h[0], h[1], job["active"])
 
     def _quiesce(self):
         self.s_head.synchronize()
@@ -436,9 +526,9 @@ class PipelinedRunner(FrameRunner):
             return None
         return self._finish(self.queue.pop(0))
 
-    def step(self, img, metas, force_eager=False):
+    def step(self, img, metas, force_eager=False, active=None):
         """Feed frame t; returns the detections of frame t-1 (None on the very first call)."""
-        self.launch(img, metas, force_eager)
+        self.launch(img, metas, force_eager, active)
         return self.collect()
 
     @torch.no_grad()
@@ -475,7 +565,10 @@ class SplitPipelinedRunner(PipelinedRunner):
         the flags B(t) looks at): SimPBHead.forward_split, `overflow_split`;
       * eager (warm-up, re-run) frames run A and B back to back on the decoder stream: only replayed graphs run A on the
         backbone stream, so no tensor of the caching allocator crosses streams.
-    """
+
+    This is the single-stream form: it takes no paused streams (pausing its one stream means not calling step)."""
+
+    SUPPORTS_PAUSE = False
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
                  raw_input=None, img_norm_cfg=None):
@@ -553,7 +646,7 @@ class SplitPipelinedRunner(PipelinedRunner):
             outs["classification2d"], outs["prediction2d"], alloc, aug)
         return rec3d, rec2d, outs["overflow"]
 
-    def _enqueue_decoder(self, slot, metas, prev, force_eager):
+    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None):
         warm = prev is not None
         self.prev_metas = prev
         aug = metas["img_metas"][0]["aug_config"]
@@ -597,7 +690,7 @@ class SplitPipelinedRunner(PipelinedRunner):
             if graph_ok:
                 self.head_runs[slot] += 1
         done = self._enqueue_readback(slot, rec)
-        return dict(slot=slot, metas=metas, prev=prev, warm=warm, rec=rec, done=done)
+        return dict(slot=slot, metas=metas, prev=prev, warm=warm, rec=rec, done=done, active=None)
 
     def _quiesce(self):
         self.s_pre.synchronize()
