@@ -544,6 +544,33 @@ int simpb_decode2d_record_ragged(float* rec2d, const float* cls2d, const float* 
 int simpb_record2d_compact(float* out, long long out_stride, const float* rec2d, long long in_stride, int batch_size, int rows_in,
                            int rows_out, void* stream);
 
+/* World record (csrc/world.hip): a frame's rec3d as a serving caller consumes it -- boxes in the global frame, score
+ * threshold and per-class range limit applied, surviving rows packed in rank order -- restating `_format_bbox`,
+ * `output_to_nusc_box` and `lidar_nusc_box_to_global` (datasets/nuscenes_dataset.py:504-586, 824-899) in double.
+ *   rec3d f32 [streams, num_output, 15] as simpb_decode3d_record writes it;
+ *   pose f64 [streams, 14] = lidar->ego quaternion (w, x, y, z) and translation, ego->global quaternion and translation, raw
+ *   (rotation matrices come from q / |q|, quaternion products from q itself); active u8 [streams] or NULL.
+ *   A row is kept when its label is a class of the table with class_range >= 0, the ego-frame distance of its centre in
+ *   the plane is not above class_range[label], and (has_threshold) its score before the re-score (lane 12) >= threshold.
+ *   world f64 [streams, num_output, SIMPB_WORLD_WIDTH = 16] (16-byte aligned) = translation (3) | size w l h (3) | rotation
+ *   quaternion (4) | velocity x y (2) | scores_3d | label | attribute code (attr_moving[label] when the global-frame speed
+ *   in the plane is above 0.2, attr_still[label] otherwise) | the int64 track id, bit-cast. Kept rows first, in rank order;
+ *   every row behind them is zeros with label -1. count i32 [streams] = kept rows, or -1 for a stream with active == 0
+ *   (all its rows are pad rows). The tables travel by value: nothing is allocated, so the launch can sit in a capture.
+ *   num_output <= 512, one thread per row. */
+#define SIMPB_WORLD_WIDTH 16
+#define SIMPB_WORLD_MAX_CLASSES 32
+typedef struct simpb_world_tables {
+  float class_range[SIMPB_WORLD_MAX_CLASSES];        /* metres; negative: the class is never kept */
+  unsigned char attr_moving[SIMPB_WORLD_MAX_CLASSES]; /* attribute codes (simpb_amd/results.py: ATTRIBUTE_NAMES) */
+  unsigned char attr_still[SIMPB_WORLD_MAX_CLASSES];
+  float threshold;
+  int has_threshold;
+  int num_output;
+} simpb_world_tables;
+int simpb_world_record(double* world, int* count, const float* rec3d, const double* pose, const unsigned char* active,
+                       simpb_world_tables tables, int num_streams, void* stream);
+
 /* Top-k of each score row, sorted descending (ties: lower index first): values f32 [bs, k], indices
  * i32 [bs, k] from scores f32 [bs, n], n <= 2048, k <= n. What `topk` of models/instance_bank.py:13-20
  * and the ranking of SparseBox3DDecoder.decode (models/detection3d/decoder.py:145-167) ask of torch.topk /

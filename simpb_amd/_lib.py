@@ -12,6 +12,13 @@ _I = ctypes.c_int
 _F = ctypes.c_float
 _LL = ctypes.c_longlong
 
+
+class WorldTables(ctypes.Structure):
+    """simpb_world_tables of include/simpb_hip.h, passed by value."""
+    _fields_ = [("class_range", _F * 32), ("attr_moving", ctypes.c_ubyte * 32), ("attr_still", ctypes.c_ubyte * 32),
+                ("threshold", _F), ("has_threshold", _I), ("num_output", _I)]
+
+
 SIGNATURES = {
     "simpb_abi_version": ([], _I),
     "simpb_last_error": ([], ctypes.c_char_p),
@@ -55,6 +62,7 @@ SIGNATURES = {
     "simpb_decode2d_record": ([_P] * 6 + [_I] * 4 + [_F] * 4 + [_P], _I),
     "simpb_record2d_compact": ([_P, _LL, _P, _LL, _I, _I, _I, _P], _I),
     "simpb_decode2d_record_ragged": ([_P] * 7 + [_I] * 5 + [_F] * 4 + [_P], _I),
+    "simpb_world_record": ([_P] * 5 + [WorldTables, _I, _P], _I),
     "simpb_topk_rows": ([_P, _P, _P, _I, _I, _I, _P], _I),
     "simpb_rowdot_sigmoid": ([_P, _P, _I, _P, _P, _I, _I, _P, _P], _I),
     "simpb_anchor_projection": ([_P] * 4 + [_I] * 2 + [_P], _I),

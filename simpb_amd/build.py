@@ -22,7 +22,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # foreign one as well. Costs nothing measurable in these latency-bound kernels (the whole library without SLP: +0.6 % per frame).
 NO_PACKED_FP32 = ["-fno-slp-vectorize", "-fno-vectorize"]
 ROW_KERNEL_FILES = ("deform_agg", "deform_agg_fused", "msda", "msda_lin", "alloc", "bank", "rowops", "dfa_prep", "decode", "format",
-                    "preprocess")   # (integer resampling + a table: nothing to pack, and it runs beside the decoder)
+                    "preprocess",   # (integer resampling + a table: nothing to pack, and it runs beside the decoder)
+                    "world")        # (double arithmetic on record rows, the last launch of the decoder stream)
 
 
 def flags_for(src):

@@ -443,6 +443,39 @@ class SparseBox3DDecoder(object):
                                                  float(crop[1]), float(resize), _stream()), "simpb_decode2d_record")
         return rec3d, rec2d
 
+    def world_record(self, rec3d, pose_buf, active_buf, tables, threshold):
+        """The world record of a frame's rec3d (csrc/world.hip; simpb_amd/results.py for the lanes): boxes in the global
+        frame, score threshold (None: no cut; applied here as the reference's output_to_nusc_box does, not in the ranking)
+        and per-class range limit applied, kept rows packed in rank order. rec3d f32 [streams, num_output, 15]; pose_buf
+        f64 [streams, 14] (results.pose_row per stream); active_buf u8 [streams] or None; tables from results.world_tables.
+        Returns (world f64 [streams, num_output, 16], count i32 [streams]). On the device one launch, nothing allocated but
+        the two outputs (capturable); off the device results.world_record_host."""
+        from .. import results
+        if not rec3d.is_cuda:
+            world, count = results.world_record_host(
+                rec3d.numpy(), pose_buf.numpy(), tables, threshold, active_buf.numpy() if active_buf is not None else None)
+            return torch.from_numpy(world), torch.from_numpy(count)
+        from .. import _lib
+        from .ops import _ptr, _stream
+        streams, k, width = rec3d.shape
+        if width != 15 or rec3d.dtype != torch.float32 or not rec3d.is_contiguous():
+            raise ValueError("world_record takes the contiguous f32 [streams, num_output, 15] record of decode_static_device")
+        if pose_buf.dtype != torch.float64 or tuple(pose_buf.shape) != (streams, 14) or not pose_buf.is_contiguous():
+            raise ValueError(f"pose buffer must be contiguous f64 [{streams}, 14]")
+        if active_buf is not None and (active_buf.dtype != torch.uint8 or active_buf.numel() != streams):
+            raise ValueError(f"activity mask must be u8 [{streams}]")
+        t = _lib.WorldTables()
+        t.class_range[:] = [float(x) for x in tables["class_range"]]
+        t.attr_moving[:] = [int(x) for x in tables["attr_moving"]]
+        t.attr_still[:] = [int(x) for x in tables["attr_still"]]
+        t.threshold, t.has_threshold, t.num_output = (float(threshold) if threshold is not None else 0.0), int(threshold is not None), k
+        world = torch.empty(streams, k, 16, dtype=torch.float64, device=rec3d.device)
+        count = torch.empty(streams, dtype=torch.int32, device=rec3d.device)
+        _lib.check(_lib.lib().simpb_world_record(_ptr(world), _ptr(count), _ptr(rec3d), _ptr(pose_buf),
+                                                 _ptr(active_buf) if active_buf is not None else None, t, streams, _stream()),
+                   "simpb_world_record")
+        return world, count
+
     @staticmethod
     def decode_static_host(rec3d, rec2d, num_cams=6, independent=False):
         """Host half: the reference's per-sample dict (decoder.py:176-251) from the two records.

@@ -60,14 +60,19 @@ def carry_inactive_metas(prev, metas, active):
 
 class FrameRunner:
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None):
+                 raw_input=None, img_norm_cfg=None, world_output=None):
         """independent_streams: the batch is a set of independent camera streams, each decoded exactly as a batch of one
         would be (`capacity` 2D slots per stream; SimPBHead.independent_streams) -- the throughput form of BASELINE config
         #3. False: the reference's batch semantics (camera groups padded to the max over the batch).
 
         raw_input=(Hs, Ws): frames arrive as the decoder's u8 [bs, cams, Hs, Ws, 3] (device or pinned host memory) and the
         reference's resize / crop / flip / normalise (img_norm_cfg, default: the shipped configs') runs on the device as the
-        first launches of the frame (csrc/preprocess.hip), keyed by the frame's own aug_config: see _ensure_plan."""
+        first launches of the frame (csrc/preprocess.hip), keyed by the frame's own aug_config: see _ensure_plan.
+
+        world_output=dict(classes=..., tracking=bool, threshold=float | None): a second output per frame, the WORLD RECORD
+        (csrc/world.hip, results.py): boxes in the global frame, threshold and class ranges applied, kept rows packed, a
+        row count per stream -- one more launch at the end of the decoder, inside its graph. Each stream's img_metas entry
+        must then carry results.POSE_KEYS. None (default): nothing of this exists."""
         self.model = model
         self.head = model.head
         self.bs = batch_size
@@ -115,8 +120,49 @@ class FrameRunner:
         # frame live in graph memory: EVERY graph of this runner that may write that memory waits for it before its next
         # replay (the decoder graphs and, in SplitPipelinedRunner, part A, which shares the pool of part B)
         self.rec_consumed = None
+        self.world_output = None
+        if world_output is not None:
+            from . import results
+            tracking = bool(world_output.get("tracking", False))
+            self.world_output = dict(classes=tuple(world_output["classes"]), tracking=tracking,
+                                     threshold=world_output.get("threshold"),
+                                     tables=results.world_tables(world_output["classes"], tracking))
+            self.pose_buf = torch.zeros(batch_size, 14, dtype=torch.float64, device=dev)
+            self.pin_pose = torch.zeros(batch_size, 14, dtype=torch.float64).pin_memory()
+            self.host_world = self.host_count = None
+            self.last_world = None          # device world record f64 [bs, num_output, 16] of the frame last returned ...
+            self.last_world_count = None    # ... and its row counts i32 [bs] (-1: the stream was paused); as last_rec3d
 
     # ------------------------------------------------------------------ per-frame host work
+    def _check_pose(self, metas, mask):
+        """world_output: every stream that takes part brings its pose (checked before anything is enqueued)."""
+        if self.world_output is None:
+            return
+        from .results import POSE_KEYS
+        for i, m in enumerate(metas["img_metas"]):
+            missing = [k for k in POSE_KEYS if k not in m]
+            if missing and (mask is None or mask[i]):
+                raise ValueError(f"world_output: img_metas[{i}] lacks {missing}")
+
+    @staticmethod
+    def _fill_pose(pin, metas):
+        """The streams' poses into a pinned f64 [bs, 14] buffer; a paused stream's row keeps what it held."""
+        from .results import POSE_KEYS, pose_row
+        rows = pin.numpy()
+        for i, m in enumerate(metas["img_metas"]):
+            if all(k in m for k in POSE_KEYS):
+                rows[i] = pose_row(m)
+
+    def _with_world(self, rec3d, rec2d, overflow, pose=None):
+        """A frame's record tuple; with world_output the world record's launch behind it (the last node of the frame) and
+        its two tensors at the end of the tuple."""
+        if self.world_output is None:
+            return rec3d, rec2d, overflow
+        cfg = self.world_output
+        world, count = self.head.decoder.world_record(rec3d, self.pose_buf if pose is None else pose,
+                                                      self.active_buf if self.masked else None, cfg["tables"], cfg["threshold"])
+        return rec3d, rec2d, overflow, world, count
+
     def _ensure_plan(self, metas):
         """raw_input mode: the ingest tables follow the frame's aug_config (metas["img_metas"][0], the dict the decoder reads
         as well). A frame whose (source size, resize_dims, crop, flip) differ from the resident plan's gets a new plan, and
@@ -178,6 +224,9 @@ class FrameRunner:
         current stream)."""
         self.pin_proj.copy_(metas["projection_mat"] if not metas["projection_mat"].is_cuda else metas["projection_mat"].cpu())
         self.proj.copy_(self.pin_proj, non_blocking=True)
+        if self.world_output is not None:
+            self._fill_pose(self.pin_pose, metas)
+            self.pose_buf.copy_(self.pin_pose, non_blocking=True)
         if self.masked:
             self.pin_active.copy_(torch.tensor(mask if mask is not None else (True,) * self.bs, dtype=torch.uint8))
             self.active_buf.copy_(self.pin_active, non_blocking=True)
@@ -201,15 +250,27 @@ class FrameRunner:
             out["active"] = self.active_buf
         return out
 
-    def _results(self, rec3d, rec2d, mask):
+    def _results(self, rec3d, rec2d, mask, world=None, count=None):
         self.last_active = mask if mask is not None else (True,) * self.bs
         rec3d, rec2d = rec3d.numpy(), rec2d.numpy()
         if mask is None:
             results = SparseBox3DDecoder.decode_static_host(rec3d, rec2d, self.head.num_cams, self.independent)
-            return [{"img_bbox": r} for r in results]
+            return self._add_world([{"img_bbox": r} for r in results], world, count)
         # independent streams: each record is a batch of one; a paused stream's rows are unspecified and are not decoded
         one = lambda i: SparseBox3DDecoder.decode_static_host(rec3d[i:i + 1], rec2d[i:i + 1], self.head.num_cams)[0]  # noqa: E731
-        return [{"img_bbox": one(i)} if a else None for i, a in enumerate(mask)]
+        return self._add_world([{"img_bbox": one(i)} if a else None for i, a in enumerate(mask)], world, count)
+
+    @staticmethod
+    def _add_world(results, world, count):
+        """world_output: each active stream's kept rows (views of one host copy of the frame's world record) and their number."""
+        if world is None:
+            return results
+        world, count = world.numpy().copy(), count.numpy()
+        for i, res in enumerate(results):
+            if res is not None:
+                n = int(count[i])
+                res["img_bbox"]["world"] = dict(record=world[i, :n], count=n)
+        return results
 
     def _frame(self, dmetas, aug_config):
         """The device part of one frame; every tensor it returns has a fixed shape."""
@@ -219,7 +280,7 @@ class FrameRunner:
         rec3d, rec2d = self.head.decoder.decode_static_device(
             outs["classification"], outs["prediction"], outs["instance_id"], outs["quality"],
             outs["classification2d"], outs["prediction2d"], alloc, aug_config)
-        return rec3d, rec2d, outs["overflow"]
+        return self._with_world(rec3d, rec2d, outs["overflow"])
 
     # ------------------------------------------------------------------ capacity overflow
     def _drop_graphs(self):
@@ -242,11 +303,17 @@ class FrameRunner:
         self.stats["overflow"] += 1
         self._drop_graphs()
 
-    def _read_back(self, rec3d, rec2d, flags):
+    def _read_back(self, rec3d, rec2d, flags, world=None, count=None):
         if self.host3d is None or self.host2d.shape != rec2d.shape:
             self.host3d = torch.empty(rec3d.shape, dtype=rec3d.dtype).pin_memory()
             self.host2d = torch.empty(rec2d.shape, dtype=rec2d.dtype).pin_memory()
             self.host_flag = torch.empty(flags.shape, dtype=flags.dtype).pin_memory()
+        if world is not None:
+            if self.host_world is None:
+                self.host_world = torch.empty(world.shape, dtype=world.dtype).pin_memory()
+                self.host_count = torch.empty(count.shape, dtype=count.dtype).pin_memory()
+            self.host_world.copy_(world, non_blocking=True)
+            self.host_count.copy_(count, non_blocking=True)
         self.host3d.copy_(rec3d, non_blocking=True)
         self.host2d.copy_(rec2d, non_blocking=True)
         self.host_flag.copy_(flags, non_blocking=True)
@@ -267,6 +334,7 @@ class FrameRunner:
         mask = self._activity(active, self.prev_metas is None)
         if mask is not None:
             metas = self._carry(self.prev_metas, metas, mask)
+        self._check_pose(metas, mask)
         aug = metas["img_metas"][0]["aug_config"]
         if self.raw is not None:
             self._check_frames(img)
@@ -301,7 +369,10 @@ class FrameRunner:
         self.last_rec3d, self.last_rec2d = rec[0], rec[1]
         self.prev_metas = dict(img_metas=metas["img_metas"])
         self.head.instance_bank.metas = self.prev_metas
-        return self._results(rec3d, rec2d, mask)
+        if self.world_output is None:
+            return self._results(rec3d, rec2d, mask)
+        self.last_world, self.last_world_count = rec[3], rec[4]
+        return self._results(rec3d, rec2d, mask, self.host_world, self.host_count)
 
 
 class PipelinedRunner(FrameRunner):
@@ -323,12 +394,13 @@ class PipelinedRunner(FrameRunner):
     set (`overflow_chain`, plugin/head.py), and collect() then re-runs both, in order, on the state frame t-1 found."""
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None):
+                 raw_input=None, img_norm_cfg=None, world_output=None):
         # two streams side by side from here on: a convolution that misses the in-tree kernels' shape rules must not slip to a
         # vendor kernel silently (plugin/detector.py: STRICT_NO_VENDOR)
         from .plugin import detector
         detector.STRICT_NO_VENDOR = True
-        super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg)
+        super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg,
+                         world_output)
         dev = self.device
         # the decoder of frame t is the critical path (a chain of ~170 dependent small launches); the
         # backbone of frame t+1 only has to be done by the time that chain ends: decoder stream first
@@ -388,7 +460,7 @@ class PipelinedRunner(FrameRunner):
         rec3d, rec2d = self.head.decoder.decode_static_device(
             outs["classification"], outs["prediction"], outs["instance_id"], outs["quality"],
             outs["classification2d"], outs["prediction2d"], alloc, aug)
-        return rec3d, rec2d, outs["overflow"]
+        return self._with_world(rec3d, rec2d, outs["overflow"])
 
     def _drop_graphs(self):
         self.head_graph, self.head_out, self.head_runs = [None, None], [None, None], [0, 0]
@@ -469,6 +541,7 @@ class PipelinedRunner(FrameRunner):
         mask = self._activity(active, self.last_metas is None)
         if mask is not None:
             metas = self._carry(self.last_metas, metas, mask)
+        self._check_pose(metas, mask)
         slot = self.count % 2
         if self.raw is not None:
             self._check_frames(img)
@@ -510,7 +583,10 @@ class PipelinedRunner(FrameRunner):
                 self.queue.append(self._enqueue_decoder(b["slot"], b["metas"], b["prev"], True, b["active"]))
         self.last_rec3d, self.last_rec2d = job["rec"][0], job["rec"][1]
         self.prev_metas = dict(img_metas=job["metas"]["img_metas"])
-        return self._results(h[0], h[1], job["active"])
+        if self.world_output is None:
+            return self._results(h[0], h[1], job["active"])
+        self.last_world, self.last_world_count = job["rec"][3], job["rec"][4]
+        return self._results(h[0], h[1], job["active"], h[3], h[4])
 
     def _quiesce(self):
         self.s_head.synchronize()
@@ -571,8 +647,9 @@ class SplitPipelinedRunner(PipelinedRunner):
     SUPPORTS_PAUSE = False
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None):
-        super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg)
+                 raw_input=None, img_norm_cfg=None, world_output=None):
+        super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg,
+                         world_output)
         dev = self.device
         # part A rides on the backbone stream, right behind backbone(t): as fast for one stream as a third stream of its own
         # (350 frames/s either way) and cheaper when several runners share the GPU (8 runners: 368 against 308 frames/s)
@@ -590,6 +667,10 @@ class SplitPipelinedRunner(PipelinedRunner):
         self.staged2 = [None, None]
         self.pre_graph = [None, None]
         self.pre_done = [torch.cuda.Event(), torch.cuda.Event()]
+        if self.world_output is not None:   # the pose is a per-frame decoder input like the others: one buffer per slot
+            self.pose2 = [torch.zeros(batch_size, 14, dtype=torch.float64, device=dev) for _ in range(2)]
+            for pin in self.pin2:
+                pin["pose"] = torch.zeros(batch_size, 14, dtype=torch.float64).pin_memory()
 
     def _drop_graphs(self):
         super()._drop_graphs()
@@ -603,6 +684,8 @@ class SplitPipelinedRunner(PipelinedRunner):
         bank = self.head.instance_bank
         pin["proj"].copy_(metas["projection_mat"] if not metas["projection_mat"].is_cuda else metas["projection_mat"].cpu())
         pin["ti"].fill_(float(bank.default_time_interval))
+        if self.world_output is not None:
+            self._fill_pose(pin["pose"], metas)
         if prev is not None:
             for i, m in enumerate(metas["img_metas"]):
                 t = m["T_global_inv"] @ prev["img_metas"][i]["T_global"]
@@ -615,6 +698,8 @@ class SplitPipelinedRunner(PipelinedRunner):
         with torch.cuda.stream(stream):
             self.proj2[slot].copy_(pin["proj"], non_blocking=True)
             self.ti_buf2[slot].copy_(pin["ti"], non_blocking=True)
+            if self.world_output is not None:
+                self.pose2[slot].copy_(pin["pose"], non_blocking=True)
             if prev is not None:
                 self.t_buf2[slot].copy_(pin["t"], non_blocking=True)
                 self.dt_buf2[slot].copy_(pin["dt"], non_blocking=True)
@@ -633,7 +718,7 @@ class SplitPipelinedRunner(PipelinedRunner):
         next(gen)
         return gen
 
-    def _part_b(self, gen, aug):
+    def _part_b(self, gen, aug, slot):
         try:
             gen.send(None)
         except StopIteration as done:
@@ -644,7 +729,7 @@ class SplitPipelinedRunner(PipelinedRunner):
         rec3d, rec2d = self.head.decoder.decode_static_device(
             outs["classification"], outs["prediction"], outs["instance_id"], outs["quality"],
             outs["classification2d"], outs["prediction2d"], alloc, aug)
-        return rec3d, rec2d, outs["overflow"]
+        return self._with_world(rec3d, rec2d, outs["overflow"], self.pose2[slot] if self.world_output is not None else None)
 
     def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None):
         warm = prev is not None
@@ -663,7 +748,7 @@ class SplitPipelinedRunner(PipelinedRunner):
                 with torch.cuda.graph(ga, stream=self.s_head, capture_error_mode=CAPTURE_MODE):
                     gen = self._part_a(slot, dmetas)
                 with torch.cuda.graph(gb, stream=self.s_head, pool=ga.pool(), capture_error_mode=CAPTURE_MODE):
-                    self.head_out[slot] = self._part_b(gen, aug)
+                    self.head_out[slot] = self._part_b(gen, aug, slot)
                 del gen
             self.pre_graph[slot], self.head_graph[slot] = ga, gb
         if graph_ok and self.head_graph[slot] is not None:
@@ -685,7 +770,7 @@ class SplitPipelinedRunner(PipelinedRunner):
             self.s_head.wait_stream(self.s_pre)   # (covers backbone(t) and a replayed A of the other slot)
             self._stage_slot(slot, metas, prev, self.s_head)
             with torch.cuda.stream(self.s_head):
-                rec = self._part_b(self._part_a(slot, dmetas), aug)
+                rec = self._part_b(self._part_a(slot, dmetas), aug, slot)
             self.stats["eager"] += 1
             if graph_ok:
                 self.head_runs[slot] += 1
