@@ -198,6 +198,27 @@ int simpb_preprocess_u8_nhwc4_f16(void* out, const void* src, void* mid, const i
                                   int src_height, int src_width, int out_height, int out_width, int taps_x, int taps_y,
                                   int src_row0, int src_rows, int flip, int swap_rb, void* stream);
 
+/* The same ingest for 4:2:0 semi-planar YCbCr frames (NV12 / NV21), what hardware video and JPEG decoders deliver: the
+ * horizontal pass stages a luma row and its chroma row, converts them once to the (B, G, R) bytes the entry point above
+ * stages, and goes on as above; `out` equals simpb_preprocess_u8_nhwc4_f16 on the converted frames bit for bit.
+ *   src  u8  [num_images, src_height * 3 / 2, src_width]: src_height luma rows, then src_height / 2 rows of interleaved
+ *        chroma pairs, (Cb, Cr) with vu_order = 0 (NV12) or (Cr, Cb) with vu_order = 1 (NV21). Row pitch = src_width.
+ *        Chroma sample (i, j) belongs to luma rows 2i, 2i + 1 and columns 2j, 2j + 1 (replicated, not interpolated).
+ * Conversion, int32 with 16 fractional bits (>> arithmetic, clamp to 0..255):
+ *   c = iy * (Y - yoff) + 2^15
+ *   R = clamp((c + irv * (Cr - 128)) >> 16)
+ *   G = clamp((c + igu * (Cb - 128) + igv * (Cr - 128)) >> 16)
+ *   B = clamp((c + ibu * (Cb - 128)) >> 16)
+ * The coefficients are the caller's (simpb_amd/preprocess.py:yuv_coefficients: JFIF full range, BT.601 and BT.709 limited
+ * range); that every partial sum stays inside int32 is the caller's to assert. Every other argument, the scratch and the
+ * refusals are those of simpb_preprocess_u8_nhwc4_f16; SIMPB_EINVAL also for an odd src_height or src_width, a vu_order
+ * outside {0, 1} and iy <= 0. Two launches on `stream`; no allocation, no synchronisation (graph capture safe). */
+int simpb_preprocess_yuv420sp_nhwc4_f16(void* out, const void* src, void* mid, const int* kx, const int* xlo, const int* xn,
+                                        const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
+                                        int src_height, int src_width, int out_height, int out_width, int taps_x, int taps_y,
+                                        int src_row0, int src_rows, int flip, int swap_rb, int vu_order, int yoff, int iy,
+                                        int irv, int igu, int igv, int ibu, void* stream);
+
 /* Bytes of one row of the `mid` scratch above (whole groups of 4 pixels, rounded up to 16); 0 for a width outside 1..2048. */
 int simpb_preprocess_mid_pitch(int out_width);
 

@@ -16,6 +16,9 @@
 //      goes through LDS again and leaves as 16-byte chunks.
 //   2. vertical + table: a thread owns 4 neighbouring output pixels = 12 intermediate bytes per tap row (three aligned
 //      dwords), and writes them as two 16-byte stores.
+// 4:2:0 semi-planar YCbCr frames (NV12 / NV21, u8 [N, Hs * 3 / 2, Ws]: what hardware video and JPEG decoders deliver) enter
+// through a second horizontal kernel: it stages the luma row and its chroma row (Ws bytes each) and converts them once, in
+// int32 with 16 fractional bits, into the same (B, G, R) LDS row; filter, store and the vertical pass are the BGR route's own.
 // Every load of a thread is retired before its stores are issued (store_fence.h).
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
@@ -35,24 +38,13 @@ constexpr int kPrecision = 22;
 
 __device__ __forceinline__ int clip8(int acc) { return min(max(acc >> kPrecision, 0), 255); }
 
-// mid[n][r][j][c] = clip8(2^21 + sum_t src[n][row0 + r][xlo[jj] + t][c] * kx[jj][t]),  jj = flip ? w - 1 - j : j
-__global__ __launch_bounds__(kThreads) void resample_rows_kernel(unsigned char* __restrict__ mid, const unsigned char* __restrict__ src,
-                                                                 const int* __restrict__ kx, const int* __restrict__ xlo,
-                                                                 const int* __restrict__ xn, int Hs, int Ws, int row0, int rows,
-                                                                 int w, int taps, int flip, int pitch, int vec16) {
-  __shared__ __attribute__((aligned(16))) unsigned char s_src[kMaxSrcW * 3];
-  __shared__ __attribute__((aligned(16))) unsigned char s_out[kMaxOutW * 3 + 16];
-  const int tid = threadIdx.x, r = blockIdx.x, n = blockIdx.y;
-  const size_t row_bytes = (size_t)Ws * 3;
-  const unsigned char* p = src + ((size_t)n * Hs + row0 + r) * row_bytes;
-  if (vec16) {
-    const uint4* p16 = reinterpret_cast<const uint4*>(p);
-    uint4* s16 = reinterpret_cast<uint4*>(s_src);
-    for (int i = tid; i < (int)(row_bytes >> 4); i += kThreads) s16[i] = p16[i];
-  } else {
-    for (int i = tid; i < (int)row_bytes; i += kThreads) s_src[i] = p[i];
-  }
-  __syncthreads();
+// The part of the horizontal pass both source formats share: the staged [Ws][3] row `s_src` (complete: the caller has
+// synchronised) -> row `mid_row` of the intermediate.
+//   mid_row[j][c] = clip8(2^21 + sum_t s_src[xlo[jj] + t][c] * kx[jj][t]),  jj = flip ? w - 1 - j : j
+__device__ __forceinline__ void filter_row_and_store(unsigned char* __restrict__ mid_row, const unsigned char* s_src, unsigned char* s_out,
+                                                     const int* __restrict__ kx, const int* __restrict__ xlo,
+                                                     const int* __restrict__ xn, int Ws, int w, int taps, int flip, int pitch) {
+  const int tid = threadIdx.x;
   const int wpad = pitch / 3;   // (columns past w are padding the vertical pass may read and never uses)
   for (int j = tid; j < wpad; j += kThreads) {
     int v0 = 0, v1 = 0, v2 = 0;
@@ -79,9 +71,75 @@ __global__ __launch_bounds__(kThreads) void resample_rows_kernel(unsigned char* 
   for (int i = wpad * 3 + tid; i < pitch; i += kThreads) s_out[i] = 0;
   simpb::loads_retired();
   __syncthreads();
-  uint4* o16 = reinterpret_cast<uint4*>(mid + ((size_t)n * rows + r) * pitch);   // pitch % 16 == 0, mid 16-byte aligned
+  uint4* o16 = reinterpret_cast<uint4*>(mid_row);   // pitch % 16 == 0, mid 16-byte aligned
   const uint4* s16 = reinterpret_cast<const uint4*>(s_out);
   for (int i = tid; i < (pitch >> 4); i += kThreads) o16[i] = s16[i];
+}
+
+// `bytes` of one source row into LDS: 16-byte chunks where the caller found pointer and width to allow them
+__device__ __forceinline__ void stage_row(unsigned char* s_dst, const unsigned char* __restrict__ p, int bytes, int vec16) {
+  const int tid = threadIdx.x;
+  if (vec16) {
+    const uint4* p16 = reinterpret_cast<const uint4*>(p);
+    uint4* s16 = reinterpret_cast<uint4*>(s_dst);
+    for (int i = tid; i < (bytes >> 4); i += kThreads) s16[i] = p16[i];
+  } else {
+    for (int i = tid; i < bytes; i += kThreads) s_dst[i] = p[i];
+  }
+}
+
+// mid[n][r][j][c] = clip8(2^21 + sum_t src[n][row0 + r][xlo[jj] + t][c] * kx[jj][t]),  jj = flip ? w - 1 - j : j
+__global__ __launch_bounds__(kThreads) void resample_rows_kernel(unsigned char* __restrict__ mid, const unsigned char* __restrict__ src,
+                                                                 const int* __restrict__ kx, const int* __restrict__ xlo,
+                                                                 const int* __restrict__ xn, int Hs, int Ws, int row0, int rows,
+                                                                 int w, int taps, int flip, int pitch, int vec16) {
+  __shared__ __attribute__((aligned(16))) unsigned char s_src[kMaxSrcW * 3];
+  __shared__ __attribute__((aligned(16))) unsigned char s_out[kMaxOutW * 3 + 16];
+  const int r = blockIdx.x, n = blockIdx.y;
+  const size_t row_bytes = (size_t)Ws * 3;
+  stage_row(s_src, src + ((size_t)n * Hs + row0 + r) * row_bytes, (int)row_bytes, vec16);
+  __syncthreads();
+  filter_row_and_store(mid + ((size_t)n * rows + r) * pitch, s_src, s_out, kx, xlo, xn, Ws, w, taps, flip, pitch);
+}
+
+// 4:2:0 semi-planar source (NV12 / NV21): one image is u8 [Hs * 3 / 2][Ws], Hs luma rows, then Hs / 2 rows of interleaved
+// chroma pairs, (Cb, Cr) or with `vu` (Cr, Cb); chroma sample (i, j) covers luma rows 2i, 2i + 1 and columns 2j, 2j + 1
+// (replicated). The luma row and its chroma row are staged, converted once into the (B, G, R) row the BGR kernel stages,
+//   c = iy * (Y - yoff) + 2^15,  R = clamp((c + irv * (Cr - 128)) >> 16),  G = clamp((c + igu * (Cb - 128) + igv * (Cr - 128)) >> 16),
+//   B = clamp((c + ibu * (Cb - 128)) >> 16)     (int32, arithmetic shift, clamp to 0..255),
+// and filtered by the same code.
+struct YuvCoeffs { int yoff, iy, irv, igu, igv, ibu; };
+
+__device__ __forceinline__ int clamp8(int v) { return min(max(v, 0), 255); }
+
+__global__ __launch_bounds__(kThreads) void resample_rows_yuv420sp_kernel(unsigned char* __restrict__ mid, const unsigned char* __restrict__ src,
+                                                                          const int* __restrict__ kx, const int* __restrict__ xlo,
+                                                                          const int* __restrict__ xn, int Hs, int Ws, int row0, int rows,
+                                                                          int w, int taps, int flip, int pitch, int vec16, int vu, YuvCoeffs q) {
+  __shared__ __attribute__((aligned(16))) unsigned char s_src[kMaxSrcW * 3];
+  __shared__ __attribute__((aligned(16))) unsigned char s_out[kMaxOutW * 3 + 16];
+  __shared__ __attribute__((aligned(16))) unsigned char s_luma[kMaxSrcW];
+  __shared__ __attribute__((aligned(16))) unsigned char s_chroma[kMaxSrcW];
+  const int tid = threadIdx.x, r = blockIdx.x, n = blockIdx.y;
+  const int row = row0 + r;
+  const unsigned char* image = src + (size_t)n * (Hs + (Hs >> 1)) * Ws;
+  stage_row(s_luma, image + (size_t)row * Ws, Ws, vec16);
+  stage_row(s_chroma, image + (size_t)(Hs + (row >> 1)) * Ws, Ws, vec16);
+  __syncthreads();
+  for (int x = 2 * tid; x < Ws; x += 2 * kThreads) {   // a chroma pair and its two luma samples (Ws is even)
+    const int cb = (int)s_chroma[x + vu] - 128, cr = (int)s_chroma[x + 1 - vu] - 128;
+    const int dr = q.irv * cr, dg = q.igu * cb + q.igv * cr, db = q.ibu * cb;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = q.iy * ((int)s_luma[x + i] - q.yoff) + (1 << 15);
+      unsigned char* d = s_src + (x + i) * 3;
+      d[0] = (unsigned char)clamp8((c + db) >> 16);
+      d[1] = (unsigned char)clamp8((c + dg) >> 16);
+      d[2] = (unsigned char)clamp8((c + dr) >> 16);
+    }
+  }
+  __syncthreads();
+  filter_row_and_store(mid + ((size_t)n * rows + r) * pitch, s_src, s_out, kx, xlo, xn, Ws, w, taps, flip, pitch);
 }
 
 // out[n][y][x][c] = lut[c][clip8(2^21 + sum_t mid[n][ylo[y] - row0 + t][x][swap ? 2 - c : c] * ky[y][t])], out[..][3] = 0
@@ -151,21 +209,40 @@ extern "C" int simpb_preprocess_mid_pitch(int out_width) {
   return (out_width <= 0 || out_width > kMaxOutW) ? 0 : mid_pitch(out_width);
 }
 
+// what both entry points refuse (before any HIP call)
+static bool bad_arguments(const void* out, const void* src, const void* mid, const int* kx, const int* xlo, const int* xn, const int* ky,
+                          const int* ylo, const int* yn, const void* lut, int num_images, int src_height, int src_width, int out_height,
+                          int out_width, int taps_x, int taps_y, int src_row0, int src_rows) {
+  if (!out || !src || !mid || !kx || !xlo || !xn || !ky || !ylo || !yn || !lut) return true;
+  if (num_images <= 0 || num_images > 65535 || src_height <= 0 || src_width <= 0 || out_height <= 0 || out_width <= 0 ||
+      out_height > 65535 || src_width > kMaxSrcW || out_width > kMaxOutW)
+    return true;
+  if (taps_x <= 0 || taps_y <= 0 || taps_x > kMaxTaps || taps_y > kMaxTaps) return true;
+  if (src_row0 < 0 || src_rows <= 0 || (long long)src_row0 + src_rows > src_height) return true;
+  if ((reinterpret_cast<size_t>(out) | reinterpret_cast<size_t>(mid)) & 15) return true;
+  if ((reinterpret_cast<size_t>(kx) | reinterpret_cast<size_t>(xlo) | reinterpret_cast<size_t>(xn) | reinterpret_cast<size_t>(ky) |
+       reinterpret_cast<size_t>(ylo) | reinterpret_cast<size_t>(yn)) & 3)
+    return true;
+  return (reinterpret_cast<size_t>(lut) & 1) != 0;
+}
+
+// the vertical pass + table, and the status of both launches
+static int finish_vertical(void* out, const void* mid, const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
+                           int out_height, int out_width, int taps_y, int src_row0, int src_rows, int swap_rb, int pitch, hipStream_t s) {
+  const int groups = (out_width + 3) / 4;
+  hipLaunchKernelGGL(resample_cols_lut_kernel, dim3((groups + kThreads - 1) / kThreads, out_height, num_images), dim3(kThreads), 0, s,
+                     static_cast<_Float16*>(out), static_cast<const unsigned char*>(mid), ky, ylo, yn,
+                     static_cast<const _Float16*>(lut), src_row0, src_rows, out_height, out_width, taps_y, swap_rb ? 1 : 0, pitch);
+  return simpb_check_launch();
+}
+
 extern "C" int simpb_preprocess_u8_nhwc4_f16(void* out, const void* src, void* mid, const int* kx, const int* xlo, const int* xn,
                                              const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
                                              int src_height, int src_width, int out_height, int out_width, int taps_x, int taps_y,
                                              int src_row0, int src_rows, int flip, int swap_rb, void* stream) {
-  if (!out || !src || !mid || !kx || !xlo || !xn || !ky || !ylo || !yn || !lut) return SIMPB_EINVAL;
-  if (num_images <= 0 || num_images > 65535 || src_height <= 0 || src_width <= 0 || out_height <= 0 || out_width <= 0 ||
-      out_height > 65535 || src_width > kMaxSrcW || out_width > kMaxOutW)
+  if (bad_arguments(out, src, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height, out_width, taps_x,
+                    taps_y, src_row0, src_rows))
     return SIMPB_EINVAL;
-  if (taps_x <= 0 || taps_y <= 0 || taps_x > kMaxTaps || taps_y > kMaxTaps) return SIMPB_EINVAL;
-  if (src_row0 < 0 || src_rows <= 0 || (long long)src_row0 + src_rows > src_height) return SIMPB_EINVAL;
-  if ((reinterpret_cast<size_t>(out) | reinterpret_cast<size_t>(mid)) & 15) return SIMPB_EINVAL;
-  if ((reinterpret_cast<size_t>(kx) | reinterpret_cast<size_t>(xlo) | reinterpret_cast<size_t>(xn) | reinterpret_cast<size_t>(ky) |
-       reinterpret_cast<size_t>(ylo) | reinterpret_cast<size_t>(yn)) & 3)
-    return SIMPB_EINVAL;
-  if (reinterpret_cast<size_t>(lut) & 1) return SIMPB_EINVAL;
   const int pitch = mid_pitch(out_width);
   const int vec16 = ((size_t)src_width * 3 % 16 == 0 && (reinterpret_cast<size_t>(src) & 15) == 0) ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -173,9 +250,26 @@ extern "C" int simpb_preprocess_u8_nhwc4_f16(void* out, const void* src, void* m
   hipLaunchKernelGGL(resample_rows_kernel, dim3(src_rows, num_images), dim3(kThreads), 0, s, static_cast<unsigned char*>(mid),
                      static_cast<const unsigned char*>(src), kx, xlo, xn, src_height, src_width, src_row0, src_rows, out_width,
                      taps_x, flip ? 1 : 0, pitch, vec16);
-  const int groups = (out_width + 3) / 4;
-  hipLaunchKernelGGL(resample_cols_lut_kernel, dim3((groups + kThreads - 1) / kThreads, out_height, num_images), dim3(kThreads), 0, s,
-                     static_cast<_Float16*>(out), static_cast<const unsigned char*>(mid), ky, ylo, yn,
-                     static_cast<const _Float16*>(lut), src_row0, src_rows, out_height, out_width, taps_y, swap_rb ? 1 : 0, pitch);
-  return simpb_check_launch();
+  return finish_vertical(out, mid, ky, ylo, yn, lut, num_images, out_height, out_width, taps_y, src_row0, src_rows, swap_rb, pitch, s);
+}
+
+extern "C" int simpb_preprocess_yuv420sp_nhwc4_f16(void* out, const void* src, void* mid, const int* kx, const int* xlo, const int* xn,
+                                                   const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
+                                                   int src_height, int src_width, int out_height, int out_width, int taps_x,
+                                                   int taps_y, int src_row0, int src_rows, int flip, int swap_rb, int vu_order, int yoff,
+                                                   int iy, int irv, int igu, int igv, int ibu, void* stream) {
+  if (bad_arguments(out, src, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height, out_width, taps_x,
+                    taps_y, src_row0, src_rows))
+    return SIMPB_EINVAL;
+  if ((src_height & 1) || (src_width & 1) || (vu_order != 0 && vu_order != 1) || iy <= 0) return SIMPB_EINVAL;
+  const int pitch = mid_pitch(out_width);
+  // every luma and chroma row starts on a 16-byte boundary when the width is a multiple of 16 and the first image does
+  const int vec16 = (src_width % 16 == 0 && (reinterpret_cast<size_t>(src) & 15) == 0) ? 1 : 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  (void)hipGetLastError();
+  const YuvCoeffs q = {yoff, iy, irv, igu, igv, ibu};
+  hipLaunchKernelGGL(resample_rows_yuv420sp_kernel, dim3(src_rows, num_images), dim3(kThreads), 0, s, static_cast<unsigned char*>(mid),
+                     static_cast<const unsigned char*>(src), kx, xlo, xn, src_height, src_width, src_row0, src_rows, out_width,
+                     taps_x, flip ? 1 : 0, pitch, vec16, vu_order, q);
+  return finish_vertical(out, mid, ky, ylo, yn, lut, num_images, out_height, out_width, taps_y, src_row0, src_rows, swap_rb, pitch, s);
 }

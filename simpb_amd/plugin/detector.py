@@ -354,17 +354,20 @@ class SimPB(BaseModule):
         return self
 
     def extract_feat(self, img, return_depth=False, metas=None, raw_plan=None):
-        """simpb.py:64-91. A uint8 `img` is the raw form: camera frames [bs, cams, Hs, Ws, 3] (or [N, Hs, Ws, 3]) as decoded,
-        resized / cropped / flipped / normalised on the device by `raw_plan` (simpb_amd.preprocess.ResamplePlan) straight into
-        the stem's operand."""
+        """simpb.py:64-91. A uint8 `img` is the raw form: camera frames as decoded, in the layout of `raw_plan`
+        (simpb_amd.preprocess.ResamplePlan): [bs, cams, Hs, Ws, 3] or [N, Hs, Ws, 3] for a "bgr" plan, [bs, cams, Hs * 3 / 2, Ws] or
+        [N, Hs * 3 / 2, Ws] for an "nv12" / "nv21" one. They are converted / resized / cropped / flipped / normalised on the device
+        straight into the stem's operand; a frame whose shape is not the plan's is refused."""
         bs = img.shape[0]
         raw = img.dtype == torch.uint8
         if raw:
             if raw_plan is None:
                 raise ValueError("uint8 frames need raw_plan= (simpb_amd.preprocess.ResamplePlan): the resize / crop / normalise to apply")
-            if img.dim() not in (4, 5):
-                raise ValueError(f"raw frames are u8 [bs, cams, Hs, Ws, 3] or [N, Hs, Ws, 3], got {tuple(img.shape)}")
-            num_cams = img.shape[1] if img.dim() == 5 else 1
+            lead = img.dim() - len(raw_plan.frame_shape)
+            if lead not in (1, 2):
+                raise ValueError(f"raw frames are [bs, cams] or [N] images of {raw_plan.layout()}, got {tuple(img.shape)}")
+            raw_plan.check_frames(img)
+            num_cams = img.shape[1] if lead == 2 else 1
             img = raw_plan.run(img)
         elif img.dim() == 5:
             num_cams = img.shape[1]

@@ -7,7 +7,11 @@ point. `coefficients` restates Pillow's precompute_coeffs / normalize_coeffs_8bp
 everything after it is integer, so the device result equals Pillow's byte for byte (tests/test_preprocess_host.py pins
 the statement to Pillow and to the reference's own function). `NormalizeMultiviewImage` (transform_3d.py:438-466) delegates
 to mmcv.imnormalize, which is not vendored: (x - mean) * (1 / std) in fp32 after the BGR -> RGB swap is restated from its
-published behaviour and parity-unpinned. This module computes tables only; no pixel is resampled on the host."""
+published behaviour and parity-unpinned. This module computes tables only; no pixel is resampled on the host.
+
+Frames may also arrive as 4:2:0 semi-planar YCbCr (NV12 / NV21), the form hardware video and JPEG decoders deliver:
+`yuv_coefficients` defines the integer conversion to the (B, G, R) bytes above that the horizontal pass applies while it
+stages a row; everything behind it is the BGR route's own."""
 import ctypes
 import math
 
@@ -16,6 +20,54 @@ import numpy as np
 PRECISION_BITS = 22   # Pillow: 32 - 8 - 2
 # img_norm_cfg of the shipped configs (:320-322)
 IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
+
+
+FRAME_FORMATS = ("bgr", "nv12", "nv21")
+YUV_BITS = 16         # fractional bits of the YCbCr -> BGR coefficients
+# standard -> (Kr, Kb, full range)
+YUV_STANDARDS = {"jfif": (0.299, 0.114, True), "bt601": (0.299, 0.114, False), "bt709": (0.2126, 0.0722, False)}
+
+
+def yuv_coefficients(standard="jfif"):
+    """(yoff, iy, irv, igu, igv, ibu) of a YCbCr standard: each floor(2^16 * x + 0.5) of the float64 matrix entry, for
+
+        c = iy * (Y - yoff) + 2^15
+        R = clip8((c + irv * (Cr - 128)) >> 16)
+        G = clip8((c + igu * (Cb - 128) + igv * (Cr - 128)) >> 16)
+        B = clip8((c + ibu * (Cb - 128)) >> 16)                      (>> arithmetic, clip8 clamps to 0..255)
+
+    "jfif": full range, Kr = 0.299, Kb = 0.114 (what a JPEG holds; the default). "bt601": limited range (luma 16..235, chroma
+    16..240), the same Kr / Kb. "bt709": limited range, Kr = 0.2126, Kb = 0.0722."""
+    if standard not in YUV_STANDARDS:
+        raise ValueError(f"colour standard {standard!r}: one of {sorted(YUV_STANDARDS)}")
+    kr, kb, full = YUV_STANDARDS[standard]
+    kg = 1.0 - kr - kb
+    ys, cs = (1.0, 1.0) if full else (255.0 / 219.0, 255.0 / 224.0)
+    entries = (ys, 2.0 * (1.0 - kr) * cs, -2.0 * kb * (1.0 - kb) / kg * cs, -2.0 * kr * (1.0 - kr) / kg * cs, 2.0 * (1.0 - kb) * cs)
+    iy, irv, igu, igv, ibu = (int(math.floor(v * (1 << YUV_BITS) + 0.5)) for v in entries)
+    yoff = 0 if full else 16
+    # every partial sum stays far inside int32
+    luma = max(abs(iy * (0 - yoff)), abs(iy * (255 - yoff))) + (1 << (YUV_BITS - 1))
+    assert iy > 0 and luma + 128 * max(abs(irv), abs(ibu), abs(igu) + abs(igv)) < (1 << 31)
+    return yoff, iy, irv, igu, igv, ibu
+
+
+def _check_format(frame_format, colour):
+    if frame_format not in FRAME_FORMATS:
+        raise ValueError(f"frame format {frame_format!r}: one of {FRAME_FORMATS}")
+    if colour not in YUV_STANDARDS:
+        raise ValueError(f"colour standard {colour!r}: one of {sorted(YUV_STANDARDS)}")
+
+
+def frame_shape(src_hw, frame_format="bgr"):
+    """Trailing dimensions of one image of `src_hw` = (Hs, Ws): (Hs, Ws, 3) interleaved BGR, or (Hs * 3 / 2, Ws) for NV12 / NV21
+    (Hs luma rows, then Hs / 2 rows of interleaved chroma pairs; row pitch Ws)."""
+    hs, ws = int(src_hw[0]), int(src_hw[1])
+    if frame_format == "bgr":
+        return (hs, ws, 3)
+    if hs % 2 or ws % 2:
+        raise ValueError(f"{frame_format} frames have even sizes (one chroma pair per 2 x 2 luma samples), got {ws} x {hs}")
+    return (hs * 3 // 2, ws)
 
 
 def _bicubic(x):
@@ -96,10 +148,12 @@ def resolve_aug(src_hw, aug_config):
     return dims, crop, bool(aug.get("flip", False))
 
 
-def plan_key(src_hw, aug_config):
-    """What a ResamplePlan depends on: a frame whose key differs must not run on the plan's tables."""
+def plan_key(src_hw, aug_config, frame_format="bgr", colour="jfif"):
+    """What a ResamplePlan depends on: a frame whose key differs must not run on the plan's tables (nor a frame of another
+    format or colour standard on the plan's kernel; the standard says nothing about BGR frames and is left out of their key)."""
+    _check_format(frame_format, colour)
     dims, crop, flip = resolve_aug(src_hw, aug_config)
-    return (int(src_hw[0]), int(src_hw[1]), dims, crop, flip)
+    return (int(src_hw[0]), int(src_hw[1]), dims, crop, flip, frame_format, colour if frame_format != "bgr" else None)
 
 
 def _device(device):
@@ -112,12 +166,24 @@ def _device(device):
 
 
 class ResamplePlan:
-    """Tables of one ingest configuration; `upload(device)` makes them resident, `run(frames)` launches."""
+    """Tables of one ingest configuration; `upload(device)` makes them resident, `run(frames)` launches.
 
-    def __init__(self, src_hw, aug_config=None, img_norm_cfg=None):
+    frame_format "bgr": u8 [..., Hs, Ws, 3] interleaved pixels. "nv12" / "nv21": one image is a contiguous u8 [Hs * 3 / 2, Ws]:
+    rows 0 .. Hs - 1 are luma, rows Hs .. Hs * 3 / 2 - 1 interleaved chroma pairs, (Cb, Cr) for nv12 and (Cr, Cb) for nv21;
+    chroma sample (i, j) belongs to luma rows 2i, 2i + 1 and columns 2j, 2j + 1 and is replicated, not interpolated (the
+    antialiased bicubic reduction behind it makes the choice of chroma up-sampler immaterial). Hs and Ws are even and the row
+    pitch is Ws (a decoder's padded pitch is not taken). `colour` names the standard of `yuv_coefficients`. The converted
+    pixel is staged as (B, G, R), so to_rgb, the table and the output mean what they mean for BGR frames: the output equals
+    the BGR plan's on the converted frames bit for bit."""
+
+    def __init__(self, src_hw, aug_config=None, img_norm_cfg=None, frame_format="bgr", colour="jfif"):
         self.src_hw = (int(src_hw[0]), int(src_hw[1]))
+        _check_format(frame_format, colour)
+        self.frame_format, self.colour = frame_format, colour
+        self.frame_shape = frame_shape(self.src_hw, frame_format)
+        self.yuv = None if frame_format == "bgr" else yuv_coefficients(colour)
         self.resize_dims, self.crop, self.flip = resolve_aug(self.src_hw, aug_config)
-        self.key = plan_key(self.src_hw, aug_config)
+        self.key = plan_key(self.src_hw, aug_config, frame_format, colour)
         cfg = IMG_NORM_CFG if img_norm_cfg is None else img_norm_cfg
         self.img_norm_cfg = dict(mean=list(cfg["mean"]), std=list(cfg["std"]), to_rgb=bool(cfg.get("to_rgb", True)))
         self.swap_rb = self.img_norm_cfg["to_rgb"]
@@ -141,7 +207,12 @@ class ResamplePlan:
     def bytes_per_image(self, mid_pitch):
         h, w = self.out_hw
         mid = self.src_rows * mid_pitch
-        return dict(source=self.src_rows * self.src_hw[1] * 3, mid_write=mid, mid_read=mid, out=h * w * 8)
+        if self.yuv is None:
+            source = self.src_rows * self.src_hw[1] * 3
+        else:   # the needed luma rows and the distinct chroma rows under them (needed bytes: both luma rows of a pair stage it)
+            last = self.src_row0 + self.src_rows - 1
+            source = (self.src_rows + (last >> 1) - (self.src_row0 >> 1) + 1) * self.src_hw[1]
+        return dict(source=source, mid_write=mid, mid_read=mid, out=h * w * 8)
 
     # ------------------------------------------------------------------ device
     def upload(self, device):
@@ -167,19 +238,35 @@ class ResamplePlan:
             d["mid"] = torch.empty(num_images * self.src_rows * d["pitch"], dtype=torch.uint8, device=d["device"])
         return self
 
+    def layout(self):
+        """The frames `run` takes, in words (for error messages)."""
+        hs, ws = self.src_hw
+        if self.yuv is None:
+            return f"u8 [..., {hs}, {ws}, 3] frames (interleaved BGR)"
+        pair = "(Cb, Cr)" if self.frame_format == "nv12" else "(Cr, Cb)"
+        return (f"u8 [..., {hs * 3 // 2}, {ws}] {self.frame_format} frames ({hs} luma rows, then {hs // 2} rows of interleaved {pair} "
+                f"pairs, row pitch {ws}: a padded pitch is not taken)")
+
+    def check_frames(self, frames):
+        """ValueError unless `frames` is u8 with this plan's frame layout behind at least one leading dimension."""
+        import torch
+        k = len(self.frame_shape)
+        if frames.dtype != torch.uint8 or frames.dim() <= k or tuple(frames.shape[-k:]) != self.frame_shape:
+            raise ValueError(f"ingest takes {self.layout()}, got {frames.dtype} {tuple(frames.shape)}")
+
     def run(self, frames, out=None):
-        """frames u8 [..., Hs, Ws, 3] on the device (contiguous) -> f16 [N, h, w, 4] (N = product of the leading dimensions),
-        channel 3 = 0. Launches on the current stream; the intermediate buffer is allocated on first use and kept."""
+        """frames u8 [..., Hs, Ws, 3] (u8 [..., Hs * 3 / 2, Ws] for nv12 / nv21) on the device (contiguous) -> f16 [N, h, w, 4]
+        (N = product of the leading dimensions), channel 3 = 0. Launches on the current stream; the intermediate buffer is
+        allocated on first use and kept."""
         import torch
         from . import _lib
         hs, ws = self.src_hw
-        if frames.dtype != torch.uint8 or frames.dim() < 3 or tuple(frames.shape[-3:]) != (hs, ws, 3):
-            raise ValueError(f"ingest takes u8 [..., {hs}, {ws}, 3] frames, got {frames.dtype} {tuple(frames.shape)}")
+        self.check_frames(frames)
         if not frames.is_cuda:
             raise RuntimeError("simpb_amd operators run on the GPU only (got a CPU tensor); there is no CPU fallback")
         if not frames.is_contiguous():
-            raise ValueError("ingest takes contiguous frames (interleaved pixels)")
-        n = int(frames.numel() // (hs * ws * 3))
+            raise ValueError("ingest takes contiguous frames" + (" (interleaved pixels)" if self.yuv is None else ""))
+        n = int(frames.numel() // int(np.prod(self.frame_shape)))
         h, w = self.out_hw
         if n == 0:
             raise ValueError("ingest of an empty batch")
@@ -190,9 +277,12 @@ class ResamplePlan:
         elif out.dtype != torch.float16 or tuple(out.shape) != (n, h, w, 4) or not out.is_contiguous():
             raise ValueError(f"ingest writes f16 [{n}, {h}, {w}, 4]")
         p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
-        status = _lib.lib().simpb_preprocess_u8_nhwc4_f16(
-            p(out), p(frames), p(d["mid"]), p(d["kx"]), p(d["xlo"]), p(d["xn"]), p(d["ky"]), p(d["ylo"]), p(d["yn"]), p(d["lut"]),
-            n, hs, ws, h, w, self.taps_x, self.taps_y, self.src_row0, self.src_rows, int(self.flip), int(self.swap_rb),
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(status, "simpb_preprocess_u8_nhwc4_f16")
+        args = (p(out), p(frames), p(d["mid"]), p(d["kx"]), p(d["xlo"]), p(d["xn"]), p(d["ky"]), p(d["ylo"]), p(d["yn"]), p(d["lut"]),
+                n, hs, ws, h, w, self.taps_x, self.taps_y, self.src_row0, self.src_rows, int(self.flip), int(self.swap_rb))
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self.yuv is None:
+            _lib.check(_lib.lib().simpb_preprocess_u8_nhwc4_f16(*args, stream), "simpb_preprocess_u8_nhwc4_f16")
+        else:
+            _lib.check(_lib.lib().simpb_preprocess_yuv420sp_nhwc4_f16(*args, int(self.frame_format == "nv21"), *self.yuv, stream),
+                       "simpb_preprocess_yuv420sp_nhwc4_f16")
         return out

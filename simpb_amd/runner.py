@@ -60,7 +60,7 @@ def carry_inactive_metas(prev, metas, active):
 
 class FrameRunner:
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None, world_output=None):
+                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif"):
         """independent_streams: the batch is a set of independent camera streams, each decoded exactly as a batch of one
         would be (`capacity` 2D slots per stream; SimPBHead.independent_streams) -- the throughput form of BASELINE config
         #3. False: the reference's batch semantics (camera groups padded to the max over the batch).
@@ -68,6 +68,9 @@ class FrameRunner:
         raw_input=(Hs, Ws): frames arrive as the decoder's u8 [bs, cams, Hs, Ws, 3] (device or pinned host memory) and the
         reference's resize / crop / flip / normalise (img_norm_cfg, default: the shipped configs') runs on the device as the
         first launches of the frame (csrc/preprocess.hip), keyed by the frame's own aug_config: see _ensure_plan.
+        raw_format="nv12" | "nv21", raw_colour="jfif" | "bt601" | "bt709" (with raw_input only): the frames are 4:2:0
+        semi-planar YCbCr, u8 [bs, cams, Hs * 3 / 2, Ws] (preprocess.ResamplePlan has the layout), converted to BGR inside the
+        ingest's first launch. The default "bgr" is the packed form above.
 
         world_output=dict(classes=..., tracking=bool, threshold=float | None): a second output per frame, the WORLD RECORD
         (csrc/world.hip, results.py): boxes in the global frame, threshold and class ranges applied, kept rows packed, a
@@ -88,10 +91,16 @@ class FrameRunner:
         self.raw_input = (int(raw_input[0]), int(raw_input[1])) if raw_input is not None else None
         self.img_norm_cfg = img_norm_cfg
         self.plan = None                    # preprocess.ResamplePlan of the stream's aug_config (raw_input mode)
+        self.raw_format, self.raw_colour = raw_format, raw_colour
         if self.raw_input is None:
+            if (raw_format, raw_colour) != ("bgr", "jfif"):
+                raise ValueError(f"raw_format={raw_format!r} / raw_colour={raw_colour!r} describe raw frames: they need raw_input=(Hs, Ws)")
             self.img, self.raw = torch.zeros(batch_size, cams, 3, h, w, device=dev), None
         else:   # (no fp32 staging buffer in this mode)
-            self.img, self.raw = None, torch.zeros(batch_size, cams, *self.raw_input, 3, dtype=torch.uint8, device=dev)
+            from .preprocess import frame_shape, plan_key
+            plan_key(self.raw_input, None, raw_format, raw_colour)   # (an unknown format or standard is refused here)
+            self.img = None
+            self.raw = torch.zeros(batch_size, cams, *frame_shape(self.raw_input, raw_format), dtype=torch.uint8, device=dev)
         self.proj = torch.zeros(batch_size, cams, 4, 4, device=dev)
         self.wh = torch.tensor([float(w), float(h)], device=dev).view(1, 1, 2).repeat(batch_size, cams, 1)
         self.wh_host = (int(w), int(h))
@@ -165,14 +174,14 @@ class FrameRunner:
 
     def _ensure_plan(self, metas):
         """raw_input mode: the ingest tables follow the frame's aug_config (metas["img_metas"][0], the dict the decoder reads
-        as well). A frame whose (source size, resize_dims, crop, flip) differ from the resident plan's gets a new plan, and
-        every captured graph is dropped first (they bake the old tables' addresses and the decoder's crop / resize in):
-        a frame never runs on stale tables."""
+        as well). A frame whose (source size, resize_dims, crop, flip, format, colour) differ from the resident plan's gets a
+        new plan, and every captured graph is dropped first (they bake the old tables' addresses and the decoder's crop /
+        resize in): a frame never runs on stale tables."""
         from .preprocess import ResamplePlan, plan_key
         aug = metas["img_metas"][0]["aug_config"]
-        if self.plan is not None and self.plan.key == plan_key(self.raw_input, aug):
+        if self.plan is not None and self.plan.key == plan_key(self.raw_input, aug, self.raw_format, self.raw_colour):
             return
-        plan = ResamplePlan(self.raw_input, aug, self.img_norm_cfg)
+        plan = ResamplePlan(self.raw_input, aug, self.img_norm_cfg, self.raw_format, self.raw_colour)
         if plan.out_hw != self.image_hw:
             raise ValueError(f"aug_config {aug} turns {self.raw_input} frames into {plan.out_hw} images; this runner was built for "
                              f"{self.image_hw}")
@@ -183,7 +192,8 @@ class FrameRunner:
 
     def _check_frames(self, img):
         if img.dtype != torch.uint8 or tuple(img.shape) != tuple(self.raw.shape):
-            raise ValueError(f"raw_input runner takes u8 {tuple(self.raw.shape)} frames, got {img.dtype} {tuple(img.shape)}")
+            what = "" if self.raw_format == "bgr" else f" {self.raw_format}"
+            raise ValueError(f"raw_input runner takes u8 {tuple(self.raw.shape)}{what} frames, got {img.dtype} {tuple(img.shape)}")
 
     def _extract(self, img, raw):
         return self.model.extract_feat(raw, raw_plan=self.plan) if raw is not None else self.model.extract_feat(img)
@@ -323,7 +333,8 @@ class FrameRunner:
     # ------------------------------------------------------------------ public
     @torch.no_grad()
     def step(self, img, metas, force_eager=False, active=None):
-        """One frame for all streams: img f32 [bs, cams, 3, H, W] (device; u8 [bs, cams, Hs, Ws, 3] with raw_input), metas as the reference's
+        """One frame for all streams: img f32 [bs, cams, 3, H, W] (device; u8 [bs, cams, Hs, Ws, 3] with raw_input, u8
+        [bs, cams, Hs * 3 / 2, Ws] with raw_format "nv12" / "nv21"), metas as the reference's
         test pipeline collects them (projection_mat, timestamp, img_metas with T_global/T_global_inv/
         aug_config). Returns the reference's list of {'img_bbox': {...}} (simpb_head.py:1089-1123).
 
@@ -394,13 +405,13 @@ class PipelinedRunner(FrameRunner):
     set (`overflow_chain`, plugin/head.py), and collect() then re-runs both, in order, on the state frame t-1 found."""
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None, world_output=None):
+                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif"):
         # two streams side by side from here on: a convolution that misses the in-tree kernels' shape rules must not slip to a
         # vendor kernel silently (plugin/detector.py: STRICT_NO_VENDOR)
         from .plugin import detector
         detector.STRICT_NO_VENDOR = True
         super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg,
-                         world_output)
+                         world_output, raw_format, raw_colour)
         dev = self.device
         # the decoder of frame t is the critical path (a chain of ~170 dependent small launches); the
         # backbone of frame t+1 only has to be done by the time that chain ends: decoder stream first
@@ -537,7 +548,7 @@ class PipelinedRunner(FrameRunner):
     @torch.no_grad()
     def launch(self, img, metas, force_eager=False, active=None):
         """Enqueue backbone(t) and decoder(t) without waiting for either (several runners -- several independent
-        camera streams on one GPU -- can be launched back to back and collected after). active: as FrameRunner.step."""
+        camera streams on one GPU -- can be launched back to back and collected after). img, active: as FrameRunner.step."""
         mask = self._activity(active, self.last_metas is None)
         if mask is not None:
             metas = self._carry(self.last_metas, metas, mask)
@@ -647,9 +658,9 @@ class SplitPipelinedRunner(PipelinedRunner):
     SUPPORTS_PAUSE = False
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None, world_output=None):
+                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif"):
         super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg,
-                         world_output)
+                         world_output, raw_format, raw_colour)
         dev = self.device
         # part A rides on the backbone stream, right behind backbone(t): as fast for one stream as a third stream of its own
         # (350 frames/s either way) and cheaper when several runners share the GPU (8 runners: 368 against 308 frames/s)

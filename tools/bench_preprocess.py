@@ -2,15 +2,18 @@
 
   (a) `kernel`: HIP-event time of the two ingest launches alone, warmed, --launches (>= 200) timed launches back to back
       between one pair of events, for the R50 configuration (1600 x 900 -> 704 x 396 -> crop to 704 x 256) and the derived
-      R101 one (-> 1408 x 792 -> 1408 x 512), bs 1 and 8 (N = 6 and 48 images). Bytes are the ones the algorithm needs,
-      computed from the plan: the needed source rows read once, the u8 intermediate written and read, the output written.
+      R101 one (-> 1408 x 792 -> 1408 x 512), bs 1 and 8 (N = 6 and 48 images), for packed BGR frames and for the same
+      pictures as NV12 (keys `..._nv12`), in the same run. Bytes are the ones the algorithm needs, computed from the plan:
+      the needed source rows read once, the u8 intermediate written and read, the output written.
       Share of the bound = (bytes / HBM peak) / time; the peak is MI355X_MICROARCH.md's 8.0 TB/s spec figure (6.29 TB/s is
       what a float4 copy reaches there).
-  (b) `runner`: frames/s of SplitPipelinedRunner at bs = 1 with three input forms in one process, alternated in blocks:
+  (b) `runner`: frames/s of SplitPipelinedRunner at bs = 1 with these input forms in one process, alternated in blocks:
       fp32 frames resident in HBM (what bench.py times), fp32 frames in pinned host memory (bench.py --h2d, 13.0 MB per
-      frame), raw u8 frames in pinned host memory with the device ingest (25.9 MB per frame); plus raw frames resident in
-      HBM, which splits the raw form's cost into launches and copy. Same weights, and the same pictures: the fp32 frames
-      are the ingest's own output widened to fp32, so every form decodes the same operands.
+      frame), raw u8 BGR frames in pinned host memory with the device ingest (25.9 MB per frame), NV12 frames in pinned
+      host memory (13.0 MB per frame, raw_format="nv12"); plus raw and NV12 frames resident in HBM, which splits each
+      raw form's cost into launches and copy. Same weights, and the same pictures: the BGR frames are the NV12 frames
+      converted by the ingest's own rule, and the fp32 frames are the ingest's output widened to fp32, so every form
+      decodes the same operands.
   (c) `cpu_pillow_ms`: the same preprocessing of one six-camera frame with Pillow + numpy on one CPU thread, if Pillow
       imports (a CPU number about CPU work).
 
@@ -34,17 +37,38 @@ HBM_COPY = 6.29e12      # bytes/s, measured float4 copy (same table)
 CONFIGS = {"r50_704x256": dict(resize=0.44, crop=(0, 140, 704, 396)), "r101_1408x512": dict(resize=0.88, crop=(0, 280, 1408, 792))}
 
 
+def nv12_frames(torch, frame_idx):
+    """The synthetic generator's frame as NV12 u8 [1, 6, 1350, 1600] (JFIF forward transform, 2 x 2 chroma means, in fp32 on
+    the device) and as the BGR u8 [1, 6, 900, 1600, 3] the ingest's own rule turns it into: the same picture in both forms."""
+    from simpb_amd import synth
+    from simpb_amd.preprocess import yuv_coefficients
+    x = synth.raw_frames(1, frame_idx).cuda().float()
+    b, g, r = x[..., 0], x[..., 1], x[..., 2]
+    y = 0.299 * r + 0.587 * g + 0.114 * b
+    pool = lambda c: c.reshape(c.shape[:-2] + (450, 2, 800, 2)).mean(dim=(-3, -1))   # noqa: E731
+    q = lambda v: (v + 0.5).floor().clamp(0, 255).to(torch.uint8)   # noqa: E731
+    chroma = torch.stack([q(pool((b - y) / 1.772) + 128), q(pool((r - y) / 1.402) + 128)], -1)       # [1, 6, 450, 800, 2]
+    nv12 = torch.cat([q(y), chroma.reshape(1, 6, 450, 1600)], dim=-2).contiguous()
+    yoff, iy, irv, igu, igv, ibu = yuv_coefficients("jfif")
+    up = lambda c: c.repeat_interleave(2, -2).repeat_interleave(2, -1).int() - 128   # noqa: E731
+    c = iy * (nv12[..., :900, :].int() - yoff) + (1 << 15)
+    cb, cr = up(chroma[..., 0]), up(chroma[..., 1])
+    bgr = torch.stack([(c + ibu * cb) >> 16, (c + igu * cb + igv * cr) >> 16, (c + irv * cr) >> 16], -1).clamp(0, 255).to(torch.uint8)
+    return nv12.cpu(), bgr.contiguous().cpu()
+
+
 def kernel_leg(torch, args):
-    from simpb_amd import _lib, synth
+    from simpb_amd import _lib
     from simpb_amd.preprocess import ResamplePlan
-    six = synth.raw_frames(1, 0).cuda()
+    nv12, bgr = nv12_frames(torch, 0)
     out = {}
-    for name, aug in CONFIGS.items():
-        plan = ResamplePlan((900, 1600), aug)
+    for name, aug, fmt in [(n, a, f) for n, a in CONFIGS.items() for f in ("bgr", "nv12")]:
+        plan = ResamplePlan((900, 1600), aug, frame_format=fmt)
+        six = (bgr if fmt == "bgr" else nv12).cuda()
         pitch = int(_lib.lib().simpb_preprocess_mid_pitch(plan.out_hw[1]))
         per_image = plan.bytes_per_image(pitch)
         for bs in (1, 8):
-            frames = six.repeat(bs, 1, 1, 1, 1).contiguous()
+            frames = six.repeat(bs, *([1] * (six.dim() - 1))).contiguous()
             n = bs * 6
             dst = torch.empty(n, *plan.out_hw, 4, dtype=torch.float16, device="cuda")
             plan.reserve(n, "cuda")
@@ -60,7 +84,7 @@ def kernel_leg(torch, args):
             ms = e0.elapsed_time(e1) / args.launches
             nbytes = n * sum(per_image.values())
             floor_ms = nbytes / HBM_PEAK * 1e3
-            out[f"{name}_bs{bs}"] = dict(
+            out[f"{name}_bs{bs}" + ("" if fmt == "bgr" else "_" + fmt)] = dict(
                 ms=round(ms, 5), images=n, launches=args.launches, bytes=nbytes, bytes_per_image=per_image,
                 bytes_per_s=round(nbytes / (ms * 1e-3), 1), share_of_hbm_peak=round(floor_ms / ms, 4),
                 share_of_measured_copy_rate=round(nbytes / HBM_COPY * 1e3 / ms, 4),
@@ -85,7 +109,8 @@ def runner_leg(torch, args):
     from simpb_amd.preprocess import ResamplePlan
     from simpb_amd.runner import SplitPipelinedRunner
     ring = 4
-    raws = [synth.raw_frames(1, f) for f in range(ring)]
+    pairs = [nv12_frames(torch, f) for f in range(ring)]
+    nv12s, raws = [p[0] for p in pairs], [p[1] for p in pairs]
     plan = ResamplePlan((900, 1600), CONFIGS["r50_704x256"])
     # the fp32 form of the same pictures: the ingest's f16 operand widened (exact), as [1, 6, 3, 256, 704]
     fp32 = [plan.run(r.cuda())[..., :3].permute(0, 3, 1, 2).float().contiguous()[None] for r in raws]
@@ -93,18 +118,20 @@ def runner_leg(torch, args):
         "fp32_hbm": dict(frames=fp32, raw=False, bytes_per_frame=0),
         "fp32_pinned_host": dict(frames=[x.cpu().pin_memory() for x in fp32], raw=False, bytes_per_frame=fp32[0].numel() * 4),
         "raw_u8_pinned_host": dict(frames=[r.pin_memory() for r in raws], raw=True, bytes_per_frame=raws[0].numel()),
-        # not a deployment form (a decoder's frames start on the host): raw frames resident in HBM, which splits the raw
-        # form's cost into the ingest launches (this minus fp32_hbm) and the copy (raw_u8_pinned_host minus this)
+        "nv12_pinned_host": dict(frames=[r.pin_memory() for r in nv12s], raw="nv12", bytes_per_frame=nv12s[0].numel()),
+        # not deployment forms (a decoder's frames start on the host): raw frames resident in HBM, which split a raw
+        # form's cost into the ingest launches (this minus fp32_hbm) and the copy (the pinned form minus this)
         "raw_u8_hbm": dict(frames=[r.cuda() for r in raws], raw=True, bytes_per_frame=0),
+        "nv12_hbm": dict(frames=[r.cuda() for r in nv12s], raw="nv12", bytes_per_frame=0),
     }
     if args.profile_raw:   # the run for rocprofv3 --kernel-trace --stats: the raw form alone
         forms = {"raw_u8_pinned_host": forms["raw_u8_pinned_host"]}
     dev = torch.device("cuda")
-    runners = {False: None if args.profile_raw else SplitPipelinedRunner(build_model(torch), 1, (256, 704), capacity=1536, device=dev,
-                                                                          use_graph=True),
-               True: SplitPipelinedRunner(build_model(torch), 1, (256, 704), capacity=1536, device=dev, use_graph=True,
-                                          raw_input=(900, 1600))}
-    count = {False: 0, True: 0}
+    make = lambda **kw: SplitPipelinedRunner(build_model(torch), 1, (256, 704), capacity=1536, device=dev, use_graph=True, **kw)   # noqa: E731
+    runners = {False: None if args.profile_raw else make(),
+               True: make(raw_input=(900, 1600)),
+               "nv12": None if args.profile_raw else make(raw_input=(900, 1600), raw_format="nv12")}
+    count = {False: 0, True: 0, "nv12": 0}
 
     def run(form, steps):
         r = runners[form["raw"]]
@@ -138,6 +165,11 @@ def runner_leg(torch, args):
     out["fp32_copy_ms"] = round(out["fp32_pinned_host"]["ms_per_step"] - out["fp32_hbm"]["ms_per_step"], 4)
     out["raw_minus_fp32_pinned_ms"] = round(out["raw_u8_pinned_host"]["ms_per_step"] - out["fp32_pinned_host"]["ms_per_step"], 4)
     out["raw_minus_fp32_hbm_ms"] = round(out["raw_u8_pinned_host"]["ms_per_step"] - out["fp32_hbm"]["ms_per_step"], 4)
+    out["nv12_ingest_launches_ms"] = round(out["nv12_hbm"]["ms_per_step"] - out["fp32_hbm"]["ms_per_step"], 4)
+    out["nv12_copy_ms"] = round(out["nv12_pinned_host"]["ms_per_step"] - out["nv12_hbm"]["ms_per_step"], 4)
+    out["nv12_minus_raw_pinned_ms"] = round(out["nv12_pinned_host"]["ms_per_step"] - out["raw_u8_pinned_host"]["ms_per_step"], 4)
+    out["nv12_minus_fp32_pinned_ms"] = round(out["nv12_pinned_host"]["ms_per_step"] - out["fp32_pinned_host"]["ms_per_step"], 4)
+    out["noise_ms"] = max(v["spread_ms"] for v in out.values() if isinstance(v, dict))   # the largest spread between blocks
     return out
 
 
