@@ -73,6 +73,19 @@ int simpb_dfa_fused_forward(
     const float* anchor, const float* learnable, const float* fix_scale, const float* projection_mat, const float* image_wh,
     const float* feat_logits, const float* cam_logits, float* loc_out, float* weights_out, int batch_size, int num_cams,
     int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups, void* stream);
+/* The same with `cam_valid` u8 [batch_size, num_cams] (device; NULL = every camera, identical to simpb_dfa_fused_forward): a
+ * camera with 0 delivered no frame, and stream b is aggregated exactly as the reference aggregates it when given the
+ * remaining cameras only. The softmax over (cam, level, point) runs over the valid cameras: a masked camera's logits count
+ * as -inf by substitution, so its weights are exactly 0.0 (weights_out too) and its locations are (-1, -1) (loc_out too).
+ * Nothing of a masked camera is read -- not its tokens (no tap is issued), its projection_mat / image_wh rows or its
+ * cam_logits row: they may hold anything, NaN included. A stream with no valid camera gives zeros (callers refuse it). */
+int simpb_dfa_fused_forward_cams(
+    float* output, const void* mc_ms_feat, int feat_is_f16, const int* spatial_shape, const int* scale_start_index,
+    const float* anchor, const float* learnable, const float* fix_scale, const float* projection_mat, const float* image_wh,
+    const float* feat_logits, const float* cam_logits, float* loc_out, float* weights_out, int batch_size, int num_cams,
+    int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups,
+    const unsigned char* cam_valid, void* stream);
+
 
 /* Replaces `deformable_aggregation_grad(...)` (ops/src/deformable_aggregation.cpp:64-84, launcher
  * ops/src/deformable_aggregation_cuda.cu:291-318, kernels :62-126,190-262), the backward of the
@@ -631,6 +644,13 @@ int simpb_msda_prep(float* sampling_loc, float* attn_weight, const float* raw, i
 int simpb_dfa_points(float* loc, float* key_points, const float* anchor, const float* learnable,
                      const float* fix_scale, const float* projection_mat, const float* image_wh, int batch_size,
                      int num_anchors, int num_fix, int num_learn, int num_cams, void* stream);
+/* The same with `cam_valid` u8 [batch_size, num_cams] (device; NULL = every camera, identical to simpb_dfa_points): a camera
+ * with 0 gets loc = (-1, -1), which the aggregation operator skips (outside (0, 1)), so its tokens are never touched; its
+ * projection_mat and image_wh rows are not read and may hold anything. */
+int simpb_dfa_points_cams(float* loc, float* key_points, const float* anchor, const float* learnable,
+                          const float* fix_scale, const float* projection_mat, const float* image_wh, int batch_size,
+                          int num_anchors, int num_fix, int num_learn, int num_cams, const unsigned char* cam_valid,
+                          void* stream);
 
 /* Weights of the 3D deformable aggregation in its own layout (models/blocks.py:164-187 + :132-143):
  *   feat_logits f32 [bs, A, lvl*pts*groups] = weights_fc(feature + anchor_embed)
@@ -638,6 +658,12 @@ int simpb_dfa_points(float* loc, float* key_points, const float* anchor, const f
  *   weights     f32 [bs, A, pts, cams, lvl, groups] = softmax over (cam, lvl, pts) per group of their sum */
 int simpb_dfa_weights(float* weights, const float* feat_logits, const float* cam_logits, int batch_size,
                       int num_anchors, int num_cams, int num_levels, int num_pts, int num_groups, void* stream);
+/* The same with `cam_valid` u8 [batch_size, num_cams] (device; NULL = every camera, identical to simpb_dfa_weights): the
+ * softmax runs over the valid cameras only. A masked camera's logits count as -inf without its cam_logits row being read
+ * (it may hold NaN): its weights are exactly 0.0, the others are renormalised. No valid camera: all weights 0.0. */
+int simpb_dfa_weights_cams(float* weights, const float* feat_logits, const float* cam_logits, int batch_size,
+                           int num_anchors, int num_cams, int num_levels, int num_pts, int num_groups,
+                           const unsigned char* cam_valid, void* stream);
 
 /* Adaptive query allocation, replaces DynamicQueryAllocation.projection_allocation
  * (models/allocation.py:27-144) in three steps; the caller reads `count` back between steps 2
@@ -653,6 +679,14 @@ int simpb_dfa_weights(float* weights, const float* feat_logits, const float* cam
 int simpb_alloc_project(unsigned char* flag, float* sel_xy, float* depth, const float* anchor,
                         const float* projection_mat, int batch_size, int num_anchors, int num_cams,
                         float img_w, float img_h, float limit_w, float limit_l, float limit_h, void* stream);
+/* The same with `cam_valid` u8 [batch_size, num_cams] (device; NULL = every camera, identical to simpb_alloc_project): a
+ * (stream, camera) with 0 delivered no frame -- its flag row is 0 (forced: its matrix is not read and may hold anything), so
+ * step 2 counts 0 and step 3 gives it an empty camera group. This is the single place of the allocation that knows the
+ * camera mask: the stepwise, static and independent-streams forms all get it through this step. */
+int simpb_alloc_project_cams(unsigned char* flag, float* sel_xy, float* depth, const float* anchor,
+                             const float* projection_mat, int batch_size, int num_anchors, int num_cams, float img_w,
+                             float img_h, float limit_w, float limit_l, float limit_h, const unsigned char* cam_valid,
+                             void* stream);
 
 /* Step 2 (:86-123): per (batch, cam) stable compaction in ascending anchor order.
  *   count i32 [batch_size, num_cams]; order i32 [batch_size, num_cams, num_anchors] (first count valid) */
@@ -688,6 +722,13 @@ int simpb_alloc_static(unsigned char* flag, float* sel_xy, float* depth, int* co
                        int* query_cam, const float* anchor, const float* projection_mat, int batch_size, int num_anchors,
                        int num_cams, int capacity, float img_w, float img_h, float limit_w, float limit_l, float limit_h,
                        void* stream);
+/* The same with `cam_valid` u8 [batch_size, num_cams] (device; NULL = every camera, identical to simpb_alloc_static): see
+ * simpb_alloc_project_cams. A masked (stream, camera) has count 0 and a2q = -1 and cannot raise overflow. */
+int simpb_alloc_static_cams(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order, int* group_start,
+                            int* overflow, float* ref_pts2d, float* ref_depth2d, int* q2a, int* is_center, int* a2q,
+                            int* query_cam, const float* anchor, const float* projection_mat, int batch_size,
+                            int num_anchors, int num_cams, int capacity, float img_w, float img_h, float limit_w,
+                            float limit_l, float limit_h, const unsigned char* cam_valid, void* stream);
 
 /* The allocation for a batch of INDEPENDENT camera streams ("keep per-sample counts in the native path"):
  * DynamicQueryAllocation.projection_allocation (models/allocation.py:27-144) pads every camera group to the max over the
@@ -713,6 +754,16 @@ int simpb_alloc_ragged_active(unsigned char* flag, float* sel_xy, float* depth, 
                               int* query_cam, const float* anchor, const float* projection_mat, int batch_size,
                               int num_anchors, int num_cams, int per_stream, float img_w, float img_h, float limit_w,
                               float limit_l, float limit_h, const unsigned char* active, void* stream);
+/* The same with `cam_valid` u8 [batch_size, num_cams] as well (device; NULL = every camera, identical to
+ * simpb_alloc_ragged_active): a camera with 0 in an active stream is an empty group -- flag row 0 without its matrix being
+ * read, count 0, a2q = -1 -- and the groups behind it move down, as the streams behind a paused one do. A paused stream's
+ * camera row is not looked at. */
+int simpb_alloc_ragged_cams(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order, int* group_start,
+                            int* overflow, float* ref_pts2d, float* ref_depth2d, int* q2a, int* is_center, int* a2q,
+                            int* query_cam, const float* anchor, const float* projection_mat, int batch_size,
+                            int num_anchors, int num_cams, int per_stream, float img_w, float img_h, float limit_w,
+                            float limit_l, float limit_h, const unsigned char* active, const unsigned char* cam_valid,
+                            void* stream);
 
 /* out[b, s, :] = src[b, q2a[b, s], :], zeros where q2a < 0: replaces
  * torch.matmul(ref_trans_matrix, instance_feature) (models/simpb_head.py:438). channels % 4 == 0. */

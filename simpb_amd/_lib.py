@@ -27,6 +27,7 @@ SIGNATURES = {
     "simpb_timing_reset": ([], None),
     "simpb_deformable_aggregation_forward": ([_P] * 6 + [_I] * 8 + [_P], _I),
     "simpb_dfa_fused_forward": ([_P, _P, _I] + [_P] * 11 + [_I] * 9 + [_P], _I),
+    "simpb_dfa_fused_forward_cams": ([_P, _P, _I] + [_P] * 11 + [_I] * 9 + [_P, _P], _I),
     "simpb_deformable_aggregation_backward": ([_P] * 9 + [_I] * 8 + [_P], _I),
     "simpb_ms_deform_attn_grouped_forward": ([_P] * 7 + [_I] * 8 + [_P], _I),
     "simpb_msda_linear_forward": ([_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P] + [_I] * 8 + [_P], _I),
@@ -70,6 +71,9 @@ SIGNATURES = {
     "simpb_msda_prep": ([_P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P], _I),
     "simpb_dfa_points": ([_P] * 7 + [_I] * 5 + [_P], _I),
     "simpb_dfa_weights": ([_P] * 3 + [_I] * 6 + [_P], _I),
+    "simpb_dfa_points_cams": ([_P] * 7 + [_I] * 5 + [_P, _P], _I),
+    "simpb_dfa_weights_cams": ([_P] * 3 + [_I] * 6 + [_P, _P], _I),
+    "simpb_alloc_project_cams": ([_P] * 5 + [_I] * 3 + [_F] * 5 + [_P, _P], _I),
     "simpb_alloc_project": ([_P] * 5 + [_I] * 3 + [_F] * 5 + [_P], _I),
     "simpb_alloc_compact": ([_P] * 3 + [_I] * 3 + [_P], _I),
     "simpb_alloc_group_start": ([_P] * 3 + [_I] * 3 + [_P], _I),
@@ -77,6 +81,8 @@ SIGNATURES = {
     "simpb_alloc_static": ([_P] * 15 + [_I] * 4 + [_F] * 5 + [_P], _I),
     "simpb_alloc_ragged": ([_P] * 15 + [_I] * 4 + [_F] * 5 + [_P], _I),
     "simpb_alloc_ragged_active": ([_P] * 15 + [_I] * 4 + [_F] * 5 + [_P, _P], _I),
+    "simpb_alloc_static_cams": ([_P] * 15 + [_I] * 4 + [_F] * 5 + [_P, _P], _I),
+    "simpb_alloc_ragged_cams": ([_P] * 15 + [_I] * 4 + [_F] * 5 + [_P, _P, _P], _I),
     "simpb_gather_rows": ([_P] * 3 + [_I] * 4 + [_P], _I),
     "simpb_aggregate_2d_to_3d": ([_P] * 8 + [_I] * 5 + [_P], _I),
     "simpb_aggregate_2d_to_3d_alpha": ([_P] * 9 + [_I, _I, _P, _P] + [_I] * 5 + [_P], _I),

@@ -16,18 +16,24 @@ constexpr int kMaxStaticCams = 8;   // cameras of the static-capacity path (simp
 
 // ---- step 1: one thread per (batch, anchor, cam): 9 projected points -> flag, 2D ref, depth. `active` (u8 [bs], may be
 // NULL = every stream): a stream that sits this frame out gets flag 0 for every (anchor, cam) without its anchors or
-// matrices being read (they may hold anything), so steps 2-3 give it no slots.
+// matrices being read (they may hold anything), so steps 2-3 give it no slots. MASKED: `cam_valid` (u8 [bs, cams]) is read
+// as well, and a (stream, camera) with 0 takes the same exit -- a camera that delivered no frame is an empty camera group,
+// its matrix is not read. The unmasked instantiation is the kernel as it was (cam_valid unused).
+template <bool MASKED>
 __global__ void alloc_project_kernel(unsigned char* __restrict__ flag, float* __restrict__ sel_xy,
                                      float* __restrict__ depth, const float* __restrict__ anchor,
                                      const float* __restrict__ proj, int bs, int A, int cams, float img_w, float img_h,
                                      float lim_w, float lim_l, float lim_h, int* __restrict__ a2q_fill,
-                                     const unsigned char* __restrict__ active) {
+                                     const unsigned char* __restrict__ active,
+                                     const unsigned char* __restrict__ cam_valid) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= bs * A * cams) return;
   const int cam = idx % cams;
   const int a = (idx / cams) % A;
   const int b = idx / (cams * A);
-  if (active && !active[b]) {
+  bool off = active && !active[b];
+  if (MASKED) off = off || !cam_valid[b * cams + cam];
+  if (off) {
     const size_t o = ((size_t)b * cams + cam) * A + a;
     flag[o] = 0;
     sel_xy[2 * o] = 0.f;
@@ -350,23 +356,43 @@ __global__ __launch_bounds__(64) void aggregate_kernel(float* __restrict__ out_q
   }
 }
 
+// step 1 of every form: the masked instantiation only where a camera mask is given
+inline void launch_project(hipStream_t s, unsigned char* flag, float* sel_xy, float* depth, const float* anchor,
+                           const float* proj, int bs, int A, int cams, float img_w, float img_h, float lim_w, float lim_l,
+                           float lim_h, int* a2q_fill, const unsigned char* active, const unsigned char* cam_valid) {
+  const int n = bs * A * cams;
+  if (cam_valid)
+    hipLaunchKernelGGL(alloc_project_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, flag, sel_xy, depth, anchor, proj, bs,
+                       A, cams, img_w, img_h, lim_w, lim_l, lim_h, a2q_fill, active, cam_valid);
+  else
+    hipLaunchKernelGGL(alloc_project_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, s, flag, sel_xy, depth, anchor, proj,
+                       bs, A, cams, img_w, img_h, lim_w, lim_l, lim_h, a2q_fill, active,
+                       static_cast<const unsigned char*>(nullptr));
+}
+
 inline int status() { return simpb_check_launch(); }
 inline void clear_stale() { (void)hipGetLastError(); }  // errors left by the caller's earlier runtime calls
 
 }  // namespace
 
+extern "C" int simpb_alloc_project_cams(unsigned char* flag, float* sel_xy, float* depth, const float* anchor,
+                                        const float* projection_mat, int batch_size, int num_anchors, int num_cams,
+                                        float img_w, float img_h, float limit_w, float limit_l, float limit_h,
+                                        const unsigned char* cam_valid, void* stream) {
+  if (!flag || !sel_xy || !depth || !anchor || !projection_mat || batch_size <= 0 || num_anchors <= 0 || num_cams <= 0)
+    return SIMPB_EINVAL;
+  clear_stale();
+  launch_project(static_cast<hipStream_t>(stream), flag, sel_xy, depth, anchor, projection_mat, batch_size, num_anchors,
+                 num_cams, img_w, img_h, limit_w, limit_l, limit_h, nullptr, nullptr, cam_valid);
+  return status();
+}
+
 extern "C" int simpb_alloc_project(unsigned char* flag, float* sel_xy, float* depth, const float* anchor,
                                    const float* projection_mat, int batch_size, int num_anchors, int num_cams,
                                    float img_w, float img_h, float limit_w, float limit_l, float limit_h,
                                    void* stream) {
-  if (!flag || !sel_xy || !depth || !anchor || !projection_mat || batch_size <= 0 || num_anchors <= 0 || num_cams <= 0)
-    return SIMPB_EINVAL;
-  const int n = batch_size * num_anchors * num_cams;
-  clear_stale();
-  hipLaunchKernelGGL(alloc_project_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), flag,
-                     sel_xy, depth, anchor, projection_mat, batch_size, num_anchors, num_cams, img_w, img_h, limit_w,
-                     limit_l, limit_h, static_cast<int*>(nullptr), static_cast<const unsigned char*>(nullptr));
-  return status();
+  return simpb_alloc_project_cams(flag, sel_xy, depth, anchor, projection_mat, batch_size, num_anchors, num_cams, img_w, img_h,
+                                  limit_w, limit_l, limit_h, nullptr, stream);
 }
 
 extern "C" int simpb_alloc_compact(int* count, int* order, const unsigned char* flag, int batch_size, int num_anchors,
@@ -451,26 +477,58 @@ extern "C" int simpb_aggregate_2d_to_3d(float* out_q, float* out_pos, const floa
                                         batch_size, num_anchors, num_cams, num_query, channels, stream);
 }
 
-extern "C" int simpb_alloc_static(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order, int* group_start,
-                                  int* overflow, float* ref_pts2d, float* ref_depth2d, int* q2a, int* is_center, int* a2q,
-                                  int* query_cam, const float* anchor, const float* projection_mat, int batch_size,
-                                  int num_anchors, int num_cams, int capacity, float img_w, float img_h, float limit_w,
-                                  float limit_l, float limit_h, void* stream) {
+extern "C" int simpb_alloc_static_cams(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order,
+                                       int* group_start, int* overflow, float* ref_pts2d, float* ref_depth2d, int* q2a,
+                                       int* is_center, int* a2q, int* query_cam, const float* anchor,
+                                       const float* projection_mat, int batch_size, int num_anchors, int num_cams, int capacity,
+                                       float img_w, float img_h, float limit_w, float limit_l, float limit_h,
+                                       const unsigned char* cam_valid, void* stream) {
   if (!flag || !sel_xy || !depth || !count || !order || !group_start || !overflow || !ref_pts2d || !ref_depth2d || !q2a ||
       !is_center || !a2q || !query_cam || !anchor || !projection_mat || batch_size <= 0 || num_anchors <= 0 ||
       num_cams <= 0 || num_cams > kMaxStaticCams || capacity <= 0)
     return SIMPB_EINVAL;
   clear_stale();
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int n = batch_size * num_anchors * num_cams;
-  hipLaunchKernelGGL(alloc_project_kernel, dim3((n + 255) / 256), dim3(256), 0, s, flag, sel_xy, depth, anchor, projection_mat,
-                     batch_size, num_anchors, num_cams, img_w, img_h, limit_w, limit_l, limit_h, a2q,
-                     static_cast<const unsigned char*>(nullptr));
+  launch_project(s, flag, sel_xy, depth, anchor, projection_mat, batch_size, num_anchors, num_cams, img_w, img_h, limit_w,
+                 limit_l, limit_h, a2q, nullptr, cam_valid);
   hipLaunchKernelGGL(alloc_compact_kernel, dim3(batch_size * num_cams), dim3(256), 0, s, count, order, flag, num_anchors);
   const int ns = batch_size * capacity;
   hipLaunchKernelGGL(alloc_scatter_kernel, dim3((ns + 255) / 256), dim3(256), 0, s, ref_pts2d, ref_depth2d, q2a, is_center, a2q,
                      query_cam, static_cast<const int*>(nullptr), count, order, flag, sel_xy, depth, batch_size, num_anchors,
                      num_cams, capacity, img_w, img_h, group_start, overflow);
+  return status();
+}
+
+extern "C" int simpb_alloc_static(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order, int* group_start,
+                                  int* overflow, float* ref_pts2d, float* ref_depth2d, int* q2a, int* is_center, int* a2q,
+                                  int* query_cam, const float* anchor, const float* projection_mat, int batch_size,
+                                  int num_anchors, int num_cams, int capacity, float img_w, float img_h, float limit_w,
+                                  float limit_l, float limit_h, void* stream) {
+  return simpb_alloc_static_cams(flag, sel_xy, depth, count, order, group_start, overflow, ref_pts2d, ref_depth2d, q2a, is_center,
+                                 a2q, query_cam, anchor, projection_mat, batch_size, num_anchors, num_cams, capacity, img_w, img_h,
+                                 limit_w, limit_l, limit_h, nullptr, stream);
+}
+
+extern "C" int simpb_alloc_ragged_cams(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order,
+                                       int* group_start, int* overflow, float* ref_pts2d, float* ref_depth2d, int* q2a,
+                                       int* is_center, int* a2q, int* query_cam, const float* anchor,
+                                       const float* projection_mat, int batch_size, int num_anchors, int num_cams,
+                                       int per_stream, float img_w, float img_h, float limit_w, float limit_l, float limit_h,
+                                       const unsigned char* active, const unsigned char* cam_valid, void* stream) {
+  if (!flag || !sel_xy || !depth || !count || !order || !group_start || !overflow || !ref_pts2d || !ref_depth2d || !q2a ||
+      !is_center || !a2q || !query_cam || !anchor || !projection_mat || batch_size <= 0 || num_anchors <= 0 ||
+      num_cams <= 0 || batch_size * num_cams > kMaxRaggedGroups || per_stream <= 0 ||
+      (long long)batch_size * per_stream > 0x7fffffffll / 4 || (long long)batch_size * num_anchors > 0x7fffffffll / 4)
+    return SIMPB_EINVAL;
+  clear_stale();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_project(s, flag, sel_xy, depth, anchor, projection_mat, batch_size, num_anchors, num_cams, img_w, img_h, limit_w,
+                 limit_l, limit_h, a2q, active, cam_valid);
+  hipLaunchKernelGGL(alloc_compact_kernel, dim3(batch_size * num_cams), dim3(256), 0, s, count, order, flag, num_anchors);
+  const int ns = batch_size * per_stream;
+  hipLaunchKernelGGL(alloc_scatter_ragged_kernel, dim3((ns + 255) / 256), dim3(256), 0, s, ref_pts2d, ref_depth2d, q2a,
+                     is_center, a2q, query_cam, count, order, flag, sel_xy, depth, batch_size, num_anchors, num_cams, per_stream,
+                     img_w, img_h, group_start, overflow);
   return status();
 }
 
@@ -480,22 +538,9 @@ extern "C" int simpb_alloc_ragged_active(unsigned char* flag, float* sel_xy, flo
                                          const float* projection_mat, int batch_size, int num_anchors, int num_cams,
                                          int per_stream, float img_w, float img_h, float limit_w, float limit_l, float limit_h,
                                          const unsigned char* active, void* stream) {
-  if (!flag || !sel_xy || !depth || !count || !order || !group_start || !overflow || !ref_pts2d || !ref_depth2d || !q2a ||
-      !is_center || !a2q || !query_cam || !anchor || !projection_mat || batch_size <= 0 || num_anchors <= 0 ||
-      num_cams <= 0 || batch_size * num_cams > kMaxRaggedGroups || per_stream <= 0 ||
-      (long long)batch_size * per_stream > 0x7fffffffll / 4 || (long long)batch_size * num_anchors > 0x7fffffffll / 4)
-    return SIMPB_EINVAL;
-  clear_stale();
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int n = batch_size * num_anchors * num_cams;
-  hipLaunchKernelGGL(alloc_project_kernel, dim3((n + 255) / 256), dim3(256), 0, s, flag, sel_xy, depth, anchor, projection_mat,
-                     batch_size, num_anchors, num_cams, img_w, img_h, limit_w, limit_l, limit_h, a2q, active);
-  hipLaunchKernelGGL(alloc_compact_kernel, dim3(batch_size * num_cams), dim3(256), 0, s, count, order, flag, num_anchors);
-  const int ns = batch_size * per_stream;
-  hipLaunchKernelGGL(alloc_scatter_ragged_kernel, dim3((ns + 255) / 256), dim3(256), 0, s, ref_pts2d, ref_depth2d, q2a,
-                     is_center, a2q, query_cam, count, order, flag, sel_xy, depth, batch_size, num_anchors, num_cams, per_stream,
-                     img_w, img_h, group_start, overflow);
-  return status();
+  return simpb_alloc_ragged_cams(flag, sel_xy, depth, count, order, group_start, overflow, ref_pts2d, ref_depth2d, q2a, is_center,
+                                 a2q, query_cam, anchor, projection_mat, batch_size, num_anchors, num_cams, per_stream, img_w,
+                                 img_h, limit_w, limit_l, limit_h, active, nullptr, stream);
 }
 
 extern "C" int simpb_alloc_ragged(unsigned char* flag, float* sel_xy, float* depth, int* count, int* order, int* group_start,

@@ -80,6 +80,7 @@ struct DfaArgs {
   float* loc_out;             // optional [bs, A, P, cams, 2]      (tests / measurement)
   float* w_out;               // optional [bs, A, P, cams, L, G]   (tests)
   int cams, num_feat, C, L, A, num_fix, num_learn, G;
+  const unsigned char* cam_valid;   // optional u8 [bs, cams] (masked instantiation only): 0 = the camera delivered no frame
 };
 
 // operands of one sampling location (key point p in camera cam), fetched before anything is computed from them
@@ -90,9 +91,14 @@ struct PointOps {
   bool fixed;
 };
 
-template <int CAMS, int NUM_FIX, int NUM_LEARN>
-__device__ __forceinline__ void fetch_point(PointOps& o, const DfaArgs& k, size_t row, int b, int i) {
-  const int p = i / CAMS, cam = i - p * CAMS;
+// vmask (masked form): bit c = camera c of this stream is valid; `spare` a valid camera (or 0). The rows of a masked camera
+// are not read: its loads go to the spare camera's rows and their results are dropped.
+template <int CAMS, int NUM_FIX, int NUM_LEARN, bool MASKED = false>
+__device__ __forceinline__ void fetch_point(PointOps& o, const DfaArgs& k, size_t row, int b, int i, unsigned vmask = 0,
+                                            int spare = 0) {
+  const int p = i / CAMS;
+  int cam = i - p * CAMS;
+  if (MASKED) cam = ((vmask >> cam) & 1u) ? cam : spare;
   o.fixed = p < NUM_FIX;
   const float* f = o.fixed ? k.fix_scale + p * 3 : k.learn + (row * NUM_LEARN + (p - NUM_FIX)) * 3;
   o.f0 = f[0]; o.f1 = f[1]; o.f2 = f[2];
@@ -126,7 +132,13 @@ __device__ __forceinline__ float2 project_point(const PointOps& o, const float* 
 
 // CAMS / L / NUM_FIX / NUM_LEARN / G / C are compile-time: the index arithmetic of the prologue (entry -> (cam, level, point))
 // is then shifts and multiplies; with run-time divisors it was ~3 000 instructions per thread and as long as the gather.
-template <class FEAT, int CAMS, int L, int NUM_FIX, int NUM_LEARN, int G, int C>
+//
+// MASKED (k.cam_valid given): the mask row of stream b is workgroup-uniform and loaded once. A masked camera's logits are
+// -inf by substitution (its cam_logits row is not read), so its weights are exactly 0.0 and the softmax runs over the valid
+// cameras; its sampling locations are (-1, -1) without its matrix being read, and its bits are cleared from the tap
+// ballots, so no tap of its tokens is ever issued (they may hold NaN). A stream with no valid camera (refused on the host)
+// gives zeros: no division by the zero sum. MASKED = false is the kernel as it was.
+template <class FEAT, int CAMS, int L, int NUM_FIX, int NUM_LEARN, int G, int C, bool MASKED>
 __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
   __shared__ float s_w[kMaxW];            // [(p * cams + cam) * L + lvl][G]: exp(logit - max), NOT yet divided by the sum
   __shared__ float4 s_red[kWaves][64];    // softmax reductions first, the waves' partial rows at the end
@@ -144,6 +156,15 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
   // ---- every global operand of the prologue is requested up front (indices clamped, loads unconditional): the
   // prologue then costs ONE memory round trip, not one per dependent step (all workgroups of the launch are resident at
   // once and walk their phases in step, so prologue latency adds to the launch time in full)
+  unsigned vmask = (1u << CAMS) - 1u;   // bit c: camera c of this stream delivered a frame
+  int spare = 0;
+  if (MASKED) {
+    vmask = 0u;
+#pragma unroll
+    for (int cam = 0; cam < CAMS; ++cam) vmask |= (k.cam_valid[b * CAMS + cam] ? 1u : 0u) << cam;
+    vmask = __builtin_amdgcn_readfirstlane(vmask);
+    spare = vmask ? __builtin_ctz(vmask) : 0;
+  }
   float av[8];
   {
     const float* an = k.anchor + row * 11;
@@ -151,7 +172,8 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
     for (int j = 0; j < 8; ++j) av[j] = an[j];
   }
   PointOps op;   // thread i < PK computes sampling location i = p * cams + cam, once per workgroup
-  fetch_point<CAMS, NUM_FIX, NUM_LEARN>(op, k, row, b, min(tid, PK - 1));
+  if (MASKED) fetch_point<CAMS, NUM_FIX, NUM_LEARN, true>(op, k, row, b, min(tid, PK - 1), vmask, spare);
+  else fetch_point<CAMS, NUM_FIX, NUM_LEARN>(op, k, row, b, min(tid, PK - 1));
   // softmax entries of this thread: group g_sm, (level, point) pairs lp = slice + j * slices, every camera
   constexpr int NJ = (LP + slices - 1) / slices;
   float lg[NJ][CAMS];
@@ -163,13 +185,27 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
       const int lp = min(slice + j * slices, LP - 1);
       const float f = fl[lp * G + g_sm];
 #pragma unroll
-      for (int cam = 0; cam < CAMS; ++cam) lg[j][cam] = f + cl[cam * LPG + lp * G + g_sm];   // (blocks.py:177-179)
+      for (int cam = 0; cam < CAMS; ++cam) {
+        if (MASKED) {   // a masked camera: -inf by substitution, the load goes to the spare camera's row
+          const bool on = (vmask >> cam) & 1u;
+          const float c = cl[(on ? cam : spare) * LPG + lp * G + g_sm];
+          lg[j][cam] = on ? f + c : -INFINITY;
+        } else {
+          lg[j][cam] = f + cl[cam * LPG + lp * G + g_sm];   // (blocks.py:177-179)
+        }
+      }
     }
   }
 
   // ---- sampling locations (dfa_points_kernel's arithmetic), published through LDS
-  if (tid < PK) s_loc[tid] = project_point(op, av);
-  else if (tid < 128) s_loc[tid] = make_float2(-1.f, -1.f);
+  if (MASKED) {
+    const bool on = (vmask >> (min(tid, PK - 1) % CAMS)) & 1u;
+    if (tid < PK) s_loc[tid] = on ? project_point(op, av) : make_float2(-1.f, -1.f);
+    else if (tid < 128) s_loc[tid] = make_float2(-1.f, -1.f);
+  } else {
+    if (tid < PK) s_loc[tid] = project_point(op, av);
+    else if (tid < 128) s_loc[tid] = make_float2(-1.f, -1.f);
+  }
 
   // ---- softmax over the cams * L * P entries of each group (dfa_weights_kernel's arithmetic): thread -> (group, slice);
   // lanes of one group sit G apart inside a wave, so a group's reduction is xor shuffles + one LDS meeting. The division
@@ -197,7 +233,8 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
         float* w = s_w + (pt * cams * L + lvl) * G + g_sm;   // [(pt * cams + cam) * L + lvl][G]
 #pragma unroll
         for (int cam = 0; cam < CAMS; ++cam) {
-          const float v = expf(lg[j][cam] - m);
+          float v = expf(lg[j][cam] - m);
+          if (MASKED && !((vmask >> cam) & 1u)) v = 0.f;   // exactly 0.0 (and not exp(-inf - -inf) when no camera is valid)
           w[cam * L * G] = v;
           sum += v;
         }
@@ -207,13 +244,15 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
     if (lane < G) red[256 + wave * 64 + lane] = sum;
     __syncthreads();   // s_w and s_loc complete, sums in place
     if (k.w_out) {
-      const float inv = 1.f / (red[256 + g_sm] + red[256 + 64 + g_sm] + red[256 + 128 + g_sm] + red[256 + 192 + g_sm]);
+      float inv = 1.f / (red[256 + g_sm] + red[256 + 64 + g_sm] + red[256 + 128 + g_sm] + red[256 + 192 + g_sm]);
+      if (MASKED && vmask == 0u) inv = 0.f;
       float* wo = k.w_out + row * (size_t)n * G;
       for (int e = slice; e < n; e += slices) wo[e * G + g_sm] = s_w[e * G + g_sm] * inv;   // (same layout)
       simpb::stores_retired();
     }
     const int gch = (lane * 4 < C ? lane * 4 : 0) / (C / G);   // group of this lane's channels in the aggregation below
     inv_sum = 1.f / (red[256 + gch] + red[256 + 64 + gch] + red[256 + 128 + gch] + red[256 + 192 + gch]);
+    if (MASKED && vmask == 0u) inv_sum = 0.f;   // no valid camera: zeros out, not 0 x inf
   }
   // lane i (and i + 64) of EVERY wave holds location i
   const float2 l0 = s_loc[lane], l1 = s_loc[lane + 64];
@@ -223,8 +262,10 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
     if (lane + 64 < PK) lo[lane + 64] = l1;
     simpb::stores_retired();   // (measurement-only output: nothing of it in flight beside the gather's counted waits)
   }
-  const unsigned long long m0 = __ballot(l0.x > 0.f && l0.x < 1.f && l0.y > 0.f && l0.y < 1.f);
-  const unsigned long long m1 = __ballot(l1.x > 0.f && l1.x < 1.f && l1.y > 0.f && l1.y < 1.f);
+  // (masked form: location i belongs to camera i % cams; a masked camera's bit is cleared whatever its location holds)
+  const bool on0 = !MASKED || ((vmask >> (lane % CAMS)) & 1u), on1 = !MASKED || ((vmask >> ((lane + 64) % CAMS)) & 1u);
+  const unsigned long long m0 = __ballot(on0 && l0.x > 0.f && l0.x < 1.f && l0.y > 0.f && l0.y < 1.f);
+  const unsigned long long m1 = __ballot(on1 && l1.x > 0.f && l1.x < 1.f && l1.y > 0.f && l1.y < 1.f);
 
   // ---- the aggregation itself (daf_fwd_rows' loop with the weights in LDS)
   const int coff = lane * 4;
@@ -278,11 +319,12 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
 
 }  // namespace
 
-extern "C" int simpb_dfa_fused_forward(
+extern "C" int simpb_dfa_fused_forward_cams(
     float* output, const void* mc_ms_feat, int feat_is_f16, const int* spatial_shape, const int* scale_start_index,
     const float* anchor, const float* learnable, const float* fix_scale, const float* projection_mat, const float* image_wh,
     const float* feat_logits, const float* cam_logits, float* loc_out, float* weights_out, int batch_size, int num_cams,
-    int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups, void* stream) {
+    int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups,
+    const unsigned char* cam_valid, void* stream) {
   if (!output || !mc_ms_feat || !spatial_shape || !scale_start_index || !anchor || !fix_scale || !projection_mat ||
       !image_wh || !feat_logits || !cam_logits || (num_learn > 0 && !learnable))
     return SIMPB_EINVAL;
@@ -299,15 +341,32 @@ extern "C" int simpb_dfa_fused_forward(
   k.anchor = anchor; k.learn = learnable; k.fix_scale = fix_scale; k.proj = projection_mat; k.image_wh = image_wh;
   k.feat_logits = feat_logits; k.cam_logits = cam_logits; k.loc_out = loc_out; k.w_out = weights_out;
   k.cams = num_cams; k.num_feat = num_feat; k.C = num_embeds; k.L = num_scale; k.A = num_anchors; k.num_fix = num_fix;
-  k.num_learn = num_learn; k.G = num_groups;
+  k.num_learn = num_learn; k.G = num_groups; k.cam_valid = cam_valid;
   hipStream_t s = static_cast<hipStream_t>(stream);
   dim3 grid(num_anchors, batch_size);
   const int tslot = simpb_timing_begin(SIMPB_KERNEL_DAF, stream);
   // the shipped layout (config :221-238: 6 cameras, 4 levels, 7 fixed + 6 learnable key points, 8 groups of 32 channels)
-  if (feat_is_f16)
-    hipLaunchKernelGGL((daf_fused_rows<_Float16, 6, 4, 7, 6, 8, 256>), grid, dim3(kThreads), 0, s, k);
-  else
-    hipLaunchKernelGGL((daf_fused_rows<float, 6, 4, 7, 6, 8, 256>), grid, dim3(kThreads), 0, s, k);
+  if (cam_valid) {
+    if (feat_is_f16)
+      hipLaunchKernelGGL((daf_fused_rows<_Float16, 6, 4, 7, 6, 8, 256, true>), grid, dim3(kThreads), 0, s, k);
+    else
+      hipLaunchKernelGGL((daf_fused_rows<float, 6, 4, 7, 6, 8, 256, true>), grid, dim3(kThreads), 0, s, k);
+  } else if (feat_is_f16) {
+    hipLaunchKernelGGL((daf_fused_rows<_Float16, 6, 4, 7, 6, 8, 256, false>), grid, dim3(kThreads), 0, s, k);
+  } else {
+    hipLaunchKernelGGL((daf_fused_rows<float, 6, 4, 7, 6, 8, 256, false>), grid, dim3(kThreads), 0, s, k);
+  }
   simpb_timing_end(tslot, stream);
   return simpb_check_launch();
+}
+
+extern "C" int simpb_dfa_fused_forward(
+    float* output, const void* mc_ms_feat, int feat_is_f16, const int* spatial_shape, const int* scale_start_index,
+    const float* anchor, const float* learnable, const float* fix_scale, const float* projection_mat, const float* image_wh,
+    const float* feat_logits, const float* cam_logits, float* loc_out, float* weights_out, int batch_size, int num_cams,
+    int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups, void* stream) {
+  return simpb_dfa_fused_forward_cams(output, mc_ms_feat, feat_is_f16, spatial_shape, scale_start_index, anchor, learnable,
+                                      fix_scale, projection_mat, image_wh, feat_logits, cam_logits, loc_out, weights_out,
+                                      batch_size, num_cams, num_feat, num_embeds, num_scale, num_anchors, num_fix, num_learn,
+                                      num_groups, nullptr, stream);
 }

@@ -17,12 +17,15 @@ extern "C" int simpb_check_launch(void);
 
 namespace {
 
-// thread per (b, a, p): computes the key point once, projects it into every camera
+// thread per (b, a, p): computes the key point once, projects it into every camera. MASKED: a camera with
+// cam_valid[b, cam] = 0 (u8 [bs, cams]) delivered no frame: its location is (-1, -1), which the aggregation kernel skips
+// (csrc/deform_agg.hip: outside (0, 1)), and neither its matrix nor its image_wh row is read.
+template <bool MASKED>
 __global__ void dfa_points_kernel(float* __restrict__ loc, float* __restrict__ key_points,
                                   const float* __restrict__ anchor, const float* __restrict__ learn,
                                   const float* __restrict__ fix_scale, const float* __restrict__ proj,
                                   const float* __restrict__ image_wh, int bs, int A, int num_fix, int num_learn,
-                                  int cams) {
+                                  int cams, const unsigned char* __restrict__ cam_valid) {
   const int P = num_fix + num_learn;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= bs * A * P) return;
@@ -61,6 +64,18 @@ __global__ void dfa_points_kernel(float* __restrict__ loc, float* __restrict__ k
     kp[0] = px; kp[1] = py; kp[2] = pz;
   }
   for (int c = 0; c < cams; ++c) {
+    if (MASKED) {
+      const unsigned char on = cam_valid[b * cams + c];
+      simpb::loads_retired();  // also retires the previous camera's stores
+      if (!on) {
+        float r0 = -1.f, r1 = -1.f;
+        simpb::pin(r0); simpb::pin(r1);
+        float* o = loc + ((size_t)idx * cams + c) * 2;
+        o[0] = r0;
+        o[1] = r1;
+        continue;
+      }
+    }
     const float* M = proj + ((size_t)b * cams + c) * 16;
     const float* wh = image_wh + ((size_t)b * cams + c) * 2;
     float m[12];
@@ -79,11 +94,16 @@ __global__ void dfa_points_kernel(float* __restrict__ loc, float* __restrict__ k
   }
 }
 
-// workgroup per (b, a); thread t -> (group g = t % G, slice) ; softmax over the cams*L*P entries of a group
+// workgroup per (b, a); thread t -> (group g = t % G, slice) ; softmax over the cams*L*P entries of a group. MASKED: the
+// entries of a camera with cam_valid[b, cam] = 0 count as -inf WITHOUT its cam_logits row being read (it may hold NaN):
+// their weights are exactly 0.0 and the softmax runs over the valid cameras. No valid camera at all (refused on the host):
+// every weight is 0.0, no division by the zero sum.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void dfa_weights_kernel(float* __restrict__ w_out,
                                                           const float* __restrict__ feat_logits,
                                                           const float* __restrict__ cam_logits, int A, int cams,
-                                                          int L, int P, int G) {
+                                                          int L, int P, int G,
+                                                          const unsigned char* __restrict__ cam_valid) {
   extern __shared__ float s_val[];  // [cams*L*P][G]
   __shared__ float s_red[256];
   const int a = blockIdx.x, b = blockIdx.y;
@@ -97,7 +117,9 @@ __global__ __launch_bounds__(256) void dfa_weights_kernel(float* __restrict__ w_
   float m = -INFINITY;
   for (int e = slice; e < n; e += slices) {  // e = (cam, lvl, pt) flattened cam-major
     const int cam = e / (L * P), lp = e - cam * (L * P);
-    const float v = fl[lp * G + g] + cl[(size_t)cam * LPG + lp * G + g];
+    float v;
+    if (MASKED && !cam_valid[b * cams + cam]) v = -INFINITY;
+    else v = fl[lp * G + g] + cl[(size_t)cam * LPG + lp * G + g];
     s_val[e * G + g] = v;
     m = fmaxf(m, v);
   }
@@ -111,7 +133,8 @@ __global__ __launch_bounds__(256) void dfa_weights_kernel(float* __restrict__ w_
   __syncthreads();
   float sum = 0.f;
   for (int e = slice; e < n; e += slices) {
-    const float v = expf(s_val[e * G + g] - m);
+    float v = expf(s_val[e * G + g] - m);
+    if (MASKED && s_val[e * G + g] == -INFINITY) v = 0.f;   // (also where every camera is masked: -inf - -inf is NaN)
     s_val[e * G + g] = v;
     sum += v;
   }
@@ -121,7 +144,8 @@ __global__ __launch_bounds__(256) void dfa_weights_kernel(float* __restrict__ w_
     if (slice < s) s_red[tid] += s_red[tid + s * G];
     __syncthreads();
   }
-  const float inv = 1.f / s_red[g];
+  float inv = 1.f / s_red[g];
+  if (MASKED && s_red[g] == 0.f) inv = 0.f;
   // write [a, pt, cam, lvl, g]
   float* wo = w_out + ((size_t)b * A + a) * (size_t)n * G;
   for (int e = slice; e < n; e += slices) {
@@ -133,24 +157,37 @@ __global__ __launch_bounds__(256) void dfa_weights_kernel(float* __restrict__ w_
 
 }  // namespace
 
-extern "C" int simpb_dfa_points(float* loc, float* key_points, const float* anchor, const float* learnable,
-                                const float* fix_scale, const float* projection_mat, const float* image_wh,
-                                int batch_size, int num_anchors, int num_fix, int num_learn, int num_cams,
-                                void* stream) {
+extern "C" int simpb_dfa_points_cams(float* loc, float* key_points, const float* anchor, const float* learnable,
+                                     const float* fix_scale, const float* projection_mat, const float* image_wh,
+                                     int batch_size, int num_anchors, int num_fix, int num_learn, int num_cams,
+                                     const unsigned char* cam_valid, void* stream) {
   if (!loc || !anchor || !fix_scale || !projection_mat || !image_wh || batch_size <= 0 || num_anchors <= 0 ||
       num_fix < 0 || num_learn < 0 || num_fix + num_learn <= 0 || num_cams <= 0 || (num_learn > 0 && !learnable))
     return SIMPB_EINVAL;
   (void)hipGetLastError();
   const int n = batch_size * num_anchors * (num_fix + num_learn);
-  hipLaunchKernelGGL(dfa_points_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), loc,
-                     key_points, anchor, learnable, fix_scale, projection_mat, image_wh, batch_size, num_anchors, num_fix,
-                     num_learn, num_cams);
+  if (cam_valid)
+    hipLaunchKernelGGL(dfa_points_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), loc,
+                       key_points, anchor, learnable, fix_scale, projection_mat, image_wh, batch_size, num_anchors, num_fix,
+                       num_learn, num_cams, cam_valid);
+  else
+    hipLaunchKernelGGL(dfa_points_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), loc,
+                       key_points, anchor, learnable, fix_scale, projection_mat, image_wh, batch_size, num_anchors, num_fix,
+                       num_learn, num_cams, static_cast<const unsigned char*>(nullptr));
   return simpb_check_launch();
 }
 
-extern "C" int simpb_dfa_weights(float* weights, const float* feat_logits, const float* cam_logits, int batch_size,
-                                 int num_anchors, int num_cams, int num_levels, int num_pts, int num_groups,
-                                 void* stream) {
+extern "C" int simpb_dfa_points(float* loc, float* key_points, const float* anchor, const float* learnable,
+                                const float* fix_scale, const float* projection_mat, const float* image_wh,
+                                int batch_size, int num_anchors, int num_fix, int num_learn, int num_cams,
+                                void* stream) {
+  return simpb_dfa_points_cams(loc, key_points, anchor, learnable, fix_scale, projection_mat, image_wh, batch_size, num_anchors,
+                               num_fix, num_learn, num_cams, nullptr, stream);
+}
+
+extern "C" int simpb_dfa_weights_cams(float* weights, const float* feat_logits, const float* cam_logits, int batch_size,
+                                      int num_anchors, int num_cams, int num_levels, int num_pts, int num_groups,
+                                      const unsigned char* cam_valid, void* stream) {
   if (!weights || !feat_logits || !cam_logits || batch_size <= 0 || num_anchors <= 0 || num_cams <= 0 ||
       num_levels <= 0 || num_pts <= 0 || num_groups <= 0 || batch_size > 65535)
     return SIMPB_EINVAL;
@@ -161,8 +198,20 @@ extern "C" int simpb_dfa_weights(float* weights, const float* feat_logits, const
   const size_t lds = (size_t)num_cams * num_levels * num_pts * num_groups * sizeof(float);
   if (lds > 60 * 1024) return SIMPB_EINVAL;
   (void)hipGetLastError();
-  hipLaunchKernelGGL(dfa_weights_kernel, dim3(num_anchors, batch_size), dim3(num_groups * slices), lds,
-                     static_cast<hipStream_t>(stream), weights, feat_logits, cam_logits, num_anchors, num_cams,
-                     num_levels, num_pts, num_groups);
+  if (cam_valid)
+    hipLaunchKernelGGL(dfa_weights_kernel<true>, dim3(num_anchors, batch_size), dim3(num_groups * slices), lds,
+                       static_cast<hipStream_t>(stream), weights, feat_logits, cam_logits, num_anchors, num_cams,
+                       num_levels, num_pts, num_groups, cam_valid);
+  else
+    hipLaunchKernelGGL(dfa_weights_kernel<false>, dim3(num_anchors, batch_size), dim3(num_groups * slices), lds,
+                       static_cast<hipStream_t>(stream), weights, feat_logits, cam_logits, num_anchors, num_cams,
+                       num_levels, num_pts, num_groups, static_cast<const unsigned char*>(nullptr));
   return simpb_check_launch();
+}
+
+extern "C" int simpb_dfa_weights(float* weights, const float* feat_logits, const float* cam_logits, int batch_size,
+                                 int num_anchors, int num_cams, int num_levels, int num_pts, int num_groups,
+                                 void* stream) {
+  return simpb_dfa_weights_cams(weights, feat_logits, cam_logits, batch_size, num_anchors, num_cams, num_levels, num_pts,
+                                num_groups, nullptr, stream);
 }

@@ -54,26 +54,38 @@ class DynamicQueryAllocation(nn.Module):
         self.limit_corners_num = limit_corners_num
         self.last = None
 
-    def forward(self, anchor3d, metas, dense=True, capacity=None, overflow_out=None, independent=False, active=None):
+    def forward(self, anchor3d, metas, dense=True, capacity=None, overflow_out=None, independent=False, active=None,
+                cam_valid=None):
         """Returns the reference's 8-tuple (allocation.py:144). With dense=True the two one-hot
         matrices are materialised from the index form; with dense=False their places hold None
         and callers use `self.last` (an Allocation2D) instead."""
         if active is not None and not independent:
             raise ValueError("an activity mask needs the independent-streams layout")
         if independent:
-            alloc, ref_pts2d, ref_depth2d = self.allocate_independent(anchor3d, metas, capacity, overflow_out, active)
+            alloc, ref_pts2d, ref_depth2d = self.allocate_independent(anchor3d, metas, capacity, overflow_out, active,
+                                                                      cam_valid)
             if dense:
                 raise ValueError("independent streams: index form only (dense=False)")
             return ref_pts2d, ref_depth2d, None, None, None, None, None, None
-        alloc, ref_pts2d, ref_depth2d, trans_mask, trans_shape = self.allocate(anchor3d, metas, capacity, overflow_out)
+        alloc, ref_pts2d, ref_depth2d, trans_mask, trans_shape = self.allocate(anchor3d, metas, capacity, overflow_out,
+                                                                               cam_valid)
         trans, center = alloc.dense() if dense else (None, None)
         return ref_pts2d, ref_depth2d, trans_mask, trans_shape, trans, center, alloc.query_groups, None
 
-    def allocate_independent(self, anchor3d, metas, capacity, overflow_out=None, active=None):
+    @staticmethod
+    def _check_cam_valid(cam_valid, bs, cams, dev):
+        """cam_valid: None or contiguous u8 [bs, cams] on the anchors' device (1 = the camera delivered a frame)."""
+        if cam_valid is not None and (not torch.is_tensor(cam_valid) or cam_valid.dtype != torch.uint8
+                                      or tuple(cam_valid.shape) != (bs, cams) or cam_valid.device != dev
+                                      or not cam_valid.is_contiguous()):
+            raise ValueError("camera_valid must be contiguous u8 [bs, cams] on the anchors' device")
+
+    def allocate_independent(self, anchor3d, metas, capacity, overflow_out=None, active=None, cam_valid=None):
         """The batch as `bs` independent camera streams: every stream keeps the 2D set a batch of one gives
         it, at most `capacity` slots each; one flat slot array [1, bs * capacity] over bs * cams groups, live slots first
         (Allocation2D.streams = bs). Static shapes only. active (u8 [bs] on the device, or None): a stream with 0 sits the
-        frame out and gets no slots; the streams behind it move down."""
+        frame out and gets no slots; the streams behind it move down. cam_valid (u8 [bs, cams] on the device, or None): a
+        camera with 0 delivered no frame and is an empty group of its stream; the groups behind it move down."""
         if self.training:
             raise NotImplementedError("training-time corner sampling (allocation.py:85-87) is not on this path")
         if capacity is None:
@@ -94,6 +106,7 @@ class DynamicQueryAllocation(nn.Module):
         if active is not None and (active.dtype != torch.uint8 or active.numel() != bs or active.device != dev
                                    or not active.is_contiguous()):
             raise ValueError("active must be contiguous u8 [bs] on the anchors' device")
+        self._check_cam_valid(cam_valid, bs, cams, dev)
         lw, ll, lh = (float(v) for v in self.limit_anchor_size)
         slots = bs * int(capacity)
         flag = torch.empty(bs, cams, num_anchor, dtype=torch.uint8, device=dev)
@@ -116,19 +129,22 @@ class DynamicQueryAllocation(nn.Module):
         out.query_groups = None
         out.num_anchor = num_anchor
         out.overflow = overflow
-        _lib.check(lib.simpb_alloc_ragged_active(
+        _lib.check(lib.simpb_alloc_ragged_cams(
             _ptr(flag), _ptr(sel_xy), _ptr(depth), _ptr(out.count), _ptr(order), _ptr(out.group_start), _ptr(overflow),
             _ptr(ref_pts2d), _ptr(ref_depth2d), _ptr(out.q2a), _ptr(out.is_center), _ptr(out.a2q), _ptr(out.query_cam),
             _ptr(anchor3d), _ptr(proj), bs, num_anchor, cams, int(capacity), img_w, img_h, lw, ll, lh,
-            _ptr(active) if active is not None else None, _stream()), "simpb_alloc_ragged")
+            _ptr(active) if active is not None else None, _ptr(cam_valid) if cam_valid is not None else None, _stream()),
+            "simpb_alloc_ragged")
         self.last = out
         return out, ref_pts2d, ref_depth2d
 
-    def allocate(self, anchor3d, metas, capacity=None, overflow_out=None):
+    def allocate(self, anchor3d, metas, capacity=None, overflow_out=None, cam_valid=None):
         """capacity=None: size the 2D set exactly (one count readback, like allocation.py:94).
         capacity=N: static shapes, no host round trip; the group table stays on the device, slots
         past the last group carry query_cam = -1, and `overflow` (i32 [1]; `overflow_out` when the caller keeps the
-        flags of a frame's layers in one tensor) flags a set that did not fit."""
+        flags of a frame's layers in one tensor) flags a set that did not fit. cam_valid (u8 [bs, cams] on the device, or
+        None): a (sample, camera) with 0 delivered no frame: its column of the reference's trans_mask is all false (count
+        0, a2q = -1), whichever of the stepwise and the static route runs."""
         if self.training:
             raise NotImplementedError("training-time corner sampling (allocation.py:85-87) is not on this path")
         _require_gpu(anchor3d)
@@ -144,6 +160,8 @@ class DynamicQueryAllocation(nn.Module):
             wh = tuple(int(v) for v in metas["image_wh"][0, 0].tolist())
         img_w, img_h = float(wh[0]), float(wh[1])
         dev = anchor3d.device
+        self._check_cam_valid(cam_valid, bs, cams, dev)
+        cv = _ptr(cam_valid) if cam_valid is not None else None
         flag = torch.empty(bs, cams, num_anchor, dtype=torch.uint8, device=dev)
         sel_xy = torch.empty(bs, cams, num_anchor, 2, device=dev)
         depth = torch.empty(bs, cams, num_anchor, device=dev)
@@ -153,8 +171,8 @@ class DynamicQueryAllocation(nn.Module):
         order = torch.empty(bs, cams, num_anchor, dtype=torch.int32, device=dev)
         static = capacity is not None and routes.R.alloc_static_fused and cams <= 8
         if not static:
-            _lib.check(lib.simpb_alloc_project(_ptr(flag), _ptr(sel_xy), _ptr(depth), _ptr(anchor3d), _ptr(proj), bs,
-                                               num_anchor, cams, img_w, img_h, lw, ll, lh, st), "simpb_alloc_project")
+            _lib.check(lib.simpb_alloc_project_cams(_ptr(flag), _ptr(sel_xy), _ptr(depth), _ptr(anchor3d), _ptr(proj), bs,
+                                                    num_anchor, cams, img_w, img_h, lw, ll, lh, cv, st), "simpb_alloc_project")
             _lib.check(lib.simpb_alloc_compact(_ptr(count), _ptr(order), _ptr(flag), bs, num_anchor, cams, st),
                        "simpb_alloc_compact")
         overflow = None
@@ -188,10 +206,11 @@ class DynamicQueryAllocation(nn.Module):
         out.overflow = overflow
         if static:
             # fixed capacity: nothing returns to the host between the steps: fill and group table ride in steps 1 and 3
-            _lib.check(lib.simpb_alloc_static(_ptr(flag), _ptr(sel_xy), _ptr(depth), _ptr(count), _ptr(order), _ptr(group_start),
-                                              _ptr(overflow), _ptr(ref_pts2d), _ptr(ref_depth2d), _ptr(out.q2a),
-                                              _ptr(out.is_center), _ptr(out.a2q), _ptr(out.query_cam), _ptr(anchor3d), _ptr(proj),
-                                              bs, num_anchor, cams, n2, img_w, img_h, lw, ll, lh, st), "simpb_alloc_static")
+            _lib.check(lib.simpb_alloc_static_cams(_ptr(flag), _ptr(sel_xy), _ptr(depth), _ptr(count), _ptr(order),
+                                                   _ptr(group_start), _ptr(overflow), _ptr(ref_pts2d), _ptr(ref_depth2d),
+                                                   _ptr(out.q2a), _ptr(out.is_center), _ptr(out.a2q), _ptr(out.query_cam),
+                                                   _ptr(anchor3d), _ptr(proj), bs, num_anchor, cams, n2, img_w, img_h, lw, ll, lh,
+                                                   cv, st), "simpb_alloc_static")
         else:
             _lib.check(lib.simpb_alloc_scatter(_ptr(ref_pts2d), _ptr(ref_depth2d), _ptr(out.q2a), _ptr(out.is_center),
                                                _ptr(out.a2q), _ptr(out.query_cam), _ptr(group_start), _ptr(count),

@@ -64,6 +64,9 @@ class DeformableFeatureAggregation(BaseModule):
                 and getattr(self.kps_generator, "num_learnable_pts", 0) > 0):
             return self._forward_fused(instance_feature, anchor, anchor_embed, feature_maps, metas, keep_parts,
                                        cam_embed)
+        if metas.get("camera_valid") is not None:
+            raise NotImplementedError("metas['camera_valid'] needs the HIP route of this layer (camera embedding, image_wh, "
+                                      "learnable key points, tensors on the device): the PyTorch composition has no mask")
         bs, num_anchor = instance_feature.shape[:2]
         key_points = self.kps_generator(anchor, instance_feature)
         weights = self._get_weights(instance_feature, anchor_embed, metas)
@@ -87,7 +90,9 @@ class DeformableFeatureAggregation(BaseModule):
         """Same dataflow as forward(), with the operand producers as two HIP kernels writing the
         aggregation kernel's own layouts (csrc/dfa_prep.hip) instead of ~25 PyTorch kernels, and the
         three Linear layers in front of them (learnable_fc on the feature, weights_fc on feature +
-        anchor_embed and on the camera embedding) as one grouped GEMM launch."""
+        anchor_embed and on the camera embedding) as one grouped GEMM launch. metas["camera_valid"] (u8 [bs, cams], validated
+        by the head) goes to the launches behind the GEMM, on both routes: the camera embedding and cam_logits rows of a
+        masked camera are computed from whatever its matrix holds (row-wise, they touch no other row) and never read."""
         from .. import _lib
         from . import fused
         from .ops import _ptr, _stream
@@ -98,6 +103,8 @@ class DeformableFeatureAggregation(BaseModule):
         anchor_c = anchor.contiguous().float()
         proj = metas["projection_mat"].contiguous().float()
         wh = metas["image_wh"].contiguous().float()
+        cam_valid = metas.get("camera_valid")
+        cv = _ptr(cam_valid) if cam_valid is not None else None
         if cam_embed is None:  # the head hands in the embeddings of all its layers, computed in one launch
             cam_embed = fused.chain_forward(self.camera_encoder, proj[:, :, :3].reshape(bs, self.num_cams, -1))
         # weights_fc(f + e) = [f | e] . [W | W]^T + b; weights_fc(f + e + c) = that + c . W^T (no second bias)
@@ -121,16 +128,16 @@ class DeformableFeatureAggregation(BaseModule):
             if half is not None and half.shape == feat.shape:
                 feat = half
             features = dfa_fused(feat, feature_maps[1], feature_maps[2], anchor_c, learn, kps.fix_scale, proj, wh, feat_logits,
-                                 cam_logits, self.num_groups)
+                                 cam_logits, self.num_groups, cam_valid=cam_valid)
             return self._project_out(features, instance_feature, keep_parts)
         num_fix = kps.fix_scale.shape[0]
         loc = torch.empty(bs, num_anchor, self.num_pts, self.num_cams, 2, device=dev)
-        _lib.check(lib.simpb_dfa_points(_ptr(loc), None, _ptr(anchor_c), _ptr(learn), _ptr(kps.fix_scale), _ptr(proj),
-                                        _ptr(wh), bs, num_anchor, num_fix, kps.num_learnable_pts, self.num_cams,
-                                        _stream()), "simpb_dfa_points")
+        _lib.check(lib.simpb_dfa_points_cams(_ptr(loc), None, _ptr(anchor_c), _ptr(learn), _ptr(kps.fix_scale), _ptr(proj),
+                                             _ptr(wh), bs, num_anchor, num_fix, kps.num_learnable_pts, self.num_cams, cv,
+                                             _stream()), "simpb_dfa_points")
         weights = torch.empty(bs, num_anchor, self.num_pts, self.num_cams, self.num_levels, self.num_groups, device=dev)
-        _lib.check(lib.simpb_dfa_weights(_ptr(weights), _ptr(feat_logits), _ptr(cam_logits), bs, num_anchor,
-                                         self.num_cams, self.num_levels, self.num_pts, self.num_groups, _stream()),
+        _lib.check(lib.simpb_dfa_weights_cams(_ptr(weights), _ptr(feat_logits), _ptr(cam_logits), bs, num_anchor,
+                                              self.num_cams, self.num_levels, self.num_pts, self.num_groups, cv, _stream()),
                    "simpb_dfa_weights")
         features = DAF(*feature_maps, loc, weights).reshape(bs, num_anchor, self.embed_dims)
         return self._project_out(features, instance_feature, keep_parts)

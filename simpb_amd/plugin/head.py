@@ -267,6 +267,16 @@ class SimPBHead(BaseModule):
                 raise ValueError("metas['active'] must be a contiguous u8 [bs] tensor on the device")
             if not self.instance_bank._fusable(active):
                 raise ValueError("metas['active'] needs the fused bank route (static state, routes.fused_bank)")
+        camera_valid = metas.get("camera_valid")
+        if camera_valid is not None:
+            # u8 [bs, cams] on the device (static address): a camera with 0 delivered no frame, and its stream is decoded as
+            # the reference decodes it when given the remaining cameras only -- an empty camera group in the allocation, no
+            # share of the 3D aggregation's softmax, none of its tokens / matrices read (csrc/alloc.hip, csrc/dfa_prep.hip,
+            # csrc/deform_agg_fused.hip `cam_valid`). Every layout takes it; a stream WITHOUT any camera is paused (`active`).
+            if (not torch.is_tensor(camera_valid) or camera_valid.dtype != torch.uint8
+                    or tuple(camera_valid.shape) != (batch_size, self.num_cams) or not camera_valid.is_cuda
+                    or not camera_valid.is_contiguous()):
+                raise ValueError("metas['camera_valid'] must be a contiguous u8 [bs, cams] tensor on the device")
         if split:
             if "time_interval" not in metas or self.static_capacity is None:
                 raise ValueError("forward_split needs metas['time_interval'] (f32 [bs]) and a static capacity")
@@ -353,7 +363,8 @@ class SimPBHead(BaseModule):
                 ragged = self.independent_streams and batch_size > 1
                 anchor2d, ref_depth2d, ref_trans_mask, ref_trans_shape, _, _, ref_query_groups, _ = layer(
                     anchor, metas, dense=False, capacity=cap,
-                    overflow_out=overflow[k:k + 1] if overflow is not None else None, independent=ragged, active=active)
+                    overflow_out=overflow[k:k + 1] if overflow is not None else None, independent=ragged, active=active,
+                    cam_valid=camera_valid)
                 alloc = layer.last
                 if ragged:   # one flat slot array over batch_size * num_cams groups: the 2D operators run as a batch of one
                     groups = batch_size * self.num_cams

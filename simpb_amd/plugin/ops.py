@@ -104,11 +104,12 @@ def deformable_aggregation_function(feature_maps, spatial_shape, scale_start_ind
 
 
 def dfa_fused(feat, spatial_shape, scale_start_index, anchor, learn, fix_scale, proj, image_wh, feat_logits, cam_logits,
-              num_groups, want_operands=False):
+              num_groups, want_operands=False, cam_valid=None):
     """DeformableFeatureAggregation between its Linear layers as ONE launch (csrc/deform_agg_fused.hip): key points,
     projection, weight softmax and the aggregation. feat: the token buffer, f32 or f16 [bs, num_feat, C]. Returns the
     aggregated features [bs, A, C] (and, with want_operands, the sampling locations and weights the launch used, in the
-    drop-in operator's layouts)."""
+    drop-in operator's layouts). cam_valid: None or contiguous u8 [bs, cams] on the device; a camera with 0 delivered no
+    frame: the softmax runs over the others and nothing of it is read (include/simpb_hip.h: simpb_dfa_fused_forward_cams)."""
     _require_gpu(feat, anchor, learn, feat_logits, cam_logits, proj, image_wh)
     if feat.dtype not in (torch.float32, torch.float16) or not feat.is_contiguous():
         raise ValueError("dfa_fused: contiguous f32 or f16 token buffer expected")
@@ -128,15 +129,18 @@ def dfa_fused(feat, spatial_shape, scale_start_index, anchor, learn, fix_scale, 
             or tuple(cam_logits.shape) != (bs, cams, lpg) or tuple(proj.shape) != (bs, cams, 4, 4) or tuple(image_wh.shape) != (bs, cams, 2)
             or tuple(spatial_shape.shape) != (cams, lvls, 2) or tuple(scale_start_index.shape) != (cams, lvls)):
         raise ValueError("dfa_fused: operand shapes disagree")
+    if cam_valid is not None and (cam_valid.dtype != torch.uint8 or tuple(cam_valid.shape) != (bs, cams)
+                                  or cam_valid.device != feat.device or not cam_valid.is_contiguous()):
+        raise ValueError("dfa_fused: camera_valid must be contiguous u8 [bs, cams] on the tokens' device")
     _check_layout(spatial_shape, scale_start_index, num_feat)
     out = torch.empty(bs, a, c, device=feat.device, dtype=torch.float32)
     loc = torch.empty(bs, a, p, cams, 2, device=feat.device) if want_operands else None
     w = torch.empty(bs, a, p, cams, lvls, num_groups, device=feat.device) if want_operands else None
-    status = _lib.lib().simpb_dfa_fused_forward(
+    status = _lib.lib().simpb_dfa_fused_forward_cams(
         _ptr(out), _ptr(feat), 1 if feat.dtype == torch.float16 else 0, _ptr(spatial_shape), _ptr(scale_start_index),
         _ptr(anchor), _ptr(learn), _ptr(fix_scale), _ptr(proj), _ptr(image_wh), _ptr(feat_logits), _ptr(cam_logits),
         _ptr(loc) if loc is not None else None, _ptr(w) if w is not None else None, bs, cams, num_feat, c, lvls, a, num_fix,
-        num_learn, num_groups, _stream())
+        num_learn, num_groups, _ptr(cam_valid) if cam_valid is not None else None, _stream())
     _lib.check(status, "simpb_dfa_fused_forward")
     return (out, loc, w) if want_operands else out
 

@@ -58,6 +58,33 @@ def carry_inactive_metas(prev, metas, active):
     return out
 
 
+def normalise_cameras(cameras, num_streams, num_cams, active=None):
+    """step / launch's `cameras` -> None (every camera of every stream that takes part delivered a frame: today's path) or
+    a tuple of `num_streams` tuples of `num_cams` bools with a False somewhere. cameras: None, or one sequence of num_cams
+    bools per stream; active: None or one bool per stream. A paused stream's row is not looked at (it comes back all True:
+    `active=False` overrides it); a stream that takes part with no camera at all is refused -- a stream without any frame is
+    paused, not masked. Pure host function."""
+    if cameras is None:
+        return None
+    rows = [tuple(bool(c) for c in row) for row in cameras]
+    if len(rows) != num_streams:
+        raise ValueError(f"cameras has {len(rows)} rows for {num_streams} streams")
+    on = [True] * num_streams if active is None else [bool(a) for a in active]
+    if len(on) != num_streams:
+        raise ValueError(f"active has {len(on)} entries for {num_streams} streams")
+    out = []
+    for i, (row, a) in enumerate(zip(rows, on)):
+        if len(row) != num_cams:
+            raise ValueError(f"cameras[{i}] has {len(row)} entries for {num_cams} cameras")
+        if not a:
+            row = (True,) * num_cams
+        elif not any(row):
+            raise ValueError(f"stream {i} takes part with no valid camera: a stream without any frame is paused "
+                             "(active=False), not masked")
+        out.append(row)
+    return None if all(all(row) for row in out) else tuple(out)
+
+
 class FrameRunner:
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
                  raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif"):
@@ -115,6 +142,11 @@ class FrameRunner:
         self.pin_active = torch.ones(batch_size, dtype=torch.uint8).pin_memory()
         self.masked = False                 # True from the first frame with a paused stream on: the graphs read active_buf
         self.last_active = (True,) * batch_size   # mask of the frame last returned
+        # per-camera validity (step(..., cameras=)): staged like the activity mask once a caller has dropped a camera; until
+        # then the head is called without it and nothing here is touched (see _camera_mask)
+        self.cam_buf = torch.ones(batch_size, cams, dtype=torch.uint8, device=dev)
+        self.pin_cam = torch.ones(batch_size, cams, dtype=torch.uint8).pin_memory()
+        self.cam_masked = False             # True from the first frame with a missing camera on: the graphs read cam_buf
         self.head.instance_bank.enable_static(batch_size, dev)
         self.head.static_capacity = self.capacity
         self.prev_metas = None
@@ -220,6 +252,19 @@ class FrameRunner:
             raise ValueError("every stream takes part in the cold frame (a batch-wide dataflow without history)")
         return mask
 
+    def _camera_mask(self, cameras, mask):
+        """step / launch's `cameras` -> None or bs tuples of num_cams bools (normalise_cameras); the first frame with a
+        missing camera switches the runner to graphs that read the staged mask (all ones = the full rig from then on)."""
+        cams = normalise_cameras(cameras, self.bs, self.head.num_cams, mask)
+        if cams is not None and not self.cam_masked:
+            torch.cuda.synchronize(self.device)   # nothing in flight replays a graph that does not read the mask
+            self._drop_graphs()
+            self.cam_masked = True
+        return cams
+
+    def _fill_cameras(self, pin, cams):
+        pin.copy_(torch.tensor(cams if cams is not None else ((True,) * self.head.num_cams,) * self.bs, dtype=torch.uint8))
+
     def _carry(self, prev, metas, mask):
         """This frame's metas with the paused streams' entries held at their last active frame (whose projection matrices
         are what the pinned staging buffer still holds); the first paused frame also switches the runner to masked graphs."""
@@ -229,9 +274,9 @@ class FrameRunner:
             self.masked = True
         return carry_inactive_metas(dict(img_metas=prev["img_metas"], projection_mat=self.pin_proj), metas, mask)
 
-    def _stage_motion(self, metas, prev, mask):
-        """Projection matrices, activity mask, ego-motion and time step into the pinned buffers and on to the device (on the
-        current stream)."""
+    def _stage_motion(self, metas, prev, mask, cams=None):
+        """Projection matrices, activity mask, camera mask, ego-motion and time step into the pinned buffers and on to the
+        device (on the current stream)."""
         self.pin_proj.copy_(metas["projection_mat"] if not metas["projection_mat"].is_cuda else metas["projection_mat"].cpu())
         self.proj.copy_(self.pin_proj, non_blocking=True)
         if self.world_output is not None:
@@ -240,6 +285,9 @@ class FrameRunner:
         if self.masked:
             self.pin_active.copy_(torch.tensor(mask if mask is not None else (True,) * self.bs, dtype=torch.uint8))
             self.active_buf.copy_(self.pin_active, non_blocking=True)
+        if self.cam_masked:
+            self._fill_cameras(self.pin_cam, cams)
+            self.cam_buf.copy_(self.pin_cam, non_blocking=True)
         if prev is not None:
             t, dt = stream_motion(metas, prev)
             self.pin_t.copy_(torch.from_numpy(t))
@@ -247,10 +295,10 @@ class FrameRunner:
             self.t_buf.copy_(self.pin_t, non_blocking=True)
             self.dt_buf.copy_(self.pin_dt, non_blocking=True)
 
-    def _stage(self, img, metas, mask=None):
+    def _stage(self, img, metas, mask=None, cams=None):
         """Copy this frame's inputs into the static device buffers (a few small async copies)."""
         (self.img if self.raw is None else self.raw).copy_(img, non_blocking=True)
-        self._stage_motion(metas, self.prev_metas, mask)
+        self._stage_motion(metas, self.prev_metas, mask, cams)
 
     def _device_metas(self, metas):
         out = dict(projection_mat=self.proj, image_wh=self.wh, image_wh_host=self.wh_host, img_metas=metas["img_metas"])
@@ -258,6 +306,8 @@ class FrameRunner:
             out["bank_inputs"] = (self.t_buf, self.dt_buf)
         if self.masked:
             out["active"] = self.active_buf
+        if self.cam_masked:
+            out["camera_valid"] = self.cam_buf
         return out
 
     def _results(self, rec3d, rec2d, mask, world=None, count=None):
@@ -332,7 +382,7 @@ class FrameRunner:
 
     # ------------------------------------------------------------------ public
     @torch.no_grad()
-    def step(self, img, metas, force_eager=False, active=None):
+    def step(self, img, metas, force_eager=False, active=None, cameras=None):
         """One frame for all streams: img f32 [bs, cams, 3, H, W] (device; u8 [bs, cams, Hs, Ws, 3] with raw_input, u8
         [bs, cams, Hs * 3 / 2, Ws] with raw_format "nv12" / "nv21"), metas as the reference's
         test pipeline collects them (projection_mat, timestamp, img_metas with T_global/T_global_inv/
@@ -341,8 +391,16 @@ class FrameRunner:
         active (independent_streams only): one bool per stream; a stream with False has no frame this step. Its bank, its
         confidences and its track ids stay as they are, its rows of `img` and `metas` are ignored (they may hold anything),
         its place in the returned list holds None, and when it resumes its time step and ego-motion are measured from its
-        own last frame. None or all True: every stream takes part."""
+        own last frame. None or all True: every stream takes part.
+
+        cameras: None, or one sequence of num_cams bools per stream; a camera with False delivered no frame. The stream is
+        then decoded exactly as the reference decodes it when given the remaining cameras only: the camera's image slot (u8:
+        anything; f32: anything finite -- the backbone still runs on it) and its projection_mat row are ignored, its 2D
+        list is empty, and bank, track ids, ego-motion and time step go on as ever: a camera that comes back simply takes
+        part again. A cold frame may have missing cameras. A stream that takes part needs at least one camera (ValueError:
+        pause it instead); a paused stream's row is not looked at. An overflowed frame is re-run with its own mask."""
         mask = self._activity(active, self.prev_metas is None)
+        cams = self._camera_mask(cameras, mask)
         if mask is not None:
             metas = self._carry(self.prev_metas, metas, mask)
         self._check_pose(metas, mask)
@@ -350,7 +408,7 @@ class FrameRunner:
         if self.raw is not None:
             self._check_frames(img)
             self._ensure_plan(metas)
-        self._stage(img, metas, mask)
+        self._stage(img, metas, mask, cams)
         dmetas = self._device_metas(metas)
         warm = self.prev_metas is not None
         if warm and self.use_graph and not force_eager and self.graph is None and self.warm_frames >= 1:
@@ -516,13 +574,13 @@ class PipelinedRunner(FrameRunner):
             done.record(self.s_head)
         return done
 
-    def _stage_head_inputs(self, metas, prev, mask=None):
+    def _stage_head_inputs(self, metas, prev, mask=None, cams=None):
         """Per-frame decoder inputs (projection matrices, activity mask, ego-motion, time step) of a frame; prev = the metas
         of the frame before it (None for a cold frame)."""
         if self.staged is not None:
             self.staged.synchronize()   # the previous frame's copies out of the pinned buffers (long done in practice)
         with torch.cuda.stream(self.s_head):
-            self._stage_motion(metas, prev, mask)
+            self._stage_motion(metas, prev, mask, cams)
             self.staged = torch.cuda.Event()
             self.staged.record(self.s_head)
 
@@ -533,23 +591,27 @@ class PipelinedRunner(FrameRunner):
             out["bank_inputs"] = (self.t_buf, self.dt_buf)
         if self.masked:
             out["active"] = self.active_buf
+        if self.cam_masked:
+            out["camera_valid"] = self.cam_buf
         return out
 
-    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None):
+    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None, cams=None):
         """Stage the inputs of the frame whose features sit in `slot` and enqueue its decoder + read-back on s_head. The
-        job keeps the frame's own activity mask: a re-run (_finish) stages it again."""
+        job keeps the frame's own activity and camera masks: a re-run (_finish) stages them again."""
         warm = prev is not None
         self.prev_metas = prev   # (what the base class's helpers look at)
-        self._stage_head_inputs(metas, prev, mask)
+        self._stage_head_inputs(metas, prev, mask, cams)
         rec = self._run_head(slot, self._head_metas(metas, slot, warm), metas["img_metas"][0]["aug_config"], warm, force_eager)
         done = self._enqueue_readback(slot, rec)
-        return dict(slot=slot, metas=metas, prev=prev, warm=warm, rec=rec, done=done, active=mask)
+        return dict(slot=slot, metas=metas, prev=prev, warm=warm, rec=rec, done=done, active=mask, cameras=cams)
 
     @torch.no_grad()
-    def launch(self, img, metas, force_eager=False, active=None):
+    def launch(self, img, metas, force_eager=False, active=None, cameras=None):
         """Enqueue backbone(t) and decoder(t) without waiting for either (several runners -- several independent
-        camera streams on one GPU -- can be launched back to back and collected after). img, active: as FrameRunner.step."""
+        camera streams on one GPU -- can be launched back to back and collected after). img, active, cameras: as
+        FrameRunner.step."""
         mask = self._activity(active, self.last_metas is None)
+        cams = self._camera_mask(cameras, mask)
         if mask is not None:
             metas = self._carry(self.last_metas, metas, mask)
         self._check_pose(metas, mask)
@@ -566,7 +628,7 @@ class PipelinedRunner(FrameRunner):
         self.bb_done[slot].record(self.s_bb)
         self.s_head.wait_event(self.bb_done[slot])
         prev = dict(img_metas=self.last_metas["img_metas"]) if self.last_metas is not None else None
-        self.queue.append(self._enqueue_decoder(slot, metas, prev, force_eager, mask))
+        self.queue.append(self._enqueue_decoder(slot, metas, prev, force_eager, mask, cams))
         self.last_metas = metas
         self.count += 1
 
@@ -587,11 +649,11 @@ class PipelinedRunner(FrameRunner):
                 if not job["warm"]:
                     self.head.instance_bank.reset()  # a cold frame starts from an empty bank again
                 self._clear_hold()   # flags left by the overflowed attempt / the speculative decoder behind it
-                job = self._enqueue_decoder(job["slot"], job["metas"], job["prev"], True, job["active"])
+                job = self._enqueue_decoder(job["slot"], job["metas"], job["prev"], True, job["active"], job["cameras"])
                 job["done"].synchronize()
                 h = self.host[job["slot"]]
             for b in behind:
-                self.queue.append(self._enqueue_decoder(b["slot"], b["metas"], b["prev"], True, b["active"]))
+                self.queue.append(self._enqueue_decoder(b["slot"], b["metas"], b["prev"], True, b["active"], b["cameras"]))
         self.last_rec3d, self.last_rec2d = job["rec"][0], job["rec"][1]
         self.prev_metas = dict(img_metas=job["metas"]["img_metas"])
         if self.world_output is None:
@@ -613,9 +675,9 @@ class PipelinedRunner(FrameRunner):
             return None
         return self._finish(self.queue.pop(0))
 
-    def step(self, img, metas, force_eager=False, active=None):
+    def step(self, img, metas, force_eager=False, active=None, cameras=None):
         """Feed frame t; returns the detections of frame t-1 (None on the very first call)."""
-        self.launch(img, metas, force_eager, active)
+        self.launch(img, metas, force_eager, active, cameras)
         return self.collect()
 
     @torch.no_grad()
@@ -653,7 +715,8 @@ class SplitPipelinedRunner(PipelinedRunner):
       * eager (warm-up, re-run) frames run A and B back to back on the decoder stream: only replayed graphs run A on the
         backbone stream, so no tensor of the caching allocator crosses streams.
 
-    This is the single-stream form: it takes no paused streams (pausing its one stream means not calling step)."""
+    This is the single-stream form: it takes no paused streams (pausing its one stream means not calling step). It does
+    take `cameras`: the camera mask is one more per-frame decoder input with a device buffer per feature slot."""
 
     SUPPORTS_PAUSE = False
 
@@ -673,8 +736,10 @@ class SplitPipelinedRunner(PipelinedRunner):
         self.t_buf2 = [torch.zeros(batch_size, 4, 4, device=dev) for _ in range(2)]
         self.dt_buf2 = [torch.zeros(batch_size, device=dev) for _ in range(2)]
         self.ti_buf2 = [torch.zeros(batch_size, device=dev) for _ in range(2)]
+        self.cam2 = [torch.ones(batch_size, cams, dtype=torch.uint8, device=dev) for _ in range(2)]
         self.pin2 = [dict(proj=torch.zeros(batch_size, cams, 4, 4).pin_memory(), t=torch.zeros(batch_size, 4, 4).pin_memory(),
-                          dt=torch.zeros(batch_size).pin_memory(), ti=torch.zeros(batch_size).pin_memory()) for _ in range(2)]
+                          dt=torch.zeros(batch_size).pin_memory(), ti=torch.zeros(batch_size).pin_memory(),
+                          cam=torch.ones(batch_size, cams, dtype=torch.uint8).pin_memory()) for _ in range(2)]
         self.staged2 = [None, None]
         self.pre_graph = [None, None]
         self.pre_done = [torch.cuda.Event(), torch.cuda.Event()]
@@ -687,7 +752,7 @@ class SplitPipelinedRunner(PipelinedRunner):
         super()._drop_graphs()
         self.pre_graph = [None, None]
 
-    def _stage_slot(self, slot, metas, prev, stream):
+    def _stage_slot(self, slot, metas, prev, stream, cams=None):
         """Per-frame decoder inputs of the frame in `slot`, into that slot's own device buffers."""
         if self.staged2[slot] is not None:
             self.staged2[slot].synchronize()
@@ -695,6 +760,8 @@ class SplitPipelinedRunner(PipelinedRunner):
         bank = self.head.instance_bank
         pin["proj"].copy_(metas["projection_mat"] if not metas["projection_mat"].is_cuda else metas["projection_mat"].cpu())
         pin["ti"].fill_(float(bank.default_time_interval))
+        if self.cam_masked:
+            self._fill_cameras(pin["cam"], cams)
         if self.world_output is not None:
             self._fill_pose(pin["pose"], metas)
         if prev is not None:
@@ -709,6 +776,8 @@ class SplitPipelinedRunner(PipelinedRunner):
         with torch.cuda.stream(stream):
             self.proj2[slot].copy_(pin["proj"], non_blocking=True)
             self.ti_buf2[slot].copy_(pin["ti"], non_blocking=True)
+            if self.cam_masked:
+                self.cam2[slot].copy_(pin["cam"], non_blocking=True)
             if self.world_output is not None:
                 self.pose2[slot].copy_(pin["pose"], non_blocking=True)
             if prev is not None:
@@ -722,6 +791,8 @@ class SplitPipelinedRunner(PipelinedRunner):
                    time_interval=self.ti_buf2[slot], overflow_split=(self.hb[slot], self.sticky))
         if warm:
             out["bank_inputs"] = (self.t_buf2[slot], self.dt_buf2[slot])
+        if self.cam_masked:
+            out["camera_valid"] = self.cam2[slot]
         return out
 
     def _part_a(self, slot, dmetas):
@@ -742,7 +813,7 @@ class SplitPipelinedRunner(PipelinedRunner):
             outs["classification2d"], outs["prediction2d"], alloc, aug)
         return self._with_world(rec3d, rec2d, outs["overflow"], self.pose2[slot] if self.world_output is not None else None)
 
-    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None):
+    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None, cams=None):
         warm = prev is not None
         self.prev_metas = prev
         aug = metas["img_metas"][0]["aug_config"]
@@ -753,7 +824,7 @@ class SplitPipelinedRunner(PipelinedRunner):
             # capture A and B of this slot (both on the decoder stream; A is replayed on the backbone stream afterwards)
             self.s_pre.synchronize()
             self.s_head.synchronize()
-            self._stage_slot(slot, metas, prev, self.s_head)
+            self._stage_slot(slot, metas, prev, self.s_head, cams)
             with torch.cuda.stream(self.s_head):
                 ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
                 with torch.cuda.graph(ga, stream=self.s_head, capture_error_mode=CAPTURE_MODE):
@@ -763,7 +834,7 @@ class SplitPipelinedRunner(PipelinedRunner):
                 del gen
             self.pre_graph[slot], self.head_graph[slot] = ga, gb
         if graph_ok and self.head_graph[slot] is not None:
-            self._stage_slot(slot, metas, prev, self.s_pre)
+            self._stage_slot(slot, metas, prev, self.s_pre, cams)
             with torch.cuda.stream(self.s_pre):
                 self.s_pre.wait_event(self.bb_done[slot])
                 if self.rec_consumed is not None:   # part A shares part B's pool: the records may sit in memory A reuses
@@ -779,14 +850,14 @@ class SplitPipelinedRunner(PipelinedRunner):
             self.stats["replay"] += 1
         else:
             self.s_head.wait_stream(self.s_pre)   # (covers backbone(t) and a replayed A of the other slot)
-            self._stage_slot(slot, metas, prev, self.s_head)
+            self._stage_slot(slot, metas, prev, self.s_head, cams)
             with torch.cuda.stream(self.s_head):
                 rec = self._part_b(self._part_a(slot, dmetas), aug, slot)
             self.stats["eager"] += 1
             if graph_ok:
                 self.head_runs[slot] += 1
         done = self._enqueue_readback(slot, rec)
-        return dict(slot=slot, metas=metas, prev=prev, warm=warm, rec=rec, done=done, active=None)
+        return dict(slot=slot, metas=metas, prev=prev, warm=warm, rec=rec, done=done, active=None, cameras=cams)
 
     def _quiesce(self):
         self.s_pre.synchronize()
