@@ -232,6 +232,45 @@ int simpb_preprocess_yuv420sp_nhwc4_f16(void* out, const void* src, void* mid, c
                                         int src_row0, int src_rows, int flip, int swap_rb, int vu_order, int yoff, int iy,
                                         int irv, int igu, int igv, int ibu, void* stream);
 
+/* The same ingest for surfaces as a hardware decoder allocates them: padded row pitch, aligned plane height, the chroma
+ * plane at its own offset and pitch, 10-bit samples, and one allocation per image. `out` equals the two entry points above
+ * on the same pictures bit for bit (they pass the tight layout to the same kernel).
+ *   format        SIMPB_SURFACE_BGR (rows of src_width * 3 bytes), _NV12 / _NV21 (u8, (Cb, Cr) / (Cr, Cb) pairs) or _P010
+ *                 (semi-planar (Cb, Cr), u16 little-endian, sample = word >> 6: the low six bits are ignored)
+ *   pitch         bytes from one luma (BGR) row to the next, >= the row's sample bytes (3, 1 or 2 per pixel)
+ *   chroma_pitch  bytes from one chroma row to the next, >= src_width sample widths         } not looked at
+ *   chroma_offset bytes from the image's first byte to chroma row 0, behind the last luma sample  } for _BGR
+ *   The images, exactly one of the two non-NULL:
+ *   src           a contiguous batch: image n starts at src + n * image_stride; image_stride >= the offset one past the
+ *                 image's last sample
+ *   image_table   device array of num_images 64-bit addresses, one per image, 8-byte aligned; image_stride is not looked
+ *                 at. The kernel reads the table when it runs: a captured launch follows whatever addresses the table
+ *                 holds at each replay. Each address must be readable up to the image's last sample (even for _P010).
+ * Of a needed source row exactly the sample bytes are read: no byte between two rows, behind the last row, of a luma row
+ * outside src_row0 .. src_row0 + src_rows - 1 or of a chroma row under no such row. A row that starts on a 16-byte
+ * boundary is read in 16-byte chunks plus a bytewise tail, any other row bytewise; any pitch and base alignment is taken.
+ * 10-bit conversion, the integers of the 8-bit rule with two more fractional bits (int32, >> arithmetic):
+ *   c = iy * (Y10 - 4 * yoff) + 2^17
+ *   R = clamp((c + irv * (Cr10 - 512)) >> 18)
+ *   G = clamp((c + igu * (Cb10 - 512) + igv * (Cr10 - 512)) >> 18)
+ *   B = clamp((c + ibu * (Cb10 - 512)) >> 18)
+ * so that an 8-bit sample stored as v << 8 gives the 8-bit rule's byte. yoff .. ibu are not looked at for _BGR.
+ * SIMPB_EINVAL, and nothing launched: whatever the entry points above refuse; both or neither of src / image_table; a
+ * format outside the four; a pitch below the row's sample bytes (or above 2^30); a chroma plane that starts before the
+ * luma plane ends; an odd pitch, chroma_pitch, chroma_offset, image_stride or src for _P010; with src, an image_stride
+ * below the image's last sample. Two launches on `stream`; no allocation, no synchronisation (graph capture safe). */
+#define SIMPB_SURFACE_BGR 0
+#define SIMPB_SURFACE_NV12 1
+#define SIMPB_SURFACE_NV21 2
+#define SIMPB_SURFACE_P010 3
+int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
+                                       const int* xlo, const int* xn, const int* ky, const int* ylo, const int* yn,
+                                       const void* lut, int num_images, int src_height, int src_width, int out_height,
+                                       int out_width, int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb,
+                                       int format, long long pitch, long long chroma_pitch, long long chroma_offset,
+                                       long long image_stride, int yoff, int iy, int irv, int igu, int igv, int ibu,
+                                       void* stream);
+
 /* Bytes of one row of the `mid` scratch above (whole groups of 4 pixels, rounded up to 16); 0 for a width outside 1..2048. */
 int simpb_preprocess_mid_pitch(int out_width);
 

@@ -45,6 +45,7 @@ SIGNATURES = {
     "simpb_image_to_nhwc4_f16": ([_P, _P] + [ctypes.c_longlong] * 4 + [_I] * 4 + [_P], _I),
     "simpb_preprocess_u8_nhwc4_f16": ([_P] * 10 + [_I] * 11 + [_P], _I),
     "simpb_preprocess_yuv420sp_nhwc4_f16": ([_P] * 10 + [_I] * 18 + [_P], _I),
+    "simpb_preprocess_surface_nhwc4_f16": ([_P] * 11 + [_I] * 12 + [_LL] * 4 + [_I] * 6 + [_P], _I),
     "simpb_preprocess_mid_pitch": ([_I], _I),
     "simpb_linear_f16in_split": ([_P] * 5 + [_I] * 3 + [_P], _I),
     "simpb_format_tokens": ([_P, _P, _P, _P, _I, _I, _I, _I, _P], _I),

@@ -11,14 +11,18 @@
 // instruction (and no contraction rule of the compiler) enters the result.
 //
 // Two launches with a u8 intermediate [N, rows, pitch] in HBM (1.2 MB per camera at 1600 x 900 -> 704 x 256):
-//   1. horizontal: one workgroup per (needed source row, image). The row (Ws x 3 bytes) is staged in LDS in 16-byte chunks
-//      (neighbouring output columns share almost all of their taps), a thread makes whole output pixels, the resampled row
-//      goes through LDS again and leaves as 16-byte chunks.
+//   1. horizontal: one workgroup per (needed source row, image). The row is staged in LDS (16-byte chunks where the row
+//      starts on a 16-byte boundary; neighbouring output columns share almost all of their taps), a thread makes whole
+//      output pixels, the resampled row goes through LDS again and leaves as 16-byte chunks.
 //   2. vertical + table: a thread owns 4 neighbouring output pixels = 12 intermediate bytes per tap row (three aligned
 //      dwords), and writes them as two 16-byte stores.
 // 4:2:0 semi-planar YCbCr frames (NV12 / NV21, u8 [N, Hs * 3 / 2, Ws]: what hardware video and JPEG decoders deliver) enter
 // through a second horizontal kernel: it stages the luma row and its chroma row (Ws bytes each) and converts them once, in
 // int32 with 16 fractional bits, into the same (B, G, R) LDS row; filter, store and the vertical pass are the BGR route's own.
+// A decoder's SURFACE (simpb_preprocess_surface_nhwc4_f16) enters through a third horizontal kernel, a template over the
+// source format (BGR, NV12, NV21, and P010 in u16): row pitch, chroma pitch and offset and the image stride are arguments,
+// and the images are either one contiguous batch or a device table of one address per image. It reads no byte outside a
+// needed row's samples and shares filter, store and the vertical pass with the other two, which keep the tight forms.
 // Every load of a thread is retired before its stores are issued (store_fence.h).
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
@@ -142,6 +146,92 @@ __global__ __launch_bounds__(kThreads) void resample_rows_yuv420sp_kernel(unsign
   filter_row_and_store(mid + ((size_t)n * rows + r) * pitch, s_src, s_out, kx, xlo, xn, Ws, w, taps, flip, pitch);
 }
 
+// One image as a decoder delivers it (include/simpb_hip.h, simpb_preprocess_surface_nhwc4_f16): image n starts at
+// src + n * image_stride, or at table[n] when `table` is given; luma (or BGR) row r at + r * pitch, chroma row i at
+// + chroma_offset + i * chroma_pitch. The table is read by the kernel: a captured launch follows the addresses written
+// into it before each replay.
+struct Surface {
+  const unsigned char* src;
+  const unsigned long long* table;
+  long long image_stride, chroma_offset, pitch, chroma_pitch;
+};
+
+constexpr int kBgr = SIMPB_SURFACE_BGR, kNv12 = SIMPB_SURFACE_NV12, kNv21 = SIMPB_SURFACE_NV21, kP010 = SIMPB_SURFACE_P010;
+
+// Exactly `bytes` of one source row into LDS, never a byte past them (a surface may end at its last sample, and what lies
+// between two rows is not the caller's to read). A row that starts on a 16-byte boundary goes as floor(bytes / 16) chunks and
+// a bytewise tail; any other row bytewise. The choice is made here, from the row's own address (uniform over the workgroup):
+// with a pitch that is no multiple of 16 it alternates from row to row, and under a captured graph the address table
+// changes between replays while the kernel arguments do not.
+__device__ __forceinline__ void stage_row(unsigned char* s_dst, const unsigned char* __restrict__ p, int bytes) {
+  const int tid = threadIdx.x;
+  if ((reinterpret_cast<size_t>(p) & 15) == 0) {
+    const int chunks = bytes >> 4;
+    const uint4* p16 = reinterpret_cast<const uint4*>(p);
+    uint4* s16 = reinterpret_cast<uint4*>(s_dst);
+    for (int i = tid; i < chunks; i += kThreads) s16[i] = p16[i];
+    for (int i = (chunks << 4) + tid; i < bytes; i += kThreads) s_dst[i] = p[i];
+  } else {
+    for (int i = tid; i < bytes; i += kThreads) s_dst[i] = p[i];
+  }
+}
+
+// The horizontal pass over a surface, one workgroup per (needed source row, image), for every source format:
+//   mid[n][r][j][c] = clip8(2^21 + sum_t bgr[n][row0 + r][xlo[jj] + t][c] * kx[jj][t]),  jj = flip ? w - 1 - j : j
+// kBgr: bgr is the surface's own interleaved row. 4:2:0 semi-planar (kNv12: (Cb, Cr) pairs, kNv21: (Cr, Cb), u8; kP010: (Cb,
+// Cr), u16 little-endian with the 10-bit sample in the high bits): chroma sample (i, j) covers luma rows 2i, 2i + 1 and
+// columns 2j, 2j + 1 (replicated). The luma row and the chroma row under it are staged and converted once into the (B, G,
+// R) row, with S = 16 fractional bits, chroma centre C = 128 for u8 and S = 18, C = 512, yoff * 4 for 10-bit samples:
+//   c = iy * (Y - yoff) + 2^(S-1),  R = clamp((c + irv * (Cr - C)) >> S),  G = clamp((c + igu * (Cb - C) + igv * (Cr - C)) >> S),
+//   B = clamp((c + ibu * (Cb - C)) >> S)     (int32, arithmetic shift, clamp to 0..255)
+// Chroma rows that lie under no needed luma row are never read.
+template <int F>
+__global__ __launch_bounds__(kThreads) void resample_rows_surface_kernel(unsigned char* __restrict__ mid, Surface sf,
+                                                                         const int* __restrict__ kx, const int* __restrict__ xlo,
+                                                                         const int* __restrict__ xn, int Ws, int row0, int rows, int w,
+                                                                         int taps, int flip, int pitch, YuvCoeffs q) {
+  __shared__ __attribute__((aligned(16))) unsigned char s_src[kMaxSrcW * 3];
+  __shared__ __attribute__((aligned(16))) unsigned char s_out[kMaxOutW * 3 + 16];
+  const int tid = threadIdx.x, r = blockIdx.x, n = blockIdx.y;
+  const int row = row0 + r;
+  const unsigned char* image = sf.table ? reinterpret_cast<const unsigned char*>(sf.table[n]) : sf.src + (size_t)n * sf.image_stride;
+  if constexpr (F == kBgr) {
+    stage_row(s_src, image + (size_t)row * sf.pitch, Ws * 3);
+    __syncthreads();
+  } else {
+    constexpr int kSample = F == kP010 ? 2 : 1;   // bytes per sample
+    __shared__ __attribute__((aligned(16))) unsigned char s_luma[kMaxSrcW * kSample];   // (a BGR row is staged where the filter reads it)
+    __shared__ __attribute__((aligned(16))) unsigned char s_chroma[kMaxSrcW * kSample];
+    constexpr int kShift = F == kP010 ? 18 : 16, kCentre = F == kP010 ? 512 : 128, kVu = F == kNv21 ? 1 : 0;
+    stage_row(s_luma, image + (size_t)row * sf.pitch, Ws * kSample);
+    stage_row(s_chroma, image + sf.chroma_offset + (size_t)(row >> 1) * sf.chroma_pitch, Ws * kSample);
+    __syncthreads();
+    const int yoff = F == kP010 ? 4 * q.yoff : q.yoff;
+    for (int x = 2 * tid; x < Ws; x += 2 * kThreads) {   // a chroma pair and its two luma samples (Ws is even)
+      int cb, cr, y0, y1;
+      if constexpr (F == kP010) {   // sample = word >> 6: the low six bits are ignored whatever they hold
+        const unsigned short* l = reinterpret_cast<const unsigned short*>(s_luma);
+        const unsigned short* c = reinterpret_cast<const unsigned short*>(s_chroma);
+        cb = (int)(c[x] >> 6); cr = (int)(c[x + 1] >> 6); y0 = (int)(l[x] >> 6); y1 = (int)(l[x + 1] >> 6);
+      } else {
+        cb = (int)s_chroma[x + kVu]; cr = (int)s_chroma[x + 1 - kVu]; y0 = (int)s_luma[x]; y1 = (int)s_luma[x + 1];
+      }
+      cb -= kCentre; cr -= kCentre;
+      const int dr = q.irv * cr, dg = q.igu * cb + q.igv * cr, db = q.ibu * cb;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int c = q.iy * ((i ? y1 : y0) - yoff) + (1 << (kShift - 1));
+        unsigned char* d = s_src + (x + i) * 3;
+        d[0] = (unsigned char)clamp8((c + db) >> kShift);
+        d[1] = (unsigned char)clamp8((c + dg) >> kShift);
+        d[2] = (unsigned char)clamp8((c + dr) >> kShift);
+      }
+    }
+    __syncthreads();
+  }
+  filter_row_and_store(mid + ((size_t)n * rows + r) * pitch, s_src, s_out, kx, xlo, xn, Ws, w, taps, flip, pitch);
+}
+
 // out[n][y][x][c] = lut[c][clip8(2^21 + sum_t mid[n][ylo[y] - row0 + t][x][swap ? 2 - c : c] * ky[y][t])], out[..][3] = 0
 __global__ __launch_bounds__(kThreads) void resample_cols_lut_kernel(_Float16* __restrict__ out, const unsigned char* __restrict__ mid,
                                                                      const int* __restrict__ ky, const int* __restrict__ ylo,
@@ -209,7 +299,7 @@ extern "C" int simpb_preprocess_mid_pitch(int out_width) {
   return (out_width <= 0 || out_width > kMaxOutW) ? 0 : mid_pitch(out_width);
 }
 
-// what both entry points refuse (before any HIP call)
+// what every entry point refuses (before any HIP call)
 static bool bad_arguments(const void* out, const void* src, const void* mid, const int* kx, const int* xlo, const int* xn, const int* ky,
                           const int* ylo, const int* yn, const void* lut, int num_images, int src_height, int src_width, int out_height,
                           int out_width, int taps_x, int taps_y, int src_row0, int src_rows) {
@@ -234,6 +324,28 @@ static int finish_vertical(void* out, const void* mid, const int* ky, const int*
                      static_cast<_Float16*>(out), static_cast<const unsigned char*>(mid), ky, ylo, yn,
                      static_cast<const _Float16*>(lut), src_row0, src_rows, out_height, out_width, taps_y, swap_rb ? 1 : 0, pitch);
   return simpb_check_launch();
+}
+
+// the horizontal pass of one source format on a checked surface, then the vertical pass
+static int launch_surface(int format, void* out, const Surface& sf, void* mid, const int* kx, const int* xlo, const int* xn, const int* ky,
+                          const int* ylo, const int* yn, const void* lut, int num_images, int src_width, int out_height, int out_width,
+                          int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb, const YuvCoeffs& q, void* stream) {
+  const int pitch = mid_pitch(out_width);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  (void)hipGetLastError();
+  const dim3 grid(src_rows, num_images), block(kThreads);
+  unsigned char* m = static_cast<unsigned char*>(mid);
+  const int f = flip ? 1 : 0;
+#define SIMPB_ROWS(F) \
+  hipLaunchKernelGGL(resample_rows_surface_kernel<F>, grid, block, 0, s, m, sf, kx, xlo, xn, src_width, src_row0, src_rows, out_width, taps_x, f, pitch, q)
+  switch (format) {
+    case kBgr: SIMPB_ROWS(kBgr); break;
+    case kNv12: SIMPB_ROWS(kNv12); break;
+    case kNv21: SIMPB_ROWS(kNv21); break;
+    default: SIMPB_ROWS(kP010); break;
+  }
+#undef SIMPB_ROWS
+  return finish_vertical(out, mid, ky, ylo, yn, lut, num_images, out_height, out_width, taps_y, src_row0, src_rows, swap_rb, pitch, s);
 }
 
 extern "C" int simpb_preprocess_u8_nhwc4_f16(void* out, const void* src, void* mid, const int* kx, const int* xlo, const int* xn,
@@ -272,4 +384,43 @@ extern "C" int simpb_preprocess_yuv420sp_nhwc4_f16(void* out, const void* src, v
                      static_cast<const unsigned char*>(src), kx, xlo, xn, src_height, src_width, src_row0, src_rows, out_width,
                      taps_x, flip ? 1 : 0, pitch, vec16, vu_order, q);
   return finish_vertical(out, mid, ky, ylo, yn, lut, num_images, out_height, out_width, taps_y, src_row0, src_rows, swap_rb, pitch, s);
+}
+
+extern "C" int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
+                                                  const int* xlo, const int* xn, const int* ky, const int* ylo, const int* yn,
+                                                  const void* lut, int num_images, int src_height, int src_width, int out_height,
+                                                  int out_width, int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb,
+                                                  int format, long long pitch, long long chroma_pitch, long long chroma_offset,
+                                                  long long image_stride, int yoff, int iy, int irv, int igu, int igv, int ibu,
+                                                  void* stream) {
+  if ((src != nullptr) == (image_table != nullptr)) return SIMPB_EINVAL;   // exactly one form of the images
+  if (bad_arguments(out, src ? src : image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height,
+                    out_width, taps_x, taps_y, src_row0, src_rows))
+    return SIMPB_EINVAL;
+  if (format != kBgr && format != kNv12 && format != kNv21 && format != kP010) return SIMPB_EINVAL;
+  if (reinterpret_cast<size_t>(image_table) & 7) return SIMPB_EINVAL;
+  constexpr long long kMaxPitch = 1LL << 30;   // (keeps every offset below far inside 63 bits)
+  const long long sample = format == kP010 ? 2 : 1;
+  const long long row = (long long)src_width * (format == kBgr ? 3 : sample);   // sample bytes of a luma (BGR) and of a chroma row
+  if (pitch < row || pitch > kMaxPitch) return SIMPB_EINVAL;
+  long long end = (long long)(src_height - 1) * pitch + row;   // one past the image's last sample
+  if (format == kBgr) {
+    chroma_pitch = chroma_offset = 0;   // (not looked at)
+  } else {
+    if ((src_height & 1) || (src_width & 1) || iy <= 0) return SIMPB_EINVAL;
+    if (chroma_pitch < row || chroma_pitch > kMaxPitch) return SIMPB_EINVAL;
+    if (chroma_offset < end || chroma_offset > (1LL << 40)) return SIMPB_EINVAL;   // the chroma plane lies behind the luma plane
+    end = chroma_offset + (long long)(src_height / 2 - 1) * chroma_pitch + row;
+    if (format == kP010 && ((pitch | chroma_pitch | chroma_offset) & 1)) return SIMPB_EINVAL;
+  }
+  if (src) {
+    if (image_stride < end || image_stride > (1LL << 40)) return SIMPB_EINVAL;
+    if (format == kP010 && ((image_stride | (long long)reinterpret_cast<size_t>(src)) & 1)) return SIMPB_EINVAL;
+  } else {
+    image_stride = 0;   // (not looked at)
+  }
+  const Surface sf = {static_cast<const unsigned char*>(src), static_cast<const unsigned long long*>(image_table), image_stride,
+                      chroma_offset, pitch, chroma_pitch};
+  return launch_surface(format, out, sf, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_width, out_height, out_width, taps_x, taps_y,
+                        src_row0, src_rows, flip, swap_rb, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream);
 }

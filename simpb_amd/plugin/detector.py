@@ -356,11 +356,19 @@ class SimPB(BaseModule):
     def extract_feat(self, img, return_depth=False, metas=None, raw_plan=None):
         """simpb.py:64-91. A uint8 `img` is the raw form: camera frames as decoded, in the layout of `raw_plan`
         (simpb_amd.preprocess.ResamplePlan): [bs, cams, Hs, Ws, 3] or [N, Hs, Ws, 3] for a "bgr" plan, [bs, cams, Hs * 3 / 2, Ws] or
-        [N, Hs * 3 / 2, Ws] for an "nv12" / "nv21" one. They are converted / resized / cropped / flipped / normalised on the device
-        straight into the stem's operand; a frame whose shape is not the plan's is refused."""
+        [N, Hs * 3 / 2, Ws] for an "nv12" / "nv21" one, [bs, cams, image_bytes] or [N, image_bytes] for a plan with a padded
+        surface layout. They are converted / resized / cropped / flipped / normalised on the device
+        straight into the stem's operand; a frame whose shape is not the plan's is refused. An int64 `img` [bs, cams] or [N] on
+        the device is the pointer form of the same: the address of one surface per image (ResamplePlan.run_table)."""
         bs = img.shape[0]
-        raw = img.dtype == torch.uint8
-        if raw:
+        table = img.dtype == torch.int64
+        raw = table or img.dtype == torch.uint8
+        if table:
+            if raw_plan is None or img.dim() not in (1, 2):
+                raise ValueError("a surface table is int64 [bs, cams] or [N] and needs raw_plan= (simpb_amd.preprocess.ResamplePlan)")
+            num_cams = img.shape[1] if img.dim() == 2 else 1
+            img = raw_plan.run_table(img)
+        elif raw:
             if raw_plan is None:
                 raise ValueError("uint8 frames need raw_plan= (simpb_amd.preprocess.ResamplePlan): the resize / crop / normalise to apply")
             lead = img.dim() - len(raw_plan.frame_shape)

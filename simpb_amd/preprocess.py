@@ -11,7 +11,9 @@ published behaviour and parity-unpinned. This module computes tables only; no pi
 
 Frames may also arrive as 4:2:0 semi-planar YCbCr (NV12 / NV21), the form hardware video and JPEG decoders deliver:
 `yuv_coefficients` defines the integer conversion to the (B, G, R) bytes above that the horizontal pass applies while it
-stages a row; everything behind it is the BGR route's own."""
+stages a row; everything behind it is the BGR route's own. `SurfaceLayout` describes how a decoder lays such an image out
+in memory (padded row pitch, aligned plane height, the chroma plane's own pitch and offset, tail padding) and adds P010, the
+10-bit form of NV12 (`p010_coefficients`); `ResamplePlan.run_surfaces` takes one allocation per image."""
 import ctypes
 import math
 
@@ -22,7 +24,8 @@ PRECISION_BITS = 22   # Pillow: 32 - 8 - 2
 IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 
 
-FRAME_FORMATS = ("bgr", "nv12", "nv21")
+FRAME_FORMATS = ("bgr", "nv12", "nv21", "p010")
+SURFACE_FORMAT = {"bgr": 0, "nv12": 1, "nv21": 2, "p010": 3}   # SIMPB_SURFACE_* of include/simpb_hip.h
 YUV_BITS = 16         # fractional bits of the YCbCr -> BGR coefficients
 # standard -> (Kr, Kb, full range)
 YUV_STANDARDS = {"jfif": (0.299, 0.114, True), "bt601": (0.299, 0.114, False), "bt709": (0.2126, 0.0722, False)}
@@ -52,22 +55,142 @@ def yuv_coefficients(standard="jfif"):
     return yoff, iy, irv, igu, igv, ibu
 
 
+def p010_coefficients(standard):
+    """The six integers of `yuv_coefficients(standard)` for 10-bit samples (P010: sample = u16 word >> 6), used with two more
+    fractional bits:
+
+        c = iy * (Y10 - 4 * yoff) + 2^17
+        R = clip8((c + irv * (Cr10 - 512)) >> 18)
+        G = clip8((c + igu * (Cb10 - 512) + igv * (Cr10 - 512)) >> 18)
+        B = clip8((c + ibu * (Cb10 - 512)) >> 18)
+
+    An 8-bit sample stored as v << 8 (10-bit value 4 v) gives the 8-bit rule's byte, since (4 A) >> 18 == A >> 16. Limited
+    range only ("bt601", "bt709"): JFIF is the 8-bit JPEG convention, and full-range 10-bit video scales by 1023, not by
+    4 x 255."""
+    if standard not in YUV_STANDARDS:
+        raise ValueError(f"colour standard {standard!r}: one of {sorted(YUV_STANDARDS)}")
+    if YUV_STANDARDS[standard][2]:
+        raise ValueError(f"colour standard {standard!r} is the full-range 8-bit JPEG convention: p010 frames take 'bt601' or 'bt709'")
+    yoff, iy, irv, igu, igv, ibu = yuv_coefficients(standard)
+    # every partial sum stays far inside int32 (below 1.45e8 for both standards)
+    luma = max(abs(iy * (0 - 4 * yoff)), abs(iy * (1023 - 4 * yoff))) + (1 << (YUV_BITS + 1))
+    assert luma + 512 * max(abs(irv), abs(ibu), abs(igu) + abs(igv)) < 145_000_000 < (1 << 31)
+    return yoff, iy, irv, igu, igv, ibu
+
+
 def _check_format(frame_format, colour):
     if frame_format not in FRAME_FORMATS:
         raise ValueError(f"frame format {frame_format!r}: one of {FRAME_FORMATS}")
     if colour not in YUV_STANDARDS:
         raise ValueError(f"colour standard {colour!r}: one of {sorted(YUV_STANDARDS)}")
+    if frame_format == "p010":
+        p010_coefficients(colour)   # (refuses "jfif")
 
 
 def frame_shape(src_hw, frame_format="bgr"):
-    """Trailing dimensions of one image of `src_hw` = (Hs, Ws): (Hs, Ws, 3) interleaved BGR, or (Hs * 3 / 2, Ws) for NV12 / NV21
-    (Hs luma rows, then Hs / 2 rows of interleaved chroma pairs; row pitch Ws)."""
+    """Trailing dimensions of one tightly packed image of `src_hw` = (Hs, Ws): (Hs, Ws, 3) interleaved BGR, or (Hs * 3 / 2, Ws) for
+    NV12 / NV21 (Hs luma rows, then Hs / 2 rows of interleaved chroma pairs; row pitch Ws), or (Hs * 3 / 2, Ws * 2) for P010 (the
+    bytes of u16 little-endian samples in the NV12 arrangement)."""
     hs, ws = int(src_hw[0]), int(src_hw[1])
     if frame_format == "bgr":
         return (hs, ws, 3)
     if hs % 2 or ws % 2:
         raise ValueError(f"{frame_format} frames have even sizes (one chroma pair per 2 x 2 luma samples), got {ws} x {hs}")
-    return (hs * 3 // 2, ws)
+    return (hs * 3 // 2, ws * (2 if frame_format == "p010" else 1))
+
+
+class SurfaceLayout:
+    """Where the samples of one image lie in a decoder's surface; the same for all images of a plan or runner.
+
+    frame_format "bgr": one plane of Hs rows, 3 bytes per pixel. "nv12" / "nv21" / "p010": a luma plane of Hs rows, 1 byte per
+    sample (2 for p010), and a chroma plane of Hs / 2 rows of interleaved pairs of the same row width.
+      pitch          bytes from one luma (BGR) row to the next; at least the row's sample bytes (3 Ws, Ws, 2 Ws: the default)
+      luma_rows      the plane height the decoder allocated, >= Hs (default Hs)
+      chroma_pitch   bytes from one chroma row to the next (default: pitch)
+      chroma_offset  bytes from the image's first byte to chroma row 0 (default: luma_rows * pitch)
+      image_bytes    the extent of one image and the stride between the images of a contiguous batch (default: the end of the
+                     last chroma / BGR row; larger = tail padding)
+    ValueError for rows or planes that overlap, a sample outside image_bytes, and odd offsets of 16-bit samples.
+    `.tight`: every field has its default (for bgr / nv12 / nv21 the form a ResamplePlan without a layout takes). `.key`:
+    what enters `plan_key` (None when tight)."""
+
+    def __init__(self, src_hw, frame_format, pitch=None, luma_rows=None, chroma_pitch=None, chroma_offset=None, image_bytes=None):
+        if frame_format not in FRAME_FORMATS:
+            raise ValueError(f"frame format {frame_format!r}: one of {FRAME_FORMATS}")
+        hs, ws = int(src_hw[0]), int(src_hw[1])
+        if hs <= 0 or ws <= 0:
+            raise ValueError(f"source {ws} x {hs}")
+        self.src_hw, self.frame_format = (hs, ws), frame_format
+        self.tight = all(v is None for v in (pitch, luma_rows, chroma_pitch, chroma_offset, image_bytes))
+        self.sample_bytes = 2 if frame_format == "p010" else 1
+        self.row_bytes = ws * (3 if frame_format == "bgr" else self.sample_bytes)   # the samples of a luma (BGR) or chroma row
+        self.pitch = self.row_bytes if pitch is None else int(pitch)
+        if frame_format == "bgr":
+            given = [n for n, v in (("luma_rows", luma_rows), ("chroma_pitch", chroma_pitch), ("chroma_offset", chroma_offset)) if v is not None]
+            if given:
+                raise ValueError(f"a bgr surface is one plane: {', '.join(given)} must not be given")
+            self.luma_rows, self.chroma_pitch, self.chroma_offset = hs, 0, 0
+            self.sample_end = (hs - 1) * self.pitch + self.row_bytes
+        else:
+            frame_shape((hs, ws), frame_format)   # (even sizes)
+            self.luma_rows = hs if luma_rows is None else int(luma_rows)
+            self.chroma_pitch = self.pitch if chroma_pitch is None else int(chroma_pitch)
+            self.chroma_offset = self.luma_rows * self.pitch if chroma_offset is None else int(chroma_offset)
+            self.sample_end = self.chroma_offset + (hs // 2 - 1) * self.chroma_pitch + self.row_bytes
+        self.image_bytes = self.sample_end if image_bytes is None else int(image_bytes)
+        self._check()
+        self.key = None if self.tight else (self.pitch, self.luma_rows, self.chroma_pitch, self.chroma_offset, self.image_bytes)
+
+    def _check(self):
+        hs, ws = self.src_hw
+        what = self.describe()
+        if self.pitch < self.row_bytes:
+            raise ValueError(f"{what}: rows overlap (a row holds {self.row_bytes} sample bytes, the pitch is {self.pitch})")
+        if self.frame_format != "bgr":
+            if self.luma_rows < hs:
+                raise ValueError(f"{what}: luma_rows {self.luma_rows} is below the {hs} rows of the picture")
+            if self.chroma_pitch < self.row_bytes:
+                raise ValueError(f"{what}: chroma rows overlap (a row holds {self.row_bytes} sample bytes, the chroma pitch is "
+                                 f"{self.chroma_pitch})")
+            luma_end = (hs - 1) * self.pitch + self.row_bytes
+            if self.chroma_offset < luma_end:
+                raise ValueError(f"{what}: planes overlap (the luma samples end at byte {luma_end}, the chroma plane starts at "
+                                 f"{self.chroma_offset})")
+            if self.frame_format == "p010" and (self.pitch % 2 or self.chroma_pitch % 2 or self.chroma_offset % 2):
+                raise ValueError(f"{what}: p010 samples are 16-bit words: pitch, chroma_pitch and chroma_offset must be even")
+        if self.image_bytes < self.sample_end:
+            raise ValueError(f"{what}: the last sample ends at byte {self.sample_end}, outside image_bytes {self.image_bytes}")
+        if self.frame_format == "p010" and self.image_bytes % 2:
+            raise ValueError(f"{what}: p010 samples are 16-bit words: image_bytes must be even")
+        if max(self.pitch, self.chroma_pitch) > (1 << 30) or self.image_bytes > (1 << 40):
+            raise ValueError(f"{what}: outside the kernel's limits (pitch 2^30, image 2^40 bytes)")
+
+    def describe(self):
+        """The layout in words (for error messages)."""
+        hs, ws = self.src_hw
+        if self.frame_format == "bgr":
+            return f"bgr surface of {ws} x {hs} (interleaved BGR, row pitch {self.pitch})"
+        pair = "(Cr, Cb)" if self.frame_format == "nv21" else "(Cb, Cr)"
+        bits = ", u16 little-endian samples" if self.frame_format == "p010" else ""
+        return (f"{self.frame_format} surface of {ws} x {hs} ({hs} luma rows at pitch {self.pitch} in a plane of {self.luma_rows}, then "
+                f"{hs // 2} rows of interleaved {pair} pairs at pitch {self.chroma_pitch} from byte {self.chroma_offset}{bits})")
+
+    def __repr__(self):
+        return (f"SurfaceLayout({self.src_hw}, {self.frame_format!r}, pitch={self.pitch}, luma_rows={self.luma_rows}, chroma_pitch="
+                f"{self.chroma_pitch}, chroma_offset={self.chroma_offset}, image_bytes={self.image_bytes})")
+
+    @classmethod
+    def make(cls, layout, src_hw, frame_format):
+        """None, a SurfaceLayout or a dict of its keyword arguments -> the SurfaceLayout for (src_hw, frame_format)."""
+        if layout is None:
+            return cls(src_hw, frame_format)
+        if isinstance(layout, dict):
+            return cls(src_hw, frame_format, **layout)
+        if not isinstance(layout, cls):
+            raise ValueError(f"layout is a SurfaceLayout or a dict of its keyword arguments, got {type(layout).__name__}")
+        if layout.src_hw != (int(src_hw[0]), int(src_hw[1])) or layout.frame_format != frame_format:
+            raise ValueError(f"{layout.describe()} does not describe {frame_format} frames of {int(src_hw[1])} x {int(src_hw[0])}")
+        return layout
 
 
 def _bicubic(x):
@@ -148,12 +271,45 @@ def resolve_aug(src_hw, aug_config):
     return dims, crop, bool(aug.get("flip", False))
 
 
-def plan_key(src_hw, aug_config, frame_format="bgr", colour="jfif"):
+def check_surfaces(tensors, surface):
+    """A flat list of tensors, one surface (SurfaceLayout `surface`) each: u8, contiguous, all on one GPU, and each tensor's
+    storage holds the image's bytes up to its last sample from data_ptr() on. Any base alignment is taken (an even one for
+    p010). Returns the device."""
+    import torch
+    if not tensors:
+        raise ValueError("ingest of an empty batch")
+    need = surface.sample_end
+    device = None
+    for i, t in enumerate(tensors):
+        if not torch.is_tensor(t) or t.dtype != torch.uint8:
+            raise ValueError(f"surface {i}: ingest takes one device u8 tensor per image, each a {surface.describe()}")
+        if not t.is_cuda:
+            raise RuntimeError(f"surface {i} is in host memory: surfaces are read where they lie, on the GPU (there is no staging copy "
+                               "and no CPU fallback in this mode)")
+        device = t.device if device is None else device
+        if t.device != device:
+            raise ValueError(f"surface {i} is on {t.device}, surface 0 on {device}")
+        if not t.is_contiguous():
+            raise ValueError(f"surface {i} is a strided view {tuple(t.shape)} with strides {tuple(t.stride())}: a surface's bytes lie "
+                             f"dense in memory from its first on, as a {surface.describe()}")
+        have = t.untyped_storage().nbytes() - t.storage_offset()
+        if have < need:
+            raise ValueError(f"surface {i} holds {have} bytes from its first: a {surface.describe()} has its last sample at byte {need}")
+        if surface.frame_format == "p010" and t.data_ptr() % 2:
+            raise ValueError(f"surface {i} starts at an odd address: p010 samples are 16-bit words")
+    return device
+
+
+def plan_key(src_hw, aug_config, frame_format="bgr", colour="jfif", layout=None):
     """What a ResamplePlan depends on: a frame whose key differs must not run on the plan's tables (nor a frame of another
-    format or colour standard on the plan's kernel; the standard says nothing about BGR frames and is left out of their key)."""
+    format or colour standard on the plan's kernel; the standard says nothing about BGR frames and is left out of their key).
+    `layout` (a SurfaceLayout or a dict of its keyword arguments) adds its own key unless it is tight: a frame never runs on a
+    plan, or a captured graph, made for another layout."""
     _check_format(frame_format, colour)
     dims, crop, flip = resolve_aug(src_hw, aug_config)
-    return (int(src_hw[0]), int(src_hw[1]), dims, crop, flip, frame_format, colour if frame_format != "bgr" else None)
+    key = (int(src_hw[0]), int(src_hw[1]), dims, crop, flip, frame_format, colour if frame_format != "bgr" else None)
+    extra = None if layout is None else SurfaceLayout.make(layout, src_hw, frame_format).key
+    return key if extra is None else key + (extra,)
 
 
 def _device(device):
@@ -172,18 +328,24 @@ class ResamplePlan:
     rows 0 .. Hs - 1 are luma, rows Hs .. Hs * 3 / 2 - 1 interleaved chroma pairs, (Cb, Cr) for nv12 and (Cr, Cb) for nv21;
     chroma sample (i, j) belongs to luma rows 2i, 2i + 1 and columns 2j, 2j + 1 and is replicated, not interpolated (the
     antialiased bicubic reduction behind it makes the choice of chroma up-sampler immaterial). Hs and Ws are even and the row
-    pitch is Ws (a decoder's padded pitch is not taken). `colour` names the standard of `yuv_coefficients`. The converted
+    pitch is Ws (a decoder's padded pitch needs `layout`). `colour` names the standard of `yuv_coefficients`. The converted
     pixel is staged as (B, G, R), so to_rgb, the table and the output mean what they mean for BGR frames: the output equals
-    the BGR plan's on the converted frames bit for bit."""
+    the BGR plan's on the converted frames bit for bit.
 
-    def __init__(self, src_hw, aug_config=None, img_norm_cfg=None, frame_format="bgr", colour="jfif"):
+    "p010": the same arrangement in u16 little-endian samples (sample = word >> 6; `p010_coefficients`), given as bytes: u8
+    [Hs * 3 / 2, Ws * 2]. `layout` (a SurfaceLayout or a dict of its keyword arguments) describes a decoder's padded surface
+    instead: one image is then u8 [image_bytes], `run` takes a contiguous batch of them and `run_surfaces` one tensor per
+    image. Without a layout (or with a tight one) the plan is the one described above."""
+
+    def __init__(self, src_hw, aug_config=None, img_norm_cfg=None, frame_format="bgr", colour="jfif", layout=None):
         self.src_hw = (int(src_hw[0]), int(src_hw[1]))
         _check_format(frame_format, colour)
         self.frame_format, self.colour = frame_format, colour
-        self.frame_shape = frame_shape(self.src_hw, frame_format)
+        self.surface = SurfaceLayout.make(layout, self.src_hw, frame_format)
+        self.frame_shape = frame_shape(self.src_hw, frame_format) if self.surface.tight else (self.surface.image_bytes,)
         self.yuv = None if frame_format == "bgr" else yuv_coefficients(colour)
         self.resize_dims, self.crop, self.flip = resolve_aug(self.src_hw, aug_config)
-        self.key = plan_key(self.src_hw, aug_config, frame_format, colour)
+        self.key = plan_key(self.src_hw, aug_config, frame_format, colour, self.surface)
         cfg = IMG_NORM_CFG if img_norm_cfg is None else img_norm_cfg
         self.img_norm_cfg = dict(mean=list(cfg["mean"]), std=list(cfg["std"]), to_rgb=bool(cfg.get("to_rgb", True)))
         self.swap_rb = self.img_norm_cfg["to_rgb"]
@@ -211,7 +373,7 @@ class ResamplePlan:
             source = self.src_rows * self.src_hw[1] * 3
         else:   # the needed luma rows and the distinct chroma rows under them (needed bytes: both luma rows of a pair stage it)
             last = self.src_row0 + self.src_rows - 1
-            source = (self.src_rows + (last >> 1) - (self.src_row0 >> 1) + 1) * self.src_hw[1]
+            source = (self.src_rows + (last >> 1) - (self.src_row0 >> 1) + 1) * self.surface.row_bytes   # (sample bytes: no padding)
         return dict(source=source, mid_write=mid, mid_read=mid, out=h * w * 8)
 
     # ------------------------------------------------------------------ device
@@ -225,7 +387,7 @@ class ResamplePlan:
         device = _device(device)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)   # noqa: E731
         self._dev = dict(device=device, kx=t(self.kx), xlo=t(self.xlo), xn=t(self.xn), ky=t(self.ky), ylo=t(self.ylo),
-                         yn=t(self.yn), lut=t(self.lut), pitch=int(lib.simpb_preprocess_mid_pitch(self.out_hw[1])), mid=None)
+                         yn=t(self.yn), lut=t(self.lut), pitch=int(lib.simpb_preprocess_mid_pitch(self.out_hw[1])), mid=None, table=None)
         return self
 
     def reserve(self, num_images, device):
@@ -241,8 +403,13 @@ class ResamplePlan:
     def layout(self):
         """The frames `run` takes, in words (for error messages)."""
         hs, ws = self.src_hw
+        if not self.surface.tight:
+            return f"u8 [..., {self.surface.image_bytes}] images, each a {self.surface.describe()}"
         if self.yuv is None:
             return f"u8 [..., {hs}, {ws}, 3] frames (interleaved BGR)"
+        if self.frame_format == "p010":
+            return (f"u8 [..., {hs * 3 // 2}, {ws * 2}] p010 frames (the bytes of u16 little-endian samples: {hs} luma rows, then {hs // 2} "
+                    f"rows of interleaved (Cb, Cr) pairs, row pitch {ws * 2}; a padded surface needs layout=)")
         pair = "(Cb, Cr)" if self.frame_format == "nv12" else "(Cr, Cb)"
         return (f"u8 [..., {hs * 3 // 2}, {ws}] {self.frame_format} frames ({hs} luma rows, then {hs // 2} rows of interleaved {pair} "
                 f"pairs, row pitch {ws}: a padded pitch is not taken)")
@@ -255,34 +422,76 @@ class ResamplePlan:
             raise ValueError(f"ingest takes {self.layout()}, got {frames.dtype} {tuple(frames.shape)}")
 
     def run(self, frames, out=None):
-        """frames u8 [..., Hs, Ws, 3] (u8 [..., Hs * 3 / 2, Ws] for nv12 / nv21) on the device (contiguous) -> f16 [N, h, w, 4]
-        (N = product of the leading dimensions), channel 3 = 0. Launches on the current stream; the intermediate buffer is
-        allocated on first use and kept."""
-        import torch
-        from . import _lib
-        hs, ws = self.src_hw
+        """frames u8 [..., Hs, Ws, 3] (u8 [..., Hs * 3 / 2, Ws] for nv12 / nv21, [..., Hs * 3 / 2, Ws * 2] for p010, [..., image_bytes]
+        with a padded layout) on the device (contiguous) -> f16 [N, h, w, 4] (N = product of the leading dimensions), channel
+        3 = 0. Launches on the current stream; the intermediate buffer is allocated on first use and kept."""
         self.check_frames(frames)
         if not frames.is_cuda:
             raise RuntimeError("simpb_amd operators run on the GPU only (got a CPU tensor); there is no CPU fallback")
         if not frames.is_contiguous():
             raise ValueError("ingest takes contiguous frames" + (" (interleaved pixels)" if self.yuv is None else ""))
         n = int(frames.numel() // int(np.prod(self.frame_shape)))
-        h, w = self.out_hw
         if n == 0:
             raise ValueError("ingest of an empty batch")
-        self.reserve(n, frames.device)
+        if self.frame_format == "p010" and frames.data_ptr() % 2:
+            raise ValueError("p010 frames are 16-bit words: the batch starts at an odd address")
+        return self._launch(n, frames.device, out, src=frames)
+
+    def surface_table(self, tensors):
+        """(addresses, device) of a flat list of device u8 tensors, one surface each, checked by `check_surfaces`."""
+        tensors = list(tensors)
+        return [t.data_ptr() for t in tensors], check_surfaces(tensors, self.surface)
+
+    def run_surfaces(self, tensors, out=None):
+        """One device u8 tensor per image (a flat list; each its own allocation, or a view into one) -> f16 [N, h, w, 4] as
+        `run`. The addresses go into a resident int64 table that the launch reads; the tensors must stay alive and unchanged
+        until the launch has run."""
+        import torch
+        ptrs, device = self.surface_table(tensors)
+        n = len(ptrs)
+        self.reserve(n, device)
+        d = self._dev
+        if d["table"] is None or d["table"].numel() < n:
+            d["table"] = torch.zeros(n, dtype=torch.int64, device=d["device"])
+        # (a copy out of pageable memory: the host buffer is free again when the call returns)
+        d["table"][:n].copy_(torch.tensor(ptrs, dtype=torch.int64))
+        return self.run_table(d["table"][:n], out)
+
+    def run_table(self, table, out=None):
+        """table: device int64 [...], contiguous: the address of one surface per image (as `surface_table` checks them). The
+        launch reads the table when it runs, so a captured launch follows the addresses written into it before each replay."""
+        import torch
+        if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.numel() == 0:
+            raise ValueError("the surface table is a contiguous device int64 tensor with one address per image")
+        return self._launch(int(table.numel()), table.device, out, table=table)
+
+    def _launch(self, n, device, out, src=None, table=None):
+        import torch
+        from . import _lib
+        hs, ws = self.src_hw
+        h, w = self.out_hw
+        self.reserve(n, device)
         d = self._dev
         if out is None:
-            out = torch.empty(n, h, w, 4, dtype=torch.float16, device=frames.device)
+            out = torch.empty(n, h, w, 4, dtype=torch.float16, device=device)
         elif out.dtype != torch.float16 or tuple(out.shape) != (n, h, w, 4) or not out.is_contiguous():
             raise ValueError(f"ingest writes f16 [{n}, {h}, {w}, 4]")
         p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
-        args = (p(out), p(frames), p(d["mid"]), p(d["kx"]), p(d["xlo"]), p(d["xn"]), p(d["ky"]), p(d["ylo"]), p(d["yn"]), p(d["lut"]),
-                n, hs, ws, h, w, self.taps_x, self.taps_y, self.src_row0, self.src_rows, int(self.flip), int(self.swap_rb))
+        tables = (p(d["mid"]), p(d["kx"]), p(d["xlo"]), p(d["xn"]), p(d["ky"]), p(d["ylo"]), p(d["yn"]), p(d["lut"]))
+        ints = (n, hs, ws, h, w, self.taps_x, self.taps_y, self.src_row0, self.src_rows, int(self.flip), int(self.swap_rb))
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if self.yuv is None:
-            _lib.check(_lib.lib().simpb_preprocess_u8_nhwc4_f16(*args, stream), "simpb_preprocess_u8_nhwc4_f16")
-        else:
-            _lib.check(_lib.lib().simpb_preprocess_yuv420sp_nhwc4_f16(*args, int(self.frame_format == "nv21"), *self.yuv, stream),
-                       "simpb_preprocess_yuv420sp_nhwc4_f16")
+        sf = self.surface
+        if table is None and sf.tight and self.frame_format != "p010":   # today's forms, through today's entry points
+            if self.yuv is None:
+                _lib.check(_lib.lib().simpb_preprocess_u8_nhwc4_f16(p(out), p(src), *tables, *ints, stream), "simpb_preprocess_u8_nhwc4_f16")
+            else:
+                _lib.check(_lib.lib().simpb_preprocess_yuv420sp_nhwc4_f16(p(out), p(src), *tables, *ints, int(self.frame_format == "nv21"),
+                                                                          *self.yuv, stream), "simpb_preprocess_yuv420sp_nhwc4_f16")
+            return out
+        null = ctypes.c_void_p(0)
+        yuv = self.yuv if self.yuv is not None else (0, 1, 0, 0, 0, 0)
+        _lib.check(_lib.lib().simpb_preprocess_surface_nhwc4_f16(
+            p(out), p(src) if table is None else null, null if table is None else p(table), *tables, *ints,
+            SURFACE_FORMAT[self.frame_format], sf.pitch, sf.chroma_pitch, sf.chroma_offset, sf.image_bytes, *yuv, stream),
+            "simpb_preprocess_surface_nhwc4_f16")
         return out

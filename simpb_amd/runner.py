@@ -87,7 +87,8 @@ def normalise_cameras(cameras, num_streams, num_cams, active=None):
 
 class FrameRunner:
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif"):
+                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
+                 raw_layout=None, raw_surfaces=False):
         """independent_streams: the batch is a set of independent camera streams, each decoded exactly as a batch of one
         would be (`capacity` 2D slots per stream; SimPBHead.independent_streams) -- the throughput form of BASELINE config
         #3. False: the reference's batch semantics (camera groups padded to the max over the batch).
@@ -97,7 +98,15 @@ class FrameRunner:
         first launches of the frame (csrc/preprocess.hip), keyed by the frame's own aug_config: see _ensure_plan.
         raw_format="nv12" | "nv21", raw_colour="jfif" | "bt601" | "bt709" (with raw_input only): the frames are 4:2:0
         semi-planar YCbCr, u8 [bs, cams, Hs * 3 / 2, Ws] (preprocess.ResamplePlan has the layout), converted to BGR inside the
-        ingest's first launch. The default "bgr" is the packed form above.
+        ingest's first launch. The default "bgr" is the packed form above. "p010": the 10-bit form of NV12, u8 [bs, cams,
+        Hs * 3 / 2, Ws * 2] (raw_colour "bt601" or "bt709").
+        raw_layout=preprocess.SurfaceLayout or a dict of its keyword arguments (with raw_input only): every image is a decoder
+        surface with a padded pitch / plane height / chroma offset; frames are then u8 [bs, cams, image_bytes].
+        raw_surfaces=True (with raw_input only, with or without raw_layout): `img` is a nested list [bs][cams] of device u8
+        tensors, one surface each, read where they lie: there is no staging buffer and no frame copy, only a table of
+        bs * cams addresses per frame. A surface stays valid and unchanged until the results of its frame have been returned
+        (step's return, the collect that yields the frame, or flush); the runner holds a reference to each until then. A
+        paused stream or a masked camera takes None in place of a tensor.
 
         world_output=dict(classes=..., tracking=bool, threshold=float | None): a second output per frame, the WORLD RECORD
         (csrc/world.hip, results.py): boxes in the global frame, threshold and class ranges applied, kept rows packed, a
@@ -119,15 +128,23 @@ class FrameRunner:
         self.img_norm_cfg = img_norm_cfg
         self.plan = None                    # preprocess.ResamplePlan of the stream's aug_config (raw_input mode)
         self.raw_format, self.raw_colour = raw_format, raw_colour
+        self.raw_layout = None              # preprocess.SurfaceLayout of every image (raw_layout=; None: the tight form)
+        self.surfaces = bool(raw_surfaces)  # img is a nested list of device tensors; self.raw is then the int64 address table
         if self.raw_input is None:
             if (raw_format, raw_colour) != ("bgr", "jfif"):
                 raise ValueError(f"raw_format={raw_format!r} / raw_colour={raw_colour!r} describe raw frames: they need raw_input=(Hs, Ws)")
+            if raw_layout is not None or raw_surfaces:
+                raise ValueError("raw_layout / raw_surfaces describe raw frames: they need raw_input=(Hs, Ws)")
             self.img, self.raw = torch.zeros(batch_size, cams, 3, h, w, device=dev), None
         else:   # (no fp32 staging buffer in this mode)
-            from .preprocess import frame_shape, plan_key
+            from .preprocess import SurfaceLayout, frame_shape, plan_key
             plan_key(self.raw_input, None, raw_format, raw_colour)   # (an unknown format or standard is refused here)
             self.img = None
-            self.raw = torch.zeros(batch_size, cams, *frame_shape(self.raw_input, raw_format), dtype=torch.uint8, device=dev)
+            if raw_layout is not None:
+                self.raw_layout = SurfaceLayout.make(raw_layout, self.raw_input, raw_format)
+            self.raw = self._raw_buffer()
+            if self.surfaces:   # (FrameRunner: one pinned table; its copy is over when step returns)
+                self.pin_table = torch.zeros(batch_size, cams, dtype=torch.int64).pin_memory()
         self.proj = torch.zeros(batch_size, cams, 4, 4, device=dev)
         self.wh = torch.tensor([float(w), float(h)], device=dev).view(1, 1, 2).repeat(batch_size, cams, 1)
         self.wh_host = (int(w), int(h))
@@ -204,6 +221,37 @@ class FrameRunner:
                                                       self.active_buf if self.masked else None, cfg["tables"], cfg["threshold"])
         return rec3d, rec2d, overflow, world, count
 
+    def _raw_buffer(self):
+        """The device buffer the ingest reads: the frames' staging buffer, or with raw_surfaces the table of their addresses."""
+        from .preprocess import frame_shape
+        cams = self.head.num_cams
+        if self.surfaces:
+            return torch.zeros(self.bs, cams, dtype=torch.int64, device=self.device)
+        shape = (frame_shape(self.raw_input, self.raw_format) if self.raw_layout is None or self.raw_layout.tight
+                 else (self.raw_layout.image_bytes,))
+        return torch.zeros(self.bs, cams, *shape, dtype=torch.uint8, device=self.device)
+
+    def set_raw_layout(self, raw_layout):
+        """The decoder's surfaces change their layout (raw_layout as in the constructor; None: the tight form) from the next
+        frame on: a changed layout is a changed plan key, so every graph is dropped and the staging buffers are made anew.
+        A pipelined runner takes the change between frames only: with a frame still in flight it is refused (`flush()` first)."""
+        from .preprocess import SurfaceLayout
+        if self.raw_input is None:
+            raise ValueError("raw_layout describes raw frames: it needs raw_input=(Hs, Ws)")
+        if getattr(self, "queue", None):
+            raise RuntimeError(f"set_raw_layout with {len(self.queue)} frame(s) in flight: flush() the runner first (their results "
+                               "have not been returned, and the buffers they were staged in would be replaced)")
+        new = None if raw_layout is None else SurfaceLayout.make(raw_layout, self.raw_input, self.raw_format)
+        if (new.key if new is not None else None) == (self.raw_layout.key if self.raw_layout is not None else None):
+            return
+        torch.cuda.synchronize(self.device)   # nothing in flight reads the old buffers
+        self._drop_all_graphs()
+        self.raw_layout, self.plan = new, None
+        self._new_raw_buffers()
+
+    def _new_raw_buffers(self):
+        self.raw = self._raw_buffer()
+
     def _ensure_plan(self, metas):
         """raw_input mode: the ingest tables follow the frame's aug_config (metas["img_metas"][0], the dict the decoder reads
         as well). A frame whose (source size, resize_dims, crop, flip, format, colour) differ from the resident plan's gets a
@@ -211,9 +259,9 @@ class FrameRunner:
         resize in): a frame never runs on stale tables."""
         from .preprocess import ResamplePlan, plan_key
         aug = metas["img_metas"][0]["aug_config"]
-        if self.plan is not None and self.plan.key == plan_key(self.raw_input, aug, self.raw_format, self.raw_colour):
+        if self.plan is not None and self.plan.key == plan_key(self.raw_input, aug, self.raw_format, self.raw_colour, self.raw_layout):
             return
-        plan = ResamplePlan(self.raw_input, aug, self.img_norm_cfg, self.raw_format, self.raw_colour)
+        plan = ResamplePlan(self.raw_input, aug, self.img_norm_cfg, self.raw_format, self.raw_colour, self.raw_layout)
         if plan.out_hw != self.image_hw:
             raise ValueError(f"aug_config {aug} turns {self.raw_input} frames into {plan.out_hw} images; this runner was built for "
                              f"{self.image_hw}")
@@ -222,10 +270,56 @@ class FrameRunner:
             self._drop_all_graphs()
         self.plan = plan.reserve(self.bs * self.head.num_cams, self.device)
 
-    def _check_frames(self, img):
-        if img.dtype != torch.uint8 or tuple(img.shape) != tuple(self.raw.shape):
-            what = "" if self.raw_format == "bgr" else f" {self.raw_format}"
-            raise ValueError(f"raw_input runner takes u8 {tuple(self.raw.shape)}{what} frames, got {img.dtype} {tuple(img.shape)}")
+    def _check_frames(self, img, mask=None, cams=None):
+        """The frames of a step as `_stage_frames` takes them; a wrong form is refused before anything is enqueued."""
+        if self.surfaces:
+            return self._check_surfaces(img, mask, cams)
+        if not torch.is_tensor(img) or img.dtype != torch.uint8 or tuple(img.shape) != tuple(self.raw.shape):
+            what = " frames" if self.raw_format == "bgr" else f" {self.raw_format} frames"
+            if self.raw_layout is not None and not self.raw_layout.tight:
+                what = f" images, each a {self.raw_layout.describe()}"
+            got = f"{img.dtype} {tuple(img.shape)}" if torch.is_tensor(img) else type(img).__name__
+            raise ValueError(f"raw_input runner takes u8 {tuple(self.raw.shape)}{what}, got {got}")
+        return img
+
+    def _check_surfaces(self, img, mask, cams):
+        """raw_surfaces: img [bs][cams] of device u8 tensors -> (addresses [bs][cams], the tensors). None stands for the surface
+        of a paused stream or a masked camera (a paused stream's whole row may be None); its table entry is another surface of
+        the same step: the kernel runs on every slot, and what it makes of that one is never looked at."""
+        from .preprocess import SurfaceLayout, check_surfaces
+        num_cams = self.head.num_cams
+        if torch.is_tensor(img) or not isinstance(img, (list, tuple)) or len(img) != self.bs:
+            raise ValueError(f"raw_surfaces runner takes a nested list [{self.bs}][{num_cams}] of device u8 tensors, one surface each "
+                             f"(got {type(img).__name__})")
+        rows, held = [], []
+        for i, row in enumerate(img):
+            paused = mask is not None and not mask[i]
+            if row is None and paused:
+                row = [None] * num_cams
+            if not isinstance(row, (list, tuple)) or len(row) != num_cams:
+                raise ValueError(f"raw_surfaces: stream {i} brings {num_cams} surfaces, one per camera")
+            for c, t in enumerate(row):
+                if t is None and not (paused or (cams is not None and not cams[i][c])):
+                    raise ValueError(f"raw_surfaces: stream {i} camera {c} has no surface, and is neither paused nor masked")
+            rows.append(list(row))
+            held += [t for t in row if t is not None]
+        if not held:
+            raise ValueError("raw_surfaces: this step brings no surface at all (every camera of every active stream is masked): "
+                             "the address table needs one live surface")
+        layout = self.raw_layout if self.raw_layout is not None else SurfaceLayout(self.raw_input, self.raw_format)
+        if check_surfaces(held, layout) != torch.device(self.raw.device):
+            raise ValueError(f"raw_surfaces: the surfaces are on {held[0].device}, the runner on {self.raw.device}")
+        spare = held[0].data_ptr()
+        return [[spare if t is None else t.data_ptr() for t in row] for row in rows], held
+
+    def _stage_frames(self, dst, frames, pin=None):
+        """This frame's images into the buffer the ingest reads (on the current stream): the frames themselves, or with
+        raw_surfaces their bs * cams addresses through the pinned table `pin` -- the surfaces are not copied."""
+        if not self.surfaces:
+            dst.copy_(frames, non_blocking=True)
+            return
+        pin.copy_(torch.tensor(frames[0], dtype=torch.int64))
+        dst.copy_(pin, non_blocking=True)
 
     def _extract(self, img, raw):
         return self.model.extract_feat(raw, raw_plan=self.plan) if raw is not None else self.model.extract_feat(img)
@@ -297,7 +391,10 @@ class FrameRunner:
 
     def _stage(self, img, metas, mask=None, cams=None):
         """Copy this frame's inputs into the static device buffers (a few small async copies)."""
-        (self.img if self.raw is None else self.raw).copy_(img, non_blocking=True)
+        if self.raw is None:
+            self.img.copy_(img, non_blocking=True)
+        else:
+            self._stage_frames(self.raw, img, getattr(self, "pin_table", None))
         self._stage_motion(metas, self.prev_metas, mask, cams)
 
     def _device_metas(self, metas):
@@ -406,7 +503,7 @@ class FrameRunner:
         self._check_pose(metas, mask)
         aug = metas["img_metas"][0]["aug_config"]
         if self.raw is not None:
-            self._check_frames(img)
+            img = self._check_frames(img, mask, cams)   # (raw_surfaces: the tensors stay referenced until this step returns)
             self._ensure_plan(metas)
         self._stage(img, metas, mask, cams)
         dmetas = self._device_metas(metas)
@@ -463,13 +560,14 @@ class PipelinedRunner(FrameRunner):
     set (`overflow_chain`, plugin/head.py), and collect() then re-runs both, in order, on the state frame t-1 found."""
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif"):
+                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
+                 raw_layout=None, raw_surfaces=False):
         # two streams side by side from here on: a convolution that misses the in-tree kernels' shape rules must not slip to a
         # vendor kernel silently (plugin/detector.py: STRICT_NO_VENDOR)
         from .plugin import detector
         detector.STRICT_NO_VENDOR = True
         super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg,
-                         world_output, raw_format, raw_colour)
+                         world_output, raw_format, raw_colour, raw_layout, raw_surfaces)
         dev = self.device
         # the decoder of frame t is the critical path (a chain of ~170 dependent small launches); the
         # backbone of frame t+1 only has to be done by the time that chain ends: decoder stream first
@@ -481,6 +579,9 @@ class PipelinedRunner(FrameRunner):
         # captured backbone graph and reads the slot's own buffer)
         self.imgs = [self.img, torch.zeros_like(self.img)] if self.raw is None else [None, None]
         self.raws = [self.raw, torch.zeros_like(self.raw)] if self.raw is not None else [None, None]
+        if self.surfaces:   # one pinned address table per feature slot, reused once its copy has run (as the motion pins)
+            self.pin_tables = [self.pin_table, torch.zeros_like(self.pin_table).pin_memory()]
+            self.table_staged = [None, None]
         self.fm = [None, None]              # feature maps of the frame last produced into each slot
         self.bb_graph = [None, None]
         self.bb_out = [None, None]
@@ -537,6 +638,10 @@ class PipelinedRunner(FrameRunner):
     def _drop_all_graphs(self):
         self._drop_graphs()
         self.bb_graph, self.bb_out, self.bb_runs = [None, None], [None, None], [0, 0]
+
+    def _new_raw_buffers(self):
+        super()._new_raw_buffers()
+        self.raws = [self.raw, torch.zeros_like(self.raw)]
 
     def _run_head(self, slot, dmetas, aug, warm, force_eager):
         """Enqueue the decoder of the frame whose features sit in slot `slot` on s_head."""
@@ -617,18 +722,29 @@ class PipelinedRunner(FrameRunner):
         self._check_pose(metas, mask)
         slot = self.count % 2
         if self.raw is not None:
-            self._check_frames(img)
+            img = self._check_frames(img, mask, cams)
             self._ensure_plan(metas)
         cur = torch.cuda.current_stream()
         self.s_bb.wait_stream(cur)
         self.s_head.wait_stream(cur)
         with torch.cuda.stream(self.s_bb):
-            (self.imgs[slot] if self.raw is None else self.raws[slot]).copy_(img, non_blocking=True)
+            if self.raw is None:
+                self.imgs[slot].copy_(img, non_blocking=True)
+            elif not self.surfaces:
+                self._stage_frames(self.raws[slot], img)
+            else:   # 8 * bs * cams bytes in front of the backbone graph, whose ingest node reads the slot's table
+                if self.table_staged[slot] is not None:
+                    self.table_staged[slot].synchronize()   # the slot's last copy out of its pinned table (long done)
+                self._stage_frames(self.raws[slot], img, self.pin_tables[slot])
+                self.table_staged[slot] = torch.cuda.Event()
+                self.table_staged[slot].record(self.s_bb)
         self._run_backbone(slot, force_eager)
         self.bb_done[slot].record(self.s_bb)
         self.s_head.wait_event(self.bb_done[slot])
         prev = dict(img_metas=self.last_metas["img_metas"]) if self.last_metas is not None else None
         self.queue.append(self._enqueue_decoder(slot, metas, prev, force_eager, mask, cams))
+        if self.surfaces:
+            self.queue[-1]["surfaces"] = img[1]   # held until the frame's results have been returned (_finish)
         self.last_metas = metas
         self.count += 1
 
@@ -649,11 +765,14 @@ class PipelinedRunner(FrameRunner):
                 if not job["warm"]:
                     self.head.instance_bank.reset()  # a cold frame starts from an empty bank again
                 self._clear_hold()   # flags left by the overflowed attempt / the speculative decoder behind it
+                held = job.get("surfaces")
                 job = self._enqueue_decoder(job["slot"], job["metas"], job["prev"], True, job["active"], job["cameras"])
+                job["surfaces"] = held
                 job["done"].synchronize()
                 h = self.host[job["slot"]]
             for b in behind:
                 self.queue.append(self._enqueue_decoder(b["slot"], b["metas"], b["prev"], True, b["active"], b["cameras"]))
+                self.queue[-1]["surfaces"] = b.get("surfaces")
         self.last_rec3d, self.last_rec2d = job["rec"][0], job["rec"][1]
         self.prev_metas = dict(img_metas=job["metas"]["img_metas"])
         if self.world_output is None:
@@ -721,9 +840,10 @@ class SplitPipelinedRunner(PipelinedRunner):
     SUPPORTS_PAUSE = False
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif"):
+                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
+                 raw_layout=None, raw_surfaces=False):
         super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg,
-                         world_output, raw_format, raw_colour)
+                         world_output, raw_format, raw_colour, raw_layout, raw_surfaces)
         dev = self.device
         # part A rides on the backbone stream, right behind backbone(t): as fast for one stream as a third stream of its own
         # (350 frames/s either way) and cheaper when several runners share the GPU (8 runners: 368 against 308 frames/s)

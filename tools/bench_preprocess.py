@@ -17,9 +17,16 @@
   (c) `cpu_pillow_ms`: the same preprocessing of one six-camera frame with Pillow + numpy on one CPU thread, if Pillow
       imports (a CPU number about CPU work).
 
+  (d) `surface`: decoder surfaces (SurfaceLayout, simpb_preprocess_surface_nhwc4_f16) at R50 with 6 and 48 images.
+      `launch`: the two ingest launches alone, timed as in (a), for tight NV12 (the existing entry point), NV12 at pitch 1792
+      with 912 luma rows as one contiguous batch, the same surfaces as separate allocations behind the pointer table,
+      tight P010 (twice the source bytes), and tight NV12 and BGR through the surface kernel beside their own kernels. `runner`: SplitPipelinedRunner frames/s with device-resident NV12 surfaces as a
+      tight tensor, as a padded tensor (raw_layout) and as a pointer list (raw_surfaces) whose surfaces alternate between
+      two pools -- the tensor forms pay the 13 / 14.5 MB device-to-device staging copy per frame, the pointer list 48 bytes.
+
 A run that finds no GPU fails.
 
-    python tools/bench_preprocess.py [--launches 200] [--blocks 5] [--block-steps 40]
+    python tools/bench_preprocess.py [--launches 200] [--blocks 5] [--block-steps 40] [--only-surface | --skip-surface]
 """
 import argparse
 import json
@@ -173,6 +180,132 @@ def runner_leg(torch, args):
     return out
 
 
+PADDED = dict(pitch=1792, luma_rows=912)   # 1600 x 900 as a hardware decoder allocates it
+
+
+def pack_nv12(torch, nv12, layout):
+    """Tight NV12 u8 [..., 1350, 1600] -> surfaces u8 [..., image_bytes] of `layout` (pad bytes 0xFF)."""
+    hs, ws = layout.src_hw
+    out = torch.full(nv12.shape[:-2] + (layout.image_bytes,), 0xFF, dtype=torch.uint8)
+    for r in range(hs):
+        out[..., r * layout.pitch:r * layout.pitch + ws] = nv12[..., r, :]
+    for i in range(hs // 2):
+        off = layout.chroma_offset + i * layout.chroma_pitch
+        out[..., off:off + ws] = nv12[..., hs + i, :]
+    assert off + ws == layout.sample_end
+    return out
+
+
+def surface_launch_leg(torch, args):
+    from simpb_amd import _lib
+    from simpb_amd.preprocess import ResamplePlan, SurfaceLayout
+    aug = CONFIGS["r50_704x256"]
+    nv12, bgr = nv12_frames(torch, 0)
+    six, six_bgr = nv12[0], bgr[0]                                 # [6, 1350, 1600], [6, 900, 1600, 3]
+    layout = SurfaceLayout((900, 1600), "nv12", **PADDED)
+    padded = pack_nv12(torch, six, layout)
+    p010 = (six.to(torch.int16) << 8).view(torch.uint8).reshape(6, 1350, 3200)    # v << 8, little-endian words as bytes
+    forms = {"nv12_tight": (ResamplePlan((900, 1600), aug, frame_format="nv12", colour="bt601"), six, False),
+             "nv12_padded": (ResamplePlan((900, 1600), aug, frame_format="nv12", colour="bt601", layout=layout), padded, False),
+             "nv12_padded_pointer_table": (ResamplePlan((900, 1600), aug, frame_format="nv12", colour="bt601", layout=layout), padded, True),
+             "p010_tight": (ResamplePlan((900, 1600), aug, frame_format="p010", colour="bt601"), p010, False),
+             # the tight forms through the surface kernel (a layout whose every field is spelled out takes the new entry point)
+             # beside the kernels of the two older entry points: what those would cost as callers of the surface kernel
+             "nv12_tight_surface_kernel": (ResamplePlan((900, 1600), aug, frame_format="nv12", colour="bt601",
+                                                        layout=dict(image_bytes=1350 * 1600)), six.reshape(6, -1), False),
+             "bgr_tight": (ResamplePlan((900, 1600), aug), six_bgr, False),
+             "bgr_tight_surface_kernel": (ResamplePlan((900, 1600), aug, layout=dict(image_bytes=900 * 1600 * 3)), six_bgr.reshape(6, -1), False)}
+    out = {}
+    refs = {}
+    for name, (plan, host, pointer) in forms.items():
+        pitch = int(_lib.lib().simpb_preprocess_mid_pitch(plan.out_hw[1]))
+        per_image = plan.bytes_per_image(pitch)
+        for bs in (1, 8):
+            n = bs * 6
+            frames = host.cuda().repeat(bs, *([1] * (host.dim() - 1))).contiguous()
+            dst = torch.empty(n, *plan.out_hw, 4, dtype=torch.float16, device="cuda")
+            plan.reserve(n, "cuda")
+            if pointer:   # one allocation per image; the table is written once, the launches read it
+                singles = [frames[i].clone() for i in range(n)]
+                table = torch.tensor(plan.surface_table(singles)[0], dtype=torch.int64, device="cuda")
+                go = lambda: plan.run_table(table, out=dst)   # noqa: E731
+            else:
+                go = lambda: plan.run(frames, out=dst)   # noqa: E731
+            for _ in range(20):
+                go()
+            torch.cuda.synchronize()
+            ref = refs.setdefault(plan.frame_format == "bgr", dst[:6].clone())   # (the BGR pictures follow the jfif rule)
+            assert torch.equal(dst[:6], ref), name        # every form decodes the same pictures to the same operand
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.launches):
+                go()
+            e1.record()
+            e1.synchronize()
+            ms = e0.elapsed_time(e1) / args.launches
+            nbytes = n * sum(per_image.values())
+            out[f"{name}_bs{bs}"] = dict(ms=round(ms, 5), images=n, launches=args.launches, bytes=nbytes, source_bytes_per_image=per_image["source"],
+                                         bytes_per_s=round(nbytes / (ms * 1e-3), 1), share_of_hbm_peak=round(nbytes / HBM_PEAK * 1e3 / ms, 4))
+    for bs in (1, 8):
+        t = out[f"nv12_tight_bs{bs}"]["ms"]
+        for name in ("nv12_padded", "nv12_padded_pointer_table", "p010_tight"):
+            out[f"{name}_bs{bs}"]["ms_minus_tight_nv12"] = round(out[f"{name}_bs{bs}"]["ms"] - t, 5)
+        for name in ("nv12_tight", "bgr_tight"):
+            out[f"{name}_surface_kernel_bs{bs}"]["ms_minus_older_kernel"] = round(out[f"{name}_surface_kernel_bs{bs}"]["ms"] - out[f"{name}_bs{bs}"]["ms"], 5)
+    return out
+
+
+def surface_runner_leg(torch, args):
+    from simpb_amd import synth
+    from simpb_amd.preprocess import SurfaceLayout
+    from simpb_amd.runner import SplitPipelinedRunner
+    ring = 4
+    layout = SurfaceLayout((900, 1600), "nv12", **PADDED)
+    tight = [nv12_frames(torch, f)[0] for f in range(ring)]
+    padded = [pack_nv12(torch, x, layout) for x in tight]
+    dev = torch.device("cuda")
+    make = lambda **kw: SplitPipelinedRunner(build_model(torch), 1, (256, 704), capacity=1536, device=dev, use_graph=True,   # noqa: E731
+                                             raw_input=(900, 1600), raw_format="nv12", **kw)
+    # two surface pools of `ring` frames each, one allocation per camera: frame f reads pool f % 2 (a decoder hands out a
+    # different surface every frame; the pictures are resident, as in the tensor forms, so only the form of delivery differs)
+    pools = [[[padded[f][0, c].cuda().clone() for c in range(6)] for f in range(ring)] for _ in range(2)]
+    forms = {"tight_tensor": dict(r=make(), feed=[x.cuda() for x in tight], copy_bytes=tight[0].numel()),
+             "padded_tensor": dict(r=make(raw_layout=layout), feed=[x.cuda() for x in padded], copy_bytes=padded[0].numel()),
+             "pointer_list": dict(r=make(raw_layout=layout, raw_surfaces=True), feed=None, copy_bytes=8 * 6)}
+    count = dict.fromkeys(forms, 0)
+
+    def run(name, steps):
+        form = forms[name]
+        for _ in range(steps):
+            f = count[name]
+            img = form["feed"][f % ring] if form["feed"] is not None else [pools[f % 2][f % ring]]
+            form["r"].step(img, synth.frame_metas(1, f))
+            count[name] = f + 1
+
+    for name in forms:
+        run(name, 12)
+    torch.cuda.synchronize()
+    blocks = {k: [] for k in forms}
+    for _ in range(args.blocks):
+        for name in forms:
+            run(name, 4)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(name, args.block_steps)
+            torch.cuda.synchronize()
+            blocks[name].append((time.perf_counter() - t0) / args.block_steps * 1e3)
+    out = {}
+    for name, ms in blocks.items():
+        mean = float(np.mean(ms))
+        out[name] = dict(ms_per_step=round(mean, 4), frames_per_s=round(1e3 / mean, 1), block_ms=[round(v, 4) for v in ms],
+                         spread_ms=round(max(ms) - min(ms), 4), timed_frames=args.blocks * args.block_steps,
+                         device_copy_bytes_per_frame=forms[name]["copy_bytes"], replays=forms[name]["r"].stats["replay"])
+    out["pointer_minus_padded_tensor_ms"] = round(out["pointer_list"]["ms_per_step"] - out["padded_tensor"]["ms_per_step"], 4)
+    out["padded_minus_tight_tensor_ms"] = round(out["padded_tensor"]["ms_per_step"] - out["tight_tensor"]["ms_per_step"], 4)
+    out["noise_ms"] = max(v["spread_ms"] for v in out.values() if isinstance(v, dict))
+    return out
+
+
 def cpu_leg(frames=3):
     try:
         from PIL import Image
@@ -206,6 +339,8 @@ def main():
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--block-steps", type=int, default=40)
     ap.add_argument("--skip-runner", action="store_true")
+    ap.add_argument("--skip-surface", action="store_true", help="leave out the decoder-surface leg (d)")
+    ap.add_argument("--only-surface", action="store_true", help="the decoder-surface leg (d) alone")
     ap.add_argument("--profile-raw", action="store_true",
                     help="only the runner leg's raw form: the program to put behind `rocprofv3 --kernel-trace --stats --`")
     args = ap.parse_args()
@@ -215,9 +350,14 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_preprocess.py needs a GPU: nothing here is measured on a CPU in its place")
     with torch.no_grad():
+        surface = None
+        if not (args.skip_surface or args.profile_raw):
+            surface = dict(launch=surface_launch_leg(torch, args), runner=None if args.skip_runner else surface_runner_leg(torch, args))
+        older = not args.only_surface
         result = dict(tool="bench_preprocess", device=torch.cuda.get_device_name(0), hbm_peak_bytes_per_s=HBM_PEAK,
-                      kernel=None if args.profile_raw else kernel_leg(torch, args), runner=None if args.skip_runner else runner_leg(torch, args),
-                      cpu_pillow=None if args.profile_raw else cpu_leg())
+                      kernel=kernel_leg(torch, args) if older and not args.profile_raw else None,
+                      runner=runner_leg(torch, args) if older and not args.skip_runner else None,
+                      cpu_pillow=cpu_leg() if older and not args.profile_raw else None, surface=surface)
     print(json.dumps(result))
 
 
