@@ -16,10 +16,13 @@ are re-captured at the new capacity, and results never silently degrade. Pipelin
 decoder one step early (before the previous frame's flags have reached the host) and therefore chains the
 hold on the device: see its docstring.
 """
+from dataclasses import dataclass
+
 import numpy as np
 import torch
 
 from .plugin.detection3d import SparseBox3DDecoder
+from .results import POSE_KEYS, pose_row, world_tables
 
 
 # Captures are taken in thread-local mode: with a process group initialised (one process per GPU, dist.py) the collective
@@ -36,6 +39,15 @@ def stream_motion(metas, prev):
                   for m, p in zip(metas["img_metas"], prev["img_metas"])])
     dt = np.array([float(m["timestamp"] - p["timestamp"]) for m, p in zip(metas["img_metas"], prev["img_metas"])], np.float32)
     return t, dt
+
+
+def refinement_time_step(dt, max_time_interval, default_time_interval):
+    """The time step the refinement heads divide velocities by (instance_bank.py:87,108-113; csrc/bank.hip bank_get_kernel):
+    the gap to the previous frame where it is usable (non-zero and within max_time_interval), the default otherwise. f32
+    in, f32 out, compared in f32 like the kernel does."""
+    dt = np.asarray(dt, np.float32)
+    ok = (dt != 0) & (np.abs(dt) <= np.float32(max_time_interval))
+    return np.where(ok, dt, np.float32(default_time_interval)).astype(np.float32)
 
 
 def carry_inactive_metas(prev, metas, active):
@@ -85,7 +97,94 @@ def normalise_cameras(cameras, num_streams, num_cams, active=None):
     return None if all(all(row) for row in out) else tuple(out)
 
 
+class FrameInputs:
+    """The per-frame decoder inputs of ONE frame in flight: a host buffer (pinned where the device is a GPU) and a device
+    buffer for each, by name in `host` / `dev`:
+        proj    f32 [bs, cams, 4, 4]  projection matrices
+        t, dt   f32 [bs, 4, 4], [bs]  ego-motion T_temp2cur and time step to the stream's previous frame (stream_motion)
+        ti      f32 [bs]              the refinement time step; only with time_step=(max_time_interval, default_time_interval)
+        active  u8 [bs]               1: the stream takes part
+        cam     u8 [bs, cams]         1: the camera delivered a frame
+        pose    f64 [bs, 14]          results.pose_row per stream; only with pose=True
+    The device buffers are allocated here and never replaced: captured graphs bake their addresses in. `fill` is pure host
+    work, `upload` the frame's copies to the device, `metas` the dict the head reads them through."""
+
+    def __init__(self, bs, cams, device, time_step=None, pose=False):
+        device = torch.device(device)
+        self.time_step = time_step
+        spec = dict(proj=((bs, cams, 4, 4), torch.float32, 0), t=((bs, 4, 4), torch.float32, 0), dt=((bs,), torch.float32, 0),
+                    active=((bs,), torch.uint8, 1), cam=((bs, cams), torch.uint8, 1))
+        if time_step is not None:
+            spec["ti"] = ((bs,), torch.float32, 0)
+        if pose:
+            spec["pose"] = ((bs, 14), torch.float64, 0)
+        self.host, self.dev = {}, {}
+        for name, (shape, dtype, value) in spec.items():
+            host = torch.full(shape, value, dtype=dtype)
+            self.host[name] = host.pin_memory() if device.type == "cuda" else host
+            self.dev[name] = torch.full(shape, value, dtype=dtype, device=device)
+        self.warm = self.masked = self.cam_masked = False   # of the frame last filled: what upload copies and metas names
+        self.uploaded = None                # event: the host buffers have been copied to the device and may be refilled
+
+    def fill(self, metas, prev, mask, cams, masked=False, cam_masked=False):
+        """One frame into the host buffers. metas: the frame's (paused streams already carried); prev: the metas of the
+        frame before it (None: a cold frame, whose motion rows stay as they are); mask / cams: the frame's activity and
+        camera masks (None: all ones); masked / cam_masked: the runner's graphs read the activity / camera buffer. A stream
+        whose img_metas entry lacks results.POSE_KEYS (a paused one) keeps the pose row it had."""
+        if self.uploaded is not None:
+            self.uploaded.synchronize()     # the previous frame's copies out of these buffers (long done in practice)
+        h = self.host
+        proj = metas["projection_mat"]
+        h["proj"].copy_(proj.cpu() if proj.is_cuda else proj)
+        self.warm, self.masked, self.cam_masked = prev is not None, masked, cam_masked
+        if self.warm:
+            t, dt = stream_motion(metas, prev)
+            h["t"].copy_(torch.from_numpy(t))
+            h["dt"].copy_(torch.from_numpy(dt))
+        if "ti" in h:
+            # the time step the refinement heads divide by (instance_bank.py:108-113, csrc/bank.hip bank_get_kernel): the
+            # frame gap where it is usable, the default otherwise -- a function of the time stamps alone, in f32 like there
+            max_dt, default = self.time_step
+            h["ti"].numpy()[:] = refinement_time_step(dt, max_dt, default) if self.warm else np.float32(default)
+        h["active"].numpy()[:] = 1 if mask is None else mask
+        h["cam"].numpy()[:] = 1 if cams is None else cams
+        if "pose" in h:
+            rows = h["pose"].numpy()
+            for i, m in enumerate(metas["img_metas"]):
+                if all(k in m for k in POSE_KEYS):
+                    rows[i] = pose_row(m)
+
+    def upload(self, stream):
+        """The filled frame's host-to-device copies, on `stream`: the projection matrices, time step and pose always, motion
+        for a warm frame, a mask once the runner's graphs read it."""
+        live = dict(proj=True, ti=True, pose=True, active=self.masked, cam=self.cam_masked, t=self.warm, dt=self.warm)
+        with torch.cuda.stream(stream):
+            for name, dev in self.dev.items():
+                if live[name]:
+                    dev.copy_(self.host[name], non_blocking=True)
+            self.uploaded = torch.cuda.Event()
+            self.uploaded.record(stream)
+
+    def metas(self, img_metas, wh, wh_host):
+        """The metas dict the head reads the filled frame through (its overflow key is the runner's to add)."""
+        d = self.dev
+        out = dict(projection_mat=d["proj"], image_wh=wh, image_wh_host=wh_host, img_metas=img_metas)
+        if self.warm:
+            out["bank_inputs"] = (d["t"], d["dt"])
+        if self.masked:
+            out["active"] = d["active"]
+        if self.cam_masked:
+            out["camera_valid"] = d["cam"]
+        if "ti" in d:
+            out["time_interval"] = d["ti"]
+        return out
+
+
 class FrameRunner:
+    # a frame's inputs are staged while the frame before it still reads its own (SplitPipelinedRunner: part A(t) runs
+    # beside part B(t-1)): one FrameInputs per feature slot, with the refinement time step that part A needs staged
+    SLOT_INPUTS = False
+
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
                  raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
                  raw_layout=None, raw_surfaces=False):
@@ -130,6 +229,7 @@ class FrameRunner:
         self.raw_format, self.raw_colour = raw_format, raw_colour
         self.raw_layout = None              # preprocess.SurfaceLayout of every image (raw_layout=; None: the tight form)
         self.surfaces = bool(raw_surfaces)  # img is a nested list of device tensors; self.raw is then the int64 address table
+        self.pin_table = None               # raw_surfaces: the pinned host side of that table
         if self.raw_input is None:
             if (raw_format, raw_colour) != ("bgr", "jfif"):
                 raise ValueError(f"raw_format={raw_format!r} / raw_colour={raw_colour!r} describe raw frames: they need raw_input=(Hs, Ws)")
@@ -145,26 +245,20 @@ class FrameRunner:
             self.raw = self._raw_buffer()
             if self.surfaces:   # (FrameRunner: one pinned table; its copy is over when step returns)
                 self.pin_table = torch.zeros(batch_size, cams, dtype=torch.int64).pin_memory()
-        self.proj = torch.zeros(batch_size, cams, 4, 4, device=dev)
         self.wh = torch.tensor([float(w), float(h)], device=dev).view(1, 1, 2).repeat(batch_size, cams, 1)
         self.wh_host = (int(w), int(h))
-        self.t_buf = torch.zeros(batch_size, 4, 4, device=dev)
-        self.dt_buf = torch.zeros(batch_size, device=dev)
-        self.pin_t = torch.zeros(batch_size, 4, 4).pin_memory()
-        self.pin_dt = torch.zeros(batch_size).pin_memory()
-        self.pin_proj = torch.zeros(batch_size, cams, 4, 4).pin_memory()
-        # per-stream activity (step(..., active=)): staged like proj / t_buf once a caller has paused a stream; until then
-        # the head is called without it and nothing here is touched (see _activity)
-        self.active_buf = torch.ones(batch_size, dtype=torch.uint8, device=dev)
-        self.pin_active = torch.ones(batch_size, dtype=torch.uint8).pin_memory()
-        self.masked = False                 # True from the first frame with a paused stream on: the graphs read active_buf
+        # per-stream activity (step(..., active=)) and per-camera validity (step(..., cameras=)): uploaded and handed to the
+        # head once a caller has paused a stream / dropped a camera; until then the head is called without them (see
+        # _activity, _camera_mask)
+        self.masked = False                 # True from the first frame with a paused stream on: the graphs read `active`
         self.last_active = (True,) * batch_size   # mask of the frame last returned
-        # per-camera validity (step(..., cameras=)): staged like the activity mask once a caller has dropped a camera; until
-        # then the head is called without it and nothing here is touched (see _camera_mask)
-        self.cam_buf = torch.ones(batch_size, cams, dtype=torch.uint8, device=dev)
-        self.pin_cam = torch.ones(batch_size, cams, dtype=torch.uint8).pin_memory()
-        self.cam_masked = False             # True from the first frame with a missing camera on: the graphs read cam_buf
-        self.head.instance_bank.enable_static(batch_size, dev)
+        self.cam_masked = False             # True from the first frame with a missing camera on: the graphs read `cam`
+        bank = self.head.instance_bank
+        time_step = (bank.max_time_interval, bank.default_time_interval) if self.SLOT_INPUTS else None
+        self.slot_inputs = [FrameInputs(batch_size, cams, dev, time_step, pose=world_output is not None)
+                            for _ in range(2 if self.SLOT_INPUTS else 1)]
+        self.inputs = self.slot_inputs[0]   # the set last filled
+        bank.enable_static(batch_size, dev)
         self.head.static_capacity = self.capacity
         self.prev_metas = None
         self.graph = None
@@ -180,13 +274,10 @@ class FrameRunner:
         self.rec_consumed = None
         self.world_output = None
         if world_output is not None:
-            from . import results
             tracking = bool(world_output.get("tracking", False))
             self.world_output = dict(classes=tuple(world_output["classes"]), tracking=tracking,
                                      threshold=world_output.get("threshold"),
-                                     tables=results.world_tables(world_output["classes"], tracking))
-            self.pose_buf = torch.zeros(batch_size, 14, dtype=torch.float64, device=dev)
-            self.pin_pose = torch.zeros(batch_size, 14, dtype=torch.float64).pin_memory()
+                                     tables=world_tables(world_output["classes"], tracking))
             self.host_world = self.host_count = None
             self.last_world = None          # device world record f64 [bs, num_output, 16] of the frame last returned ...
             self.last_world_count = None    # ... and its row counts i32 [bs] (-1: the stream was paused); as last_rec3d
@@ -196,30 +287,24 @@ class FrameRunner:
         """world_output: every stream that takes part brings its pose (checked before anything is enqueued)."""
         if self.world_output is None:
             return
-        from .results import POSE_KEYS
         for i, m in enumerate(metas["img_metas"]):
             missing = [k for k in POSE_KEYS if k not in m]
             if missing and (mask is None or mask[i]):
                 raise ValueError(f"world_output: img_metas[{i}] lacks {missing}")
 
-    @staticmethod
-    def _fill_pose(pin, metas):
-        """The streams' poses into a pinned f64 [bs, 14] buffer; a paused stream's row keeps what it held."""
-        from .results import POSE_KEYS, pose_row
-        rows = pin.numpy()
-        for i, m in enumerate(metas["img_metas"]):
-            if all(k in m for k in POSE_KEYS):
-                rows[i] = pose_row(m)
-
-    def _with_world(self, rec3d, rec2d, overflow, pose=None):
-        """A frame's record tuple; with world_output the world record's launch behind it (the last node of the frame) and
-        its two tensors at the end of the tuple."""
+    def _records(self, outs, aug_config, inputs):
+        """The record tail of a frame whose per-frame inputs are `inputs`: the head's outputs -> the frame's record tuple
+        (every tensor of a fixed shape); with world_output the world record's launch behind it (the last node of the frame)
+        and its two tensors at the end of the tuple."""
+        rec3d, rec2d = self.head.decoder.decode_static_device(
+            outs["classification"], outs["prediction"], outs["instance_id"], outs["quality"],
+            outs["classification2d"], outs["prediction2d"], outs["alloc_list"][-1], aug_config)
         if self.world_output is None:
-            return rec3d, rec2d, overflow
+            return rec3d, rec2d, outs["overflow"]
         cfg = self.world_output
-        world, count = self.head.decoder.world_record(rec3d, self.pose_buf if pose is None else pose,
-                                                      self.active_buf if self.masked else None, cfg["tables"], cfg["threshold"])
-        return rec3d, rec2d, overflow, world, count
+        world, count = self.head.decoder.world_record(rec3d, inputs.dev["pose"], inputs.dev["active"] if self.masked else None,
+                                                      cfg["tables"], cfg["threshold"])
+        return rec3d, rec2d, outs["overflow"], world, count
 
     def _raw_buffer(self):
         """The device buffer the ingest reads: the frames' staging buffer, or with raw_surfaces the table of their addresses."""
@@ -238,8 +323,8 @@ class FrameRunner:
         from .preprocess import SurfaceLayout
         if self.raw_input is None:
             raise ValueError("raw_layout describes raw frames: it needs raw_input=(Hs, Ws)")
-        if getattr(self, "queue", None):
-            raise RuntimeError(f"set_raw_layout with {len(self.queue)} frame(s) in flight: flush() the runner first (their results "
+        if self._in_flight():
+            raise RuntimeError(f"set_raw_layout with {self._in_flight()} frame(s) in flight: flush() the runner first (their results "
                                "have not been returned, and the buffers they were staged in would be replaced)")
         new = None if raw_layout is None else SurfaceLayout.make(raw_layout, self.raw_input, self.raw_format)
         if (new.key if new is not None else None) == (self.raw_layout.key if self.raw_layout is not None else None):
@@ -251,6 +336,10 @@ class FrameRunner:
 
     def _new_raw_buffers(self):
         self.raw = self._raw_buffer()
+
+    def _in_flight(self):
+        """Frames fed whose results have not been returned (a step of this runner returns its own frame's)."""
+        return 0
 
     def _ensure_plan(self, metas):
         """raw_input mode: the ingest tables follow the frame's aug_config (metas["img_metas"][0], the dict the decoder reads
@@ -356,56 +445,45 @@ class FrameRunner:
             self.cam_masked = True
         return cams
 
-    def _fill_cameras(self, pin, cams):
-        pin.copy_(torch.tensor(cams if cams is not None else ((True,) * self.head.num_cams,) * self.bs, dtype=torch.uint8))
-
     def _carry(self, prev, metas, mask):
         """This frame's metas with the paused streams' entries held at their last active frame (whose projection matrices
-        are what the pinned staging buffer still holds); the first paused frame also switches the runner to masked graphs."""
+        are what the host buffer of the inputs last filled still holds); the first paused frame also switches the runner to
+        masked graphs."""
         if not self.masked:
             torch.cuda.synchronize(self.device)   # nothing in flight replays a graph that does not read the mask
             self._drop_graphs()
             self.masked = True
-        return carry_inactive_metas(dict(img_metas=prev["img_metas"], projection_mat=self.pin_proj), metas, mask)
+        return carry_inactive_metas(dict(img_metas=prev["img_metas"], projection_mat=self.inputs.host["proj"]), metas, mask)
 
-    def _stage_motion(self, metas, prev, mask, cams=None):
-        """Projection matrices, activity mask, camera mask, ego-motion and time step into the pinned buffers and on to the
-        device (on the current stream)."""
-        self.pin_proj.copy_(metas["projection_mat"] if not metas["projection_mat"].is_cuda else metas["projection_mat"].cpu())
-        self.proj.copy_(self.pin_proj, non_blocking=True)
-        if self.world_output is not None:
-            self._fill_pose(self.pin_pose, metas)
-            self.pose_buf.copy_(self.pin_pose, non_blocking=True)
-        if self.masked:
-            self.pin_active.copy_(torch.tensor(mask if mask is not None else (True,) * self.bs, dtype=torch.uint8))
-            self.active_buf.copy_(self.pin_active, non_blocking=True)
-        if self.cam_masked:
-            self._fill_cameras(self.pin_cam, cams)
-            self.cam_buf.copy_(self.pin_cam, non_blocking=True)
-        if prev is not None:
-            t, dt = stream_motion(metas, prev)
-            self.pin_t.copy_(torch.from_numpy(t))
-            self.pin_dt.copy_(torch.from_numpy(dt))
-            self.t_buf.copy_(self.pin_t, non_blocking=True)
-            self.dt_buf.copy_(self.pin_dt, non_blocking=True)
+    def _admit(self, prev, img, metas, active, cameras):
+        """What step / launch open with: the frame's activity mask, camera mask, metas (paused streams carried from `prev`,
+        the metas of the frame before) and checked frames. Everything that can refuse a frame does so here, before anything
+        is enqueued."""
+        mask = self._activity(active, prev is None)
+        cams = self._camera_mask(cameras, mask)
+        if mask is not None:
+            metas = self._carry(prev, metas, mask)
+        self._check_pose(metas, mask)
+        if self.raw is not None:
+            img = self._check_frames(img, mask, cams)   # (raw_surfaces: the tensors stay referenced until the frame is returned)
+            self._ensure_plan(metas)
+        return mask, cams, metas, img
+
+    def _fill_inputs(self, inputs, metas, prev, mask, cams):
+        """The frame's decoder inputs into `inputs` (host side) -> the metas dict the head reads them through."""
+        self.inputs = inputs
+        inputs.fill(metas, prev, mask, cams, self.masked, self.cam_masked)
+        return inputs.metas(metas["img_metas"], self.wh, self.wh_host)
 
     def _stage(self, img, metas, mask=None, cams=None):
-        """Copy this frame's inputs into the static device buffers (a few small async copies)."""
+        """Copy this frame's inputs into the static device buffers (a few small async copies); returns the head's metas."""
         if self.raw is None:
             self.img.copy_(img, non_blocking=True)
         else:
-            self._stage_frames(self.raw, img, getattr(self, "pin_table", None))
-        self._stage_motion(metas, self.prev_metas, mask, cams)
-
-    def _device_metas(self, metas):
-        out = dict(projection_mat=self.proj, image_wh=self.wh, image_wh_host=self.wh_host, img_metas=metas["img_metas"])
-        if self.prev_metas is not None:
-            out["bank_inputs"] = (self.t_buf, self.dt_buf)
-        if self.masked:
-            out["active"] = self.active_buf
-        if self.cam_masked:
-            out["camera_valid"] = self.cam_buf
-        return out
+            self._stage_frames(self.raw, img, self.pin_table)
+        dmetas = self._fill_inputs(self.inputs, metas, self.prev_metas, mask, cams)
+        self.inputs.upload(torch.cuda.current_stream())
+        return dmetas
 
     def _results(self, rec3d, rec2d, mask, world=None, count=None):
         self.last_active = mask if mask is not None else (True,) * self.bs
@@ -432,12 +510,7 @@ class FrameRunner:
     def _frame(self, dmetas, aug_config):
         """The device part of one frame; every tensor it returns has a fixed shape."""
         feature_maps = self._extract(self.img, self.raw)
-        outs = self.head(feature_maps, dmetas)
-        alloc = outs["alloc_list"][-1]
-        rec3d, rec2d = self.head.decoder.decode_static_device(
-            outs["classification"], outs["prediction"], outs["instance_id"], outs["quality"],
-            outs["classification2d"], outs["prediction2d"], alloc, aug_config)
-        return self._with_world(rec3d, rec2d, outs["overflow"])
+        return self._records(self.head(feature_maps, dmetas), aug_config, self.inputs)
 
     # ------------------------------------------------------------------ capacity overflow
     def _drop_graphs(self):
@@ -496,17 +569,9 @@ class FrameRunner:
         list is empty, and bank, track ids, ego-motion and time step go on as ever: a camera that comes back simply takes
         part again. A cold frame may have missing cameras. A stream that takes part needs at least one camera (ValueError:
         pause it instead); a paused stream's row is not looked at. An overflowed frame is re-run with its own mask."""
-        mask = self._activity(active, self.prev_metas is None)
-        cams = self._camera_mask(cameras, mask)
-        if mask is not None:
-            metas = self._carry(self.prev_metas, metas, mask)
-        self._check_pose(metas, mask)
+        mask, cams, metas, img = self._admit(self.prev_metas, img, metas, active, cameras)
         aug = metas["img_metas"][0]["aug_config"]
-        if self.raw is not None:
-            img = self._check_frames(img, mask, cams)   # (raw_surfaces: the tensors stay referenced until this step returns)
-            self._ensure_plan(metas)
-        self._stage(img, metas, mask, cams)
-        dmetas = self._device_metas(metas)
+        dmetas = self._stage(img, metas, mask, cams)
         warm = self.prev_metas is not None
         if warm and self.use_graph and not force_eager and self.graph is None and self.warm_frames >= 1:
             torch.cuda.synchronize()
@@ -541,6 +606,20 @@ class FrameRunner:
         return self._results(rec3d, rec2d, mask, self.host_world, self.host_count)
 
 
+@dataclass
+class Job:
+    """A decoder in flight. It keeps what a re-run (_finish) stages again: the frame's metas, the metas of the frame before
+    (None: a cold frame) and the frame's own activity and camera masks."""
+    slot: int
+    metas: dict
+    prev: dict
+    rec: tuple          # the frame's device records (_records)
+    done: object        # event: the records have reached the slot's pinned read-back buffers
+    active: tuple
+    cameras: tuple
+    surfaces: list      # raw_surfaces: the frame's tensors, held until its results have been returned
+
+
 class PipelinedRunner(FrameRunner):
     """FrameRunner with the backbone of frame t+1 overlapped with the decoder of frame t.
 
@@ -559,27 +638,28 @@ class PipelinedRunner(FrameRunner):
     is chained on the device: a frame's commit also holds back when the flags of the frame enqueued before it are
     set (`overflow_chain`, plugin/head.py), and collect() then re-runs both, in order, on the state frame t-1 found."""
 
-    def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
-                 raw_layout=None, raw_surfaces=False):
+    # the decoder of frame t is the critical path (a chain of ~170 dependent small launches); the
+    # backbone of frame t+1 only has to be done by the time that chain ends: decoder stream first
+    STREAM_PRIORITIES = (0, -1)             # (backbone, decoder)
+
+    def __init__(self, *args, **kwargs):
+        """Arguments: FrameRunner's."""
         # two streams side by side from here on: a convolution that misses the in-tree kernels' shape rules must not slip to a
         # vendor kernel silently (plugin/detector.py: STRICT_NO_VENDOR)
         from .plugin import detector
         detector.STRICT_NO_VENDOR = True
-        super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg,
-                         world_output, raw_format, raw_colour, raw_layout, raw_surfaces)
+        super().__init__(*args, **kwargs)
         dev = self.device
-        # the decoder of frame t is the critical path (a chain of ~170 dependent small launches); the
-        # backbone of frame t+1 only has to be done by the time that chain ends: decoder stream first
-        prio = getattr(self, "STREAM_PRIORITIES", (0, -1))
-        self.s_bb = torch.cuda.Stream(device=dev, priority=prio[0])
-        self.s_head = torch.cuda.Stream(device=dev, priority=prio[1])
+        self.s_bb = torch.cuda.Stream(device=dev, priority=self.STREAM_PRIORITIES[0])
+        self.s_head = torch.cuda.Stream(device=dev, priority=self.STREAM_PRIORITIES[1])
         self.s_rec = self.s_head            # the stream the detection records are written on (for their consumers)
+        if not self.SLOT_INPUTS:            # both feature slots stage through the one set: the decoders run in stream order
+            self.slot_inputs = self.slot_inputs * 2
         # one input buffer per feature slot: fp32 images, or raw u8 frames (raw_input: the ingest is the first node of the
         # captured backbone graph and reads the slot's own buffer)
         self.imgs = [self.img, torch.zeros_like(self.img)] if self.raw is None else [None, None]
         self.raws = [self.raw, torch.zeros_like(self.raw)] if self.raw is not None else [None, None]
-        if self.surfaces:   # one pinned address table per feature slot, reused once its copy has run (as the motion pins)
+        if self.surfaces:   # one pinned address table per feature slot, reused once its copy has run (as the FrameInputs)
             self.pin_tables = [self.pin_table, torch.zeros_like(self.pin_table).pin_memory()]
             self.table_staged = [None, None]
         self.fm = [None, None]              # feature maps of the frame last produced into each slot
@@ -592,10 +672,9 @@ class PipelinedRunner(FrameRunner):
         self.count = 0
         n_alloc = sum(op == "allocation" for op in self.head.operation_order)
         self.flags = torch.zeros(2, n_alloc, dtype=torch.int32, device=dev)   # overflow flags, one row per feature slot
-        self.queue = []                     # decoders in flight, oldest first: dict(slot, metas, prev, warm, rec)
+        self.queue = []                     # decoders in flight, oldest first: Job
         self.last_metas = None              # metas of the frame whose decoder was enqueued last
         self.bb_done = [torch.cuda.Event(), torch.cuda.Event()]
-        self.staged = None                  # event: the pinned staging buffers have been copied to the device
         self.host = [None, None]            # pinned read-back buffers per slot: (rec3d, rec2d, flags)
 
     def _run_backbone(self, slot, force_eager):
@@ -624,13 +703,11 @@ class PipelinedRunner(FrameRunner):
             fm.append(self.head.precompute_values(fm))
         return fm
 
-    def _decode(self, fm, dmetas, aug):
-        outs = self.head(fm, dmetas)
-        alloc = outs["alloc_list"][-1]
-        rec3d, rec2d = self.head.decoder.decode_static_device(
-            outs["classification"], outs["prediction"], outs["instance_id"], outs["quality"],
-            outs["classification2d"], outs["prediction2d"], alloc, aug)
-        return self._with_world(rec3d, rec2d, outs["overflow"])
+    def _decode(self, slot, dmetas, aug, inputs):
+        return self._records(self.head(self.fm[slot], dmetas), aug, inputs)
+
+    def _in_flight(self):
+        return len(self.queue)
 
     def _drop_graphs(self):
         self.head_graph, self.head_out, self.head_runs = [None, None], [None, None], [0, 0]
@@ -643,8 +720,10 @@ class PipelinedRunner(FrameRunner):
         super()._new_raw_buffers()
         self.raws = [self.raw, torch.zeros_like(self.raw)]
 
-    def _run_head(self, slot, dmetas, aug, warm, force_eager):
-        """Enqueue the decoder of the frame whose features sit in slot `slot` on s_head."""
+    def _run_head(self, slot, inputs, dmetas, aug, warm, force_eager):
+        """Upload the filled `inputs` and enqueue the decoder of the frame whose features sit in slot `slot`, on s_head."""
+        dmetas["overflow_chain"] = (self.flags, slot)
+        inputs.upload(self.s_head)
         with torch.cuda.stream(self.s_head):
             graph_ok = (self.use_graph and not force_eager and warm and self.bb_graph[slot] is not None
                         and self.fm[slot] is self.bb_out[slot])
@@ -652,7 +731,7 @@ class PipelinedRunner(FrameRunner):
                 self.s_head.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=self.s_head, capture_error_mode=CAPTURE_MODE):
-                    self.head_out[slot] = self._decode(self.fm[slot], dmetas, aug)
+                    self.head_out[slot] = self._decode(slot, dmetas, aug, inputs)
                 self.head_graph[slot] = g
             if graph_ok and self.head_graph[slot] is not None:
                 if self.rec_consumed is not None:  # the record buffer of this graph may still be read by its consumer
@@ -661,7 +740,7 @@ class PipelinedRunner(FrameRunner):
                 rec = self.head_out[slot]
                 self.stats["replay"] += 1
             else:
-                rec = self._decode(self.fm[slot], dmetas, aug)
+                rec = self._decode(slot, dmetas, aug, inputs)
                 self.stats["eager"] += 1
                 if graph_ok:
                     self.head_runs[slot] += 1
@@ -679,51 +758,21 @@ class PipelinedRunner(FrameRunner):
             done.record(self.s_head)
         return done
 
-    def _stage_head_inputs(self, metas, prev, mask=None, cams=None):
-        """Per-frame decoder inputs (projection matrices, activity mask, ego-motion, time step) of a frame; prev = the metas
-        of the frame before it (None for a cold frame)."""
-        if self.staged is not None:
-            self.staged.synchronize()   # the previous frame's copies out of the pinned buffers (long done in practice)
-        with torch.cuda.stream(self.s_head):
-            self._stage_motion(metas, prev, mask, cams)
-            self.staged = torch.cuda.Event()
-            self.staged.record(self.s_head)
-
-    def _head_metas(self, metas, slot, warm):
-        out = dict(projection_mat=self.proj, image_wh=self.wh, image_wh_host=self.wh_host, img_metas=metas["img_metas"],
-                   overflow_chain=(self.flags, slot))
-        if warm:
-            out["bank_inputs"] = (self.t_buf, self.dt_buf)
-        if self.masked:
-            out["active"] = self.active_buf
-        if self.cam_masked:
-            out["camera_valid"] = self.cam_buf
-        return out
-
-    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None, cams=None):
-        """Stage the inputs of the frame whose features sit in `slot` and enqueue its decoder + read-back on s_head. The
-        job keeps the frame's own activity and camera masks: a re-run (_finish) stages them again."""
-        warm = prev is not None
+    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None, cams=None, surfaces=None):
+        """Stage the inputs of the frame whose features sit in `slot` and enqueue its decoder + read-back (_run_head)."""
         self.prev_metas = prev   # (what the base class's helpers look at)
-        self._stage_head_inputs(metas, prev, mask, cams)
-        rec = self._run_head(slot, self._head_metas(metas, slot, warm), metas["img_metas"][0]["aug_config"], warm, force_eager)
-        done = self._enqueue_readback(slot, rec)
-        return dict(slot=slot, metas=metas, prev=prev, warm=warm, rec=rec, done=done, active=mask, cameras=cams)
+        inputs = self.slot_inputs[slot]
+        dmetas = self._fill_inputs(inputs, metas, prev, mask, cams)
+        rec = self._run_head(slot, inputs, dmetas, metas["img_metas"][0]["aug_config"], prev is not None, force_eager)
+        return Job(slot, metas, prev, rec, self._enqueue_readback(slot, rec), mask, cams, surfaces)
 
     @torch.no_grad()
     def launch(self, img, metas, force_eager=False, active=None, cameras=None):
         """Enqueue backbone(t) and decoder(t) without waiting for either (several runners -- several independent
         camera streams on one GPU -- can be launched back to back and collected after). img, active, cameras: as
         FrameRunner.step."""
-        mask = self._activity(active, self.last_metas is None)
-        cams = self._camera_mask(cameras, mask)
-        if mask is not None:
-            metas = self._carry(self.last_metas, metas, mask)
-        self._check_pose(metas, mask)
+        mask, cams, metas, img = self._admit(self.last_metas, img, metas, active, cameras)
         slot = self.count % 2
-        if self.raw is not None:
-            img = self._check_frames(img, mask, cams)
-            self._ensure_plan(metas)
         cur = torch.cuda.current_stream()
         self.s_bb.wait_stream(cur)
         self.s_head.wait_stream(cur)
@@ -742,17 +791,15 @@ class PipelinedRunner(FrameRunner):
         self.bb_done[slot].record(self.s_bb)
         self.s_head.wait_event(self.bb_done[slot])
         prev = dict(img_metas=self.last_metas["img_metas"]) if self.last_metas is not None else None
-        self.queue.append(self._enqueue_decoder(slot, metas, prev, force_eager, mask, cams))
-        if self.surfaces:
-            self.queue[-1]["surfaces"] = img[1]   # held until the frame's results have been returned (_finish)
+        self.queue.append(self._enqueue_decoder(slot, metas, prev, force_eager, mask, cams, img[1] if self.surfaces else None))
         self.last_metas = metas
         self.count += 1
 
     def _finish(self, job):
         """Wait for a decoder in flight, re-run it (and whatever was enqueued behind it) if its 2D set overflowed,
         return its detections."""
-        job["done"].synchronize()
-        h = self.host[job["slot"]]
+        job.done.synchronize()
+        h = self.host[job.slot]
         if bool(h[2].any()):
             # overflow: this frame's bank commit held back, and so did the commit of the frame enqueued behind it
             # (overflow_chain); the features of both still sit in their slots -> re-run them in order, eagerly, with a
@@ -762,23 +809,23 @@ class PipelinedRunner(FrameRunner):
             self._quiesce()
             while bool(h[2].any()):
                 self._grow()
-                if not job["warm"]:
+                if job.prev is None:
                     self.head.instance_bank.reset()  # a cold frame starts from an empty bank again
                 self._clear_hold()   # flags left by the overflowed attempt / the speculative decoder behind it
-                held = job.get("surfaces")
-                job = self._enqueue_decoder(job["slot"], job["metas"], job["prev"], True, job["active"], job["cameras"])
-                job["surfaces"] = held
-                job["done"].synchronize()
-                h = self.host[job["slot"]]
-            for b in behind:
-                self.queue.append(self._enqueue_decoder(b["slot"], b["metas"], b["prev"], True, b["active"], b["cameras"]))
-                self.queue[-1]["surfaces"] = b.get("surfaces")
-        self.last_rec3d, self.last_rec2d = job["rec"][0], job["rec"][1]
-        self.prev_metas = dict(img_metas=job["metas"]["img_metas"])
+                job = self._rerun(job)
+                job.done.synchronize()
+                h = self.host[job.slot]
+            self.queue.extend(self._rerun(b) for b in behind)
+        self.last_rec3d, self.last_rec2d = job.rec[0], job.rec[1]
+        self.prev_metas = dict(img_metas=job.metas["img_metas"])
         if self.world_output is None:
-            return self._results(h[0], h[1], job["active"])
-        self.last_world, self.last_world_count = job["rec"][3], job["rec"][4]
-        return self._results(h[0], h[1], job["active"], h[3], h[4])
+            return self._results(h[0], h[1], job.active)
+        self.last_world, self.last_world_count = job.rec[3], job.rec[4]
+        return self._results(h[0], h[1], job.active, h[3], h[4])
+
+    def _rerun(self, job):
+        """The same frame again, eagerly, with its own masks (and its surfaces still held)."""
+        return self._enqueue_decoder(job.slot, job.metas, job.prev, True, job.active, job.cameras, job.surfaces)
 
     def _quiesce(self):
         self.s_head.synchronize()
@@ -808,15 +855,6 @@ class PipelinedRunner(FrameRunner):
         return out
 
 
-def refinement_time_step(dt, max_time_interval, default_time_interval):
-    """The time step the refinement heads divide velocities by (instance_bank.py:87,108-113; csrc/bank.hip bank_get_kernel):
-    the gap to the previous frame where it is usable (non-zero and within max_time_interval), the default otherwise. f32
-    in, f32 out, compared in f32 like the kernel does."""
-    dt = np.asarray(dt, np.float32)
-    ok = (dt != 0) & (np.abs(dt) <= np.float32(max_time_interval))
-    return np.where(ok, dt, np.float32(default_time_interval)).astype(np.float32)
-
-
 class SplitPipelinedRunner(PipelinedRunner):
     """PipelinedRunner with the single-frame decoder layer taken off the temporal chain.
 
@@ -828,7 +866,7 @@ class SplitPipelinedRunner(PipelinedRunner):
     of dependent launches a frame adds to the critical path shrinks by A.
 
     What changes with A(t) running while B(t-1) is still in flight:
-      * per-frame decoder inputs (projection matrices, ego-motion, time step) get one device buffer per feature slot;
+      * per-frame decoder inputs (projection matrices, ego-motion, time step) get one FrameInputs per feature slot;
       * the overflow hold is chained through a `sticky` word that B writes at its end (A(t+1) must not be able to disturb
         the flags B(t) looks at): SimPBHead.forward_split, `overflow_split`;
       * eager (warm-up, re-run) frames run A and B back to back on the decoder stream: only replayed graphs run A on the
@@ -838,12 +876,11 @@ class SplitPipelinedRunner(PipelinedRunner):
     take `cameras`: the camera mask is one more per-frame decoder input with a device buffer per feature slot."""
 
     SUPPORTS_PAUSE = False
+    SLOT_INPUTS = True
 
-    def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
-                 raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
-                 raw_layout=None, raw_surfaces=False):
-        super().__init__(model, batch_size, image_hw, capacity, device, use_graph, independent_streams, raw_input, img_norm_cfg,
-                         world_output, raw_format, raw_colour, raw_layout, raw_surfaces)
+    def __init__(self, *args, **kwargs):
+        """Arguments: FrameRunner's."""
+        super().__init__(*args, **kwargs)
         dev = self.device
         # part A rides on the backbone stream, right behind backbone(t): as fast for one stream as a third stream of its own
         # (350 frames/s either way) and cheaper when several runners share the GPU (8 runners: 368 against 308 frames/s)
@@ -851,110 +888,47 @@ class SplitPipelinedRunner(PipelinedRunner):
         n_alloc = self.flags.shape[1]
         self.hb = torch.zeros(2, n_alloc + 1, dtype=torch.int32, device=dev)   # per slot: the frame's flags | sticky copy
         self.sticky = torch.zeros(1, dtype=torch.int32, device=dev)
-        cams = self.head.num_cams
-        self.proj2 = [torch.zeros(batch_size, cams, 4, 4, device=dev) for _ in range(2)]
-        self.t_buf2 = [torch.zeros(batch_size, 4, 4, device=dev) for _ in range(2)]
-        self.dt_buf2 = [torch.zeros(batch_size, device=dev) for _ in range(2)]
-        self.ti_buf2 = [torch.zeros(batch_size, device=dev) for _ in range(2)]
-        self.cam2 = [torch.ones(batch_size, cams, dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.pin2 = [dict(proj=torch.zeros(batch_size, cams, 4, 4).pin_memory(), t=torch.zeros(batch_size, 4, 4).pin_memory(),
-                          dt=torch.zeros(batch_size).pin_memory(), ti=torch.zeros(batch_size).pin_memory(),
-                          cam=torch.ones(batch_size, cams, dtype=torch.uint8).pin_memory()) for _ in range(2)]
-        self.staged2 = [None, None]
         self.pre_graph = [None, None]
         self.pre_done = [torch.cuda.Event(), torch.cuda.Event()]
-        if self.world_output is not None:   # the pose is a per-frame decoder input like the others: one buffer per slot
-            self.pose2 = [torch.zeros(batch_size, 14, dtype=torch.float64, device=dev) for _ in range(2)]
-            for pin in self.pin2:
-                pin["pose"] = torch.zeros(batch_size, 14, dtype=torch.float64).pin_memory()
 
     def _drop_graphs(self):
         super()._drop_graphs()
         self.pre_graph = [None, None]
-
-    def _stage_slot(self, slot, metas, prev, stream, cams=None):
-        """Per-frame decoder inputs of the frame in `slot`, into that slot's own device buffers."""
-        if self.staged2[slot] is not None:
-            self.staged2[slot].synchronize()
-        pin = self.pin2[slot]
-        bank = self.head.instance_bank
-        pin["proj"].copy_(metas["projection_mat"] if not metas["projection_mat"].is_cuda else metas["projection_mat"].cpu())
-        pin["ti"].fill_(float(bank.default_time_interval))
-        if self.cam_masked:
-            self._fill_cameras(pin["cam"], cams)
-        if self.world_output is not None:
-            self._fill_pose(pin["pose"], metas)
-        if prev is not None:
-            for i, m in enumerate(metas["img_metas"]):
-                t = m["T_global_inv"] @ prev["img_metas"][i]["T_global"]
-                pin["t"][i] = torch.from_numpy(np.asarray(t, np.float32))
-                pin["dt"][i] = float(m["timestamp"] - prev["img_metas"][i]["timestamp"])
-            # the time step the refinement heads divide by (instance_bank.py:108-113, csrc/bank.hip bank_get_kernel): the
-            # frame gap where it is usable, the default otherwise -- a function of the time stamps alone, in f32 like there
-            pin["ti"].copy_(torch.from_numpy(refinement_time_step(pin["dt"].numpy(), bank.max_time_interval,
-                                                                  bank.default_time_interval)))
-        with torch.cuda.stream(stream):
-            self.proj2[slot].copy_(pin["proj"], non_blocking=True)
-            self.ti_buf2[slot].copy_(pin["ti"], non_blocking=True)
-            if self.cam_masked:
-                self.cam2[slot].copy_(pin["cam"], non_blocking=True)
-            if self.world_output is not None:
-                self.pose2[slot].copy_(pin["pose"], non_blocking=True)
-            if prev is not None:
-                self.t_buf2[slot].copy_(pin["t"], non_blocking=True)
-                self.dt_buf2[slot].copy_(pin["dt"], non_blocking=True)
-            self.staged2[slot] = torch.cuda.Event()
-            self.staged2[slot].record(stream)
-
-    def _split_metas(self, metas, slot, warm):
-        out = dict(projection_mat=self.proj2[slot], image_wh=self.wh, image_wh_host=self.wh_host, img_metas=metas["img_metas"],
-                   time_interval=self.ti_buf2[slot], overflow_split=(self.hb[slot], self.sticky))
-        if warm:
-            out["bank_inputs"] = (self.t_buf2[slot], self.dt_buf2[slot])
-        if self.cam_masked:
-            out["camera_valid"] = self.cam2[slot]
-        return out
 
     def _part_a(self, slot, dmetas):
         gen = self.head.forward_split(self.fm[slot], dmetas)
         next(gen)
         return gen
 
-    def _part_b(self, gen, aug, slot):
+    def _part_b(self, gen, aug, inputs):
         try:
             gen.send(None)
         except StopIteration as done:
             outs = done.value
         else:
             raise RuntimeError("forward_split paused twice")
-        alloc = outs["alloc_list"][-1]
-        rec3d, rec2d = self.head.decoder.decode_static_device(
-            outs["classification"], outs["prediction"], outs["instance_id"], outs["quality"],
-            outs["classification2d"], outs["prediction2d"], alloc, aug)
-        return self._with_world(rec3d, rec2d, outs["overflow"], self.pose2[slot] if self.world_output is not None else None)
+        return self._records(outs, aug, inputs)
 
-    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None, cams=None):
-        warm = prev is not None
-        self.prev_metas = prev
-        aug = metas["img_metas"][0]["aug_config"]
-        dmetas = self._split_metas(metas, slot, warm)
+    def _run_head(self, slot, inputs, dmetas, aug, warm, force_eager):
+        """Upload the slot's filled `inputs` and enqueue parts A and B of the frame whose features sit in `slot`."""
+        dmetas["overflow_split"] = (self.hb[slot], self.sticky)
         graph_ok = (self.use_graph and not force_eager and warm and self.bb_graph[slot] is not None
                     and self.fm[slot] is self.bb_out[slot])
         if graph_ok and self.head_graph[slot] is None and self.head_runs[slot] >= 1:
             # capture A and B of this slot (both on the decoder stream; A is replayed on the backbone stream afterwards)
             self.s_pre.synchronize()
             self.s_head.synchronize()
-            self._stage_slot(slot, metas, prev, self.s_head, cams)
+            inputs.upload(self.s_head)
             with torch.cuda.stream(self.s_head):
                 ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
                 with torch.cuda.graph(ga, stream=self.s_head, capture_error_mode=CAPTURE_MODE):
                     gen = self._part_a(slot, dmetas)
                 with torch.cuda.graph(gb, stream=self.s_head, pool=ga.pool(), capture_error_mode=CAPTURE_MODE):
-                    self.head_out[slot] = self._part_b(gen, aug, slot)
+                    self.head_out[slot] = self._part_b(gen, aug, inputs)
                 del gen
             self.pre_graph[slot], self.head_graph[slot] = ga, gb
         if graph_ok and self.head_graph[slot] is not None:
-            self._stage_slot(slot, metas, prev, self.s_pre, cams)
+            inputs.upload(self.s_pre)
             with torch.cuda.stream(self.s_pre):
                 self.s_pre.wait_event(self.bb_done[slot])
                 if self.rec_consumed is not None:   # part A shares part B's pool: the records may sit in memory A reuses
@@ -970,14 +944,13 @@ class SplitPipelinedRunner(PipelinedRunner):
             self.stats["replay"] += 1
         else:
             self.s_head.wait_stream(self.s_pre)   # (covers backbone(t) and a replayed A of the other slot)
-            self._stage_slot(slot, metas, prev, self.s_head, cams)
+            inputs.upload(self.s_head)
             with torch.cuda.stream(self.s_head):
-                rec = self._part_b(self._part_a(slot, dmetas), aug, slot)
+                rec = self._part_b(self._part_a(slot, dmetas), aug, inputs)
             self.stats["eager"] += 1
             if graph_ok:
                 self.head_runs[slot] += 1
-        done = self._enqueue_readback(slot, rec)
-        return dict(slot=slot, metas=metas, prev=prev, warm=warm, rec=rec, done=done, active=None, cameras=cams)
+        return rec
 
     def _quiesce(self):
         self.s_pre.synchronize()

@@ -142,7 +142,7 @@ def test_independent_streams_each_vs_its_own_subset_oracle(monkeypatch):
             res = runner.step(runner.img, metas, cameras=C.mask_rows(kept))
             outs = captured["outs"]
             assert runner.stats["overflow"] == 0
-            assert ("camera_valid" in runner._device_metas(metas)) == runner.cam_masked == (f >= 1)
+            assert ("camera_valid" in runner.inputs.metas(metas["img_metas"], runner.wh, runner.wh_host)) == runner.cam_masked == (f >= 1)
             for b in range(bs):
                 groups = []
                 for alloc in outs["alloc_list"]:

@@ -166,7 +166,7 @@ def test_pipelined_runner_vs_golden(split):
 def test_pipelined_runner_batched_stream_with_a_time_gap(split):
     """The small golden stream (bs = 2, one stream jumps in time: the bank's max_time_interval mask, instance_bank.py:87,
     and the default time step in the refinement heads, :108-113) through both pipelined runners. In the split runner the
-    time step of the single-frame layer is derived on the host from the time stamps (runner._stage_slot)."""
+    time step of the single-frame layer is derived on the host from the time stamps (runner.FrameInputs.fill)."""
     g = load_golden("head_small.npz")
     spec = spec_of(g)
     model, runner = _golden_pipelined_runner(spec, split, capacity=96)
@@ -757,3 +757,60 @@ def test_replayed_frames_of_the_bench_configuration_vs_oracle():
             checked += 1
         prev = metas
     assert checked == 3 and runner.stats["overflow"] == 0
+
+
+def test_frame_inputs_upload_alone():
+    """runner.FrameInputs by itself (bs 2, 6 cameras, with time step and pose): fill + upload on a side stream for three
+    frames -- after the upload's event every device buffer equals its host buffer, and the device buffers never move
+    (captured graphs bake their addresses in); a mask is not copied until the runner's graphs read it; and a fill issued
+    while the previous upload is still pending behind a long kernel waits for it: that upload delivers its own frame."""
+    from simpb_amd.results import pose_row
+    from simpb_amd.runner import FrameInputs
+    bs, cams, wh = 2, 6, (352, 128)
+
+    def frame(f):
+        m = synth.frame_metas(bs, f, wh, jump=(1, 2, 3.0))
+        m["projection_mat"] = m["projection_mat"] * (1.0 + 0.125 * f)
+        for b in range(bs):
+            m["img_metas"][b].update(lidar2ego_rotation=[1.0, 0.0, 0.0, float(f)], lidar2ego_translation=[float(b), 1.0, 2.0],
+                                     ego2global_rotation=[0.5, 0.5, float(f), 0.5], ego2global_translation=[3.0, float(b + f), 4.0])
+        return m
+
+    inp = FrameInputs(bs, cams, torch.device("cuda"), time_step=(2.0, 0.5), pose=True)
+    assert all(h.is_pinned() for h in inp.host.values()) and all(d.is_cuda for d in inp.dev.values())
+    ptrs = {name: d.data_ptr() for name, d in inp.dev.items()}
+    side = torch.cuda.Stream()
+    metas = [frame(f) for f in range(4)]
+    masks = [(None, None), ((True, False), ((True,) * cams, (False,) + (True,) * (cams - 1))), (None, None)]
+    for f in range(3):
+        inp.fill(metas[f], metas[f - 1] if f else None, *masks[f], masked=True, cam_masked=True)
+        inp.upload(side)
+        inp.uploaded.synchronize()
+        for name, d in inp.dev.items():
+            assert torch.equal(d.cpu(), inp.host[name]), (f, name)
+        assert torch.equal(inp.dev["pose"][1].cpu(), torch.from_numpy(pose_row(metas[f]["img_metas"][1])))
+    assert inp.dev["active"].tolist() == [1, 1] and inp.dev["dt"].tolist() == [0.5, 3.5] and inp.dev["ti"].tolist() == [0.5, 0.5]
+    assert {name: d.data_ptr() for name, d in inp.dev.items()} == ptrs
+
+    # a runner that has not switched to masked graphs uploads no mask
+    inp.fill(metas[2], metas[1], (False, True), None)
+    inp.upload(side)
+    inp.uploaded.synchronize()
+    assert inp.host["active"].tolist() == [0, 1] and inp.dev["active"].tolist() == [1, 1]
+
+    # a fill while the previous upload is pending
+    inp.fill(metas[2], metas[1], None, None, masked=True, cam_masked=True)
+    want = {name: h.clone() for name, h in inp.host.items()}
+    spin = torch.empty(64 * 1024 * 1024, device="cuda")
+    with torch.cuda.stream(side):   # keep the side stream busy: the copies below stay pending for a while
+        for _ in range(100):
+            spin.add_(1.0)
+    inp.upload(side)
+    pending = not inp.uploaded.query()
+    inp.fill(metas[3], metas[2], (True, False), None, masked=True, cam_masked=True)
+    assert pending and inp.uploaded.query()     # the fill waited for the copies out of the buffers it overwrites
+    assert not torch.equal(inp.host["proj"], want["proj"]) and not torch.equal(inp.host["pose"], want["pose"])
+    torch.cuda.synchronize()
+    for name, d in inp.dev.items():
+        assert torch.equal(d.cpu(), want[name]), name
+    assert {name: d.data_ptr() for name, d in inp.dev.items()} == ptrs

@@ -211,7 +211,7 @@ def test_option_off_changes_nothing(kind):
     r_off, off = _drive(kind, None)
     r_on, on = _drive(kind, WORLD)
     assert r_old.stats == r_off.stats == r_on.stats
-    assert not hasattr(r_off, "pose_buf") and not hasattr(r_off, "last_world")
+    assert not any("pose" in s.dev or "pose" in s.host for s in r_off.slot_inputs) and not hasattr(r_off, "last_world")
     for step in range(STEPS):
         for s in range(BS):
             a, b, c = old[step][s]["img_bbox"], off[step][s]["img_bbox"], on[step][s]["img_bbox"]

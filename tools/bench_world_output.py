@@ -102,7 +102,7 @@ def measure(bs, args, device):
         host[name] = dict(format_sample_ms_per_step=round(fs, 3), world_record_host_ms_per_step=round(wh_ms, 3),
                           boxes_kept_per_stream=round(kept / bs, 1), boxes_per_stream=k)
     # the launch alone
-    pose = r.pose2[0] if bs == 1 else r.pose_buf
+    pose = r.slot_inputs[0].dev["pose"]
     dec, cfg = r.head.decoder, r.world_output
     for _ in range(20):
         dec.world_record(rec3d, pose, None, cfg["tables"], cfg["threshold"])

@@ -18,7 +18,7 @@ acc = dict(stage=0, launch=0, gpu_wait=0, readback=0, host_decode=0)
 n = 20
 for f in range(6, 6 + n):
     t0 = time.perf_counter()
-    r._stage(imgs[f % 4], metas[f]); dm = r._device_metas(metas[f])
+    dm = r._stage(imgs[f % 4], metas[f])
     t1 = time.perf_counter()
     if r.graph is not None:
         r.graph.replay(); rec = r.outputs

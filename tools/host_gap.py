@@ -43,7 +43,7 @@ for f in range(20, 20 + n):
     a = time.perf_counter()
     r.launch(imgs[f % 4], metas[f])       # backbone(f) and decoder(f) enqueued; decoder(f-1) is what collect() waits for
     b = time.perf_counter()
-    r.queue[0]["done"].synchronize()
+    r.queue[0].done.synchronize()
     c = time.perf_counter()
     r.collect()
     d = time.perf_counter()
