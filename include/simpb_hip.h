@@ -384,7 +384,10 @@ int simpb_conv1x1_nhwc_f16(void* y, const void* x, const void* weight, const voi
  *          (projects/mmdet3d_plugin/ops/__init__.py:63-92); image n is camera block n, this level's pixels start at row
  *          level_start of the block; the value written is the f16 result widened to f32 (what a separate format pass over
  *          the f16 map would write): the FPN's output convolutions produce the tokens themselves. tokens_f16 (f16, same
- *          layout, or NULL): the same rows without the widening, for simpb_linear_f16in_split (value_proj).
+ *          layout, or NULL): the same rows without the widening, for the samplers and simpb_linear_f16in_split
+ *          (value_proj). tokens == NULL with tokens_f16 set: the f16 rows ALONE -- kernels without the fp32 conversions
+ *          and stores (what a replayed frame runs: every reader of the tokens takes f16 rows). Exactly one of y and the
+ *          token form; all three NULL is SIMPB_EINVAL.
  * These are conv2 of every ResNet bottleneck and FPN.fpn_convs (mmdet ResNet + FPN of
  * projects/configs/simpb_nus_r50_img_704x256.py:79-99 after tools/fuse_conv_bn.py:10-48). stride 1 or 2;
  * in_channels % 64 == 0, out_channels % 8 == 0; 16-byte aligned. variant 0 = choose the tiling from the shape; 1-8 force one
@@ -396,7 +399,8 @@ int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, int tokens_
                            int out_channels, int stride, int relu, int variant, void* stream);
 
 /* The same 3x3 / stride 1 convolution for up to four inputs of one channel count in ONE launch, each result written as its
- * level's token rows (f32 `tokens`, and f16 `tokens_f16` or NULL) exactly as simpb_conv3x3_nhwc_f16 does with `tokens`:
+ * level's token rows (f32 `tokens`, and f16 `tokens_f16` or NULL; or tokens == NULL and the f16 rows alone) exactly as
+ * simpb_conv3x3_nhwc_f16 does with `tokens`:
  * the four `fpn_convs[i].conv` of mmdet's FPN (projects/configs/simpb_nus_r50_img_704x256.py:92-99) behind
  * feature_maps_format (ops/__init__.py:63-92). x[j] f16 NHWC [num_images, in_h[j], in_w[j], Cin]; weight[j] f16
  * [Cout, 3, 3, Cin]; bias[j] f16 [Cout]; level_start[j] = the level's first row inside a camera's tokens_per_cam rows.
@@ -448,6 +452,9 @@ int simpb_attention_split_halfs(float* out, const void* q, const void* k, const 
  *                            a refinement head (models/simpb_head.py operation_order "norm", "refine*") inside the head's
  *                            launch; ln_out (row stride ld_ln_out, may be NULL) receives LayerNorm(x), the operator's
  *                            own output (rows >= *m_live as zeros). 4-row / 32-row kernels (weights_transposed == 2, 3) only.
+ *                            With out == NULL, n_ops == 0 and ln_out set the job is that stage ALONE (the operator in front
+ *                            of a head whose outputs nothing reads): the same prologue code, so ln_out is bit-equal to what
+ *                            the job with its chain behind it writes. out == NULL in any other form is SIMPB_EINVAL.
  *   chain output: out rows of the last width, row stride ldo; out_scale (or NULL) multiplies column-wise
  *                 (mmcv Scale after the last Linear); then the optional `post` stage on v = out[row, t]:
  *     POST_REFINE3D  SparseBox3DRefinementModule.forward (models/detection3d/blocks.py:133-143):

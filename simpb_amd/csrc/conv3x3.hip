@@ -58,11 +58,14 @@ struct ConvArgs {
 template <int S>
 using IC = std::integral_constant<int, S>;
 
-// one 16-byte piece of an output row: bias, ReLU, one rounding to fp16; to the f16 map or, widened, to the token buffer
+// one 16-byte piece of an output row: bias, ReLU, one rounding to fp16; to the f16 map or, widened, to the token buffer.
+// TOK16 (a kernel's template argument): the launch writes the f16 token rows alone (tok == NULL, tok16 set) -- the fp32
+// conversions and stores are not in that kernel at all
+template <bool TOK16>
 __device__ __forceinline__ void emit_piece(const ConvArgs& a, int c0, bool full, int p, int c8, const float (&v)[8]) {
   if (p >= a.P_out) return;
   size_t trow = 0;
-  if (a.tok) {   // the FPN's output convolution writes the decoder's token row itself: fp32 values of the fp16 result
+  if (TOK16 || a.tok) {   // the FPN's output convolution writes the decoder's token row itself: the fp16 result, widened to fp32 or (TOK16) as it is
     const int hw = a.Ho * a.Wo;
     const int n = p / hw, pix = p - n * hw;
     trow = ((size_t)n * a.tokens_per_cam + a.level_start + pix) * a.Cout;
@@ -88,7 +91,9 @@ __device__ __forceinline__ void emit_piece(const ConvArgs& a, int c0, bool full,
       const float t = v[e] + (float)bv[e] + (float)rv[e];
       o[e] = (_Float16)(a.relu ? fmaxf(t, 0.f) : t);
     }
-    if (a.tok) {
+    if constexpr (TOK16) {
+      *reinterpret_cast<h16x8*>(a.tok16 + trow + c0 + c8) = o;
+    } else if (a.tok) {
       float* d = a.tok + trow + c0 + c8;
       *reinterpret_cast<float4*>(d) = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
       *reinterpret_cast<float4*>(d + 4) = make_float4((float)o[4], (float)o[5], (float)o[6], (float)o[7]);
@@ -104,7 +109,9 @@ __device__ __forceinline__ void emit_piece(const ConvArgs& a, int c0, bool full,
         float t = v[e] + (float)a.bias[c];
         if (a.residual) t += (float)a.residual[rrow + c];
         const _Float16 o = (_Float16)(a.relu ? fmaxf(t, 0.f) : t);
-        if (a.tok) {
+        if constexpr (TOK16) {
+          a.tok16[trow + c] = o;
+        } else if (a.tok) {
           a.tok[trow + c] = (float)o;
           if (a.tok16) a.tok16[trow + c] = o;
         } else {
@@ -115,7 +122,7 @@ __device__ __forceinline__ void emit_piece(const ConvArgs& a, int c0, bool full,
   }
 }
 
-template <int AF, bool KSPLIT>
+template <int AF, bool KSPLIT, bool TOK16>
 __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[kSmemBytes];
   _Float16* s_b = reinterpret_cast<_Float16*>(smem);
@@ -308,7 +315,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs
   // epilogue, one A fragment at a time: accumulators -> LDS (C/D layout: column = lane & 31,
   // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)), then 16-byte pieces of full rows: bias, ReLU, one rounding to fp16
   const bool full = c0 + BN <= a.Cout;
-  auto emit = [&](int p, int c8, const float (&v)[8]) __attribute__((always_inline)) { emit_piece(a, c0, full, p, c8, v); };
+  auto emit = [&](int p, int c8, const float (&v)[8]) __attribute__((always_inline)) { emit_piece<TOK16>(a, c0, full, p, c8, v); };
   float* mine = s_c + wave * 32 * LDC;
 #pragma unroll
   for (int f = 0; f < AF; ++f) {
@@ -342,14 +349,14 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs
   }
 }
 
-template <int AF, bool KSPLIT>
+template <int AF, bool KSPLIT, bool TOK16>
 void launch(ConvArgs& a, hipStream_t stream) {
   constexpr int BMt = KSPLIT ? 32 * AF : 128 * AF;
   a.gx = (a.P_out + BMt - 1) / BMt;
   a.gy = (a.Cout + BN - 1) / BN;
   const long long total = (long long)a.gx * a.gy;
   a.per_xcd = (int)((total + 7) / 8);
-  hipLaunchKernelGGL((conv3x3_f16_kernel<AF, KSPLIT>), dim3((unsigned)(a.per_xcd * 8)), dim3(kThreads), 0, stream, a);
+  hipLaunchKernelGGL((conv3x3_f16_kernel<AF, KSPLIT, TOK16>), dim3((unsigned)(a.per_xcd * 8)), dim3(kThreads), 0, stream, a);
 }
 
 
@@ -361,7 +368,7 @@ void launch(ConvArgs& a, hipStream_t stream) {
 // sets: loads run two chunks ahead), and fragments are read back with ds_read_b128 (256 B/clk per CU on gfx950, conflict-free
 // at a 144-byte row pitch). BMt x BNt output tile, WGM x WGN waves, each (BMt / WGM) x (BNt / WGN). The tile is chosen per shape so
 // that the grid fills whole rounds of the chip: 67 584 pixels are 528 tiles of 128 (two per CU and sixteen left over) but 704 of 96.
-template <int BMt, int BNt, int WGM, int WGN, int TAPS>
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
 __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int tile) {
   constexpr int NT = 64 * WGM * WGN;
   constexpr int AF = BMt / WGM / 32, NF = BNt / WGN / 32;
@@ -518,17 +525,17 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = mine[r * LDW + c8 + e];
-      emit_piece(a, cw, full, p0 + (wm * AF + f) * 32 + r, c8, v);
+      emit_piece<TOK16>(a, cw, full, p0 + (wm * AF + f) * 32 + r, c8, v);
     }
   }
 }
 
-template <int BMt, int BNt, int WGM, int WGN, int TAPS>
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
 __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 3 ? 3 : 2) void conv_staged_kernel(const ConvArgs a) {
   // each XCD (blockIdx % 8) walks a contiguous range of tiles
   const int tile = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
   if ((int)(blockIdx.x >> 3) >= a.per_xcd || tile >= a.gx * a.gy) return;
-  conv_staged_tile<BMt, BNt, WGM, WGN, TAPS>(a, tile);
+  conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16>(a, tile);
 }
 
 // Several convolutions of one tile shape in ONE launch (the FPN's four output convolutions: 240 us as four launches, of which
@@ -540,7 +547,7 @@ struct ConvGroup {
   int start[kMaxConvGroup + 1];
   int n, per_xcd;
 };
-template <int BMt, int BNt, int WGM, int WGN, int TAPS>
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
 __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 3 ? 3 : 2) void conv_staged_group_kernel(const ConvGroup g) {
   const int gt = (blockIdx.x & 7) * g.per_xcd + (blockIdx.x >> 3);
   if ((int)(blockIdx.x >> 3) >= g.per_xcd || gt >= g.start[g.n]) return;
@@ -548,16 +555,16 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 3 ? 3 : 2) void conv_s
 #pragma unroll
   for (int t = 1; t < kMaxConvGroup; ++t)
     if (t < g.n && gt >= g.start[t]) j = t;
-  conv_staged_tile<BMt, BNt, WGM, WGN, TAPS>(g.a[j], gt - g.start[j]);
+  conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16>(g.a[j], gt - g.start[j]);
 }
 
-template <int BMt, int BNt, int WGM, int WGN, int TAPS>
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
 void launch_staged(ConvArgs& a, hipStream_t stream) {
   a.gx = (a.P_out + BMt - 1) / BMt;
   a.gy = (a.Cout + BNt - 1) / BNt;
   const long long total = (long long)a.gx * a.gy;
   a.per_xcd = (int)((total + 7) / 8);
-  hipLaunchKernelGGL((conv_staged_kernel<BMt, BNt, WGM, WGN, TAPS>), dim3((unsigned)(a.per_xcd * 8)), dim3(64 * WGM * WGN), 0,
+  hipLaunchKernelGGL((conv_staged_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16>), dim3((unsigned)(a.per_xcd * 8)), dim3(64 * WGM * WGN), 0,
                      stream, a);
 }
 
@@ -566,7 +573,8 @@ void launch_staged(ConvArgs& a, hipStream_t stream) {
 extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, int tokens_per_cam, int level_start,
                                       const void* x, const void* weight, const void* bias, int num_images, int in_h, int in_w,
                                       int in_channels, int out_channels, int stride, int relu, int variant, void* stream) {
-  if ((!y && !tokens) || (y && tokens) || (tokens_f16 && !tokens) || (reinterpret_cast<size_t>(tokens_f16) & 15) || !x || !weight || !bias || num_images <= 0 || in_h <= 0 || in_w <= 0 ||
+  const bool to_tokens = tokens || tokens_f16;   // tokens == NULL with tokens_f16 set: the f16 rows alone
+  if ((!y && !to_tokens) || (y && to_tokens) || (reinterpret_cast<size_t>(tokens_f16) & 15) || !x || !weight || !bias || num_images <= 0 || in_h <= 0 || in_w <= 0 ||
       in_channels <= 0 || out_channels <= 0 || (stride != 1 && stride != 2) || in_channels % BK != 0 || out_channels % 8 != 0 ||
       variant < 0 || variant > 8)
     return SIMPB_EINVAL;
@@ -577,7 +585,7 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
   const long long p_out = (long long)num_images * ho * wo;
   const long long in_elems = (long long)num_images * in_h * in_w * in_channels;
   if (p_out > (1ll << 30) || in_elems > (1ll << 31) - 1) return SIMPB_EINVAL;   // tap offsets are 32-bit
-  if (tokens && (tokens_per_cam < ho * wo || level_start < 0 || level_start + ho * wo > tokens_per_cam)) return SIMPB_EINVAL;
+  if (to_tokens && (tokens_per_cam < ho * wo || level_start < 0 || level_start + ho * wo > tokens_per_cam)) return SIMPB_EINVAL;
   (void)hipGetLastError();
   ConvArgs a{static_cast<_Float16*>(y), tokens, static_cast<_Float16*>(tokens_f16), static_cast<const _Float16*>(x), static_cast<const _Float16*>(weight),
              static_cast<const _Float16*>(bias), nullptr, 0, (int)p_out, in_channels, out_channels, relu, stride, ho, wo, in_h, in_w,
@@ -596,28 +604,33 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
     else variant = 3;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (variant) {
-    case 1: launch<1, false>(a, s); break;   // 128 pixels x 64 channels, weights through LDS
-    case 2: launch<2, false>(a, s); break;   // 256 x 64
-    case 3: launch<1, true>(a, s); break;    // 32 x 64, K split over the waves
-    case 4: launch<2, true>(a, s); break;    // 64 x 64, K split over the waves
-    case 5: launch_staged<128, 64, 4, 1, 9>(a, s); break;    // 128 x 64, operands staged through LDS
-    case 6: launch_staged<128, 128, 2, 2, 9>(a, s); break;  // 128 x 128
-    case 7: launch_staged<96, 64, 3, 1, 9>(a, s); break;     // 96 x 64, three waves: 704 workgroups for 67 584 pixels
-    default: launch_staged<96, 128, 1, 4, 9>(a, s); break;   // 96 x 128, waves side by side along the channels
-  }
+  auto dispatch = [&](auto tok16_c) {
+    constexpr bool T = decltype(tok16_c)::value;
+    switch (variant) {
+      case 1: launch<1, false, T>(a, s); break;   // 128 pixels x 64 channels, weights through LDS
+      case 2: launch<2, false, T>(a, s); break;   // 256 x 64
+      case 3: launch<1, true, T>(a, s); break;    // 32 x 64, K split over the waves
+      case 4: launch<2, true, T>(a, s); break;    // 64 x 64, K split over the waves
+      case 5: launch_staged<128, 64, 4, 1, 9, T>(a, s); break;    // 128 x 64, operands staged through LDS
+      case 6: launch_staged<128, 128, 2, 2, 9, T>(a, s); break;  // 128 x 128
+      case 7: launch_staged<96, 64, 3, 1, 9, T>(a, s); break;     // 96 x 64, three waves: 704 workgroups for 67 584 pixels
+      default: launch_staged<96, 128, 1, 4, 9, T>(a, s); break;   // 96 x 128, waves side by side along the channels
+    }
+  };
+  if (!tokens && tokens_f16) dispatch(std::true_type{});   // the f16 token rows alone: kernels without the fp32 stores
+  else dispatch(std::false_type{});
   return simpb_check_launch();
 }
 
 // The FPN's output convolutions (3x3, stride 1, Cin -> Cout, bias, no ReLU; mmdet FPN `fpn_convs[i].conv` after
 // tools/fuse_conv_bn.py:10-48) of up to four levels in ONE launch, each writing its level's token rows (f32 and, optionally,
-// f16) as simpb_conv3x3_nhwc_f16 does with `tokens`: x[j] f16 NHWC [num_images, in_h[j], in_w[j], Cin], weight[j] f16
+// f16; or, with tokens == NULL, f16 alone) as simpb_conv3x3_nhwc_f16 does with `tokens`: x[j] f16 NHWC [num_images, in_h[j], in_w[j], Cin], weight[j] f16
 // [Cout, 3, 3, Cin], bias[j] f16 [Cout], level_start[j] the level's first row inside a camera's tokens_per_cam rows.
 extern "C" int simpb_conv3x3_group_tokens_f16(int num_levels, float* tokens, void* tokens_f16, int tokens_per_cam,
                                               const int* level_start, const void* const* x, const void* const* weight,
                                               const void* const* bias, int num_images, const int* in_h, const int* in_w,
                                               int in_channels, int out_channels, int relu, void* stream) {
-  if (num_levels < 1 || num_levels > kMaxConvGroup || !tokens || !level_start || !x || !weight || !bias || !in_h || !in_w ||
+  if (num_levels < 1 || num_levels > kMaxConvGroup || (!tokens && !tokens_f16) || !level_start || !x || !weight || !bias || !in_h || !in_w ||
       num_images <= 0 || in_channels <= 0 || out_channels <= 0 || in_channels % BK != 0 || out_channels % 8 != 0 ||
       ((reinterpret_cast<size_t>(tokens) | reinterpret_cast<size_t>(tokens_f16)) & 15))
     return SIMPB_EINVAL;
@@ -645,8 +658,12 @@ extern "C" int simpb_conv3x3_group_tokens_f16(int num_levels, float* tokens, voi
   g.n = num_levels;
   g.per_xcd = (int)((total + 7) / 8);
   (void)hipGetLastError();
-  hipLaunchKernelGGL((conv_staged_group_kernel<96, 128, 1, 4, 9>), dim3((unsigned)(g.per_xcd * 8)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), g);
+  if (!tokens)   // the f16 token rows alone
+    hipLaunchKernelGGL((conv_staged_group_kernel<96, 128, 1, 4, 9, true>), dim3((unsigned)(g.per_xcd * 8)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), g);
+  else
+    hipLaunchKernelGGL((conv_staged_group_kernel<96, 128, 1, 4, 9, false>), dim3((unsigned)(g.per_xcd * 8)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), g);
   return simpb_check_launch();
 }
 
@@ -659,7 +676,7 @@ extern "C" int simpb_conv_pointwise_staged(void* y, const void* x, const void* w
              static_cast<const _Float16*>(bias), static_cast<const _Float16*>(residual), residual_upsample2x ? 1 : 0,
              p_out, in_channels, out_channels, relu, stride, ho, wo, in_h, in_w, 0, 0, 0, 0, 0};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (tiling == 0) launch_staged<128, 64, 4, 1, 1>(a, s);
-  else launch_staged<128, 128, 2, 2, 1>(a, s);
+  if (tiling == 0) launch_staged<128, 64, 4, 1, 1, false>(a, s);
+  else launch_staged<128, 128, 2, 2, 1, false>(a, s);
   return simpb_check_launch();
 }

@@ -62,10 +62,11 @@ __device__ __forceinline__ bool skip_dead_rows(const simpb_mlp_args& args, const
   int width = ch.in_mode == SIMPB_MLP_IN_SINE2D ? 256 : ch.in_dim;
   for (int o = 0; o < ch.n_ops; ++o)
     if (ch.ops[o].type == SIMPB_MLP_LINEAR) width = ch.ops[o].out_dim;
-  for (int idx = tid; idx < rows * width; idx += nthreads) {
-    const int r = idx / width, t = idx - r * width;
-    if (row0 + r < args.num_rows) ch.out[(size_t)(row0 + r) * ch.ldo + t] = 0.f;
-  }
+  if (ch.out)   // (NULL: the leading LayerNorm stage alone, below)
+    for (int idx = tid; idx < rows * width; idx += nthreads) {
+      const int r = idx / width, t = idx - r * width;
+      if (row0 + r < args.num_rows) ch.out[(size_t)(row0 + r) * ch.ldo + t] = 0.f;
+    }
   if (ch.in_mode == SIMPB_MLP_IN_ROWS_LN && ch.ln_out)
     for (int idx = tid; idx < rows * ch.in_dim; idx += nthreads) {
       const int r = idx / ch.in_dim, t = idx - r * ch.in_dim;
@@ -582,6 +583,7 @@ __global__ __launch_bounds__(256) void mlp_chain_r4_kernel(simpb_mlp_args args) 
         act[0][r][e] = y + x2v[j];
       }
     }
+    if (!ch.out) return;   // the `norm` operator alone (no chain behind it, workgroup-uniform): ln_out is the job's product
   } else {
     for (int idx = tid; idx < kR4 * ch.in_dim; idx += kThreads) {
       const int r = idx / ch.in_dim, k = idx - r * ch.in_dim;
@@ -794,6 +796,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void mlp_chain_r32_kernel(simpb_mlp_
         }
       }
     }
+    if (!ch.out) return;   // the `norm` operator alone (no chain behind it, workgroup-uniform)
   } else {
     for (int idx = tid; idx < kR32 * ch.in_dim; idx += kThreads) {
       const int r = idx / ch.in_dim, k = idx - r * ch.in_dim;
@@ -947,7 +950,9 @@ extern "C" int simpb_mlp_chain_forward(const simpb_mlp_args* args, void* stream)
     return SIMPB_EINVAL;
   for (int c = 0; c < args->num_chains; ++c) {
     const simpb_mlp_chain& ch = args->chain[c];
-    if (!ch.x || !ch.out || ch.n_ops < 0 || ch.n_ops > SIMPB_MLP_MAX_OPS) return SIMPB_EINVAL;
+    if (!ch.x || ch.n_ops < 0 || ch.n_ops > SIMPB_MLP_MAX_OPS) return SIMPB_EINVAL;
+    // no `out`: the leading LayerNorm stage alone -- IN_ROWS_LN with ln_out and no op behind it
+    if (!ch.out && (ch.in_mode != SIMPB_MLP_IN_ROWS_LN || !ch.ln_out || ch.n_ops != 0)) return SIMPB_EINVAL;
     int width = ch.in_mode == SIMPB_MLP_IN_SINE2D ? 256 : ch.in_dim;
     if (width <= 0 || width > kMaxDim) return SIMPB_EINVAL;
     if (ch.post < 0 || ch.post > SIMPB_MLP_POST_SIGMOID) return SIMPB_EINVAL;

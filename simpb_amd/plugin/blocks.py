@@ -123,13 +123,16 @@ class DeformableFeatureAggregation(BaseModule):
         if routes.R.fused_dfa and routes.R.dense and shipped_layout:
             # key points + projection + weight softmax inside the aggregation launch (csrc/deform_agg_fused.hip), reading the
             # f16 copy of the tokens where the FPN left one (the tokens are f16 numbers: same bits, half the gather bytes)
-            feat = feature_maps[0]
+            feat = feature_maps[0]   # (f16 itself in a frame captured with routes.lean_tokens)
             half = getattr(feat, "simpb_f16", None) if routes.R.dfa_f16_tokens else None
             if half is not None and half.shape == feat.shape:
                 feat = half
             features = dfa_fused(feat, feature_maps[1], feature_maps[2], anchor_c, learn, kps.fix_scale, proj, wh, feat_logits,
                                  cam_logits, self.num_groups, cam_valid=cam_valid)
             return self._project_out(features, instance_feature, keep_parts)
+        if getattr(feature_maps[0], "dtype", torch.float32) != torch.float32:
+            raise RuntimeError("f16-only camera tokens need the one-launch aggregation (routes.fused_dfa, the shipped layout): "
+                               "the drop-in operator reads fp32 rows")
         num_fix = kps.fix_scale.shape[0]
         loc = torch.empty(bs, num_anchor, self.num_pts, self.num_cams, 2, device=dev)
         _lib.check(lib.simpb_dfa_points_cams(_ptr(loc), None, _ptr(anchor_c), _ptr(learn), _ptr(kps.fix_scale), _ptr(proj),

@@ -105,9 +105,27 @@ class SparseBox2DRefinementModule(BaseModule):
         if self.with_cls_branch:
             nn.init.constant_(self.cls_layers[-1].bias, bias_init_with_prob(0.01))
 
+    def norm_alone(self, instance_feature, norm, m_live=None):
+        """The `norm` operator in front of this head WITHOUT the head (a captured frame whose refinement outputs nothing
+        reads, routes.lean_refine2d): the chain launch's leading LayerNorm stage alone, bit-equal to what forward(norm=...)
+        leaves in norm_out; on the routes without that stage, the LayerNorm launch forward() would have used."""
+        if not (instance_feature.is_cuda and routes.R.chain_rows4):
+            from . import dense
+            self.norm_out = dense.layernorm(instance_feature, norm, m_live=m_live)
+            return self.norm_out
+        from . import fused
+        xf, ldx = fused._rows(instance_feature, instance_feature.shape[-1])
+        normed = torch.empty(xf.shape[0], xf.shape[1], device=xf.device)
+        self.norm_out = normed.reshape(instance_feature.shape)
+        if xf.shape[0]:
+            fused.run_chains([dict(plan=None, x=(xf, ldx, 0), ln=(norm, (normed, xf.shape[1])))], xf.shape[0], xf.device,
+                             m_live=m_live)
+        return self.norm_out
+
     def forward(self, instance_feature, anchor2d, anchor2d_embed, metas=None, return_cls=True, query_groups=None, m_live=None,
-                norm=None):
-        """norm: as SparseBox3DRefinementModule.forward (the `norm` operator in front of this head, not applied yet)."""
+                norm=None, with_alpha=True):
+        """norm: as SparseBox3DRefinementModule.forward (the `norm` operator in front of this head, not applied yet).
+        with_alpha=False: the alpha branch is not run (its entry is None): nothing at inference reads it."""
         fused_ok = instance_feature.is_cuda
         self.norm_out = None
         if norm is not None and not (fused_ok and routes.R.chain_rows4):
@@ -134,7 +152,7 @@ class SparseBox2DRefinementModule(BaseModule):
             if return_cls:
                 cls_t = torch.empty(n, self.num_cls, device=xf.device)
                 jobs.append(dict(plan=fused.plan_of(self.cls_layers), x=(xf, ldx, 0), out=(cls_t, self.num_cls, 0), ln=ln_r))
-            if self.with_alpha_branch:
+            if self.with_alpha_branch and with_alpha:
                 adim = fused.plan_of(self.alpha_layers).out_dim
                 alpha_t = torch.empty(n, adim, device=xf.device)
                 jobs.append(dict(plan=fused.plan_of(self.alpha_layers), x=(xf, ldx, 0), out=(alpha_t, adim, 0), ln=ln_r))
@@ -152,5 +170,5 @@ class SparseBox2DRefinementModule(BaseModule):
             return output, cls, None, alpha
         output = torch.cat([output[..., :k] + inverse_sigmoid(anchor2d), output[..., k:]], dim=-1)  # :122-125
         cls = self.cls_layers(instance_feature) if return_cls else None
-        alpha = self.alpha_layers(instance_feature) if self.with_alpha_branch else None
+        alpha = self.alpha_layers(instance_feature) if self.with_alpha_branch and with_alpha else None
         return output.sigmoid(), cls, None, alpha

@@ -108,8 +108,9 @@ class SparseBox3DRefinementModule(BaseModule):
         if self.with_cls_branch:
             nn.init.constant_(self.cls_layers[-1].bias, bias_init_with_prob(0.01))
 
-    def forward(self, instance_feature, anchor, anchor_embed, time_interval=1.0, return_cls=True, norm=None):
-        """norm (an nn.LayerNorm, or None): the decoder's `norm` operator in front of this head has NOT been applied to
+    def forward(self, instance_feature, anchor, anchor_embed, time_interval=1.0, return_cls=True, norm=None, with_quality=True):
+        """with_quality=False: the quality branch is not run (None comes back), for a layer whose quality nothing reads.
+        norm (an nn.LayerNorm, or None): the decoder's `norm` operator in front of this head has NOT been applied to
         instance_feature yet; the head's chain launch applies it (and leaves its output in self.norm_out), or, on the
         routes without that stage, it is applied here first."""
         fused_ok = instance_feature.is_cuda
@@ -147,7 +148,7 @@ class SparseBox3DRefinementModule(BaseModule):
                 assert self.with_cls_branch, "Without classification layers !!!"
                 cls = torch.empty(n, self.num_cls, device=xf.device)  # cls_layers(feature), :145-147
                 jobs.append(dict(plan=fused.plan_of(self.cls_layers), x=(xf, ldx, 0), out=(cls, self.num_cls, 0), ln=ln_r))
-                if self.with_quality_estimation:  # quality_layers(feature + embed), :149-152
+                if self.with_quality_estimation and with_quality:  # quality_layers(feature + embed), :149-152
                     quality = torch.empty(n, 2, device=xf.device)
                     jobs.append(dict(plan=fused.plan_of(self.quality_layers), x=(xf, ldx, 0), x2=(ef, lde, 0),
                                      out=(quality, 2, 0), ln=ln_r))
@@ -180,15 +181,15 @@ class SparseBox3DRefinementModule(BaseModule):
         if return_cls:
             assert self.with_cls_branch, "Without classification layers !!!"
             if fused_ok:
-                cls, quality = self._heads_fused(instance_feature, anchor_embed)
+                cls, quality = self._heads_fused(instance_feature, anchor_embed, with_quality)
                 return output, cls, quality
             cls = self.cls_layers(instance_feature)
         else:
             cls = None
-        quality = self.quality_layers(feature) if return_cls and self.with_quality_estimation else None
+        quality = self.quality_layers(feature) if return_cls and self.with_quality_estimation and with_quality else None
         return output, cls, quality
 
-    def _heads_fused(self, instance_feature, anchor_embed):
+    def _heads_fused(self, instance_feature, anchor_embed, with_quality=True):
         """cls_layers(feature) and quality_layers(feature + embed) (:145-152) in one launch."""
         from . import fused
         xf, ldx = fused._rows(instance_feature, instance_feature.shape[-1])
@@ -198,7 +199,7 @@ class SparseBox3DRefinementModule(BaseModule):
         cls = torch.empty(n, self.num_cls, device=xf.device)
         jobs = [dict(plan=fused.plan_of(self.cls_layers), x=(xf, ldx, 0), out=(cls, self.num_cls, 0))]
         quality = None
-        if self.with_quality_estimation:
+        if self.with_quality_estimation and with_quality:
             quality = torch.empty(n, 2, device=xf.device)
             jobs.append(dict(plan=fused.plan_of(self.quality_layers), x=(xf, ldx, 0), x2=(ef, lde, 0), out=(quality, 2, 0)))
         fused.run_chains(jobs, n, xf.device)

@@ -256,8 +256,11 @@ class FPN(BaseModule):
                 shapes = tuple(tuple(t.shape[-2:]) for t in laterals)
                 per_cam = sum(h * w for h, w in shapes)
                 cout = self.fpn_convs[0].conv.out_channels
-                col = torch.empty(bs, num_cams * per_cam, cout, device=x0.device, dtype=torch.float32)
-                # the same rows without the widening: value_proj (group_attn.py:176) reads these (two-pass split product)
+                # f16_tokens_only: set by a frame runner for the length of a graph capture, and for nothing else
+                # (runner.FrameRunner._capturing, routes.lean_tokens): a replayed frame has no fp32 rows at all
+                lean = bool(getattr(self, "f16_tokens_only", False))
+                col = None if lean else torch.empty(bs, num_cams * per_cam, cout, device=x0.device, dtype=torch.float32)
+                # the same rows without the widening: the samplers and value_proj (group_attn.py:176) read these
                 col16 = torch.empty(bs, num_cams * per_cam, cout, device=x0.device, dtype=torch.float16)
                 starts = [sum(h * w for h, w in shapes[:i]) for i in range(n)]
                 if (routes.R.fpn_grouped_out and 1 < n <= 4 and len({m.conv.in_channels for m in self.fpn_convs}) == 1
@@ -270,9 +273,10 @@ class FPN(BaseModule):
                     for i in range(n):
                         conv = self.fpn_convs[i].conv
                         conv3x3_nhwc(laterals[i], conv.weight, conv.bias, relu=False, tokens=(col, per_cam, starts[i], col16))
-                col.simpb_f16 = col16
+                if col is not None:
+                    col.simpb_f16 = col16
                 self.deferred_output_bias = False
-                self.wrote_tokens = [col, *token_tables(shapes, num_cams, col.device)]
+                self.wrote_tokens = [col if col is not None else col16, *token_tables(shapes, num_cams, col16.device)]
                 return ()
             _vendor_fallback("FPN output convolutions", routes.R.conv3x3_kernel and tokens_for is not None,
                              "3x3, " + ", ".join(f"{m.conv.in_channels}->{m.conv.out_channels}" for m in self.fpn_convs))

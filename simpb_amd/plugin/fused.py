@@ -175,6 +175,8 @@ def run_chains(jobs, num_rows, device, m_live=None):
     """jobs: list of dicts(plan, x=(tensor2d, ld, col), x2=(tensor2d, ld, col) or None, out=(tensor2d, ld, col),
     sine=bool, post=dict(kind, res=(tensor2d, ld), res_cols, div=tensor or None, div_rows, div_col0) or None,
     ln=(nn.LayerNorm over x, (out tensor2d, ld) or None) or None: input = LayerNorm(x) + x2, LayerNorm(x) written to out).
+    A job with plan=None and out=None is the leading LayerNorm stage ALONE (ln with its out given): the launch's prologue
+    and nothing behind it, so LayerNorm(x) comes out bit-equal to what the same job with a chain behind it writes.
     All tensors f32 on `device`, 2-D views with unit inner stride. m_live: device i32 [1] or None; rows past it are capacity
     slots of the static 2D query set and come out as zeros (their workgroups do no work)."""
     if not jobs or len(jobs) > MAX_CHAINS:
@@ -189,7 +191,9 @@ def run_chains(jobs, num_rows, device, m_live=None):
     keep = []
     for c, job in enumerate(jobs):
         ch = args.chain[c]
-        plan = job["plan"]
+        plan = job.get("plan")
+        if plan is None and (job.get("ln") is None or job["ln"][1] is None or job.get("out") is not None or job.get("post")):
+            raise ValueError("a job without a chain is the leading LayerNorm alone: ln=(norm, (out, ld)), no out, no post")
         xt, ldx, xcol = job["x"]
         ch.x = xt.data_ptr() + 4 * xcol
         ch.ldx = ldx
@@ -198,13 +202,17 @@ def run_chains(jobs, num_rows, device, m_live=None):
             ch.x2, ch.ldx2 = x2t.data_ptr() + 4 * x2col, ldx2
         else:
             ch.x2, ch.ldx2 = None, 0
-        ot, ldo, ocol = job["out"]
-        ch.out, ch.ldo = ot.data_ptr() + 4 * ocol, ldo
+        if plan is not None:
+            ot, ldo, ocol = job["out"]
+            ch.out, ch.ldo = ot.data_ptr() + 4 * ocol, ldo
+            keep.append(ot)
+        else:
+            ch.out, ch.ldo = None, 0
         ch.in_mode = IN_SINE2D if job.get("sine") else IN_ROWS
-        ch.in_dim = plan.in_dim
+        ch.in_dim = plan.in_dim if plan is not None else job["ln"][0].normalized_shape[0]
         if job.get("ln") is not None:
             ln, ln_out = job["ln"]
-            if not routes.R.chain_rows4 or ln.normalized_shape != (plan.in_dim,) or abs(ln.eps - 1e-5) > 1e-12 or job.get("sine"):
+            if not routes.R.chain_rows4 or ln.normalized_shape != (ch.in_dim,) or abs(ln.eps - 1e-5) > 1e-12 or job.get("sine"):
                 raise ValueError("a leading LayerNorm needs the 4-row chain kernel and a norm of the chain's input width")
             ch.in_mode = IN_ROWS_LN
             ch.ln_w, ch.ln_b = ln.weight.data_ptr(), ln.bias.data_ptr()
@@ -221,8 +229,11 @@ def run_chains(jobs, num_rows, device, m_live=None):
             if post.get("div") is not None:
                 ch.div, ch.div_rows, ch.div_col0 = post["div"].data_ptr(), post["div_rows"], post["div_col0"]
                 keep.append(post["div"])
-        plan.fill(ch, keep, wide)
-        keep += [xt, ot]
+        if plan is not None:
+            plan.fill(ch, keep, wide)
+        else:
+            ch.n_ops, ch.out_scale = 0, None
+        keep.append(xt)
     status = _lib.lib().simpb_mlp_chain_forward(ctypes.byref(args), _stream())
     _lib.check(status, "simpb_mlp_chain_forward")
 

@@ -108,6 +108,8 @@ class QueryGroupMultiScaleDeformableAttention(BaseModule):
         half = getattr(value, "simpb_f16", None)   # the FPN left the same tokens in f16 (detector.FPN): two passes suffice
         if routes.R.split_value_proj and half is not None and half.shape == value.shape:
             value = half
+        elif value.dtype == torch.float16 and not routes.R.split_value_proj:
+            value = value.float()   # f16 rows alone (a frame captured with routes.lean_tokens) on the exact-fp32 kernel: widened here
         value = lin(value, self.value_proj.weight, self.value_proj.bias)
         if key_padding_mask is not None:
             value = value.masked_fill(key_padding_mask[..., None], 0.0)

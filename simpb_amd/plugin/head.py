@@ -143,7 +143,9 @@ class SimPBHead(BaseModule):
                             spatial_shape[0].long().contiguous(), scale_start[0].long().contiguous())
         _, ss32, st32, ss_cam, st_cam = self._tables
         feat_flatten = col.reshape(bs, nc, -1, dim).flatten(0, 1)
-        half = getattr(col, "simpb_f16", None)   # the same tokens as the fp16 backbone left them (detector.FPN)
+        # the same tokens as the fp16 backbone left them (detector.FPN); f16 rows alone (a frame captured with
+        # routes.lean_tokens) are their own f16 copy
+        half = col if col.dtype == torch.float16 else getattr(col, "simpb_f16", None)
         encoder2d_dict = {
             "value_f16": half.reshape(bs, nc, -1, dim).flatten(0, 1) if half is not None and half.shape == col.shape else None,
             "value": feat_flatten,
@@ -209,14 +211,21 @@ class SimPBHead(BaseModule):
         if proj is None or not proj.is_cuda or not idx or len(idx) > 8 or not routes.R.dense:
             return {}
         from . import fused
-        cam_in = proj[:, :, :3].reshape(batch_size * self.num_cams, -1).float().contiguous()
+        if (routes.R.lean_glue and proj.dtype == torch.float32 and proj.is_contiguous() and proj.dim() == 4
+                and tuple(proj.shape[-2:]) == (4, 4)):
+            # the first three rows of a 4 x 4 matrix are the first 12 floats of its 16: the chain reads them where they lie
+            # (row stride 16, width 12) -- no strided-to-contiguous copy in front of the launch
+            cam_in, ld_in, in_dim = proj.view(batch_size * self.num_cams, 16), 16, 12
+        else:
+            cam_in = proj[:, :, :3].reshape(batch_size * self.num_cams, -1).float().contiguous()
+            ld_in = in_dim = cam_in.shape[1]
         jobs, outs = [], {}
         for i in idx:
             plan = fused.plan_of(self.layers[i].camera_encoder)
-            if plan.in_dim != cam_in.shape[1]:
+            if plan.in_dim != in_dim:
                 return {}
             out = torch.empty(cam_in.shape[0], plan.out_dim, device=cam_in.device)
-            jobs.append(dict(plan=plan, x=(cam_in, cam_in.shape[1], 0), out=(out, plan.out_dim, 0)))
+            jobs.append(dict(plan=plan, x=(cam_in, ld_in, 0), out=(out, plan.out_dim, 0)))
             outs[i] = out.reshape(batch_size, self.num_cams, plan.out_dim)
         fused.run_chains(jobs, cam_in.shape[0], cam_in.device)
         return outs
@@ -227,25 +236,30 @@ class SimPBHead(BaseModule):
         return i + 1 < len(self.operation_order) and self.operation_order[i + 1] == "ffn"
 
     # ------------------------------------------------------------------ forward
-    def forward(self, feature_maps, metas: dict):
-        """simpb_head.py:323-747 (inference)."""
-        gen = self._forward(feature_maps, metas, split=False)
+    def forward(self, feature_maps, metas: dict, lean: bool = False):
+        """simpb_head.py:323-747 (inference). lean (this call only; a runner passes it for the frames it captures,
+        routes.lean_refine2d): compute what the frame's records read and nothing else -- the refinement heads of every 2D
+        layer but the last are not run (their entries of prediction2d / classification2d / prediction_alpha2d are None; the
+        `norm` operator in front of them still is), the last 2D layer has no alpha entry, the single-frame refine3d no
+        quality entry. Every other output, and the bank, are what they are without it, bit for bit."""
+        gen = self._forward(feature_maps, metas, split=False, lean=lean)
         try:
             next(gen)
         except StopIteration as done:
             return done.value
         raise RuntimeError("unsplit forward does not pause")
 
-    def forward_split(self, feature_maps, metas: dict):
+    def forward_split(self, feature_maps, metas: dict, lean: bool = False):
         """The same forward as a two-step generator, for callers that overlap frames (runner.SplitPipelinedRunner):
         `next(gen)` runs the single-frame decoder layer(s) -- everything up to the first InstanceBank.update
         (simpb_head.py:690-696), which reads nothing the previous frame's decoder wrote (learned anchors only; the time
         step comes in as metas["time_interval"]) -- and pauses; `gen.send(None)` runs the temporal rest (bank.get,
         update, the remaining layers, cache) and ends with StopIteration carrying the output dict. Same launches, same
-        numbers as forward() except that the two anchor sets are embedded by two encoder launches instead of one."""
-        return self._forward(feature_maps, metas, split=True)
+        numbers as forward() except that the two anchor sets are embedded by two encoder launches instead of one. lean: as
+        forward()."""
+        return self._forward(feature_maps, metas, split=True, lean=lean)
 
-    def _forward(self, feature_maps, metas: dict, split: bool):
+    def _forward(self, feature_maps, metas: dict, split: bool, lean: bool = False):
         if self.training:
             raise NotImplementedError("SimPBHead here is the inference path; training (denoising, losses) is out of scope")
         if isinstance(feature_maps, torch.Tensor):
@@ -307,6 +321,7 @@ class SimPBHead(BaseModule):
         alloc = None
         self._m_live = None
         last = len(self.operation_order) - 1
+        n_refine2d = sum(op == "refine2d" and layer is not None for op, layer in zip(self.operation_order, self.layers))
         # static mode: the overflow flags of the frame's allocation layers in one tensor; the frame-end commit of the
         # bank holds back when any is set, so that the caller can re-run the frame (runner.py) on untouched state
         pending_norm = None
@@ -399,12 +414,22 @@ class SimPBHead(BaseModule):
                                          keep_parts=routes.R.dense and self._next_is_ffn(i), **enc)
             elif op == "refine2d":
                 kw = dict(m_live=self._m_live) if self._m_live is not None else {}
-                if pending_norm is not None:
-                    kw["norm"] = pending_norm
-                anchor2d, cls2d, depth2d, alpha2d = layer(instance_feature, anchor2d, anchor_embed2d, metas=metas,
-                                                          query_groups=ref_query_groups, **kw)
-                if pending_norm is not None:
-                    instance_feature, pending_norm = dense.report(pending_norm, layer.norm_out), None
+                if lean and len(prediction2d) < n_refine2d - 1:
+                    # nothing at inference reads this layer's boxes, classes or alphas: the aggregation behind it takes the
+                    # features alone and the next 2D layer allocates its anchors anew from the 3D ones. What is live is the
+                    # `norm` operator's output
+                    if pending_norm is not None:
+                        instance_feature, pending_norm = dense.report(pending_norm, layer.norm_alone(instance_feature, pending_norm, **kw)), None
+                    anchor2d = cls2d = depth2d = alpha2d = None
+                else:
+                    if pending_norm is not None:
+                        kw["norm"] = pending_norm
+                    if lean:
+                        kw["with_alpha"] = False
+                    anchor2d, cls2d, depth2d, alpha2d = layer(instance_feature, anchor2d, anchor_embed2d, metas=metas,
+                                                              query_groups=ref_query_groups, **kw)
+                    if pending_norm is not None:
+                        instance_feature, pending_norm = dense.report(pending_norm, layer.norm_out), None
                 prediction2d.append(anchor2d)
                 classification2d.append(cls2d)
                 prediction_alpha2d.append(alpha2d)
@@ -425,6 +450,8 @@ class SimPBHead(BaseModule):
                                          cam_embed=cam_embeds.get(i))
             elif op == "refine3d":
                 kw = dict(norm=pending_norm) if pending_norm is not None else {}
+                if lean and i != last:   # (only the last layer's quality reaches the records: SparseBox3DDecoder)
+                    kw["with_quality"] = False
                 anchor, cls, qt = layer(
                     instance_feature, anchor, anchor_embed, time_interval=time_interval,
                     return_cls=(len(prediction) == self.num_single_frame_decoder - 1 or i == last), **kw)

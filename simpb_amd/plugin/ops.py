@@ -495,7 +495,7 @@ def conv3x3_nhwc(x, weight, bias, relu=True, stride=1, tokens=None, variant=0):
     x [N, Cin, H, W]; weight f16 [Cout, Cin, 3, 3] (channels_last, i.e. [Cout][3][3][Cin] in memory); bias f16 [Cout].
     tokens = (col_feats f32 [bs, cams * tokens_per_cam, Cout], tokens_per_cam, level_start[, col_f16]): the result is written
     as fp32 token rows of this level (feature_maps_format layout) instead of a map (and, with col_f16, as the same rows in
-    f16), and None is returned."""
+    f16), and None is returned. col_feats None with col_f16 given: the f16 rows alone."""
     _require_gpu(x, weight, bias)
     n, cin, h, w = x.shape
     cout = weight.shape[0]
@@ -514,10 +514,14 @@ def conv3x3_nhwc(x, weight, bias, relu=True, stride=1, tokens=None, variant=0):
         col, per_cam, start = tokens[:3]
         col16 = tokens[3] if len(tokens) > 3 else None
         y = None
-        if col16 is not None and (col16.dtype != torch.float16 or not col16.is_contiguous() or col16.shape != col.shape):
+        if col is None and col16 is None:
+            raise ValueError("tokens: an f32 or an f16 token buffer")
+        if col16 is not None and (col16.dtype != torch.float16 or not col16.is_contiguous()
+                                  or (col is not None and col16.shape != col.shape)):
             raise ValueError("tokens: the f16 buffer must match col_feats")
-        if (col.dtype != torch.float32 or not col.is_contiguous() or col.shape[-1] != cout or col.numel() != n * per_cam * cout
-                or start < 0 or start + ho * wo > per_cam):
+        rows = col if col is not None else col16
+        if ((col is not None and col.dtype != torch.float32) or not rows.is_contiguous() or rows.shape[-1] != cout
+                or rows.numel() != n * per_cam * cout or start < 0 or start + ho * wo > per_cam):
             raise ValueError("tokens: (contiguous f32 [bs, cams * tokens_per_cam, Cout] with bs * cams == N, tokens_per_cam, level_start)")
     status = _lib.lib().simpb_conv3x3_nhwc_f16(_ptr(y) if y is not None else None, _ptr(col) if col is not None else None,
                                                _ptr(col16) if col16 is not None else None, per_cam, start, _ptr(x), _ptr(weight), _ptr(bias), n, h, w, cin, cout, stride,
@@ -529,9 +533,13 @@ def conv3x3_nhwc(x, weight, bias, relu=True, stride=1, tokens=None, variant=0):
 def conv3x3_group_tokens(xs, weights, biases, col, per_cam, starts, col16=None, relu=False):
     """conv3x3_nhwc(..., tokens=...) of up to four levels in ONE launch (csrc/conv3x3.hip: conv_staged_group_kernel): the
     FPN's output convolutions. xs: channels_last f16 [N, Cin, H_j, W_j]; weights f16 [Cout, Cin, 3, 3]; biases f16 [Cout];
-    col f32 [bs, cams * per_cam, Cout] (and col16, the same rows in f16); starts[j] = level j's first row inside a camera."""
+    col f32 [bs, cams * per_cam, Cout] (and col16, the same rows in f16; col None: the f16 rows alone); starts[j] = level j's
+    first row inside a camera."""
     import ctypes
-    _require_gpu(*xs, *weights, *biases, col)
+    if col is None and col16 is None:
+        raise ValueError("conv3x3_group_tokens: an f32 or an f16 token buffer")
+    rows = col if col is not None else col16
+    _require_gpu(*xs, *weights, *biases, rows)
     n, cin = xs[0].shape[:2]
     cout = weights[0].shape[0]
     k = len(xs)
@@ -544,12 +552,13 @@ def conv3x3_group_tokens(xs, weights, biases, col, per_cam, starts, col16=None, 
                 or not b.is_contiguous() or cin % 64 or cout % 8):
             raise ValueError("conv3x3_group_tokens takes channels_last f16 inputs of one channel count, f16 [Cout, Cin, 3, 3] weights")
         ws.append(w if w.is_contiguous(memory_format=torch.channels_last) else w.contiguous(memory_format=torch.channels_last))
-    if (col.dtype != torch.float32 or not col.is_contiguous() or col.shape[-1] != cout or col.numel() != n * per_cam * cout
-            or (col16 is not None and (col16.dtype != torch.float16 or not col16.is_contiguous() or col16.shape != col.shape))):
+    if ((col is not None and col.dtype != torch.float32) or not rows.is_contiguous() or rows.shape[-1] != cout
+            or rows.numel() != n * per_cam * cout
+            or (col16 is not None and (col16.dtype != torch.float16 or not col16.is_contiguous() or col16.shape != rows.shape))):
         raise ValueError("conv3x3_group_tokens: col = contiguous f32 [bs, cams * tokens_per_cam, Cout] with bs * cams == N")
     arr_p, arr_i = ctypes.c_void_p * k, ctypes.c_int * k
     status = _lib.lib().simpb_conv3x3_group_tokens_f16(
-        k, _ptr(col), _ptr(col16) if col16 is not None else None, int(per_cam), arr_i(*[int(v) for v in starts]),
+        k, _ptr(col) if col is not None else None, _ptr(col16) if col16 is not None else None, int(per_cam), arr_i(*[int(v) for v in starts]),
         arr_p(*[x.data_ptr() for x in xs]), arr_p(*[w.data_ptr() for w in ws]), arr_p(*[b.data_ptr() for b in biases]), n,
         arr_i(*[x.shape[2] for x in xs]), arr_i(*[x.shape[3] for x in xs]), cin, cout, 1 if relu else 0, _stream())
     _lib.check(status, "simpb_conv3x3_group_tokens_f16")
@@ -652,7 +661,7 @@ def linear_split(x, weight, bias=None):
         if hit is not None:
             weight._simpb_split_lin = hit
     if hit is None or hit[1] is None:
-        return linear_f32(x, weight, bias)
+        return linear_f32(x.float() if x.dtype == torch.float16 else x, weight, bias)   # (the cold route: exact kernel on fp32 rows)
     m, n = x.numel() // k, weight.shape[0]
     y = torch.empty(m, n, device=x.device, dtype=torch.float32)
     b = bias.contiguous().float() if bias is not None else None

@@ -71,10 +71,28 @@ DEFAULTS = dict(
     # DeformableFeatureAggregation: key points + projection + weight softmax inside the aggregation launch
     # (csrc/deform_agg_fused.hip). False: dfa_points + dfa_weights + the drop-in aggregation operator (three launches).
     fused_dfa=True,
-    # ... reading the f16 copy of the camera tokens the FPN leaves beside the fp32 rows (same numbers, half the bytes).
-    # Off: the launch is latency-bound at 900 anchors (26.5-27.4 us with f16 rows against 28.3-30.4 with fp32 rows,
-    # profiles/r03_*), so the fp32 rows of the operator's own contract (ops/src/deformable_aggregation.cpp:22-28) stay.
-    dfa_f16_tokens=False,
+    # ... reading the f16 copy of the camera tokens wherever the FPN leaves one beside the fp32 rows (the tokens ARE f16
+    # numbers: same bits into the same fp32 arithmetic, half the gather bytes; 26.5-27.4 us with f16 rows against 28.3-30.4
+    # with fp32 rows at 900 anchors, profiles/r03_*). On since a replayed frame has f16 rows only (lean_tokens): eager
+    # frames and the roofline leg of bench.py --full then run the kernel the timed frames run. The drop-in operator
+    # (ops/src/deformable_aggregation.cpp:22-28, plugin/ops.py deformable_aggregation_function) keeps its fp32 contract.
+    dfa_f16_tokens=True,
+    # A frame that a runner CAPTURES AND REPLAYS exposes nothing but its records, so it computes nothing else
+    # (profiles/lean_frames.md). Both switches act inside a capture only: head.forward / model.extract_feat called directly
+    # and a runner's eager frames keep every output. Neither changes a number a frame returns.
+    # lean_tokens: the FPN's output convolutions write the f16 token rows alone (csrc/conv3x3.hip, tokens == NULL): no fp32
+    # copy (92 MB per frame at one stream), feature_maps[0] of such a frame is the f16 tensor.
+    lean_tokens=True,
+    # lean_refine2d: the refinement heads whose outputs only the training losses read are not run: of every 2D layer but
+    # the last only the `norm` operator in front of the head (the chain launch's leading LayerNorm stage alone,
+    # csrc/mlp_chain.hip: bit-equal to the full launch's), of the last 2D layer no alpha chain, of the single-frame
+    # refine3d no quality chain. Their entries in the per-layer lists are None.
+    lean_refine2d=True,
+    # lean_glue: PyTorch glue kernels in front of decoder launches replaced by the launch reading its operand in place. Of
+    # the three named in profiles/lean_frames.md one is done: the camera-encoder chain reads the 3 x 4 part of the
+    # projection matrices where it lies (row stride 16, width 12) instead of a strided-to-contiguous copy. This one drops no
+    # output, so it acts in every frame, eager ones too.
+    lean_glue=True,
 )
 
 

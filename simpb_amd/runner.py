@@ -16,11 +16,13 @@ are re-captured at the new capacity, and results never silently degrade. Pipelin
 decoder one step early (before the previous frame's flags have reached the host) and therefore chains the
 hold on the device: see its docstring.
 """
+import contextlib
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
+from .plugin import routes
 from .plugin.detection3d import SparseBox3DDecoder
 from .results import POSE_KEYS, pose_row, world_tables
 
@@ -413,6 +415,32 @@ class FrameRunner:
     def _extract(self, img, raw):
         return self.model.extract_feat(raw, raw_plan=self.plan) if raw is not None else self.model.extract_feat(img)
 
+    # A frame that is captured and replayed exposes nothing but its records, so it computes nothing else (routes.lean_tokens,
+    # routes.lean_refine2d; profiles/lean_frames.md). Both act for the length of a capture only: eager frames (use_graph=False,
+    # the frames before a capture, force_eager, re-runs) and direct calls of the model keep every output they have.
+    @contextlib.contextmanager
+    def _capturing(self):
+        """Around a capture that runs backbone + FPN: the FPN's output convolutions write the f16 token rows alone, so the
+        captured frame's feature_maps[0] is the f16 tensor and its graph pool holds no fp32 rows. Needs the routes on which
+        every reader of the tokens takes f16 rows; restored on the way out, also after an exception."""
+        R = routes.R
+        neck = getattr(self.model, "img_neck", None)
+        on = (neck is not None and R.lean_tokens and R.dense and R.fused_dfa and (R.msda_linear or R.split_value_proj))
+        if not on:
+            yield
+            return
+        before = getattr(neck, "f16_tokens_only", False)
+        neck.f16_tokens_only = True
+        try:
+            yield
+        finally:
+            neck.f16_tokens_only = before
+
+    @staticmethod
+    def _lean_head(captured):
+        """The head's `lean` argument for a frame: only a captured frame drops the outputs its records do not read."""
+        return bool(captured and routes.R.lean_refine2d)
+
     SUPPORTS_PAUSE = True
 
     def _activity(self, active, cold):
@@ -507,10 +535,10 @@ class FrameRunner:
                 res["img_bbox"]["world"] = dict(record=world[i, :n], count=n)
         return results
 
-    def _frame(self, dmetas, aug_config):
-        """The device part of one frame; every tensor it returns has a fixed shape."""
+    def _frame(self, dmetas, aug_config, captured=False):
+        """The device part of one frame; every tensor it returns has a fixed shape. captured: inside a graph capture."""
         feature_maps = self._extract(self.img, self.raw)
-        return self._records(self.head(feature_maps, dmetas), aug_config, self.inputs)
+        return self._records(self.head(feature_maps, dmetas, lean=self._lean_head(captured)), aug_config, self.inputs)
 
     # ------------------------------------------------------------------ capacity overflow
     def _drop_graphs(self):
@@ -576,8 +604,8 @@ class FrameRunner:
         if warm and self.use_graph and not force_eager and self.graph is None and self.warm_frames >= 1:
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_MODE):
-                self.outputs = self._frame(dmetas, aug)
+            with torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_MODE), self._capturing():
+                self.outputs = self._frame(dmetas, aug, captured=True)
         if warm and self.graph is not None and not force_eager:
             if self.rec_consumed is not None:
                 torch.cuda.current_stream().wait_event(self.rec_consumed)
@@ -683,7 +711,7 @@ class PipelinedRunner(FrameRunner):
             if self.use_graph and not force_eager and self.bb_graph[slot] is None and self.bb_runs[slot] >= 1:
                 self.s_bb.synchronize()
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=self.s_bb, capture_error_mode=CAPTURE_MODE):
+                with torch.cuda.graph(g, stream=self.s_bb, capture_error_mode=CAPTURE_MODE), self._capturing():
                     self.bb_out[slot] = self._features(slot)
                 self.bb_graph[slot] = g
                 self.head_graph[slot] = None  # a decoder graph bound to the old buffer is stale
@@ -703,8 +731,8 @@ class PipelinedRunner(FrameRunner):
             fm.append(self.head.precompute_values(fm))
         return fm
 
-    def _decode(self, slot, dmetas, aug, inputs):
-        return self._records(self.head(self.fm[slot], dmetas), aug, inputs)
+    def _decode(self, slot, dmetas, aug, inputs, captured=False):
+        return self._records(self.head(self.fm[slot], dmetas, lean=self._lean_head(captured)), aug, inputs)
 
     def _in_flight(self):
         return len(self.queue)
@@ -731,7 +759,7 @@ class PipelinedRunner(FrameRunner):
                 self.s_head.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=self.s_head, capture_error_mode=CAPTURE_MODE):
-                    self.head_out[slot] = self._decode(slot, dmetas, aug, inputs)
+                    self.head_out[slot] = self._decode(slot, dmetas, aug, inputs, captured=True)
                 self.head_graph[slot] = g
             if graph_ok and self.head_graph[slot] is not None:
                 if self.rec_consumed is not None:  # the record buffer of this graph may still be read by its consumer
@@ -895,8 +923,8 @@ class SplitPipelinedRunner(PipelinedRunner):
         super()._drop_graphs()
         self.pre_graph = [None, None]
 
-    def _part_a(self, slot, dmetas):
-        gen = self.head.forward_split(self.fm[slot], dmetas)
+    def _part_a(self, slot, dmetas, captured=False):
+        gen = self.head.forward_split(self.fm[slot], dmetas, lean=self._lean_head(captured))
         next(gen)
         return gen
 
@@ -922,7 +950,7 @@ class SplitPipelinedRunner(PipelinedRunner):
             with torch.cuda.stream(self.s_head):
                 ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
                 with torch.cuda.graph(ga, stream=self.s_head, capture_error_mode=CAPTURE_MODE):
-                    gen = self._part_a(slot, dmetas)
+                    gen = self._part_a(slot, dmetas, captured=True)
                 with torch.cuda.graph(gb, stream=self.s_head, pool=ga.pool(), capture_error_mode=CAPTURE_MODE):
                     self.head_out[slot] = self._part_b(gen, aug, inputs)
                 del gen
