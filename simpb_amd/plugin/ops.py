@@ -179,9 +179,15 @@ def feature_maps_format(feature_maps, inverse=False):
         return [out]
 
     if isinstance(feature_maps[0], (list, tuple)):
+        # camera sets with pyramids of their own. The aggregation kernels index the concatenated token buffer with
+        # scale_start_index[cam, lvl], so a set's starts are moved behind the tokens of the sets in front of it (the reference
+        # concatenates them as they are, ops/__init__.py:56-61: every set after the first then reads the first set's tokens)
         formated = [feature_maps_format(x) for x in feature_maps]
-        return [torch.cat([x[0] for x in formated], dim=1), torch.cat([x[1] for x in formated], dim=0),
-                torch.cat([x[2] for x in formated], dim=0)]
+        starts, base = [], 0
+        for x in formated:
+            starts.append(x[2] + base)
+            base += x[0].shape[1]
+        return [torch.cat([x[0] for x in formated], dim=1), torch.cat([x[1] for x in formated], dim=0), torch.cat(starts, dim=0)]
 
     bs, num_cams = feature_maps[0].shape[:2]
     shapes = tuple(tuple(f.shape[-2:]) for f in feature_maps)
