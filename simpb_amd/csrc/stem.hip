@@ -188,7 +188,7 @@ extern "C" int simpb_image_to_nhwc4_f16(void* out, const float* img, long long s
 
 extern "C" int simpb_stem_conv7x7_pool_f16(void* out, const void* img_nhwc4, const void* weight_packed, const void* bias,
                                            int num_images, int height, int width, int out_channels, void* stream) {
-  if (!out || !img_nhwc4 || !weight_packed || !bias || num_images <= 0 || num_images > 65535 || height < 8 || width < 8 ||
+  if (!out || !img_nhwc4 || !weight_packed || !bias || num_images <= 0 || num_images > 65535 || height < 1 || width < 1 ||
       out_channels != kCout)
     return SIMPB_EINVAL;
   if ((reinterpret_cast<size_t>(out) | reinterpret_cast<size_t>(img_nhwc4) | reinterpret_cast<size_t>(weight_packed) |

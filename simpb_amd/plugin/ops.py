@@ -591,7 +591,7 @@ def stem_conv_pool(img, weight, bias):
     [N, 3, H, W] (any strides); weight f16/f32 [64, 3, 7, 7]; bias [64] -> f16 [N, 64, Hp, Wp] channels_last."""
     _require_gpu(img, weight, bias)
     n, c, h, w = img.shape
-    if img.dtype != torch.float32 or c != 3 or tuple(weight.shape) != (64, 3, 7, 7) or bias.numel() != 64 or h < 8 or w < 8:
+    if img.dtype != torch.float32 or c != 3 or tuple(weight.shape) != (64, 3, 7, 7) or bias.numel() != 64 or h < 1 or w < 1:
         raise ValueError("stem_conv_pool: f32 [N, 3, H, W] image, [64, 3, 7, 7] weight, 64 biases")
     lib = _lib.lib()
     x4 = torch.empty(n, h, w, 4, device=img.device, dtype=torch.float16)
@@ -605,7 +605,7 @@ def stem_conv_pool_nhwc4(x4, weight, bias):
     the camera frame ingest (preprocess_frames) wrote. -> f16 [N, 64, Hp, Wp] channels_last."""
     _require_gpu(x4, weight, bias)
     if (x4.dtype != torch.float16 or x4.dim() != 4 or x4.shape[3] != 4 or not x4.is_contiguous() or tuple(weight.shape) != (64, 3, 7, 7)
-            or bias.numel() != 64 or x4.shape[1] < 8 or x4.shape[2] < 8):
+            or bias.numel() != 64 or x4.shape[1] < 1 or x4.shape[2] < 1):
         raise ValueError("stem_conv_pool_nhwc4: contiguous f16 [N, H, W, 4] image, [64, 3, 7, 7] weight, 64 biases")
     n, h, w, _ = x4.shape
     lib = _lib.lib()
