@@ -369,8 +369,9 @@ int simpb_bias_relu_maxpool_nhwc_f16(void* y, const void* x, const void* bias, i
  * accumulate. stride 1 or 2; in_channels % 64 == 0, out_channels % 8 == 0; 16-byte aligned. These are conv1 / conv3 /
  * downsample of every ResNet bottleneck and the FPN lateral convolutions (mmdet ResNet + FPN of
  * projects/configs/simpb_nus_r50_img_704x256.py:79-99 after tools/fuse_conv_bn.py:10-48). variant 0 = choose the kernel
- * from the shape; 1 = the round-1 kernel (single LDS stage; the only one that takes input_bias); 2 / 3 = 128 x 64 / 128 x 128
- * tiles of the staged pipeline of simpb_conv3x3_nhwc_f16 (same sums up to fp32 summation order). */
+ * from the shape; 1 = the round-1 kernel (single LDS stage; the only one that takes input_bias); 2 / 3 / 4 = 128 x 64 /
+ * 128 x 128 / 64 x 64 tiles of the staged pipeline of simpb_conv3x3_nhwc_f16 (same sums up to fp32 summation order; 2 - 4
+ * give the same bits as each other). */
 int simpb_conv1x1_nhwc_f16(void* y, const void* x, const void* weight, const void* bias, const void* residual,
                            int num_images, int in_h, int in_w, int in_channels, int out_channels, int stride, int relu,
                            int residual_upsample2x, const void* input_bias, int variant, void* stream);
@@ -390,13 +391,19 @@ int simpb_conv1x1_nhwc_f16(void* y, const void* x, const void* weight, const voi
  *          token form; all three NULL is SIMPB_EINVAL.
  * These are conv2 of every ResNet bottleneck and FPN.fpn_convs (mmdet ResNet + FPN of
  * projects/configs/simpb_nus_r50_img_704x256.py:79-99 after tools/fuse_conv_bn.py:10-48). stride 1 or 2;
- * in_channels % 64 == 0, out_channels % 8 == 0; 16-byte aligned. variant 0 = choose the tiling from the shape; 1-8 force one
+ * in_channels % 64 == 0, out_channels % 8 == 0; 16-byte aligned. variant 0 = choose the tiling from the shape; 1-11 force one
  * (pixels x channels per workgroup: 1 = 128 x 64 and 2 = 256 x 64 with the activations read straight into the MFMA layout;
- * 3 = 32 x 64 and 4 = 64 x 64 with K split over the workgroup's waves; 5 = 128 x 64, 6 = 128 x 128, 7 = 96 x 64 and
- * 8 = 96 x 128 with both operands staged through LDS) -- all give the same sums up to fp32 summation order. */
+ * 3 = 32 x 64 and 4 = 64 x 64 with K split over the workgroup's waves; 5 = 128 x 64, 6 = 128 x 128, 7 = 96 x 64,
+ * 8 = 96 x 128 and 9 = 64 x 64 with both operands staged through LDS; 10 / 11 = 64 x 64 staged with K split over 2 / 4
+ * groups of four waves, the partial sums added in group order) -- all give the same sums up to fp32 summation order, each
+ * in a fixed order; 9 adds in the order of 1 and 2, 11 in the order of 3 and 4: the same bits. */
 int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, int tokens_per_cam, int level_start, const void* x,
                            const void* weight, const void* bias, int num_images, int in_h, int in_w, int in_channels,
                            int out_channels, int stride, int relu, int variant, void* stream);
+
+/* The tiling (1-11) that simpb_conv3x3_nhwc_f16 runs under variant 0 for p_out = num_images * out_h * out_w output pixels.
+ * A pure function of its arguments: nothing is launched and no device is needed. */
+int simpb_conv3x3_choose_variant(long long p_out, int in_channels, int out_channels);
 
 /* The same 3x3 / stride 1 convolution for up to four inputs of one channel count in ONE launch, each result written as its
  * level's token rows (f32 `tokens`, and f16 `tokens_f16` or NULL; or tokens == NULL and the f16 rows alone) exactly as

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kThreads) void conv1x1_f16_kernel(_Float16* __restr
 extern "C" int simpb_conv1x1_nhwc_f16(void* y, const void* x, const void* weight, const void* bias, const void* residual,
                                       int num_images, int in_h, int in_w, int in_channels, int out_channels, int stride,
                                       int relu, int residual_upsample2x, const void* input_bias, int variant, void* stream) {
-  if (variant < 0 || variant > 3 || (input_bias && variant > 1)) return SIMPB_EINVAL;
+  if (variant < 0 || variant > 4 || (input_bias && variant > 1)) return SIMPB_EINVAL;
   if (!y || !x || !weight || !bias || num_images <= 0 || in_h <= 0 || in_w <= 0 || in_channels <= 0 || out_channels <= 0 ||
       (stride != 1 && stride != 2) || in_channels % BK != 0 || out_channels % 8 != 0)  // BK = 64
     return SIMPB_EINVAL;
@@ -222,6 +222,13 @@ extern "C" int simpb_conv1x1_nhwc_f16(void* y, const void* x, const void* weight
     // stage, one barrier per chunk) wins where the K loop is long (8 chunks and more), this file's kernel on the short ones;
     // the input-side epilogue exists only here
     variant = (input_bias || in_channels < 512) ? 1 : 2;
+    if (variant == 2 && in_channels >= 1024) {
+      // the deep, small maps of stages 3-4 and the coarse FPN laterals (tools/bench_conv_small_maps.py,
+      // profiles/conv3x3_small_maps.md): 128 x 64 tiles leave the chip under-filled; 64 x 64 tiles add the same chunks in
+      // the same order, so the choice changes no output bit
+      const long long t128 = ((p_out + 127) / 128) * ((out_channels + 63) / 64);
+      if (t128 < 320) variant = 4;
+    }
   }
   if (variant > 1) {
     if ((long long)num_images * in_h * in_w * in_channels > (1ll << 31) - 1) return SIMPB_EINVAL;

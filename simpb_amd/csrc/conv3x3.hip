@@ -21,6 +21,8 @@
 //  * KSPLIT (small maps, long K: stages 3-4, coarse FPN levels): all four waves own the SAME 32*AF x 64 tile and take every
 //    fourth chunk; both operands straight from global memory, no LDS and no barrier in the loop, one LDS meeting at the end.
 //    M = 1 056 pixels (8 x 22 x 6 cameras) still yields 264 workgroups.
+// Both direct forms are bound by their load instructions (32 lines each); with Cin >= 256 the small maps run the staged
+// pipeline below at 64 x 64, K split over groups of waves inside the workgroup where the grid is small (KS).
 // FP16 matrix step = two v_mfma_f32_32x32x8f16 (csrc/mfma_f16.h; never the gfx950 double-K instruction).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -359,7 +361,6 @@ void launch(ConvArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL((conv3x3_f16_kernel<AF, KSPLIT, TOK16>), dim3((unsigned)(a.per_xcd * 8)), dim3(kThreads), 0, stream, a);
 }
 
-
 // ---- large maps: both operands staged through LDS with coalesced loads ------------------------------------------------------
 // Reading A straight into the MFMA layout costs a wave-instruction 32 different 128-byte lines (one per pixel row, two lanes
 // each), and the texture path takes them a quad of lanes at a time: the direct kernels above top out near 430 TFLOP/s on the
@@ -368,27 +369,39 @@ void launch(ConvArgs& a, hipStream_t stream) {
 // sets: loads run two chunks ahead), and fragments are read back with ds_read_b128 (256 B/clk per CU on gfx950, conflict-free
 // at a 144-byte row pitch). BMt x BNt output tile, WGM x WGN waves, each (BMt / WGM) x (BNt / WGN). The tile is chosen per shape so
 // that the grid fills whole rounds of the chip: 67 584 pixels are 528 tiles of 128 (two per CU and sixteen left over) but 704 of 96.
-template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
+//
+// KS > 1 (small maps, long K: stages 3-4): the workgroup is KS such pipelines side by side, 64 * WGM * WGN * KS threads. Group g
+// of WGM x WGN waves stages and multiplies the chunks g, g + KS, ... in that order through a stage of its own; the groups
+// share only the barrier, so one barrier passes KS chunks and a SIMD holds KS waves. At the end group 0 adds the groups'
+// partial tiles in ascending g (a fixed order) and writes the output.
+//
+// DIRECTK: lane (r32, kb) reads channels [32 * kb + 8 * j, + 8) of the chunk at matrix step j, as the direct kernels above
+// do, where the pipeline's own map is [16 * j + 8 * kb, + 8). Which eight k-values share a matrix instruction decides how
+// their sum is rounded: with the direct map, KS = 1 adds exactly what conv3x3_f16_kernel<., false> adds and KS = 4 what
+// conv3x3_f16_kernel<., true> adds, in the same order -- the same bits, so replacing one by the other changes no output.
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16, int KS = 1, bool DIRECTK = false>
 __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int tile) {
-  constexpr int NT = 64 * WGM * WGN;
+  constexpr int NT = 64 * WGM * WGN;   // threads of one K group
   constexpr int AF = BMt / WGM / 32, NF = BNt / WGN / 32;
   static_assert(AF * WGM * 32 == BMt && NF * WGN * 32 == BNt && NF <= 2, "tile = waves x 32-row / 32-column fragments");
   constexpr int NA = (BMt * 8 + NT - 1) / NT, NB = (BNt * 8 + NT - 1) / NT;   // staged 16-byte pieces per thread and chunk
   constexpr int kRows = BMt + BNt;
   constexpr int LDW = 32 * NF + 1;                                             // floats per row of a wave's epilogue tile
-  constexpr int kStage = 2 * kRows * LDH * 2, kTile = WGM * WGN * 32 * LDW * 4;
+  constexpr int kStage = KS * 2 * kRows * LDH * 2, kTile = KS * WGM * WGN * 32 * LDW * 4;
   __shared__ __attribute__((aligned(16))) unsigned char smem[kStage > kTile ? kStage : kTile];
-  _Float16* s_ab = reinterpret_cast<_Float16*>(smem);
+  const int grp = KS > 1 ? (int)threadIdx.x / NT : 0;   // wave-uniform
+  _Float16* s_ab = reinterpret_cast<_Float16*>(smem) + grp * (2 * kRows * LDH);
   float* s_c = reinterpret_cast<float*>(smem);
 
   const int tx = tile / a.gy, ty = tile - tx * a.gy;
-  const int tid = threadIdx.x;
+  const int tid = threadIdx.x - grp * NT;
   const int lane = tid & 63, wave = tid >> 6;
   const int r32 = lane & 31, kb = lane >> 5;
   const int wm = wave / WGN, wn = wave - wm * WGN;
   const int p0 = tx * BMt, c0 = ty * BNt;
   const int Cin = a.Cin, W = a.W, H = a.H;
   const int per_tap = Cin / BK, nchunks = TAPS * per_tap;
+  const int nsteps = (nchunks + KS - 1) / KS;   // a group's chunk of a step past the last chunk is staged as zeros
   const size_t K = (size_t)TAPS * Cin;
   const _Float16* __restrict__ wgt = a.w;
 
@@ -415,14 +428,16 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
   h16x8 ra[3][NA], rb[3][NB];
   unsigned alive[3];
 
-  auto fetch = [&](auto set_c, int chunk) __attribute__((always_inline)) {
+  auto fetch = [&](auto set_c, int step_i) __attribute__((always_inline)) {
     constexpr int s = decltype(set_c)::value;
+    const int chunk = step_i * KS + grp;
+    const bool exists = KS == 1 || chunk < nchunks;
     const int c = min(chunk, nchunks - 1);
     if constexpr (TAPS == 1) {   // a 1x1 convolution: the centre pixel only, always inside the image
       const int k0 = c * BK;
 #pragma unroll
       for (int i = 0; i < NA; ++i) ra[s][i] = *reinterpret_cast<const h16x8*>(actr[i] + k0);
-      alive[s] = ~0u;
+      alive[s] = exists ? ~0u : 0u;
 #pragma unroll
       for (int i = 0; i < NB; ++i) rb[s][i] = *reinterpret_cast<const h16x8*>(wgt + brow[i] + k0);
     } else {
@@ -436,7 +451,7 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
         m |= (in ? 1u : 0u) << i;
         ra[s][i] = *reinterpret_cast<const h16x8*>(actr[i] + (in ? toff : 0) + k0);
       }
-      alive[s] = m;
+      alive[s] = exists ? m : 0u;
       const size_t koff = (size_t)tap * Cin + k0;
 #pragma unroll
       for (int i = 0; i < NB; ++i) rb[s][i] = *reinterpret_cast<const h16x8*>(wgt + brow[i] + koff);
@@ -468,15 +483,16 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
       for (int r = 0; r < 16; ++r) acc[f][n][r] = 0.f;
 
   auto multiply = [&](int buf) __attribute__((always_inline)) {
-    const _Float16* sa = s_ab + buf * kRows * LDH + (wm * AF * 32 + r32) * LDH + 8 * kb;
-    const _Float16* sb = s_ab + buf * kRows * LDH + (BMt + wn * NF * 32 + r32) * LDH + 8 * kb;
+    constexpr int KLANE = DIRECTK ? 32 : 8, KSTEP = DIRECTK ? 8 : 16;   // halfs between the lane halves / the matrix steps
+    const _Float16* sa = s_ab + buf * kRows * LDH + (wm * AF * 32 + r32) * LDH + KLANE * kb;
+    const _Float16* sb = s_ab + buf * kRows * LDH + (BMt + wn * NF * 32 + r32) * LDH + KLANE * kb;
 #pragma unroll
     for (int ks = 0; ks < BK / 16; ++ks) {
       h16x8 av[AF], bv[NF];
 #pragma unroll
-      for (int f = 0; f < AF; ++f) av[f] = *reinterpret_cast<const h16x8*>(sa + f * 32 * LDH + 16 * ks);
+      for (int f = 0; f < AF; ++f) av[f] = *reinterpret_cast<const h16x8*>(sa + f * 32 * LDH + KSTEP * ks);
 #pragma unroll
-      for (int n = 0; n < NF; ++n) bv[n] = *reinterpret_cast<const h16x8*>(sb + n * 32 * LDH + 16 * ks);
+      for (int n = 0; n < NF; ++n) bv[n] = *reinterpret_cast<const h16x8*>(sb + n * 32 * LDH + KSTEP * ks);
 #pragma unroll
       for (int f = 0; f < AF; ++f)
 #pragma unroll
@@ -499,14 +515,14 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
     multiply(c & 1);
     __syncthreads();
   };
-  for (int c = 0; c < nchunks; c += 3) {   // 9 * per_tap is a multiple of 3; a 1x1 convolution has any count
+  for (int c = 0; c < nsteps; c += 3) {   // 9 * per_tap is a multiple of 3; a 1x1 convolution or a K split has any count
     step(IC<0>{}, IC<1>{}, c);
-    if (TAPS == 9 || c + 1 < nchunks) step(IC<1>{}, IC<2>{}, c + 1);
-    if (TAPS == 9 || c + 2 < nchunks) step(IC<2>{}, IC<0>{}, c + 2);
+    if ((TAPS == 9 && KS == 1) || c + 1 < nsteps) step(IC<1>{}, IC<2>{}, c + 1);
+    if ((TAPS == 9 && KS == 1) || c + 2 < nsteps) step(IC<2>{}, IC<0>{}, c + 2);
   }
 
   // epilogue, one A fragment at a time through the wave's own 32 x (32 * NF) fp32 tile: 16-byte pieces of output rows
-  float* mine = s_c + wave * 32 * LDW;
+  float* mine = s_c + (grp * WGM * WGN + wave) * 32 * LDW;
   const int cw = c0 + wn * NF * 32;
   const bool full = cw + 32 * NF <= a.Cout;
 #pragma unroll
@@ -518,6 +534,7 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
       for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * kb) * LDW + n * 32 + r32] = acc[f][n][r];
     __syncthreads();
     constexpr int PR = 4 * NF;            // pieces per row
+    if (KS > 1 && grp) continue;          // K split: group 0 adds the partial tiles of its wave's place in every group
 #pragma unroll
     for (int pass = 0; pass < 32 * PR / 64; ++pass) {
       const int idx = lane + 64 * pass;
@@ -525,6 +542,12 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = mine[r * LDW + c8 + e];
+      if constexpr (KS > 1) {
+#pragma unroll
+        for (int g = 1; g < KS; ++g)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] += mine[(g * WGM * WGN * 32 + r) * LDW + c8 + e];
+      }
       emit_piece<TOK16>(a, cw, full, p0 + (wm * AF + f) * 32 + r, c8, v);
     }
   }
@@ -536,6 +559,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 3 ? 3 : 2) void conv_s
   const int tile = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
   if ((int)(blockIdx.x >> 3) >= a.per_xcd || tile >= a.gx * a.gy) return;
   conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16>(a, tile);
+}
+
+// the small maps with long K (3x3 variants 9-11): KS groups of waves, the direct kernels' k map (their sums, bit for bit)
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16, int KS>
+__global__ __launch_bounds__(64 * WGM * WGN * KS, 2) void conv_staged_ksplit_kernel(const ConvArgs a) {
+  const int tile = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
+  if ((int)(blockIdx.x >> 3) >= a.per_xcd || tile >= a.gx * a.gy) return;
+  conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16, KS, true>(a, tile);
 }
 
 // Several convolutions of one tile shape in ONE launch (the FPN's four output convolutions: 240 us as four launches, of which
@@ -568,7 +599,36 @@ void launch_staged(ConvArgs& a, hipStream_t stream) {
                      stream, a);
 }
 
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16, int KS>
+void launch_staged_ksplit(ConvArgs& a, hipStream_t stream) {
+  a.gx = (a.P_out + BMt - 1) / BMt;
+  a.gy = (a.Cout + BNt - 1) / BNt;
+  const long long total = (long long)a.gx * a.gy;
+  a.per_xcd = (int)((total + 7) / 8);
+  hipLaunchKernelGGL((conv_staged_ksplit_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16, KS>), dim3((unsigned)(a.per_xcd * 8)),
+                     dim3(64 * WGM * WGN * KS), 0, stream, a);
+}
+
 }  // namespace
+
+// The tiling simpb_conv3x3_nhwc_f16 runs for variant 0 on p_out output pixels (no launch: tests restate the rule against it).
+extern "C" int simpb_conv3x3_choose_variant(long long p_out, int in_channels, int out_channels) {
+  // measured on the ResNet50 / FPN shapes at 6 x 256 x 704 (tools/bench_conv3x3.py): the LDS-staged 96-row tilings while
+  // they fill the chip (96 divides the pixel counts of a 6-camera rig and leaves no nearly empty last round of
+  // workgroups), then the direct ones, K split inside the workgroup for the smallest maps
+  const long long ny = (out_channels + BN - 1) / BN;
+  const long long t96 = (p_out + 95) / 96, t128 = (p_out + 127) / 128, t64 = (p_out + 63) / 64;
+  if (out_channels >= 128 && t128 * ((out_channels + 127) / 128) >= 2048) return 6;   // many rounds: the larger tile wins
+  if (out_channels >= 128 && t96 * ((out_channels + 127) / 128) >= 160) return 8;
+  if (t96 * ny >= 256) return 7;
+  // Cin >= 256 on the small maps (tools/bench_conv_small_maps.py, profiles/conv3x3_small_maps.md): the direct forms are
+  // bound by their 16-byte loads of 32 different rows per wave-instruction, not by latency (8 or 16 waves on the same loads
+  // were no faster); the staged 64 x 64 tile wins, with K split over 16 waves where 64 x 64 tiles leave half the chip empty.
+  // 9 gives the bits of 1 and 11 the bits of 4 (DIRECTK above), so neither choice changes an output
+  if (t128 * ny >= 128) return in_channels >= 256 && out_channels >= 256 ? 9 : 1;
+  if (t64 * ny >= 128) return in_channels >= 512 && out_channels >= 512 ? 11 : 4;
+  return 3;
+}
 
 extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, int tokens_per_cam, int level_start,
                                       const void* x, const void* weight, const void* bias, int num_images, int in_h, int in_w,
@@ -576,7 +636,7 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
   const bool to_tokens = tokens || tokens_f16;   // tokens == NULL with tokens_f16 set: the f16 rows alone
   if ((!y && !to_tokens) || (y && to_tokens) || (reinterpret_cast<size_t>(tokens_f16) & 15) || !x || !weight || !bias || num_images <= 0 || in_h <= 0 || in_w <= 0 ||
       in_channels <= 0 || out_channels <= 0 || (stride != 1 && stride != 2) || in_channels % BK != 0 || out_channels % 8 != 0 ||
-      variant < 0 || variant > 8)
+      variant < 0 || variant > 11)
     return SIMPB_EINVAL;
   if ((reinterpret_cast<size_t>(y) | reinterpret_cast<size_t>(tokens) | reinterpret_cast<size_t>(x) |
        reinterpret_cast<size_t>(weight) | reinterpret_cast<size_t>(bias)) & 15)
@@ -590,19 +650,7 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
   ConvArgs a{static_cast<_Float16*>(y), tokens, static_cast<_Float16*>(tokens_f16), static_cast<const _Float16*>(x), static_cast<const _Float16*>(weight),
              static_cast<const _Float16*>(bias), nullptr, 0, (int)p_out, in_channels, out_channels, relu, stride, ho, wo, in_h, in_w,
              tokens_per_cam, level_start, 0, 0, 0};
-  const long long ny = (out_channels + BN - 1) / BN;
-  if (variant == 0) {
-    // measured on the ResNet50 / FPN shapes at 6 x 256 x 704 (tools/bench_conv3x3.py): the LDS-staged 96-row tilings while
-    // they fill the chip (96 divides the pixel counts of a 6-camera rig and leaves no nearly empty last round of
-    // workgroups), then the direct ones, K split inside the workgroup for the smallest maps
-    const long long t96 = (p_out + 95) / 96, t128 = (p_out + 127) / 128, t64 = (p_out + 63) / 64;
-    if (out_channels >= 128 && t128 * ((out_channels + 127) / 128) >= 2048) variant = 6;   // many rounds: the larger tile wins
-    else if (out_channels >= 128 && t96 * ((out_channels + 127) / 128) >= 160) variant = 8;
-    else if (t96 * ny >= 256) variant = 7;
-    else if (t128 * ny >= 128) variant = 1;
-    else if (t64 * ny >= 128) variant = 4;
-    else variant = 3;
-  }
+  if (variant == 0) variant = simpb_conv3x3_choose_variant(p_out, in_channels, out_channels);
   hipStream_t s = static_cast<hipStream_t>(stream);
   auto dispatch = [&](auto tok16_c) {
     constexpr bool T = decltype(tok16_c)::value;
@@ -614,7 +662,10 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
       case 5: launch_staged<128, 64, 4, 1, 9, T>(a, s); break;    // 128 x 64, operands staged through LDS
       case 6: launch_staged<128, 128, 2, 2, 9, T>(a, s); break;  // 128 x 128
       case 7: launch_staged<96, 64, 3, 1, 9, T>(a, s); break;     // 96 x 64, three waves: 704 workgroups for 67 584 pixels
-      default: launch_staged<96, 128, 1, 4, 9, T>(a, s); break;   // 96 x 128, waves side by side along the channels
+      case 8: launch_staged<96, 128, 1, 4, 9, T>(a, s); break;    // 96 x 128, waves side by side along the channels
+      case 9: launch_staged_ksplit<64, 64, 2, 2, 9, T, 1>(a, s); break;    // 64 x 64, four waves of 32 x 32: the sums of 1
+      case 10: launch_staged_ksplit<64, 64, 2, 2, 9, T, 2>(a, s); break;   // 64 x 64, K split over 2 groups of four waves
+      default: launch_staged_ksplit<64, 64, 2, 2, 9, T, 4>(a, s); break;   // 64 x 64, K split over 4 groups (16 waves): the sums of 3 / 4
     }
   };
   if (!tokens && tokens_f16) dispatch(std::true_type{});   // the f16 token rows alone: kernels without the fp32 stores
@@ -668,7 +719,8 @@ extern "C" int simpb_conv3x3_group_tokens_f16(int num_levels, float* tokens, voi
 }
 
 // 1x1 convolutions through the same staged pipeline (TAPS = 1): csrc/conv1x1.hip validates and forwards here.
-// tiling 0: 128 x 64 per workgroup, 1: 128 x 128.
+// tiling 0: 128 x 64 per workgroup, 1: 128 x 128, 2: 64 x 64 (four waves, 32 x 32 each: twice the workgroups of tiling 0 for
+// the small maps of stages 3-4; the sums of tiling 0 bit for bit: the same chunks in the same order through the same k map).
 extern "C" int simpb_conv_pointwise_staged(void* y, const void* x, const void* weight, const void* bias, const void* residual,
                                            int p_out, int in_h, int in_w, int ho, int wo, int in_channels, int out_channels,
                                            int stride, int relu, int residual_upsample2x, int tiling, void* stream) {
@@ -677,6 +729,7 @@ extern "C" int simpb_conv_pointwise_staged(void* y, const void* x, const void* w
              p_out, in_channels, out_channels, relu, stride, ho, wo, in_h, in_w, 0, 0, 0, 0, 0};
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (tiling == 0) launch_staged<128, 64, 4, 1, 1, false>(a, s);
-  else launch_staged<128, 128, 2, 2, 1, false>(a, s);
+  else if (tiling == 1) launch_staged<128, 128, 2, 2, 1, false>(a, s);
+  else launch_staged<64, 64, 2, 2, 1, false>(a, s);
   return simpb_check_launch();
 }

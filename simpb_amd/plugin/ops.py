@@ -536,6 +536,11 @@ def conv3x3_nhwc(x, weight, bias, relu=True, stride=1, tokens=None, variant=0):
     return y
 
 
+def conv3x3_variant_for(p_out, in_channels, out_channels):
+    """The tiling conv3x3_nhwc(variant=0) runs for p_out = N * Ho * Wo output pixels (csrc/conv3x3.hip's rule; no launch)."""
+    return int(_lib.lib().simpb_conv3x3_choose_variant(int(p_out), int(in_channels), int(out_channels)))
+
+
 def conv3x3_group_tokens(xs, weights, biases, col, per_cam, starts, col16=None, relu=False):
     """conv3x3_nhwc(..., tokens=...) of up to four levels in ONE launch (csrc/conv3x3.hip: conv_staged_group_kernel): the
     FPN's output convolutions. xs: channels_last f16 [N, Cin, H_j, W_j]; weights f16 [Cout, Cin, 3, 3]; biases f16 [Cout];
