@@ -27,6 +27,10 @@
 //    unconditional, so the waits are counted); LDS is double buffered, one barrier per chunk.
 //  * Workgroups are numbered so that each XCD (blockIdx % 8) walks a contiguous range of tiles:
 //    neighbouring tiles share their X rows in that XCD's L2.
+//
+// The three kernels below differ in their wave-to-tile map and in how partial tiles meet. What they
+// have in common -- segment select, K loop, epilogue element -- stands once, ahead of them;
+// the split of x and its range window stand in csrc/mfma_f16.h, shared with csrc/linear_split.hip.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "../../include/simpb_hip.h"
@@ -38,6 +42,9 @@ namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;  // native vector: plain loads/stores, no struct memcpy
+using h16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using h16x4 = __attribute__((ext_vector_type(4))) _Float16;
+using simpb::acc_row;
 
 constexpr int BM = 32, BK = 64;  // BK: granularity the host checks; kernels use BKT = 64 or 128
 constexpr int kWaves = 8;
@@ -58,23 +65,11 @@ __device__ __forceinline__ void static_for(F&& f) {
 // (csrc/attention.hip unpack4), in the element's own 32-bit word
 __device__ __forceinline__ float out_word(float v, int fmt) {
   if (fmt != SIMPB_GEMM_OUT_SPLIT_HALFS) return v;
-  const _Float16 h = (_Float16)v;
-  const _Float16 l = (_Float16)((v - (float)h) * 2048.f);
+  _Float16 h, l;
+  simpb::split_halfs(v, h, l);
   const unsigned bits = (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
   return __uint_as_float(bits);
 }
-
-// ---- range of the split operands. x = xh + xl / 2^11 carries 22 bits only while half(x) is a normal half: |x| >= 65520
-// makes xh infinite, and a row whose largest |x| is far below 2^-14 loses its trailing bits to half subnormals. The split
-// kernels therefore stage each row as x * 2^-e with e = 0 while the row's largest |x| lies in [2^-10, 2^15) (or the row
-// is all zeros), and otherwise e = the exponent of that largest |x|; the epilogue multiplies the sum by 2^e before the
-// bias. Scaling by powers of two is exact, so rows inside the window compute exactly what they did without it.
-// The row maxima are collected while the first pass stages x (which splits unscaled, as before); only a workgroup that
-// met a row outside the window makes a second pass with the exponents. The flag is a plain LDS word behind the barrier
-// the epilogue needs anyway. (split_row_outside / split_row_exp: csrc/mfma_f16.h; the window's host-side twin for
-// weights: plugin/dense.py SPLIT_WINDOW.)
-using simpb::split_row_exp;
-using simpb::split_row_outside;
 
 struct GemmLaunch {
   simpb_gemm_args a;
@@ -82,9 +77,68 @@ struct GemmLaunch {
   int per_xcd;  // tiles per XCD range
 };
 
+// ---- the column segments of x: where the chunk that starts at column k0 of [x0 | x1 | x2 | x3] lives (scalar
+// selects; segment widths are multiples of the chunk)
+struct XSegments {
+  const float *x0, *x1, *x2, *x3;
+  int e1, e2, e3;  // first column past segments 0, 1, 2
+  unsigned l0, l1, l2, l3;
+  __device__ __forceinline__ explicit XSegments(const simpb_gemm_job& job)
+      : x0(job.x[0]), x1(job.x[1]), x2(job.x[2]), x3(job.x[3]),
+        e1(job.kseg[0]), e2(e1 + (job.num_seg > 1 ? job.kseg[1] : 0)), e3(e2 + (job.num_seg > 2 ? job.kseg[2] : 0)),
+        l0(job.ldx[0]), l1(job.ldx[1]), l2(job.ldx[2]), l3(job.ldx[3]) {}
+  __device__ __forceinline__ const float* at(int k0, unsigned& ldx) const {
+    const float* xs = x0 + k0;
+    ldx = l0;
+    if (k0 >= e1) { xs = x1 + (k0 - e1); ldx = l1; }
+    if (k0 >= e2) { xs = x2 + (k0 - e2); ldx = l2; }
+    if (k0 >= e3) { xs = x3 + (k0 - e3); ldx = l3; }
+    return xs;
+  }
+};
+
+// ---- the K loop. DEPTH register sets = DEPTH chunks in flight ahead of the one being multiplied: the operands
+// come from the Infinity Cache / HBM (activations were just written by another XCD, and every workgroup walks K in
+// step, so a chunk is a first touch for all of them at once). Chunk c lives in register set c % DEPTH and LDS buffer
+// c & 1: stashed one barrier ahead of its product. fetch(set, chunk) / stash(set) / multiply(buffer) are the kernel's.
+// Loads are UNCONDITIONAL (a fetch past the end asks for the last chunk again, never used; row / column indices are
+// clamped, and the surplus rows and columns of an edge tile are computed on repeated data and never stored): a load
+// behind a branch makes the compiler wait for every outstanding load (vmcnt(0)) instead of the oldest register set only.
+template <int DEPTH, class Fetch, class Stash, class Multiply>
+__device__ __forceinline__ void k_loop(int nchunks, Fetch&& fetch, Stash&& stash, Multiply&& multiply) {
+  static_assert(DEPTH % 2 == 0, "LDS buffer index = register set index & 1");
+  static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) { fetch(d, decltype(d)::value); });
+  const int groups = nchunks / DEPTH;
+  for (int g = 0; g < groups; ++g) {
+    static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) {
+      stash(d);
+      __syncthreads();
+      fetch(d, (g + 1) * DEPTH + decltype(d)::value);
+      multiply(decltype(d)::value & 1);
+    });
+  }
+  const int rem = nchunks - groups * DEPTH;
+  static_for<0, DEPTH - 1>([&](auto d) __attribute__((always_inline)) {
+    if (decltype(d)::value < rem) {
+      stash(d);
+      __syncthreads();
+      multiply(decltype(d)::value & 1);
+    }
+  });
+}
+
+// ---- epilogue of element (gr, gc): v is its finished sum, bcol / b2 its column's entries of bias / bias2 (0.f where
+// the job has none: the sum of accumulators that started at +0 is never -0, so adding 0.f changes no bit)
+__device__ __forceinline__ void finish_element(const simpb_gemm_job& job, float* __restrict__ y, float v, float bcol,
+                                               float b2, int gr, int gc, int live) {
+  v += bcol;
+  if (job.row_flag && job.row_flag[gr]) v += b2;
+  if (job.relu) v = fmaxf(v, 0.f);
+  y[(size_t)gr * job.ldy + gc] = gr < live ? out_word(v, job.out_fmt) : 0.f;
+}
+
 template <int BN, int DEPTH, int BKT>
 __global__ __launch_bounds__(kThreads) void gemm_f32_kernel(GemmLaunch L) {
-  static_assert(DEPTH % 2 == 0, "LDS buffer index = register set index & 1");
   constexpr int LDK = BKT + 4;            // LDS row stride: 16-lane groups of ds_read_b128 hit 16 distinct 4-bank slots
   constexpr int C4 = BKT / 4;             // 16-byte columns of a chunk row
   constexpr int WN = BN / 32;             // waves across N
@@ -102,10 +156,10 @@ __global__ __launch_bounds__(kThreads) void gemm_f32_kernel(GemmLaunch L) {
   float* s_x = smem;                     // [2][BM][LDK]
   float* s_w = smem + 2 * BM * LDK;      // [2][BN][LDK]
 
-  // ---- which tile
-  const int total = L.tile_start[L.a.num_jobs];
-  const int tile = (blockIdx.x & 7) * L.per_xcd + (blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= L.per_xcd || tile >= total) return;
+  // ---- which tile (spelled out in each of the three kernels: as one shared function, with zero scratch and equal registers, it cost
+  // every 32-row launch ~0.35 us, profiles/gemm_shared_parts.md)
+  const int tile = simpb::xcd_tile(L.per_xcd, L.tile_start[L.a.num_jobs]);
+  if (tile < 0) return;
   int j = 0;
 #pragma unroll
   for (int t = 1; t < SIMPB_GEMM_MAX_JOBS; ++t)
@@ -127,15 +181,11 @@ __global__ __launch_bounds__(kThreads) void gemm_f32_kernel(GemmLaunch L) {
     }
     return;
   }
-
   const int lane = tid & 63, wave = tid >> 6;
   const int r32 = lane & 31, half = lane >> 5;
   const int wn = wave % WN, wk = wave / WN;
 
-  // ---- staging: thread f -> (row f >> 4, 16-byte column f & 15) of a [rows][64] chunk. Loads are
-  // UNCONDITIONAL (row / column indices clamped; the surplus rows and columns of an edge tile are
-  // computed on repeated data and never stored): a load behind a branch makes the compiler wait for
-  // every outstanding load (vmcnt(0)) instead of the oldest register set only. Addresses are a
+  // ---- staging: thread f -> (row f >> 4, 16-byte column f & 15) of a [rows][64] chunk. Addresses are a
   // wave-uniform base (segment pointer + k offset, scalar registers) plus a per-thread 32-bit offset
   // that does not change along K.
   const int sr = tid / C4, sc4 = tid % C4;
@@ -147,22 +197,13 @@ __global__ __launch_bounds__(kThreads) void gemm_f32_kernel(GemmLaunch L) {
 #pragma unroll
   for (int i = 0; i < NW4; ++i) wofs[i] = (unsigned)min(col0 + sr + RS * i, N - 1) * (unsigned)job.ldw + sc4 * 4;
   const int nchunks = K / BKT;
-  const float* const x0 = job.x[0];
-  const float* const x1 = job.x[1];
-  const float* const x2 = job.x[2];
-  const float* const x3 = job.x[3];
-  const int e1 = job.kseg[0], e2 = e1 + (job.num_seg > 1 ? job.kseg[1] : 0), e3 = e2 + (job.num_seg > 2 ? job.kseg[2] : 0);
-  const unsigned l0 = job.ldx[0], l1 = job.ldx[1], l2 = job.ldx[2], l3 = job.ldx[3];
+  const XSegments seg(job);
 
   auto fetch = [&](auto set_c, int chunk) __attribute__((always_inline)) {
     constexpr int set = decltype(set_c)::value;
     const int k0 = min(chunk, nchunks - 1) * BKT;
-    // segment of this chunk (scalar selects; segment widths are multiples of the chunk)
-    const float* xs = x0 + k0;
-    unsigned ldx = l0;
-    if (k0 >= e1) { xs = x1 + (k0 - e1); ldx = l1; }
-    if (k0 >= e2) { xs = x2 + (k0 - e2); ldx = l2; }
-    if (k0 >= e3) { xs = x3 + (k0 - e3); ldx = l3; }
+    unsigned ldx;
+    const float* xs = seg.at(k0, ldx);
     const float* wk0 = w + k0;
     static_for<0, NX4>([&](auto i) __attribute__((always_inline)) {
       px[set][decltype(i)::value] = *reinterpret_cast<const f32x4*>(xs + (xrow[decltype(i)::value] * ldx + sc4 * 4));
@@ -207,37 +248,13 @@ __global__ __launch_bounds__(kThreads) void gemm_f32_kernel(GemmLaunch L) {
     for (int s = 0; s < KH; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[s], acc, 0, 0, 0);
   };
 
-  // DEPTH register sets = DEPTH chunks in flight ahead of the one being multiplied: the operands
-  // come from the Infinity Cache / HBM (activations were just written by another XCD, and every
-  // workgroup walks K in step, so a chunk is a first touch for all of them at once).
-  static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) { fetch(d, decltype(d)::value); });
-  const int groups = nchunks / DEPTH;
-  for (int g = 0; g < groups; ++g) {
-    static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) {
-      stash(d);
-      __syncthreads();
-      fetch(d, (g + 1) * DEPTH + decltype(d)::value);  // past the end: the last chunk again, never used
-      multiply(decltype(d)::value & 1);
-    });
-  }
-  const int rem = nchunks - groups * DEPTH;
-  static_for<0, DEPTH - 1>([&](auto d) __attribute__((always_inline)) {
-    if (decltype(d)::value < rem) {
-      stash(d);
-      __syncthreads();
-      multiply(decltype(d)::value & 1);
-    }
-  });
+  k_loop<DEPTH>(nchunks, fetch, stash, multiply);
 
-  // ---- the WK partial tiles meet in LDS (C/D layout of the 32x32 tile: column = lane & 31,
-  // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5))
+  // ---- the WK partial tiles meet in LDS
   __syncthreads();
   float* part = smem;  // [WK][BM][LDP]
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-    part[(wk * BM + row) * LDP + wn * 32 + r32] = acc[r];
-  }
+  for (int r = 0; r < 16; ++r) part[(wk * BM + acc_row(r, half)) * LDP + wn * 32 + r32] = acc[r];
   __syncthreads();
   const float* __restrict__ bias = job.bias;
   for (int idx = tid; idx < BM * BN; idx += kThreads) {
@@ -247,10 +264,7 @@ __global__ __launch_bounds__(kThreads) void gemm_f32_kernel(GemmLaunch L) {
       float v = part[r * LDP + c];
 #pragma unroll
       for (int p = 1; p < WK; ++p) v += part[(p * BM + r) * LDP + c];  // fixed order: deterministic
-      if (bias) v += bias[gc];
-      if (job.row_flag && job.row_flag[gr]) v += job.bias2[gc];
-      if (job.relu) v = fmaxf(v, 0.f);
-      y[(size_t)gr * job.ldy + gc] = gr < live ? out_word(v, job.out_fmt) : 0.f;
+      finish_element(job, y, v, bias ? bias[gc] : 0.f, job.row_flag ? job.bias2[gc] : 0.f, gr, gc, live);
     }
   }
 }
@@ -260,14 +274,54 @@ __global__ __launch_bounds__(kThreads) void gemm_f32_kernel(GemmLaunch L) {
 // y = xh.Wh^T + (xh.Wl^T + xl.Wh^T) / 2^11 + xl.Wl^T / 2^22 in three fp32 accumulators. A wave's share of a K chunk
 // is exactly one 16-deep matrix instruction per term (four per chunk instead of eight fp32 ones at 1/16 the
 // rate), so what remains is the staging, the LDS round trip and the barrier.
-using h16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using h16x4 = __attribute__((ext_vector_type(4))) _Float16;
+//
+// ---- range of the split operands. x = xh + xl / 2^11 carries 22 bits only while half(x) is a normal half: |x| >= 65520
+// makes xh infinite, and a row whose largest |x| is far below 2^-14 loses its trailing bits to half subnormals. The split
+// kernels therefore stage each row as x * 2^-e with e = 0 while the row's largest |x| lies in [2^-10, 2^15) (or the row
+// is all zeros), and otherwise e = the exponent of that largest |x|; the epilogue multiplies the sum by 2^e before the
+// bias. Scaling by powers of two is exact, so rows inside the window compute exactly what they did without it.
+// The row maxima are collected while the first pass stages x (which splits unscaled, as before); only a workgroup that
+// met a row outside the window makes a second pass with the exponents. (simpb::split_staged / split_needs_second_pass:
+// csrc/mfma_f16.h; the window's host-side twin for weights: plugin/dense.py SPLIT_WINDOW.)
+
+// one 16-byte load of x as it goes to LDS in two parts
+template <bool kScaled>
+__device__ __forceinline__ void stash_x_split(const f32x4& v, int e, float& xmax, _Float16* dst_h, _Float16* dst_l) {
+  h16x4 hi, lo;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    _Float16 h, l;
+    simpb::split_staged<kScaled>(v[q], e, xmax, h, l);
+    hi[q] = h;
+    lo[q] = l;
+  }
+  *reinterpret_cast<h16x4*>(dst_h) = hi;
+  *reinterpret_cast<h16x4*>(dst_l) = lo;
+}
+
+// leading term / cross terms scaled by 2^11 / trailing term scaled by 2^22. The last one (~2^-22 relative) is
+// kept here although csrc/linear_split.hip drops it: the matrix pipe has cycles to spare, and without it one 2D
+// query of the golden R50 stream changed sides of the image border (an N2 of 1129 instead of 1130): the decoder's
+// discrete decisions sit downstream of these products.
+struct SplitAcc {
+  f32x16 acc, acs, act;
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acs[r] = 0.f; act[r] = 0.f; }
+  }
+  __device__ __forceinline__ void step(const h16x8& ah, const h16x8& al, const h16x8& bh, const h16x8& bl) {
+    act = simpb::mfma_32x32x16_f16(al, bl, act);
+    acs = simpb::mfma_32x32x16_f16(al, bh, acs);
+    acs = simpb::mfma_32x32x16_f16(ah, bl, acs);
+    acc = simpb::mfma_32x32x16_f16(ah, bh, acc);
+  }
+  __device__ __forceinline__ float sum(int r) const { return acc[r] + (acs[r] + act[r] * (1.f / 2048.f)) * (1.f / 2048.f); }
+};
 
 // (four waves per SIMD = two workgroups per CU, as the LDS allows: at most 128 registers, which the row-range bookkeeping
 // below would otherwise push the 32 x 32 form past)
 template <int BN, int DEPTH, int BKT>
 __global__ __launch_bounds__(kThreads, 4) void gemm_f16x3_kernel(GemmLaunch L) {
-  static_assert(DEPTH % 2 == 0, "LDS buffer index = register set index & 1");
   constexpr int LDH = BKT + 8;            // LDS row stride in halfs: conflict-free 16-lane groups for ds_read_b128
   constexpr int WN = BN / 32, WK = kWaves / WN, KW = BKT / WK;
   static_assert(KW == 16, "one 32x32x16 step per wave per chunk");
@@ -285,9 +339,9 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_f16x3_kernel(GemmLaunch L) {
   _Float16* s_wh = s_xl + 2 * BM * LDH;                    // [2][BN][LDH]
   _Float16* s_wl = s_wh + 2 * BN * LDH;
 
-  const int total = L.tile_start[L.a.num_jobs];
-  const int tile = (blockIdx.x & 7) * L.per_xcd + (blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= L.per_xcd || tile >= total) return;
+  // ---- which tile (as gemm_f32_kernel)
+  const int tile = simpb::xcd_tile(L.per_xcd, L.tile_start[L.a.num_jobs]);
+  if (tile < 0) return;
   int j = 0;
 #pragma unroll
   for (int t = 1; t < SIMPB_GEMM_MAX_JOBS; ++t)
@@ -309,7 +363,6 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_f16x3_kernel(GemmLaunch L) {
     }
     return;
   }
-
   const int lane = tid & 63, wave = tid >> 6;
   const int r32 = lane & 31, kb = lane >> 5;
   const int wn = wave % WN, wk = wave / WN;
@@ -326,21 +379,13 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_f16x3_kernel(GemmLaunch L) {
 #pragma unroll
   for (int i = 0; i < NW8; ++i) wofs[i] = (unsigned)min(col0 + srw + RSW * i, N - 1) * (unsigned)K + scw * 8;
   const int nchunks = K / BKT;
-  const float* const x0 = job.x[0];
-  const float* const x1 = job.x[1];
-  const float* const x2 = job.x[2];
-  const float* const x3 = job.x[3];
-  const int e1 = job.kseg[0], e2 = e1 + (job.num_seg > 1 ? job.kseg[1] : 0), e3 = e2 + (job.num_seg > 2 ? job.kseg[2] : 0);
-  const unsigned l0 = job.ldx[0], l1 = job.ldx[1], l2 = job.ldx[2], l3 = job.ldx[3];
+  const XSegments seg(job);
 
   auto fetch = [&](auto set_c, int chunk) __attribute__((always_inline)) {
     constexpr int set = decltype(set_c)::value;
     const int k0 = min(chunk, nchunks - 1) * BKT;
-    const float* xs = x0 + k0;
-    unsigned ldx = l0;
-    if (k0 >= e1) { xs = x1 + (k0 - e1); ldx = l1; }
-    if (k0 >= e2) { xs = x2 + (k0 - e2); ldx = l2; }
-    if (k0 >= e3) { xs = x3 + (k0 - e3); ldx = l3; }
+    unsigned ldx;
+    const float* xs = seg.at(k0, ldx);
     static_for<0, NX4>([&](auto i) __attribute__((always_inline)) {
       px[set][decltype(i)::value] = *reinterpret_cast<const f32x4*>(xs + (xrow[decltype(i)::value] * ldx + scx * 4));
     });
@@ -356,22 +401,10 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_f16x3_kernel(GemmLaunch L) {
   auto stash = [&](auto set_c, auto scaled_c) __attribute__((always_inline)) {
     constexpr int set = decltype(set_c)::value;
     constexpr int buf = set & 1;
-    constexpr bool kScaled = decltype(scaled_c)::value;   // second pass: rows staged as x * 2^-e
     static_for<0, NX4>([&](auto i) __attribute__((always_inline)) {
       constexpr int ii = decltype(i)::value;
-      const f32x4 v = px[set][ii];
-      h16x4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float s = v[e];
-        if constexpr (kScaled) s = __builtin_amdgcn_ldexpf(s, -xe[ii]);
-        else xmax[ii] = fmaxf(xmax[ii], fabsf(s));
-        const _Float16 h = (_Float16)s;
-        hi[e] = h;
-        lo[e] = (_Float16)((s - (float)h) * 2048.f);
-      }
-      *reinterpret_cast<h16x4*>(&s_xh[(buf * BM + srx + RSX * ii) * LDH + scx * 4]) = hi;
-      *reinterpret_cast<h16x4*>(&s_xl[(buf * BM + srx + RSX * ii) * LDH + scx * 4]) = lo;
+      const int at = (buf * BM + srx + RSX * ii) * LDH + scx * 4;
+      stash_x_split<decltype(scaled_c)::value>(px[set][ii], xe[ii], xmax[ii], &s_xh[at], &s_xl[at]);
     });
     static_for<0, NW8>([&](auto i) __attribute__((always_inline)) {
       constexpr int ii = decltype(i)::value;
@@ -380,72 +413,29 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_f16x3_kernel(GemmLaunch L) {
     });
   };
 
-  // leading term / cross terms scaled by 2^11 / trailing term scaled by 2^22. The last one (~2^-22 relative) is
-  // kept here although csrc/linear_split.hip drops it: the matrix pipe has cycles to spare, and without it one 2D
-  // query of the golden R50 stream changed sides of the image border (an N2 of 1129 instead of 1130): the decoder's
-  // discrete decisions sit downstream of these products.
-  f32x16 acc, acs, act;
-
+  SplitAcc a;
   auto multiply = [&](int buf) __attribute__((always_inline)) {
     const int off = wk * KW + 8 * kb;  // lane (r32, kb) holds k = wk*16 + 8*kb .. +7 of its x row / W row
-    const h16x8 ah = *reinterpret_cast<const h16x8*>(&s_xh[(buf * BM + r32) * LDH + off]);
-    const h16x8 al = *reinterpret_cast<const h16x8*>(&s_xl[(buf * BM + r32) * LDH + off]);
-    const h16x8 bh = *reinterpret_cast<const h16x8*>(&s_wh[(buf * BN + wn * 32 + r32) * LDH + off]);
-    const h16x8 bl = *reinterpret_cast<const h16x8*>(&s_wl[(buf * BN + wn * 32 + r32) * LDH + off]);
-    act = simpb::mfma_32x32x16_f16(al, bl, act);
-    acs = simpb::mfma_32x32x16_f16(al, bh, acs);
-    acs = simpb::mfma_32x32x16_f16(ah, bl, acs);
-    acc = simpb::mfma_32x32x16_f16(ah, bh, acc);
+    a.step(*reinterpret_cast<const h16x8*>(&s_xh[(buf * BM + r32) * LDH + off]),
+           *reinterpret_cast<const h16x8*>(&s_xl[(buf * BM + r32) * LDH + off]),
+           *reinterpret_cast<const h16x8*>(&s_wh[(buf * BN + wn * 32 + r32) * LDH + off]),
+           *reinterpret_cast<const h16x8*>(&s_wl[(buf * BN + wn * 32 + r32) * LDH + off]));
   };
-
-  auto kloop = [&](auto scaled_c) __attribute__((always_inline)) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acs[r] = 0.f; act[r] = 0.f; }
-    static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) { fetch(d, decltype(d)::value); });
-    const int groups = nchunks / DEPTH;
-    for (int g = 0; g < groups; ++g) {
-      static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) {
-        stash(d, scaled_c);
-        __syncthreads();
-        fetch(d, (g + 1) * DEPTH + decltype(d)::value);
-        multiply(decltype(d)::value & 1);
-      });
-    }
-    const int rem = nchunks - groups * DEPTH;
-    static_for<0, DEPTH - 1>([&](auto d) __attribute__((always_inline)) {
-      if (decltype(d)::value < rem) {
-        stash(d, scaled_c);
-        __syncthreads();
-        multiply(decltype(d)::value & 1);
-      }
-    });
+  auto pass = [&](auto scaled_c) __attribute__((always_inline)) {
+    a.zero();
+    k_loop<DEPTH>(nchunks, fetch, [&](auto d) __attribute__((always_inline)) { stash(d, scaled_c); }, multiply);
   };
   if (tid == 0) s_any = 0;   // (ordered before any write below by the loop's barriers)
-  kloop(std::false_type{});
-  // the C4 lanes that staged a row meet on its largest |x| (consecutive lanes of one wave)
-#pragma unroll
-  for (int i = 0; i < NX4; ++i) {
-#pragma unroll
-    for (int m = 1; m < C4; m <<= 1) xmax[i] = fmaxf(xmax[i], __shfl_xor(xmax[i], m));
-    if (split_row_outside(xmax[i])) s_any = 1;
-  }
-  __syncthreads();
-  const bool scaled = s_any != 0;   // workgroup-uniform
+  pass(std::false_type{});
+  const bool scaled = simpb::split_needs_second_pass<C4>(xmax, xe, s_any, s_rowexp, srx, RSX, scx == 0);
   if (scaled) {
-#pragma unroll
-    for (int i = 0; i < NX4; ++i) {
-      xe[i] = split_row_exp(xmax[i]);
-      if (scx == 0) s_rowexp[srx + RSX * i] = xe[i];
-    }
-    kloop(std::true_type{});
+    pass(std::true_type{});
     __syncthreads();
   }
+  // ---- the WK partial tiles meet in LDS
   float* part = reinterpret_cast<float*>(smem_raw);  // [WK][BM][LDP]
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * kb;
-    part[(wk * BM + row) * LDP + wn * 32 + r32] = acc[r] + (acs[r] + act[r] * (1.f / 2048.f)) * (1.f / 2048.f);
-  }
+  for (int r = 0; r < 16; ++r) part[(wk * BM + acc_row(r, kb)) * LDP + wn * 32 + r32] = a.sum(r);
   __syncthreads();
   const float* __restrict__ bias = job.bias;
   for (int idx = tid; idx < BM * BN; idx += kThreads) {
@@ -456,10 +446,7 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_f16x3_kernel(GemmLaunch L) {
 #pragma unroll
       for (int p = 1; p < WK; ++p) v += part[(p * BM + r) * LDP + c];  // fixed order: deterministic
       if (scaled) v = __builtin_amdgcn_ldexpf(v, s_rowexp[r]);
-      if (bias) v += bias[gc];
-      if (job.row_flag && job.row_flag[gr]) v += job.bias2[gc];
-      if (job.relu) v = fmaxf(v, 0.f);
-      y[(size_t)gr * job.ldy + gc] = gr < live ? out_word(v, job.out_fmt) : 0.f;
+      finish_element(job, y, v, bias ? bias[gc] : 0.f, job.row_flag ? job.bias2[gc] : 0.f, gr, gc, live);
     }
   }
 }
@@ -475,7 +462,7 @@ constexpr int kWM = 64, kWN = 128;
 template <int DEPTH>
 __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L) {
   static_assert(DEPTH == 2, "two register sets, two LDS buffers");
-  constexpr int BKT = 64;
+  constexpr int BKT = 64;   // (the split route needs 128-aligned segments, so the chunk count is even: the K loop's tail never runs)
   constexpr int LDH = BKT + 8;
   constexpr int C4 = BKT / 4, NX4 = kWM * C4 / kThreads, RSX = kThreads / C4;   // x: 64 x 64 fp32 = 1024 float4, 2 per thread
   constexpr int C8 = BKT / 8, NW8 = kWN * C8 / kThreads, RSW = kThreads / C8;   // w: 128 x 64 halfs = 1024 x 16 B, 2 per thread (hi and lo each)
@@ -487,9 +474,9 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
   __shared__ int s_rowexp[kWM];   // row exponents of the second pass (split_row_exp)
   __shared__ int s_any;
 
-  const int total = L.tile_start[L.a.num_jobs];
-  const int tile = (blockIdx.x & 7) * L.per_xcd + (blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= L.per_xcd || tile >= total) return;
+  // ---- which tile (as gemm_f32_kernel)
+  const int tile = simpb::xcd_tile(L.per_xcd, L.tile_start[L.a.num_jobs]);
+  if (tile < 0) return;
   int j = 0;
 #pragma unroll
   for (int t = 1; t < SIMPB_GEMM_MAX_JOBS; ++t)
@@ -511,7 +498,6 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
     }
     return;
   }
-
   const int lane = tid & 63, wave = tid >> 6;
   const int r32 = lane & 31, kb = lane >> 5;
   const int wm = wave >> 2, wn = wave & 3;   // this wave's 32 x 32 tile: rows 32 wm.., columns 32 wn..
@@ -528,21 +514,13 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
 #pragma unroll
   for (int i = 0; i < NW8; ++i) wofs[i] = (unsigned)min(col0 + srw + RSW * i, N - 1) * (unsigned)K + scw * 8;
   const int nchunks = K / BKT;
-  const float* const x0 = job.x[0];
-  const float* const x1 = job.x[1];
-  const float* const x2 = job.x[2];
-  const float* const x3 = job.x[3];
-  const int e1 = job.kseg[0], e2 = e1 + (job.num_seg > 1 ? job.kseg[1] : 0), e3 = e2 + (job.num_seg > 2 ? job.kseg[2] : 0);
-  const unsigned l0 = job.ldx[0], l1 = job.ldx[1], l2 = job.ldx[2], l3 = job.ldx[3];
+  const XSegments seg(job);
 
   auto fetch = [&](auto set_c, int chunk) __attribute__((always_inline)) {
     constexpr int set = decltype(set_c)::value;
-    const int k0 = min(chunk, nchunks - 1) * BKT;   // (past the end: the last chunk again, never used -- loads stay unconditional)
-    const float* xs = x0 + k0;
-    unsigned ldx = l0;
-    if (k0 >= e1) { xs = x1 + (k0 - e1); ldx = l1; }
-    if (k0 >= e2) { xs = x2 + (k0 - e2); ldx = l2; }
-    if (k0 >= e3) { xs = x3 + (k0 - e3); ldx = l3; }
+    const int k0 = min(chunk, nchunks - 1) * BKT;
+    unsigned ldx;
+    const float* xs = seg.at(k0, ldx);
     static_for<0, NX4>([&](auto i) __attribute__((always_inline)) {
       px[set][decltype(i)::value] = *reinterpret_cast<const f32x4*>(xs + (xrow[decltype(i)::value] * ldx + scx * 4));
     });
@@ -558,22 +536,10 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
   auto stash = [&](auto set_c, auto scaled_c) __attribute__((always_inline)) {
     constexpr int set = decltype(set_c)::value;
     constexpr int buf = set & 1;
-    constexpr bool kScaled = decltype(scaled_c)::value;   // second pass: rows staged as x * 2^-e
     static_for<0, NX4>([&](auto i) __attribute__((always_inline)) {
       constexpr int ii = decltype(i)::value;
-      const f32x4 v = px[set][ii];
-      h16x4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float s = v[e];
-        if constexpr (kScaled) s = __builtin_amdgcn_ldexpf(s, -xe[ii]);
-        else xmax[ii] = fmaxf(xmax[ii], fabsf(s));
-        const _Float16 h = (_Float16)s;
-        hi[e] = h;
-        lo[e] = (_Float16)((s - (float)h) * 2048.f);
-      }
-      *reinterpret_cast<h16x4*>(&s_xh[(buf * kWM + srx + RSX * ii) * LDH + scx * 4]) = hi;
-      *reinterpret_cast<h16x4*>(&s_xl[(buf * kWM + srx + RSX * ii) * LDH + scx * 4]) = lo;
+      const int at = (buf * kWM + srx + RSX * ii) * LDH + scx * 4;
+      stash_x_split<decltype(scaled_c)::value>(px[set][ii], xe[ii], xmax[ii], &s_xh[at], &s_xl[at]);
     });
     static_for<0, NW8>([&](auto i) __attribute__((always_inline)) {
       constexpr int ii = decltype(i)::value;
@@ -582,63 +548,27 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
     });
   };
 
-  f32x16 acc, acs, act;   // leading term / cross terms (x 2^11) / trailing term (x 2^22), as gemm_f16x3_kernel
-
+  SplitAcc a;
   auto multiply = [&](int buf) __attribute__((always_inline)) {
 #pragma unroll
     for (int st = 0; st < BKT / 16; ++st) {
       const int off = 16 * st + 8 * kb;  // lane (r32, kb) holds k = 16 st + 8 kb .. +7 of its x row / W row
-      const h16x8 ah = *reinterpret_cast<const h16x8*>(&s_xh[(buf * kWM + wm * 32 + r32) * LDH + off]);
-      const h16x8 al = *reinterpret_cast<const h16x8*>(&s_xl[(buf * kWM + wm * 32 + r32) * LDH + off]);
-      const h16x8 bh = *reinterpret_cast<const h16x8*>(&s_wh[(buf * kWN + wn * 32 + r32) * LDH + off]);
-      const h16x8 bl = *reinterpret_cast<const h16x8*>(&s_wl[(buf * kWN + wn * 32 + r32) * LDH + off]);
-      act = simpb::mfma_32x32x16_f16(al, bl, act);
-      acs = simpb::mfma_32x32x16_f16(al, bh, acs);
-      acs = simpb::mfma_32x32x16_f16(ah, bl, acs);
-      acc = simpb::mfma_32x32x16_f16(ah, bh, acc);
+      a.step(*reinterpret_cast<const h16x8*>(&s_xh[(buf * kWM + wm * 32 + r32) * LDH + off]),
+             *reinterpret_cast<const h16x8*>(&s_xl[(buf * kWM + wm * 32 + r32) * LDH + off]),
+             *reinterpret_cast<const h16x8*>(&s_wh[(buf * kWN + wn * 32 + r32) * LDH + off]),
+             *reinterpret_cast<const h16x8*>(&s_wl[(buf * kWN + wn * 32 + r32) * LDH + off]));
     }
   };
-
-  // chunk c lives in register set / LDS buffer c & 1: fetched two chunks ahead, stashed one barrier ahead of its product
-  auto kloop = [&](auto scaled_c) __attribute__((always_inline)) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acs[r] = 0.f; act[r] = 0.f; }
-    static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) { fetch(d, decltype(d)::value); });
-    const int pairs = nchunks / 2;
-    for (int g = 0; g < pairs; ++g) {
-      static_for<0, DEPTH>([&](auto d) __attribute__((always_inline)) {
-        stash(d, scaled_c);
-        __syncthreads();
-        fetch(d, (g + 1) * DEPTH + decltype(d)::value);
-        multiply(decltype(d)::value & 1);
-      });
-    }
-    if (nchunks & 1) {
-      stash(std::integral_constant<int, 0>{}, scaled_c);
-      __syncthreads();
-      multiply(0);
-    }
+  auto pass = [&](auto scaled_c) __attribute__((always_inline)) {
+    a.zero();
+    k_loop<DEPTH>(nchunks, fetch, [&](auto d) __attribute__((always_inline)) { stash(d, scaled_c); }, multiply);
   };
   if (tid == 0) s_any = 0;   // (ordered before any write below by the loop's barriers)
-  kloop(std::false_type{});
-#pragma unroll
-  for (int i = 0; i < NX4; ++i) {
-#pragma unroll
-    for (int m = 1; m < C4; m <<= 1) xmax[i] = fmaxf(xmax[i], __shfl_xor(xmax[i], m));
-    if (split_row_outside(xmax[i])) s_any = 1;
-  }
-  __syncthreads();
-  const bool scaled = s_any != 0;   // workgroup-uniform
-  if (scaled) {   // (s_rowexp reaches the epilogue through the second pass's barriers)
-#pragma unroll
-    for (int i = 0; i < NX4; ++i) {
-      xe[i] = split_row_exp(xmax[i]);
-      if (scx == 0) s_rowexp[srx + RSX * i] = xe[i];
-    }
-    kloop(std::true_type{});
-  }
+  pass(std::false_type{});
+  const bool scaled = simpb::split_needs_second_pass<C4>(xmax, xe, s_any, s_rowexp, srx, RSX, scx == 0);
+  if (scaled) pass(std::true_type{});
 
-  // ---- epilogue straight from the accumulators: lane (column r32, row group kb) holds rows (r & 3) + 8 (r >> 2) + 4 kb
+  // ---- epilogue straight from the accumulators: lane (column r32, row group kb)
   const float* __restrict__ bias = job.bias;
   const int gc = col0 + wn * 32 + r32;
   if (gc < N) {
@@ -646,14 +576,11 @@ __global__ __launch_bounds__(kThreads) void gemm_f16x3_wide_kernel(GemmLaunch L)
     const float b2 = job.row_flag ? job.bias2[gc] : 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int gr = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kb;
+      const int lr = wm * 32 + acc_row(r, kb), gr = row0 + lr;
       if (gr < M) {
-        float v = acc[r] + (acs[r] + act[r] * (1.f / 2048.f)) * (1.f / 2048.f);
-        if (scaled) v = __builtin_amdgcn_ldexpf(v, s_rowexp[wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kb]);
-        v += bcol;
-        if (job.row_flag && job.row_flag[gr]) v += b2;
-        if (job.relu) v = fmaxf(v, 0.f);
-        y[(size_t)gr * job.ldy + gc] = gr < live ? out_word(v, job.out_fmt) : 0.f;
+        float v = a.sum(r);
+        if (scaled) v = __builtin_amdgcn_ldexpf(v, s_rowexp[lr]);
+        finish_element(job, y, v, bcol, b2, gr, gc, live);
       }
     }
   }
@@ -701,14 +628,22 @@ __global__ __launch_bounds__(256) void layernorm_seg_kernel(float* __restrict__ 
   }
 }
 
+// tiles of tm x tn over every job of a launch; with `start`, the first tile of each job as well
+long long count_tiles(const simpb_gemm_args* args, int tm, int tn, int* start = nullptr) {
+  long long total = 0;
+  for (int j = 0; j < args->num_jobs; ++j) {
+    if (start) start[j] = (int)total;
+    total += (long long)((args->job[j].M + tm - 1) / tm) * ((args->job[j].N + tn - 1) / tn);
+  }
+  return total;
+}
+
 }  // namespace
 
 extern "C" int simpb_gemm_f32(const simpb_gemm_args* args, void* stream) {
   if (!args || args->num_jobs <= 0 || args->num_jobs > SIMPB_GEMM_MAX_JOBS) return SIMPB_EINVAL;
   GemmLaunch L;
   L.a = *args;
-  // tile width: 64 columns once that still fills the chip, 32 otherwise
-  long long tiles64 = 0;
   bool wide_k = true;  // every segment a multiple of 128 and K >= 512
   bool split = true;   // every job brings pre-split f16 weights (dense rows: ldw == K) and 128-aligned segments
   for (int j = 0; j < args->num_jobs; ++j) {
@@ -728,25 +663,15 @@ extern "C" int simpb_gemm_f32(const simpb_gemm_args* args, void* stream) {
     if (job.K < 512) wide_k = false;
     if (!job.w_hi || !job.w_lo || ((reinterpret_cast<size_t>(job.w_hi) | reinterpret_cast<size_t>(job.w_lo)) & 15)) split = false;
     if (ksum != job.K) return SIMPB_EINVAL;
-    tiles64 += (long long)((job.M + BM - 1) / BM) * ((job.N + 63) / 64);
   }
-  const int bn = tiles64 >= 200 ? 64 : 32;
+  // tile width: 64 columns once that still fills the chip, 32 otherwise
+  const int bn = count_tiles(args, BM, 64) >= 200 ? 64 : 32;
   // the 64 x 128-tile form for launches with thousands of rows (a batch of streams: 10-20 % faster there, profiles/
   // r04_gemm_wide_tiles.txt); at one stream's ~1 k rows it has at most 288 tiles and measured no faster (q|k|v 19.0 vs 18.9 us)
   // or slower (fc1 17.3 vs 12.6 us: 120 tiles leave half the chip idle), so the switch-over sits above those
-  long long tiles_wide = 0;
-  for (int j = 0; j < args->num_jobs; ++j)
-    tiles_wide += (long long)((args->job[j].M + kWM - 1) / kWM) * ((args->job[j].N + kWN - 1) / kWN);
   constexpr long long kWideMinTiles = 400;
-  const bool wide_tiles = split && tiles_wide >= kWideMinTiles;
-  long long total = 0;
-  for (int j = 0; j < args->num_jobs; ++j) {
-    L.tile_start[j] = (int)total;
-    if (wide_tiles)
-      total += (long long)((args->job[j].M + kWM - 1) / kWM) * ((args->job[j].N + kWN - 1) / kWN);
-    else
-      total += (long long)((args->job[j].M + BM - 1) / BM) * ((args->job[j].N + bn - 1) / bn);
-  }
+  const bool wide_tiles = split && count_tiles(args, kWM, kWN) >= kWideMinTiles;
+  const long long total = wide_tiles ? count_tiles(args, kWM, kWN, L.tile_start) : count_tiles(args, BM, bn, L.tile_start);
   if (total > (1 << 24)) return SIMPB_EINVAL;
   for (int j = args->num_jobs; j <= SIMPB_GEMM_MAX_JOBS; ++j) L.tile_start[j] = (int)total;
   L.per_xcd = (int)((total + 7) / 8);

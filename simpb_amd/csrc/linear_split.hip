@@ -69,18 +69,16 @@ __global__ __launch_bounds__(kThreads) void linear_f16x3_kernel(float* __restric
       pwl[i] = *reinterpret_cast<const h16x8*>(wl + wofs[i] + k0);
     }
   };
-  float xmax = 0.f;   // largest |x| this thread staged (first pass), then its row's
-  int xe = 0;         // the row's exponent (second pass)
+  float xmax[1] = {0.f};   // largest |x| this thread staged (first pass), then its row's
+  int xe[1] = {0};         // the row's exponent (second pass)
   auto stash = [&](auto scaled_c) __attribute__((always_inline)) {
     h16x8 hi, lo;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float v = e < 4 ? px[0][e] : px[1][e - 4];
-      if constexpr (decltype(scaled_c)::value) v = __builtin_amdgcn_ldexpf(v, -xe);
-      else xmax = fmaxf(xmax, fabsf(v));
-      const _Float16 h = (_Float16)v;
+      _Float16 h, l;
+      simpb::split_staged<decltype(scaled_c)::value>(e < 4 ? px[0][e] : px[1][e - 4], xe[0], xmax[0], h, l);
       hi[e] = h;
-      lo[e] = (_Float16)((v - (float)h) * 2048.f);
+      lo[e] = l;
     }
     *reinterpret_cast<h16x8*>(&s_xh[sr * LDH + sc]) = hi;
     *reinterpret_cast<h16x8*>(&s_xl[sr * LDH + sc]) = lo;
@@ -135,18 +133,9 @@ __global__ __launch_bounds__(kThreads) void linear_f16x3_kernel(float* __restric
   };
   if (tid == 0) s_any = 0;   // (ordered before any write below by the loop's barriers)
   kloop(std::false_type{});
-  xmax = fmaxf(xmax, __shfl_xor(xmax, 1));   // the 4 lanes that staged a row
-  xmax = fmaxf(xmax, __shfl_xor(xmax, 2));
-  if (simpb::split_row_outside(xmax)) s_any = 1;
-  __syncthreads();
-  const bool scaled = s_any != 0;   // workgroup-uniform
-  if (scaled) {   // (s_rowexp reaches the epilogue through the second pass's barriers)
-    xe = simpb::split_row_exp(xmax);
-    if ((tid & 3) == 0) s_rowexp[sr] = xe;
-    kloop(std::true_type{});
-  }
+  const bool scaled = simpb::split_needs_second_pass<4>(xmax, xe, s_any, s_rowexp, sr, 0, (tid & 3) == 0);   // 4 lanes staged a row
+  if (scaled) kloop(std::true_type{});
 
-  // C/D layout of the 32x32 tile: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
     const int gc = col0 + wave * 64 + n * 32 + r32;
@@ -156,7 +145,7 @@ __global__ __launch_bounds__(kThreads) void linear_f16x3_kernel(float* __restric
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int lr = wm * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kb, gr = row0 + lr;
+        const int lr = wm * 64 + m * 32 + simpb::acc_row(r, kb), gr = row0 + lr;
         if (gr < M) {
           float v = acc[m][n][r] + acs[m][n][r] * (1.f / 2048.f);
           if (scaled) v = __builtin_amdgcn_ldexpf(v, s_rowexp[lr]);
@@ -192,8 +181,8 @@ using IC = std::integral_constant<int, S>;
 
 __global__ __launch_bounds__(kThreads2, 2) void linear_h2_kernel(const Args a) {
   __shared__ __attribute__((aligned(16))) _Float16 s_ab[2 * kRows * LDHc];
-  const int tile = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= a.per_xcd || tile >= a.gx * a.gy) return;
+  const int tile = simpb::xcd_tile(a.per_xcd, a.gx * a.gy);
+  if (tile < 0) return;
   const int tx = tile / a.gy, ty = tile - tx * a.gy;   // column blocks of one row block next to each other (same XCD: x from L2)
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -272,8 +261,7 @@ __global__ __launch_bounds__(kThreads2, 2) void linear_h2_kernel(const Args a) {
     if (c + 1 < nchunks) step(IC<1>{}, IC<2>{}, c + 1);
     if (c + 2 < nchunks) step(IC<2>{}, IC<0>{}, c + 2);
   }
-  // C/D layout of the 32x32 tile: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5): a store
-  // instruction writes two whole 128-byte lines
+  // (C/D layout of the 32x32 tile, simpb::acc_row: a store instruction writes two whole 128-byte lines)
   const int gc = col0 + wn * 32 + r32;
   if (gc < a.N) {
     const float bv = a.bias ? a.bias[gc] : 0.f;
@@ -281,7 +269,7 @@ __global__ __launch_bounds__(kThreads2, 2) void linear_h2_kernel(const Args a) {
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int gr = row0 + wm * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kb;
+        const int gr = row0 + wm * 64 + m * 32 + simpb::acc_row(r, kb);
         if (gr < a.M) a.y[(size_t)gr * a.N + gc] = acc[m][r] + acs[m][r] * (1.f / 2048.f) + bv;
       }
   }

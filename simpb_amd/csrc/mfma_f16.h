@@ -36,6 +36,23 @@ __device__ __forceinline__ C16 mfma_32x32x16_f16(const A8& a, const A8& b, const
 #endif
 }
 
+// C/D layout of the 32x32 tile: register r of lane (column lane & 31, half = lane >> 5) holds this row
+__device__ __forceinline__ constexpr int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// Workgroups are numbered so that each XCD (blockIdx.x % 8) walks a contiguous range of `per_xcd` tiles: neighbouring
+// tiles share operand rows in that XCD's L2. The tile of this workgroup, or -1 past the last of `total`.
+__device__ __forceinline__ int xcd_tile(int per_xcd, int total) {
+  const int tile = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  return ((int)(blockIdx.x >> 3) >= per_xcd || tile >= total) ? -1 : tile;
+}
+
+// THE split of the split-operand kernels: s = h + l / 2^11. The trailing part is kept scaled by 2^11 so that it stays a
+// normal half (no dependence on how the matrix pipe treats fp16 subnormals). plugin/dense.py _split_weights is its host twin.
+__device__ __forceinline__ void split_halfs(float s, _Float16& h, _Float16& l) {
+  h = (_Float16)s;
+  l = (_Float16)((s - (float)h) * 2048.f);
+}
+
 // Range window of the split operands x = half(x) + half((x - half(x)) * 2^11) / 2^11 (csrc/gemm.hip, csrc/linear_split.hip):
 // a row whose largest |x| lies in [2^-10, 2^15) (or is 0) splits to 22 bits as it is; any other finite row is staged as
 // x * 2^-e with e = split_row_exp, and its sum multiplied by 2^e. (NaN / inf: nothing to gain, e = 0.)
@@ -44,6 +61,41 @@ __device__ __forceinline__ bool split_row_outside(float m) {   // m = largest |x
 }
 __device__ __forceinline__ int split_row_exp(float m) {
   return split_row_outside(m) ? __builtin_amdgcn_frexp_expf(m) - 1 : 0;   // m * 2^-e in [1, 2)
+}
+
+// One element of x while it is staged. First pass (kScaled = false): split as it is and collect the largest |x| of the
+// row in `xmax`; second pass: split x * 2^-e, e the row's exponent.
+template <bool kScaled>
+__device__ __forceinline__ void split_staged(float s, int e, float& xmax, _Float16& h, _Float16& l) {
+  if constexpr (kScaled) s = __builtin_amdgcn_ldexpf(s, -e);
+  else xmax = fmaxf(xmax, fabsf(s));
+  split_halfs(s, h, l);
+}
+
+// After the first pass: does this workgroup need the second one? Each thread staged NR rows (tile rows row + step * i),
+// LANES consecutive lanes of a wave sharing a row; they meet on the row's largest |x|. The flag is a plain LDS word
+// (zeroed before the first pass, whose barriers order that) behind a barrier the epilogue needs anyway. When a row lies
+// outside the window, every row's exponent goes to `xe` and, from the lane with `writer`, to s_rowexp; it reaches the
+// epilogue through the second pass's barriers. The answer is workgroup-uniform.
+template <int LANES, int NR>
+__device__ __forceinline__ bool split_needs_second_pass(float (&xmax)[NR], int (&xe)[NR], int& s_any, int* s_rowexp,
+                                                        int row, int step, bool writer) {
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+#pragma unroll
+    for (int m = 1; m < LANES; m <<= 1) xmax[i] = fmaxf(xmax[i], __shfl_xor(xmax[i], m));
+    if (split_row_outside(xmax[i])) s_any = 1;
+  }
+  __syncthreads();
+  const bool scaled = s_any != 0;
+  if (scaled) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      xe[i] = split_row_exp(xmax[i]);
+      if (writer) s_rowexp[row + step * i] = xe[i];
+    }
+  }
+  return scaled;
 }
 
 }  // namespace simpb

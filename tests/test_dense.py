@@ -109,6 +109,10 @@ def _ref(xs, w, b, relu):
     (1536, 384, [256, 256], False, True),        # MSDA offsets|weights
     (33, 100, [64], True, False),                # ragged everything, single chunk
     (65, 70, [64, 64, 64, 64], False, True),     # four segments
+    # K-loop tails (the exact kernel unless noted):
+    (33, 100, [64, 128], True, False),           # depth 4, 3 chunks: no full group, remainder 3, segment boundary in the tail
+    (900, 512, [64, 128], False, True),          # depth 2, 64-wide tiles, 3 chunks: one group and a remainder of 1
+    (900, 256, [384, 256], False, True),         # depth 2, 128-deep chunks (both routes), 5 chunks: two groups + 1, boundary on chunk 3
 ])
 @pytest.mark.parametrize("split", [False, True], ids=["fp32", "split_fp16"])
 def test_gemm_vs_float64(m, n, ks, relu, bias, split):
