@@ -596,7 +596,8 @@ int simpb_bank_cache_streams_active(float* confidence, float* cached_feature, fl
 
 /* Fixed-shape detection records of SparseBox3DDecoder.decode_with2d (models/detection3d/decoder.py:124-252).
  * 3D (:133-167 with squeezed classes + decode_box :23-34), one workgroup per sample:
- *   score = max_c sigmoid(cls); the num_output best anchors; re-scored by sigmoid(quality[..., 0]) (quality
+ *   score = max_c sigmoid(cls), label = the first class whose fp32 sigmoid reaches it (torch.max on the sigmoids: not the
+ *   argmax of the logits where two of them saturate); the num_output best anchors; re-scored by sigmoid(quality[..., 0]) (quality
  *   may be NULL) and sorted again; rec3d f32 [bs, num_output, SIMPB_RECORD3D_WIDTH = 15] = x y z exp(w) exp(l) exp(h)
  *   atan2(sin, cos) vx vy vz | score | label | score before the re-score | the int64 instance id (or -1) as two
  *   32-bit lanes, low dword first, bit-cast into columns 13 and 14 (read them back through an int64 view: the
@@ -658,7 +659,8 @@ typedef struct simpb_world_tables {
 int simpb_world_record(double* world, int* count, const float* rec3d, const double* pose, const unsigned char* active,
                        simpb_world_tables tables, int num_streams, void* stream);
 
-/* Top-k of each score row, sorted descending (ties: lower index first): values f32 [bs, k], indices
+/* Top-k of each score row, sorted descending (ties: lower index first; -0.0 ties with +0.0, and the values
+ * returned are the input's own bits): values f32 [bs, k], indices
  * i32 [bs, k] from scores f32 [bs, n], n <= 2048, k <= n. What `topk` of models/instance_bank.py:13-20
  * and the ranking of SparseBox3DDecoder.decode (models/detection3d/decoder.py:145-167) ask of torch.topk /
  * torch.sort; one launch, one workgroup per row. */

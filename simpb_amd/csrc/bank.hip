@@ -41,7 +41,7 @@ __device__ __forceinline__ void bitonic_desc(unsigned long long* key, int tid) {
 __device__ __forceinline__ float row_max(const float* row, int C) {
   float m = row[0];
   for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
-  return m;
+  return m == 0.f ? 0.f : m;  // one zero: a raw -0.0 ranks with +0.0 (bank_update_rank), the lower index first
 }
 
 // ---- get (:83-113): one thread per cached anchor + one per stream for the mask / time step

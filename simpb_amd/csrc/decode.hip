@@ -13,6 +13,19 @@ namespace {
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
+// decoder.py:141-144 / :215: cls.sigmoid().max(-1) -- the best class SCORE and the first class that reaches it. The argmax
+// of the logits is not that class: two different logits can round to one sigmoid (every logit >= 17 gives exactly 1.0f),
+// and then the reference keeps the lower column.
+__device__ __forceinline__ float best_class(const float* row, int C, int& arg) {
+  float m = sigmoidf(row[0]);
+  arg = 0;
+  for (int c = 1; c < C; ++c) {
+    const float s = sigmoidf(row[c]);
+    if (s > m) { m = s; arg = c; }
+  }
+  return m;
+}
+
 __device__ __forceinline__ unsigned long long sort_key(float v, unsigned idx) {
   unsigned u = __float_as_uint(v);
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone map float -> uint
@@ -52,12 +65,10 @@ __global__ __launch_bounds__(512) void decode3d_kernel(float* __restrict__ rec3d
     unsigned long long kv = 0ull;
     if (a < A) {
       const float* row = cls + ((size_t)b * A + a) * C;
-      float m = row[0];
-      int arg = 0;
-      for (int c = 1; c < C; ++c)
-        if (row[c] > m) { m = row[c]; arg = c; }
+      int arg;
+      const float m = best_class(row, C, arg);
       label[a] = arg;
-      kv = sort_key(sigmoidf(m), (unsigned)a);  // max of sigmoids = sigmoid of the max (monotone)
+      kv = sort_key(m, (unsigned)a);
       rank_of_anchor[(size_t)b * A + a] = -1;
     }
     key[a] = kv;
@@ -124,10 +135,8 @@ __global__ __launch_bounds__(256) void decode2d_kernel(float* __restrict__ rec2d
   if (i >= bs * N2) return;
   const int b = i / N2, slot = i - b * N2;
   const float* row = cls2d + (size_t)i * C;
-  float m = row[0];
-  int arg = 0;
-  for (int c = 1; c < C; ++c)
-    if (row[c] > m) { m = row[c]; arg = c; }
+  int arg;
+  const float m = best_class(row, C, arg);
   const float* bx = box2d + (size_t)i * 4;
   const float cx = bx[0], cy = bx[1], w = bx[2], h = bx[3];
   float r[8];
@@ -135,7 +144,7 @@ __global__ __launch_bounds__(256) void decode2d_kernel(float* __restrict__ rec2d
   r[1] = (fminf(fmaxf((cy - 0.5f * h) * crop_h, 0.f), crop_h) + crop_y0) * inv_resize;
   r[2] = fminf(fmaxf((cx + 0.5f * w) * crop_w, 0.f), crop_w) * inv_resize;
   r[3] = (fminf(fmaxf((cy + 0.5f * h) * crop_h, 0.f), crop_h) + crop_y0) * inv_resize;
-  r[4] = sigmoidf(m);
+  r[4] = m;
   r[5] = (float)arg;
   const int a = q2a[i];
   r[6] = (a >= 0 && a < A) ? (float)rank_of_anchor[(size_t)b * A + a] : -1.f;
@@ -167,10 +176,8 @@ __global__ __launch_bounds__(256) void decode2d_ragged_kernel(float* __restrict_
   const bool live = lo + r_in < hi;
   const int j = live ? lo + r_in : 0;   // (slot 0 is readable whenever anything is: clamped loads, zero-weighted below)
   const float* row = cls2d + (size_t)j * C;
-  float m = row[0];
-  int arg = 0;
-  for (int c = 1; c < C; ++c)
-    if (row[c] > m) { m = row[c]; arg = c; }
+  int arg;
+  const float m = best_class(row, C, arg);
   const float* bx = box2d + (size_t)j * 4;
   const float cx = bx[0], cy = bx[1], w = bx[2], h = bx[3];
   float r[8];
@@ -178,7 +185,7 @@ __global__ __launch_bounds__(256) void decode2d_ragged_kernel(float* __restrict_
   r[1] = (fminf(fmaxf((cy - 0.5f * h) * crop_h, 0.f), crop_h) + crop_y0) * inv_resize;
   r[2] = fminf(fmaxf((cx + 0.5f * w) * crop_w, 0.f), crop_w) * inv_resize;
   r[3] = (fminf(fmaxf((cy + 0.5f * h) * crop_h, 0.f), crop_h) + crop_y0) * inv_resize;
-  r[4] = sigmoidf(m);
+  r[4] = m;
   r[5] = (float)arg;
   const int a = q2a[j];
   r[6] = (a >= 0 && a < bs * A) ? (float)rank_of_anchor[a] : -1.f;

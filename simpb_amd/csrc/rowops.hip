@@ -130,7 +130,8 @@ __global__ __launch_bounds__(CAP / 2) void topk_rows_kernel(float* __restrict__ 
   for (int i = tid; i < CAP; i += CAP / 2) {
     unsigned long long kv = 0ull;  // padding sorts last
     if (i < n) {
-      unsigned u = __float_as_uint(row[i]);
+      const float v = row[i];
+      unsigned u = v == 0.f ? 0u : __float_as_uint(v);  // -0.0 ties with +0.0 (the lower index wins, as for any equal pair)
       u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone map float -> uint
       kv = ((unsigned long long)u << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
     }
@@ -148,11 +149,13 @@ __global__ __launch_bounds__(CAP / 2) void topk_rows_kernel(float* __restrict__ 
     }
   }
   for (int i = tid; i < k; i += CAP / 2) {
-    const unsigned long long kv = key[i];
-    unsigned u = (unsigned)(kv >> 32);
-    u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-    val_out[(size_t)b * k + i] = __uint_as_float(u);
-    idx_out[(size_t)b * k + i] = (int)(0xFFFFFFFFu - (unsigned)(kv & 0xFFFFFFFFull));
+    const unsigned idx = 0xFFFFFFFFu - (unsigned)(key[i] & 0xFFFFFFFFull);
+    float v = row[idx];  // the input's own bits (the key does not keep the sign of a zero)
+    simpb::pin(v);
+    simpb::loads_retired();  // store_fence.h
+    val_out[(size_t)b * k + i] = v;
+    idx_out[(size_t)b * k + i] = (int)idx;
+    simpb::stores_retired();  // a second trip (k > CAP / 2) starts with nothing of this one in flight
   }
 }
 
