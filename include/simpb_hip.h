@@ -391,19 +391,35 @@ int simpb_conv1x1_nhwc_f16(void* y, const void* x, const void* weight, const voi
  *          token form; all three NULL is SIMPB_EINVAL.
  * These are conv2 of every ResNet bottleneck and FPN.fpn_convs (mmdet ResNet + FPN of
  * projects/configs/simpb_nus_r50_img_704x256.py:79-99 after tools/fuse_conv_bn.py:10-48). stride 1 or 2;
- * in_channels % 64 == 0, out_channels % 8 == 0; 16-byte aligned. variant 0 = choose the tiling from the shape; 1-11 force one
+ * in_channels % 64 == 0, out_channels % 8 == 0; 16-byte aligned. variant 0 = choose the tiling from the shape; 1-13 force one
  * (pixels x channels per workgroup: 1 = 128 x 64 and 2 = 256 x 64 with the activations read straight into the MFMA layout;
  * 3 = 32 x 64 and 4 = 64 x 64 with K split over the workgroup's waves; 5 = 128 x 64, 6 = 128 x 128, 7 = 96 x 64,
  * 8 = 96 x 128 and 9 = 64 x 64 with both operands staged through LDS; 10 / 11 = 64 x 64 staged with K split over 2 / 4
  * groups of four waves, the partial sums added in group order) -- all give the same sums up to fp32 summation order, each
- * in a fixed order; 9 adds in the order of 1 and 2, 11 in the order of 3 and 4: the same bits. */
+ * in a fixed order; 9 adds in the order of 1 and 2, 11 in the order of 3 and 4: the same bits.
+ * 12 / 13 = the resident form: a workgroup keeps its 2-D tile of input pixels with the one-pixel halo, all in_channels, in
+ * LDS and reads the nine taps as addresses into it (rows x columns of output pixels x channels: 12 = 4 x 16 x 64 with four
+ * waves, 13 = 8 x 16 x 128 with eight); stride 1 and in_channels 64, 128 or 256 only, SIMPB_EINVAL otherwise. They add in the
+ * order of 5-8: the same bits. */
 int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, int tokens_per_cam, int level_start, const void* x,
                            const void* weight, const void* bias, int num_images, int in_h, int in_w, int in_channels,
                            int out_channels, int stride, int relu, int variant, void* stream);
 
-/* The tiling (1-11) that simpb_conv3x3_nhwc_f16 runs under variant 0 for p_out = num_images * out_h * out_w output pixels.
+/* The tiling (1-11) that simpb_conv3x3_nhwc_f16 runs under variant 0 for p_out = num_images * out_h * out_w output pixels
+ * (where the answer is 7 or 8, variant 0 then asks simpb_conv3x3_choose_resident below).
  * A pure function of its arguments: nothing is launched and no device is needed. */
 int simpb_conv3x3_choose_variant(long long p_out, int in_channels, int out_channels);
+
+/* Where simpb_conv3x3_choose_variant answers 7 or 8, variant 0 asks this second rule whether the resident form measured
+ * faster on the shape: the resident variant (12 or 13) it then runs instead, or 0 for "stay". 0 as well wherever the first
+ * rule answers anything else, for stride 2, for in_channels other than 64, 128, 256 and for out_channels != in_channels
+ * (nothing else was measured). A pure function of its arguments. */
+int simpb_conv3x3_choose_resident(long long p_out, int in_h, int in_w, int in_channels, int out_channels, int stride);
+
+/* The same for simpb_conv3x3_group_tokens_f16, asked once for the whole launch: 13 = every level runs the resident
+ * 8 x 16 x 128 form, 0 = every level runs the staged 96 x 128 tiles. */
+int simpb_conv3x3_group_choose_resident(int num_levels, int num_images, const int* in_h, const int* in_w, int in_channels,
+                                        int out_channels);
 
 /* The same 3x3 / stride 1 convolution for up to four inputs of one channel count in ONE launch, each result written as its
  * level's token rows (f32 `tokens`, and f16 `tokens_f16` or NULL; or tokens == NULL and the f16 rows alone) exactly as
@@ -411,10 +427,19 @@ int simpb_conv3x3_choose_variant(long long p_out, int in_channels, int out_chann
  * the four `fpn_convs[i].conv` of mmdet's FPN (projects/configs/simpb_nus_r50_img_704x256.py:92-99) behind
  * feature_maps_format (ops/__init__.py:63-92). x[j] f16 NHWC [num_images, in_h[j], in_w[j], Cin]; weight[j] f16
  * [Cout, 3, 3, Cin]; bias[j] f16 [Cout]; level_start[j] = the level's first row inside a camera's tokens_per_cam rows.
- * 96 x 128 staged tiles for every level (tiling 8 above): the small levels' tiles fill the last round of the large one. */
+ * One tile form for every level (simpb_conv3x3_group_choose_resident: 96 x 128 staged tiles, tiling 8 above, or the resident
+ * tiling 13): the small levels' tiles fill the last round of the large one. */
 int simpb_conv3x3_group_tokens_f16(int num_levels, float* tokens, void* tokens_f16, int tokens_per_cam, const int* level_start,
                                    const void* const* x, const void* const* weight, const void* const* bias, int num_images,
                                    const int* in_h, const int* in_w, int in_channels, int out_channels, int relu, void* stream);
+
+/* The same with the form of every level given: variant[j] = 8 (the 96 x 128 staged tiles) or 13 (the resident 8 x 16 x 128
+ * tiles; in_channels 64, 128 or 256); variant == NULL is what simpb_conv3x3_group_tokens_f16 runs. The levels of one form
+ * share a launch, so mixed forms are two launches; the rows are the same bits whatever the forms. */
+int simpb_conv3x3_group_tokens_forms_f16(int num_levels, float* tokens, void* tokens_f16, int tokens_per_cam,
+                                         const int* level_start, const void* const* x, const void* const* weight,
+                                         const void* const* bias, int num_images, const int* in_h, const int* in_w,
+                                         int in_channels, int out_channels, int relu, const int* variant, void* stream);
 
 /* Attention core of torch.nn.MultiheadAttention (between in_proj and out_proj), exact fp32, flash
  * style, head_dim = 64: out[b,q,h*64+d] = sum_k softmax_k(scale * Q[b,q,h,:].K[b,k,h,:]) V[b,k,h,d].

@@ -42,6 +42,9 @@ SIGNATURES = {
     "simpb_conv3x3_nhwc_f16": ([_P, _P, _P, _I, _I, _P, _P, _P] + [_I] * 8 + [_P], _I),
     "simpb_conv3x3_choose_variant": ([_LL, _I, _I], _I),
     "simpb_conv3x3_group_tokens_f16": ([_I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P], _I),
+    "simpb_conv3x3_choose_resident": ([_LL, _I, _I, _I, _I, _I], _I),
+    "simpb_conv3x3_group_choose_resident": ([_I, _I, _P, _P, _I, _I], _I),
+    "simpb_conv3x3_group_tokens_forms_f16": ([_I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P], _I),
     "simpb_stem_conv7x7_pool_f16": ([_P] * 4 + [_I] * 4 + [_P], _I),
     "simpb_image_to_nhwc4_f16": ([_P, _P] + [ctypes.c_longlong] * 4 + [_I] * 4 + [_P], _I),
     "simpb_preprocess_u8_nhwc4_f16": ([_P] * 10 + [_I] * 11 + [_P], _I),

@@ -23,6 +23,8 @@
 //    M = 1 056 pixels (8 x 22 x 6 cameras) still yields 264 workgroups.
 // Both direct forms are bound by their load instructions (32 lines each); with Cin >= 256 the small maps run the staged
 // pipeline below at 64 x 64, K split over groups of waves inside the workgroup where the grid is small (KS).
+// The large maps run the staged pipeline, and at stride 1 with Cin 64 / 128 / 256 its resident form: the 2-D tile of input
+// pixels with its halo goes to LDS once and the taps are addresses into it (conv_resident_tile, further below).
 // FP16 matrix step = two v_mfma_f32_32x32x8f16 (csrc/mfma_f16.h; never the gfx950 double-K instruction).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -55,6 +57,7 @@ struct ConvArgs {
   int P_out, Cin, Cout, relu, stride, Ho, Wo, H, W;
   int tokens_per_cam, level_start;
   int gx, gy, per_xcd;    // tile grid and tiles per XCD range
+  int tiles_w, tiles_h;   // resident form: 2-D tiles across and down one image (gx = images x tiles_h x tiles_w)
 };
 
 template <int S>
@@ -609,6 +612,312 @@ void launch_staged_ksplit(ConvArgs& a, hipStream_t stream) {
                      dim3(64 * WGM * WGN * KS), 0, stream, a);
 }
 
+// ---- large maps, stride 1: the input tile stays in LDS (3x3 variants 12, 13) --------------------------------------------------
+// The staged pipeline above stages the A tile once per chunk: nine taps x Cin / 64 times the same pixels, shifted by one tap.
+// Here a workgroup owns a 2-D tile of TH x 16 output pixels of ONE image (clipped at the image's border) and loads the
+// (TH + 2) x 18 input pixels under it, all Cin channels, into LDS once, with the same coalesced 16-byte loads (8 lanes per 128
+// bytes of a pixel's row); a pixel outside the image is written as zeros -- that is the padding, there are no per-tap masks.
+// A tap is then an address: fragment row r32 of a wave is output pixel (2 * fragment + r32 / 16, r32 % 16) of the tile, and
+// tap (dy, dx) reads input pixel (row + dy, column + dx) of the halo. Only the 64-channel weight chunks still go through an
+// LDS stage, one barrier per chunk as before (1 + 9 * Cin / 64 per tile of 128 pixels, the count of the 96-pixel staged tile).
+//  * All loads of the halo are issued at once, 64 channels (what one chunk reads) per slice; slice 0 is written to LDS in
+//    front of the first barrier, slice s > 0 during chunk s - 1: the first Cin / 64 chunks run while the rest is in flight.
+//  * The weight stage is a ring of THREE chunks: chunk c + 2 is written during chunk c, so chunk c + 1 is complete and
+//    visible while chunk c runs, and a wave reads its first operands of chunk c + 1 (weights and, resident anyway, pixels)
+//    BEFORE the barrier that ends chunk c -- after the barrier the matrix pipe goes on at once instead of waiting for LDS.
+// LDS image: a pixel's channels at a pitch of 2 * Cin + 16 bytes (an odd number of 16-byte slots, like the 144 bytes of the
+// weight stage) and a halo row at a pitch that is a multiple of 256 bytes. ds_read_b128 serves lanes {0-3, 12-15, 20-27} in
+// one cycle and {4-11, 16-19, 28-31} in the next: each group is eight pixels of one tile row and the OTHER eight columns of
+// the next row, so with the row pitch a multiple of the 256-byte bank row the sixteen lanes hit sixteen different slots --
+// that is how the jump at the end of a tile row is handled (a plain 18-pixel row pitch would put two pairs of them on one
+// slot). Taps shift every lane by the same amount and keep that.
+// Every output element receives what conv_staged_tile<.., DIRECTK = false> gives it: tap-major, then 64-channel chunk, then
+// four 16-deep steps of two v_mfma_f32_32x32x8f16, lane half kb bringing halfs [16 j + 8 kb, + 8) of the chunk, zero operands
+// outside the image, one accumulator per 32 x 32 fragment -- the same bits as variants 5-8.
+constexpr int RTW = 16, RHW = RTW + 2;   // output pixels across a tile; input pixels across its halo
+constexpr int resident_row_bytes(int cin) { return (RHW * (2 * cin + 16) + 255) & ~255; }
+
+template <int CIN, int TH, int BNt, int WGM, int WGN, int RING>
+constexpr size_t resident_lds() {
+  const size_t run = (size_t)(TH + 2) * resident_row_bytes(CIN) + RING * BNt * LDH * 2;   // halo + the weight ring
+  const size_t tile = (size_t)WGM * WGN * 32 * (BNt / WGN + 1) * 4;                    // the waves' fp32 epilogue tiles
+  return run > tile ? run : tile;
+}
+
+template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
+__device__ __forceinline__ void conv_resident_tile(const ConvArgs& a, const int tile, unsigned char* smem) {
+  constexpr int NT = 64 * WGM * WGN;
+  constexpr int AF = TH * RTW / WGM / 32, NF = BNt / WGN / 32;
+  static_assert(AF * WGM * 32 == TH * RTW && NF * WGN * 32 == BNt && NF <= 2, "tile = waves x 32-row / 32-column fragments");
+  static_assert(CIN == 64 || CIN == 128 || CIN == 256, "the whole Cin is resident");
+  static_assert(RING == 2 || RING == 3, "weight chunks in LDS");
+  constexpr int D = RING - 1;                   // chunk c + D is written to the ring during chunk c
+  constexpr int PT = CIN / BK, NCH = 9 * PT;    // chunks per tap (= halo slices) and in all
+  constexpr int HEAD = PT <= 2 ? 3 : 6;         // chunks in front of the loop: a multiple of 3 that covers the slices
+  constexpr int NB = (BNt * 8 + NT - 1) / NT;   // staged 16-byte weight pieces per thread and chunk
+  constexpr int LDW = 32 * NF + 1;
+  constexpr int HP = (TH + 2) * RHW;            // pixels of the halo tile
+  constexpr int NH = (HP * 8 + NT - 1) / NT;    // 16-byte pieces per thread and slice
+  constexpr int PIX = 2 * CIN + 16, ROW = resident_row_bytes(CIN);
+  constexpr int WBUF = BNt * LDH;               // halfs of one weight chunk
+  _Float16* s_b = reinterpret_cast<_Float16*>(smem + (TH + 2) * ROW);
+  float* s_c = reinterpret_cast<float*>(smem);
+  const int W = a.W, H = a.H;
+
+  const int tx = tile / a.gy, ty = tile - tx * a.gy;
+  const int per_img = a.tiles_w * a.tiles_h;
+  const int img = tx / per_img, t2 = tx - img * per_img;
+  const int trow = t2 / a.tiles_w;
+  const int y0 = trow * TH, x0 = (t2 - trow * a.tiles_w) * RTW;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int r32 = lane & 31, kb = lane >> 5;
+  const int wm = wave / WGN, wn = wave - wm * WGN;
+  const int c0 = ty * BNt;
+  constexpr size_t K = (size_t)9 * CIN;
+  const _Float16* __restrict__ wgt = a.w;
+  const h16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+
+  const int sc = (tid & 7) * 8;
+  size_t brow[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) brow[i] = (size_t)min(c0 + ((tid + NT * i) >> 3), a.Cout - 1) * K + sc;
+  h16x8 rb[3][NB];   // set s: a chunk = s (mod 3) on its way to the ring
+  auto fetch = [&](auto set_c, int chunk) __attribute__((always_inline)) {
+    constexpr int s = decltype(set_c)::value;
+    const size_t koff = (size_t)min(chunk, NCH - 1) * BK;   // [Cout][3][3][Cin]: chunk c is halfs [64 c, 64 c + 64) of a row
+#pragma unroll
+    for (int i = 0; i < NB; ++i) rb[s][i] = *reinterpret_cast<const h16x8*>(wgt + brow[i] + koff);
+  };
+  auto stash = [&](auto set_c, int buf) __attribute__((always_inline)) {
+    constexpr int s = decltype(set_c)::value;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int idx = tid + NT * i;
+      if ((BNt * 8) % NT == 0 || idx < BNt * 8) *reinterpret_cast<h16x8*>(&s_b[buf * WBUF + (idx >> 3) * LDH + sc]) = rb[s][i];
+    }
+  };
+
+  fetch(IC<0>{}, 0);
+  fetch(IC<1>{}, 1);
+  fetch(IC<2>{}, 2);
+  // the halo tile: piece i of this thread is pixel (tid + NT * i) / 8 of the halo, 16 bytes of each 64-channel slice
+  h16x8 hv[PT][NH];
+  {
+    const _Float16* __restrict__ src = a.x + (size_t)img * H * W * CIN;
+#pragma unroll
+    for (int i = 0; i < NH; ++i) {
+      const int idx = tid + NT * i;
+      const int hp = idx >> 3;
+      const int hy = hp / RHW, hx = hp - hy * RHW;
+      const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
+      const bool in = ((HP * 8) % NT == 0 || idx < HP * 8) && iy >= 0 && iy < H && ix >= 0 && ix < W;
+      const _Float16* from = src + ((size_t)iy * W + ix) * CIN + sc;
+#pragma unroll
+      for (int s = 0; s < PT; ++s) {
+        hv[s][i] = zero;
+        if (in) hv[s][i] = *reinterpret_cast<const h16x8*>(from + s * BK);
+      }
+    }
+  }
+  auto halo_to_lds = [&](auto slice_c) __attribute__((always_inline)) {
+    constexpr int s = decltype(slice_c)::value;
+#pragma unroll
+    for (int i = 0; i < NH; ++i) {
+      const int idx = tid + NT * i;
+      const int hp = idx >> 3;
+      const int hy = hp / RHW, hx = hp - hy * RHW;
+      if ((HP * 8) % NT == 0 || idx < HP * 8) *reinterpret_cast<h16x8*>(smem + hy * ROW + hx * PIX + s * (2 * BK) + 2 * sc) = hv[s][i];
+    }
+  };
+  __builtin_amdgcn_sched_barrier(0);
+  stash(IC<0>{}, 0);
+  fetch(IC<0>{}, 3);
+  if constexpr (D == 2) {
+    stash(IC<1>{}, 1);
+    fetch(IC<1>{}, 4);
+  }
+  halo_to_lds(IC<0>{});
+  __syncthreads();
+
+  f32x16 acc[AF][NF];
+#pragma unroll
+  for (int f = 0; f < AF; ++f)
+#pragma unroll
+    for (int n = 0; n < NF; ++n)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[f][n][r] = 0.f;
+
+  // this lane's pixel of fragment 0 at tap (0, 0) and its weight row, its half of a 16-deep step
+  const unsigned char* a_lane = smem + (wm * AF * 2 + (r32 >> 4)) * ROW + (r32 & 15) * PIX + 16 * kb;
+  const _Float16* b_lane = s_b + (wn * NF * 32 + r32) * LDH + 8 * kb;
+  h16x8 av[AF], bv[NF];   // the operands of the next 16-deep step
+  auto pixels = [&](int c, int ks) __attribute__((always_inline)) {
+    const int tap = c / PT, k0 = (c - tap * PT) * BK;
+    const int dy = tap / 3, dx = tap - dy * 3;
+    const unsigned char* sa = a_lane + dy * ROW + dx * PIX + 2 * k0 + 32 * ks;
+#pragma unroll
+    for (int f = 0; f < AF; ++f) av[f] = *reinterpret_cast<const h16x8*>(sa + f * 2 * ROW);
+  };
+  auto weights = [&](int c, int ks) __attribute__((always_inline)) {
+    const _Float16* sb = b_lane + (c % RING) * WBUF + 16 * ks;
+#pragma unroll
+    for (int n = 0; n < NF; ++n) bv[n] = *reinterpret_cast<const h16x8*>(sb + n * 32 * LDH);
+  };
+  // chunk c: weights in ring buffer c % RING. Register set (c + D) % 3 holds chunk c + D (requested three chunks earlier), goes
+  // to the ring and is requested again for chunk c + D + 3. `ahead`: the first operands of chunk c were read before the
+  // barrier (with a ring of two only the pixels: the chunk's weights are written while the chunk before it runs)
+  auto step = [&](auto set_c, int c, bool ahead, bool read_ahead) __attribute__((always_inline)) {
+    stash(set_c, (c + D) % RING);
+    fetch(set_c, c + D + 3);
+    if constexpr (PT > 1) {
+      if (c == 0) halo_to_lds(IC<1>{});
+    }
+    if constexpr (PT > 2) {
+      if (c == 1) halo_to_lds(IC<2>{});
+      if (c == 2) halo_to_lds(IC<3>{});
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (!ahead) pixels(c, 0);
+    if (!ahead || D == 1) weights(c, 0);
+#pragma unroll
+    for (int ks = 0; ks < BK / 16; ++ks) {
+      h16x8 ca[AF], cb[NF];
+#pragma unroll
+      for (int f = 0; f < AF; ++f) ca[f] = av[f];
+#pragma unroll
+      for (int n = 0; n < NF; ++n) cb[n] = bv[n];
+      if (ks + 1 < BK / 16) {
+        pixels(c, ks + 1);
+        weights(c, ks + 1);
+      } else if (read_ahead) {
+        pixels(min(c + 1, NCH - 1), 0);
+        if constexpr (D == 2) weights(min(c + 1, NCH - 1), 0);
+      }
+#pragma unroll
+      for (int f = 0; f < AF; ++f)
+#pragma unroll
+        for (int n = 0; n < NF; ++n) acc[f][n] = simpb::mfma_32x32x16_f16(ca[f], cb[n], acc[f][n]);
+    }
+    __syncthreads();
+  };
+  // in front of the loop: chunk c < PT reads a slice written during chunk c - 1, so nothing of it can be read ahead
+  using S0 = IC<D % 3>;
+  using S1 = IC<(D + 1) % 3>;
+  using S2 = IC<(D + 2) % 3>;
+  step(S0{}, 0, false, 1 >= PT);
+  step(S1{}, 1, 1 >= PT, 2 >= PT);
+  step(S2{}, 2, 2 >= PT, 3 >= PT);
+  if constexpr (HEAD == 6) {
+    step(S0{}, 3, 3 >= PT, true);
+    step(S1{}, 4, true, true);
+    step(S2{}, 5, true, true);
+  }
+  for (int c = HEAD; c < NCH; c += 3) {
+    step(S0{}, c, true, true);
+    step(S1{}, c + 1, true, true);
+    step(S2{}, c + 2, true, true);
+  }
+
+  // epilogue as in conv_staged_tile, the wave's fp32 tile over the halo (nobody reads it after the last barrier)
+  float* mine = s_c + wave * 32 * LDW;
+  const int cw = c0 + wn * NF * 32;
+  const bool full = cw + 32 * NF <= a.Cout;
+#pragma unroll
+  for (int f = 0; f < AF; ++f) {
+    if (f) __syncthreads();
+#pragma unroll
+    for (int n = 0; n < NF; ++n)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * kb) * LDW + n * 32 + r32] = acc[f][n][r];
+    __syncthreads();
+    constexpr int PR = 4 * NF;
+#pragma unroll
+    for (int pass = 0; pass < 32 * PR / 64; ++pass) {
+      const int idx = lane + 64 * pass;
+      const int r = idx / PR, c8 = (idx % PR) * 8;
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = mine[r * LDW + c8 + e];
+      const int oy = y0 + (wm * AF + f) * 2 + (r >> 4), ox = x0 + (r & 15);
+      const int p = oy < H && ox < W ? (img * H + oy) * W + ox : a.P_out;   // a clipped tile: nothing to write
+      emit_piece<TOK16>(a, cw, full, p, c8, v);
+    }
+  }
+}
+
+template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
+__global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_kernel(const ConvArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char resident_smem[];
+  const int tile = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
+  if ((int)(blockIdx.x >> 3) >= a.per_xcd || tile >= a.gx * a.gy) return;
+  conv_resident_tile<CIN, TH, BNt, WGM, WGN, RING, TOK16>(a, tile, resident_smem);
+}
+
+template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
+__global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_group_kernel(const ConvGroup g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char resident_smem[];
+  const int gt = (blockIdx.x & 7) * g.per_xcd + (blockIdx.x >> 3);
+  if ((int)(blockIdx.x >> 3) >= g.per_xcd || gt >= g.start[g.n]) return;
+  int j = 0;
+#pragma unroll
+  for (int t = 1; t < kMaxConvGroup; ++t)
+    if (t < g.n && gt >= g.start[t]) j = t;
+  conv_resident_tile<CIN, TH, BNt, WGM, WGN, RING, TOK16>(g.a[j], gt - g.start[j], resident_smem);
+}
+
+inline bool resident_shape(int cin, int stride) { return stride == 1 && (cin == 64 || cin == 128 || cin == 256); }
+
+// the tile grid of the resident form: whole 2-D tiles per image, channel blocks of one tile next to each other
+template <int TH, int BNt>
+void resident_grid(ConvArgs& a) {
+  a.tiles_w = (a.Wo + RTW - 1) / RTW;
+  a.tiles_h = (a.Ho + TH - 1) / TH;
+  a.gx = a.P_out / (a.Ho * a.Wo) * a.tiles_w * a.tiles_h;
+  a.gy = (a.Cout + BNt - 1) / BNt;
+}
+
+// a kernel is allowed its dynamic LDS (more than 64 KB where Cin = 256) once
+template <typename KernelT>
+bool allow_resident_lds(KernelT kernel, size_t bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
+
+template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
+void launch_resident_cin(ConvArgs& a, hipStream_t stream) {
+  constexpr size_t lds = resident_lds<CIN, TH, BNt, WGM, WGN, RING>();
+  auto kernel = conv_resident_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>;
+  static const bool allowed = allow_resident_lds(kernel, lds);
+  (void)allowed;
+  resident_grid<TH, BNt>(a);
+  const long long total = (long long)a.gx * a.gy;
+  a.per_xcd = (int)((total + 7) / 8);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(a.per_xcd * 8)), dim3(64 * WGM * WGN), lds, stream, a);
+}
+
+template <int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
+void launch_resident(ConvArgs& a, hipStream_t stream) {
+  if (a.Cin == 64) launch_resident_cin<64, TH, BNt, WGM, WGN, RING, TOK16>(a, stream);
+  else if (a.Cin == 128) launch_resident_cin<128, TH, BNt, WGM, WGN, RING, TOK16>(a, stream);
+  else launch_resident_cin<256, TH, BNt, WGM, WGN, RING, TOK16>(a, stream);
+}
+
+template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
+void launch_resident_group_cin(const ConvGroup& g, hipStream_t stream) {
+  constexpr size_t lds = resident_lds<CIN, TH, BNt, WGM, WGN, RING>();
+  auto kernel = conv_resident_group_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>;
+  static const bool allowed = allow_resident_lds(kernel, lds);
+  (void)allowed;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(g.per_xcd * 8)), dim3(64 * WGM * WGN), lds, stream, g);
+}
+
+template <int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
+void launch_resident_group(const ConvGroup& g, hipStream_t stream) {
+  if (g.a[0].Cin == 64) launch_resident_group_cin<64, TH, BNt, WGM, WGN, RING, TOK16>(g, stream);
+  else if (g.a[0].Cin == 128) launch_resident_group_cin<128, TH, BNt, WGM, WGN, RING, TOK16>(g, stream);
+  else launch_resident_group_cin<256, TH, BNt, WGM, WGN, RING, TOK16>(g, stream);
+}
+
 }  // namespace
 
 // The tiling simpb_conv3x3_nhwc_f16 runs for variant 0 on p_out output pixels (no launch: tests restate the rule against it).
@@ -630,14 +939,48 @@ extern "C" int simpb_conv3x3_choose_variant(long long p_out, int in_channels, in
   return 3;
 }
 
+// Whether variant 0 runs the resident form on a shape where simpb_conv3x3_choose_variant answered 7 or 8: the resident
+// variant's number, or 0 for "keep the staged form". Yes only in the region where it measured faster on the device
+// (profiles/conv3x3_large_maps.md: 64 -> 64 and 256 -> 256 on 6 x 64 x 176, 128 -> 128 and 256 -> 256 on 6 x 32 x 88, the
+// highest of five rounds below the staged form's lowest): Cin = Cout of 64, 128 or 256, stride 1, and no fewer tiles than
+// the smallest measured launch had of its kind. It gives the same bits, so the answer changes no output.
+extern "C" int simpb_conv3x3_choose_resident(long long p_out, int in_h, int in_w, int in_channels, int out_channels, int stride) {
+  if (p_out <= 0 || in_h <= 0 || in_w <= 0 || p_out % ((long long)in_h * in_w) != 0 || !resident_shape(in_channels, stride) ||
+      out_channels != in_channels)
+    return 0;
+  const int staged = simpb_conv3x3_choose_variant(p_out, in_channels, out_channels);
+  if (staged != 7 && staged != 8) return 0;
+  const long long images = p_out / ((long long)in_h * in_w), across = (in_w + RTW - 1) / RTW;
+  const long long t13 = images * ((in_h + 7) / 8) * across * ((out_channels + 127) / 128);
+  const long long t12 = images * ((in_h + 3) / 4) * across * ((out_channels + 63) / 64);
+  if (in_channels == 256 && t13 >= 1024) return 13;   // four rounds of one eight-wave workgroup per CU
+  if (t12 >= 512) return 12;
+  return 0;
+}
+
+// The same question for the whole group launch of simpb_conv3x3_group_tokens_f16: 13 = every level in the resident
+// 8 x 16 x 128 form (measured on the FPN's four levels at 6 x 64 x 176: faster than the staged launch, than any split into
+// two launches and than the 4 x 16 x 64 form), 0 = the staged launch.
+extern "C" int simpb_conv3x3_group_choose_resident(int num_levels, int num_images, const int* in_h, const int* in_w, int in_channels,
+                                                   int out_channels) {
+  if (num_levels < 1 || num_levels > kMaxConvGroup || num_images <= 0 || !in_h || !in_w || in_channels != 256 || out_channels != 256) return 0;
+  long long tiles = 0;
+  for (int j = 0; j < num_levels; ++j) {
+    if (in_h[j] <= 0 || in_w[j] <= 0) return 0;
+    tiles += (long long)num_images * ((in_h[j] + 7) / 8) * ((in_w[j] + RTW - 1) / RTW) * 2;
+  }
+  return tiles >= 1024 ? 13 : 0;
+}
+
 extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, int tokens_per_cam, int level_start,
                                       const void* x, const void* weight, const void* bias, int num_images, int in_h, int in_w,
                                       int in_channels, int out_channels, int stride, int relu, int variant, void* stream) {
   const bool to_tokens = tokens || tokens_f16;   // tokens == NULL with tokens_f16 set: the f16 rows alone
   if ((!y && !to_tokens) || (y && to_tokens) || (reinterpret_cast<size_t>(tokens_f16) & 15) || !x || !weight || !bias || num_images <= 0 || in_h <= 0 || in_w <= 0 ||
       in_channels <= 0 || out_channels <= 0 || (stride != 1 && stride != 2) || in_channels % BK != 0 || out_channels % 8 != 0 ||
-      variant < 0 || variant > 11)
+      variant < 0 || variant > 13)
     return SIMPB_EINVAL;
+  if (variant >= 12 && !resident_shape(in_channels, stride)) return SIMPB_EINVAL;   // the resident form: stride 1, Cin 64 / 128 / 256
   if ((reinterpret_cast<size_t>(y) | reinterpret_cast<size_t>(tokens) | reinterpret_cast<size_t>(x) |
        reinterpret_cast<size_t>(weight) | reinterpret_cast<size_t>(bias)) & 15)
     return SIMPB_EINVAL;
@@ -650,7 +993,13 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
   ConvArgs a{static_cast<_Float16*>(y), tokens, static_cast<_Float16*>(tokens_f16), static_cast<const _Float16*>(x), static_cast<const _Float16*>(weight),
              static_cast<const _Float16*>(bias), nullptr, 0, (int)p_out, in_channels, out_channels, relu, stride, ho, wo, in_h, in_w,
              tokens_per_cam, level_start, 0, 0, 0};
-  if (variant == 0) variant = simpb_conv3x3_choose_variant(p_out, in_channels, out_channels);
+  if (variant == 0) {
+    variant = simpb_conv3x3_choose_variant(p_out, in_channels, out_channels);
+    if (variant == 7 || variant == 8) {   // the same bits either way: the resident form where it measured faster
+      const int resident = simpb_conv3x3_choose_resident(p_out, in_h, in_w, in_channels, out_channels, stride);
+      if (resident) variant = resident;
+    }
+  }
   hipStream_t s = static_cast<hipStream_t>(stream);
   auto dispatch = [&](auto tok16_c) {
     constexpr bool T = decltype(tok16_c)::value;
@@ -665,7 +1014,9 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
       case 8: launch_staged<96, 128, 1, 4, 9, T>(a, s); break;    // 96 x 128, waves side by side along the channels
       case 9: launch_staged_ksplit<64, 64, 2, 2, 9, T, 1>(a, s); break;    // 64 x 64, four waves of 32 x 32: the sums of 1
       case 10: launch_staged_ksplit<64, 64, 2, 2, 9, T, 2>(a, s); break;   // 64 x 64, K split over 2 groups of four waves
-      default: launch_staged_ksplit<64, 64, 2, 2, 9, T, 4>(a, s); break;   // 64 x 64, K split over 4 groups (16 waves): the sums of 3 / 4
+      case 11: launch_staged_ksplit<64, 64, 2, 2, 9, T, 4>(a, s); break;   // 64 x 64, K split over 4 groups (16 waves): the sums of 3 / 4
+      case 12: launch_resident<4, 64, 2, 2, 2, T>(a, s); break;     // resident 4 x 16 pixels x 64 channels, four waves of 32 x 32, weight ring of two
+      default: launch_resident<8, 128, 4, 2, 3, T>(a, s); break;    // resident 8 x 16 x 128, eight waves of 32 x 64, weight ring of three
     }
   };
   if (!tokens && tokens_f16) dispatch(std::true_type{});   // the f16 token rows alone: kernels without the fp32 stores
@@ -677,16 +1028,18 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
 // tools/fuse_conv_bn.py:10-48) of up to four levels in ONE launch, each writing its level's token rows (f32 and, optionally,
 // f16; or, with tokens == NULL, f16 alone) as simpb_conv3x3_nhwc_f16 does with `tokens`: x[j] f16 NHWC [num_images, in_h[j], in_w[j], Cin], weight[j] f16
 // [Cout, 3, 3, Cin], bias[j] f16 [Cout], level_start[j] the level's first row inside a camera's tokens_per_cam rows.
-extern "C" int simpb_conv3x3_group_tokens_f16(int num_levels, float* tokens, void* tokens_f16, int tokens_per_cam,
-                                              const int* level_start, const void* const* x, const void* const* weight,
-                                              const void* const* bias, int num_images, const int* in_h, const int* in_w,
-                                              int in_channels, int out_channels, int relu, void* stream) {
+extern "C" int simpb_conv3x3_group_tokens_forms_f16(int num_levels, float* tokens, void* tokens_f16, int tokens_per_cam,
+                                                    const int* level_start, const void* const* x, const void* const* weight,
+                                                    const void* const* bias, int num_images, const int* in_h, const int* in_w,
+                                                    int in_channels, int out_channels, int relu, const int* variant, void* stream) {
   if (num_levels < 1 || num_levels > kMaxConvGroup || (!tokens && !tokens_f16) || !level_start || !x || !weight || !bias || !in_h || !in_w ||
       num_images <= 0 || in_channels <= 0 || out_channels <= 0 || in_channels % BK != 0 || out_channels % 8 != 0 ||
       ((reinterpret_cast<size_t>(tokens) | reinterpret_cast<size_t>(tokens_f16)) & 15))
     return SIMPB_EINVAL;
-  ConvGroup g{};
-  long long total = 0;
+  // the levels of one form share a launch: form[0] the 96 x 128 staged tiles, form[1] the resident 8 x 16 x 128 tiles
+  ConvGroup form[2] = {};
+  long long total[2] = {0, 0};
+  const int rule = variant ? 0 : simpb_conv3x3_group_choose_resident(num_levels, num_images, in_h, in_w, in_channels, out_channels);
   for (int j = 0; j < num_levels; ++j) {
     if (!x[j] || !weight[j] || !bias[j] || in_h[j] <= 0 || in_w[j] <= 0 ||
         ((reinterpret_cast<size_t>(x[j]) | reinterpret_cast<size_t>(weight[j]) | reinterpret_cast<size_t>(bias[j])) & 15))
@@ -695,27 +1048,50 @@ extern "C" int simpb_conv3x3_group_tokens_f16(int num_levels, float* tokens, voi
     if (p_out > (1ll << 30) || p_out * in_channels > (1ll << 31) - 1) return SIMPB_EINVAL;   // tap offsets are 32-bit
     if (tokens_per_cam < in_h[j] * in_w[j] || level_start[j] < 0 || level_start[j] + in_h[j] * in_w[j] > tokens_per_cam)
       return SIMPB_EINVAL;
-    g.a[j] = ConvArgs{nullptr, tokens, static_cast<_Float16*>(tokens_f16), static_cast<const _Float16*>(x[j]),
-                      static_cast<const _Float16*>(weight[j]), static_cast<const _Float16*>(bias[j]), nullptr, 0, (int)p_out,
-                      in_channels, out_channels, relu, 1, in_h[j], in_w[j], in_h[j], in_w[j], tokens_per_cam, level_start[j],
-                      0, 0, 0};
-    g.a[j].gx = (int)((p_out + 95) / 96);
-    g.a[j].gy = (out_channels + 127) / 128;
-    g.start[j] = (int)total;
-    total += (long long)g.a[j].gx * g.a[j].gy;
+    const int v = variant ? variant[j] : rule ? rule : 8;
+    if (v != 8 && v != 13) return SIMPB_EINVAL;
+    if (v == 13 && !resident_shape(in_channels, 1)) return SIMPB_EINVAL;
+    const int f = v == 13;
+    ConvGroup& g = form[f];
+    ConvArgs& a = g.a[g.n];
+    a = ConvArgs{nullptr, tokens, static_cast<_Float16*>(tokens_f16), static_cast<const _Float16*>(x[j]),
+                 static_cast<const _Float16*>(weight[j]), static_cast<const _Float16*>(bias[j]), nullptr, 0, (int)p_out,
+                 in_channels, out_channels, relu, 1, in_h[j], in_w[j], in_h[j], in_w[j], tokens_per_cam, level_start[j],
+                 0, 0, 0, 0, 0};
+    if (f == 1) {
+      resident_grid<8, 128>(a);
+    } else {
+      a.gx = (int)((p_out + 95) / 96);
+      a.gy = (out_channels + 127) / 128;
+    }
+    g.start[g.n++] = (int)total[f];
+    total[f] += (long long)a.gx * a.gy;
   }
-  if (total > (1 << 24)) return SIMPB_EINVAL;
-  for (int j = num_levels; j <= kMaxConvGroup; ++j) g.start[j] = (int)total;
-  g.n = num_levels;
-  g.per_xcd = (int)((total + 7) / 8);
+  for (int f = 0; f < 2; ++f) {
+    if (total[f] > (1 << 24)) return SIMPB_EINVAL;
+    for (int j = form[f].n; j <= kMaxConvGroup; ++j) form[f].start[j] = (int)total[f];
+    form[f].per_xcd = (int)((total[f] + 7) / 8);
+  }
   (void)hipGetLastError();
-  if (!tokens)   // the f16 token rows alone
-    hipLaunchKernelGGL((conv_staged_group_kernel<96, 128, 1, 4, 9, true>), dim3((unsigned)(g.per_xcd * 8)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), g);
-  else
-    hipLaunchKernelGGL((conv_staged_group_kernel<96, 128, 1, 4, 9, false>), dim3((unsigned)(g.per_xcd * 8)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), g);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  auto launches = [&](auto tok16_c) {
+    constexpr bool T = decltype(tok16_c)::value;
+    if (form[1].n) launch_resident_group<8, 128, 4, 2, 3, T>(form[1], s);   // the large levels first: the staged launch is the short one
+    if (form[0].n)
+      hipLaunchKernelGGL((conv_staged_group_kernel<96, 128, 1, 4, 9, T>), dim3((unsigned)(form[0].per_xcd * 8)), dim3(256), 0, s, form[0]);
+  };
+  if (!tokens) launches(std::true_type{});   // the f16 token rows alone
+  else launches(std::false_type{});
   return simpb_check_launch();
+}
+
+// variant 0 for every level: what the detector runs
+extern "C" int simpb_conv3x3_group_tokens_f16(int num_levels, float* tokens, void* tokens_f16, int tokens_per_cam,
+                                              const int* level_start, const void* const* x, const void* const* weight,
+                                              const void* const* bias, int num_images, const int* in_h, const int* in_w,
+                                              int in_channels, int out_channels, int relu, void* stream) {
+  return simpb_conv3x3_group_tokens_forms_f16(num_levels, tokens, tokens_f16, tokens_per_cam, level_start, x, weight, bias, num_images,
+                                              in_h, in_w, in_channels, out_channels, relu, nullptr, stream);
 }
 
 // 1x1 convolutions through the same staged pipeline (TAPS = 1): csrc/conv1x1.hip validates and forwards here.

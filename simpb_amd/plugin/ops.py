@@ -541,11 +541,27 @@ def conv3x3_variant_for(p_out, in_channels, out_channels):
     return int(_lib.lib().simpb_conv3x3_choose_variant(int(p_out), int(in_channels), int(out_channels)))
 
 
-def conv3x3_group_tokens(xs, weights, biases, col, per_cam, starts, col16=None, relu=False):
+def conv3x3_resident_for(p_out, in_h, in_w, in_channels, out_channels, stride=1):
+    """The resident variant (12 or 13) conv3x3_nhwc(variant=0) runs where conv3x3_variant_for answers 7 or 8, or 0 for "the staged
+    form stays" (csrc/conv3x3.hip's second rule; no launch)."""
+    return int(_lib.lib().simpb_conv3x3_choose_resident(int(p_out), int(in_h), int(in_w), int(in_channels), int(out_channels), int(stride)))
+
+
+def conv3x3_group_resident_for(num_images, hws, in_channels, out_channels):
+    """13 where conv3x3_group_tokens (no variants given) runs every level (h, w) of hws in the resident form, 0 where it runs
+    the staged tiles (csrc/conv3x3.hip's rule for the whole launch; no launch)."""
+    import ctypes
+    arr = ctypes.c_int * len(hws)
+    return int(_lib.lib().simpb_conv3x3_group_choose_resident(len(hws), int(num_images), arr(*[int(h) for h, _ in hws]), arr(*[int(w) for _, w in hws]),
+                                                              int(in_channels), int(out_channels)))
+
+
+def conv3x3_group_tokens(xs, weights, biases, col, per_cam, starts, col16=None, relu=False, variants=None):
     """conv3x3_nhwc(..., tokens=...) of up to four levels in ONE launch (csrc/conv3x3.hip: conv_staged_group_kernel): the
     FPN's output convolutions. xs: channels_last f16 [N, Cin, H_j, W_j]; weights f16 [Cout, Cin, 3, 3]; biases f16 [Cout];
     col f32 [bs, cams * per_cam, Cout] (and col16, the same rows in f16; col None: the f16 rows alone); starts[j] = level j's
-    first row inside a camera."""
+    first row inside a camera. variants: per level 8 (staged tiles) or 13 (resident tiles), None = the library's rule for the
+    whole launch; the levels of one form share a launch."""
     import ctypes
     if col is None and col16 is None:
         raise ValueError("conv3x3_group_tokens: an f32 or an f16 token buffer")
@@ -568,11 +584,14 @@ def conv3x3_group_tokens(xs, weights, biases, col, per_cam, starts, col16=None, 
             or (col16 is not None and (col16.dtype != torch.float16 or not col16.is_contiguous() or col16.shape != rows.shape))):
         raise ValueError("conv3x3_group_tokens: col = contiguous f32 [bs, cams * tokens_per_cam, Cout] with bs * cams == N")
     arr_p, arr_i = ctypes.c_void_p * k, ctypes.c_int * k
-    status = _lib.lib().simpb_conv3x3_group_tokens_f16(
+    if variants is not None and len(variants) != k:
+        raise ValueError("conv3x3_group_tokens: one variant per level")
+    status = _lib.lib().simpb_conv3x3_group_tokens_forms_f16(
         k, _ptr(col) if col is not None else None, _ptr(col16) if col16 is not None else None, int(per_cam), arr_i(*[int(v) for v in starts]),
         arr_p(*[x.data_ptr() for x in xs]), arr_p(*[w.data_ptr() for w in ws]), arr_p(*[b.data_ptr() for b in biases]), n,
-        arr_i(*[x.shape[2] for x in xs]), arr_i(*[x.shape[3] for x in xs]), cin, cout, 1 if relu else 0, _stream())
-    _lib.check(status, "simpb_conv3x3_group_tokens_f16")
+        arr_i(*[x.shape[2] for x in xs]), arr_i(*[x.shape[3] for x in xs]), cin, cout, 1 if relu else 0,
+        arr_i(*[int(v) for v in variants]) if variants is not None else None, _stream())
+    _lib.check(status, "simpb_conv3x3_group_tokens_forms_f16")
 
 
 def _stem_weight_packed(weight):
