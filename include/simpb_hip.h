@@ -469,6 +469,18 @@ int simpb_attention_split_halfs(float* out, const void* q, const void* k, const 
                                 const int* group_start, int batch_size, int num_heads, int head_dim, int num_query,
                                 int num_key, int ldq, int ldk, int ldv, int ldo, void* stream);
 
+/* The ungrouped operator with one of TWO key / value sets per batch row: row b reads (k, v, num_key, ldk, ldv) where
+ * select[b] == 0 and (k2, v2, num_key2, ldk2, ldv2) otherwise (select u8 [batch_size] on the device; batches of set 2 are
+ * num_key2 * ld apart). split = 0 / 1 / 2 names the form: simpb_attention_f32, simpb_attention_f32_split,
+ * simpb_attention_split_halfs (which ignores scale). A row's output is bit for bit what that entry point gives on the set
+ * the row selected, and not a byte of the other set is read: it may hold anything. select == NULL: set 1 for every row
+ * through that entry point's own kernel (k2 / v2 are not looked at). With a selector, k2 and v2 must be given and obey the
+ * rules of k and v (k2 16-byte aligned, ldk2 % 4 == 0, ld >= num_heads * 64). */
+int simpb_attention_select(int split, float* out, const void* q, const void* k, const void* v, const void* k2, const void* v2,
+                           const unsigned char* select, int batch_size, int num_heads, int head_dim, int num_query,
+                           int num_key, int num_key2, int ldq, int ldk, int ldv, int ldk2, int ldv2, int ldo, float scale,
+                           void* stream);
+
 /* Fused small-MLP chains: a whole `linear_relu_ln` stack (models/blocks.py:32-43) -- [Linear, ReLU]*,
  * LayerNorm, ..., optional last Linear and Scale -- in one launch; up to 8 independent chains over
  * the same rows share it (e.g. the pos/size/yaw/vel branches of SparseBox3DEncoder,
@@ -618,6 +630,26 @@ int simpb_bank_cache_streams_active(float* confidence, float* cached_feature, fl
                                     int num_temp, int embed_dims, int has_previous, float confidence_decay, int has_threshold,
                                     float threshold, const int* hold, int num_hold, int* sticky, unsigned* sync_words,
                                     const unsigned char* active, void* stream);
+
+/* A batch of streams in which some RESTART: `restart` u8 [batch_size] (device; NULL = no stream, results identical to the
+ * entry point without the suffix). A stream with restart != 0 is decoded as the first frame of a fresh bank
+ * (InstanceBank.reset() + get() without history, :71-77,115-117) while the others go on:
+ *   simpb_bank_get_restart: its mask_out is 0 and its time_interval_out the default, whatever its time_interval; its
+ *     anchor_out rows are written and unspecified (simpb_bank_update_merge never reads the cached rows of a stream with a
+ *     zero mask: it keeps the stream's current set and resets its instance_id row, hold / sticky permitting).
+ *   simpb_bank_cache_streams_restart (both forms): the decay-maximum against the previous confidence (:157-162) is not applied
+ *     to it (cache() with confidence = None) and its previous confidence row is never read, so it may hold anything. Its ids
+ *     come from the running prev_id like every stream's. `active` as above; a stream should not be paused and restarted at
+ *     once (the pause wins). hold / sticky take precedence. */
+int simpb_bank_get_restart(float* anchor_out, unsigned char* mask_out, float* time_interval_out, const float* cached_anchor,
+                           const float* T_temp2cur, const float* time_interval, int batch_size, int num_temp,
+                           float max_time_interval, float default_time_interval, const unsigned char* restart, void* stream);
+int simpb_bank_cache_streams_restart(float* confidence, float* cached_feature, float* cached_anchor, long long* instance_id,
+                                     long long* prev_id, long long* ids_out, int* index_scratch, const float* feature,
+                                     const float* anchor, const float* cls, int batch_size, int num_anchors, int num_classes,
+                                     int num_temp, int embed_dims, int has_previous, float confidence_decay, int has_threshold,
+                                     float threshold, const int* hold, int num_hold, int* sticky, unsigned* sync_words,
+                                     const unsigned char* active, const unsigned char* restart, void* stream);
 
 /* Fixed-shape detection records of SparseBox3DDecoder.decode_with2d (models/detection3d/decoder.py:124-252).
  * 3D (:133-167 with squeezed classes + decode_box :23-34), one workgroup per sample:

@@ -56,8 +56,10 @@ SIGNATURES = {
     "simpb_attention_f32": ([_P] * 6 + [_I] * 9 + [_F, _P], _I),
     "simpb_attention_f32_split": ([_P] * 6 + [_I] * 9 + [_F, _P], _I),
     "simpb_attention_split_halfs": ([_P] * 6 + [_I] * 9 + [_P], _I),
+    "simpb_attention_select": ([_I] + [_P] * 7 + [_I] * 12 + [_F, _P], _I),
     "simpb_mlp_chain_forward": ([_P, _P], _I),
     "simpb_bank_get": ([_P] * 6 + [_I] * 2 + [_F] * 2 + [_P], _I),
+    "simpb_bank_get_restart": ([_P] * 6 + [_I] * 2 + [_F] * 2 + [_P, _P], _I),
     "simpb_bank_update": ([_P] * 10 + [_I] * 5 + [_P], _I),
     "simpb_bank_update_rank": ([_P, _P] + [_I] * 4 + [_P], _I),
     "simpb_bank_update_merge": ([_P] * 13 + [_I, _P] + [_I] * 5 + [_P], _I),
@@ -65,6 +67,7 @@ SIGNATURES = {
     "simpb_bank_cache": ([_P] * 10 + [_I] * 6 + [_F, _I, _F, _P, _I, _P, _P], _I),
     "simpb_bank_cache_streams": ([_P] * 10 + [_I] * 6 + [_F, _I, _F, _P, _I, _P, _P, _P], _I),
     "simpb_bank_cache_streams_active": ([_P] * 10 + [_I] * 6 + [_F, _I, _F, _P, _I, _P, _P, _P, _P], _I),
+    "simpb_bank_cache_streams_restart": ([_P] * 10 + [_I] * 6 + [_F, _I, _F, _P, _I, _P, _P, _P, _P, _P], _I),
     "simpb_decode3d_record": ([_P] * 6 + [_I] * 4 + [_P], _I),
     "simpb_decode2d_record": ([_P] * 6 + [_I] * 4 + [_F] * 4 + [_P], _I),
     "simpb_record2d_compact": ([_P, _LL, _P, _LL, _I, _I, _I, _P], _I),

@@ -31,11 +31,33 @@ constexpr int kWaves = 4;  // (8 waves per workgroup, 2 per SIMD, measured no fa
 
 __device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
-template <bool GROUPED>
+// A second key / value set for some streams of the batch (the ungrouped forms; simpb_attention_select): the workgroups of
+// stream b read the kernel's own (k, v, Nk, ldk, ldv) where select[b] == 0 and this set otherwise -- a workgroup-uniform
+// choice of five scalars taken once, in front of everything that reads them, so a stream's rows are the bits the kernel
+// gives on the set it selected alone and no address of the other set is ever formed (it may hold anything, NaN included).
+// A batch of streams in which one restarts cold: its temporal attention runs over its own current instances while its
+// neighbours attend their cached ones (simpb_amd/runner.py `restart`). The kernels take it as a trailing parameter PACK:
+// empty for the entry points that have one set, whose kernels are then the functions they were, instruction for instruction.
+struct AltKeys {
+  const unsigned char* select;
+  const float* k;
+  const float* v;
+  int Nk, ldk, ldv;
+};
+#define SIMPB_PICK_KEYS()                                                \
+  if constexpr (sizeof...(Alt) != 0) {                                   \
+    const AltKeys a[] = {alt...};                                        \
+    if (a[0].select[blockIdx.z] != 0) {                                  \
+      k = a[0].k; v = a[0].v; Nk = a[0].Nk; ldk = a[0].ldk; ldv = a[0].ldv; \
+    }                                                                    \
+  }
+
+template <bool GROUPED, class... Alt>
 __global__ __launch_bounds__(kWaves * 64) void attention_f32_kernel(
     float* __restrict__ out, const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     const int* __restrict__ query_cam, const int* __restrict__ group_start, int Nq, int Nk, int ldq, int ldk, int ldv,
-    int ldo, float scale) {
+    int ldo, float scale, Alt... alt) {
+  SIMPB_PICK_KEYS()
   __shared__ float s_m[kWaves][64];
   __shared__ float s_l[kWaves][64];
   __shared__ float s_o[kWaves][2][16][64];
@@ -231,11 +253,12 @@ __device__ __forceinline__ void unpack4(const float* w, h16x4& hi, h16x4& lo) {
   lo = __builtin_bit_cast(h16x4, l);
 }
 
-template <bool GROUPED, bool PACKED = false>
+template <bool GROUPED, bool PACKED = false, class... Alt>
 __global__ __launch_bounds__(kWaves * 64) void attention_f16s_kernel(
     float* __restrict__ out, const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     const int* __restrict__ query_cam, const int* __restrict__ group_start, int Nq, int Nk, int ldq, int ldk, int ldv,
-    int ldo, float scale) {
+    int ldo, float scale, Alt... alt) {
+  SIMPB_PICK_KEYS()
   __shared__ float s_m[kWaves][64];
   __shared__ float s_l[kWaves][64];
   __shared__ float s_o[kWaves][2][16][64];
@@ -418,11 +441,12 @@ __global__ __launch_bounds__(kWaves * 64) void attention_f16s_kernel(
 // (launch bounds: at least 8 waves per CU in either form, i.e. at most 256 registers per wave. The four-wave form -- used for the
 // camera-grouped launches, whose ~190-key groups are 6 key tiles: nothing for eight waves to split -- then fits two workgroups
 // per CU, and the 280 live workgroups of a 1 130-slot 2D set run as ONE round of the chip instead of 256 + 24.)
-template <bool GROUPED, int WAVES>
+template <bool GROUPED, int WAVES, class... Alt>
 __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void attention_halfs_kernel(
     float* __restrict__ out, const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     const int* __restrict__ query_cam, const int* __restrict__ group_start, int Nq, int Nk, int ldq, int ldk, int ldv,
-    int ldo) {
+    int ldo, Alt... alt) {
+  SIMPB_PICK_KEYS()
   static_assert(WAVES == 4 || WAVES == 8, "four waves, or eight meeting in two steps");
   __shared__ float s_m[4][64];
   __shared__ float s_l[4][64];
@@ -666,6 +690,42 @@ static int attention_launch(int split, float* out, const float* q, const float* 
   else
     hipLaunchKernelGGL(attention_f32_kernel<false>, grid, block, 0, s, out, q, k, v, query_cam, group_start, num_query,
                        num_key, ldq, ldk, ldv, ldo, scale);
+  return simpb_check_launch();
+}
+
+extern "C" int simpb_attention_select(int split, float* out, const void* q, const void* k, const void* v, const void* k2,
+                                      const void* v2, const unsigned char* select, int batch_size, int num_heads, int head_dim,
+                                      int num_query, int num_key, int num_key2, int ldq, int ldk, int ldv, int ldk2, int ldv2,
+                                      int ldo, float scale, void* stream) {
+  if (split < 0 || split > 2) return SIMPB_EINVAL;
+  const float* qf = static_cast<const float*>(q);
+  const float* kf = static_cast<const float*>(k);
+  const float* vf = static_cast<const float*>(v);
+  if (!select)   // every stream reads set 1: the kernels (and the bits) of the entry points below
+    return attention_launch(split, out, qf, kf, vf, nullptr, nullptr, batch_size, num_heads, head_dim, num_query, num_key, ldq, ldk,
+                            ldv, ldo, scale, stream);
+  if (!out || !q || !k || !v || !k2 || !v2 || batch_size <= 0 || num_heads <= 0 || num_query <= 0 || num_key <= 0 ||
+      num_key2 <= 0)
+    return SIMPB_EINVAL;
+  const int e = num_heads * kHD;
+  if (head_dim != kHD || ldq < e || ldk < e || ldv < e || ldk2 < e || ldv2 < e || ldo < e) return SIMPB_EINVAL;
+  if ((ldq | ldk | ldk2) & 3) return SIMPB_EINVAL;
+  if ((reinterpret_cast<size_t>(q) | reinterpret_cast<size_t>(k) | reinterpret_cast<size_t>(k2)) & 15) return SIMPB_EINVAL;
+  if (batch_size > 65535 || num_heads > 65535) return SIMPB_EINVAL;
+  (void)hipGetLastError();
+  const AltKeys alt{select, static_cast<const float*>(k2), static_cast<const float*>(v2), num_key2, ldk2, ldv2};
+  const int* none = nullptr;
+  dim3 grid((num_query + 31) / 32, num_heads, batch_size), block(kWaves * 64);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (split == 2)
+    hipLaunchKernelGGL((attention_halfs_kernel<false, 8, AltKeys>), grid, dim3(512), 0, s, out, qf, kf, vf, none, none, num_query,
+                       num_key, ldq, ldk, ldv, ldo, alt);
+  else if (split)
+    hipLaunchKernelGGL((attention_f16s_kernel<false, false, AltKeys>), grid, block, 0, s, out, qf, kf, vf, none, none, num_query,
+                       num_key, ldq, ldk, ldv, ldo, scale, alt);
+  else
+    hipLaunchKernelGGL((attention_f32_kernel<false, AltKeys>), grid, block, 0, s, out, qf, kf, vf, none, none, num_query, num_key,
+                       ldq, ldk, ldv, ldo, scale, alt);
   return simpb_check_launch();
 }
 

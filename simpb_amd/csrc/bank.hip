@@ -48,12 +48,14 @@ __device__ __forceinline__ float row_max(const float* row, int C) {
 __global__ __launch_bounds__(256) void bank_get_kernel(float* __restrict__ out, unsigned char* __restrict__ mask,
                                                        float* __restrict__ dt_out, const float* __restrict__ anchor,
                                                        const float* __restrict__ T, const float* __restrict__ dt, int bs,
-                                                       int n, float max_dt, float default_dt) {
+                                                       int n, float max_dt, float default_dt,
+                                                       const unsigned char* __restrict__ restart) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < bs) {
     const float t = dt[i];
+    const bool cold = restart && restart[i] != 0;
     simpb::loads_retired();
-    const bool ok = fabsf(t) <= max_dt;  // :87
+    const bool ok = fabsf(t) <= max_dt && !cold;  // :87; a restarted stream has no history (:71-77), whatever its dt
     mask[i] = ok ? 1 : 0;
     dt_out[i] = (t != 0.f && ok) ? t : default_dt;  // :108-113
     simpb::loads_retired();  // (a store fence as well: nothing in flight when the rows below are loaded)
@@ -121,6 +123,13 @@ __device__ __forceinline__ bool held(const int* hold, int num_hold, const int* s
 // persistent rows exactly as they found them (runner.py: a camera stream without a frame this step).
 __device__ __forceinline__ bool paused(const unsigned char* active, int b) { return active && active[b] == 0; }
 
+// `restart` (u8 [bs], may be NULL = no stream): a stream with a non-zero byte is decoded as the first frame of a fresh bank
+// (instance_bank.py:71-77 reset(), :115-117 get() without history) while its neighbours go on: bank_get masks its history
+// out and hands it the default time step, the merge then keeps its current set and resets its ids (a zero mask does that
+// already), and the commit ranks its new scores alone -- confidence=None in cache() (:157) -- so nothing the slot held
+// before, NaN included, reaches what the frame leaves.
+__device__ __forceinline__ bool restarted(const unsigned char* restart, int b) { return restart && restart[b] != 0; }
+
 // ---- update (:140-149): rows [0, T) = cached, rows [T, A) = current[index], per stream under its mask; one
 // wave per output row (feature C floats + anchor 11 floats [+ embedding E floats]); the ids of masked-out streams are reset
 // (:147-149) -- unless a `hold` flag is set: then this frame (or the one decoded just before it) is going to be re-run from
@@ -176,7 +185,8 @@ __global__ __launch_bounds__(512) void bank_cache_kernel(float* __restrict__ con
                                                          int bs, int A, int C, int T, int has_prev, float decay,
                                                          int has_threshold, float threshold, const int* __restrict__ hold,
                                                          int num_hold, int* __restrict__ sticky,
-                                                         const unsigned char* __restrict__ active) {
+                                                         const unsigned char* __restrict__ active,
+                                                         const unsigned char* __restrict__ restart) {
   __shared__ unsigned long long key[kCap];
   __shared__ long long ids[kCap];
   __shared__ int scan[kCap];
@@ -196,13 +206,14 @@ __global__ __launch_bounds__(512) void bank_cache_kernel(float* __restrict__ con
       continue;
     }
     // scores: sigmoid of the best class; tracked instances keep max(decayed previous, new) (:157-162)
+    const bool decay_prev = has_prev && !restarted(restart, b);   // workgroup-uniform
     for (int a = tid; a < kCap; a += 512) {
       unsigned long long kv = 0ull;
       if (a < A) {
         const float s = sigmoidf(row_max(cls + ((size_t)b * A + a) * C, C));
         fresh_score[a] = s;
         float sc = s;
-        if (has_prev && a < T) sc = fmaxf(conf[(size_t)b * T + a] * decay, s);
+        if (decay_prev && a < T) sc = fmaxf(conf[(size_t)b * T + a] * decay, s);
         kv = sort_key(sc, (unsigned)a);
       }
       key[a] = kv;
@@ -278,7 +289,8 @@ __global__ __launch_bounds__(512) void bank_cache_streams_kernel(float* __restri
                                                                  int has_threshold, float threshold,
                                                                  const int* __restrict__ hold, int num_hold,
                                                                  int* __restrict__ sticky, unsigned* __restrict__ sync,
-                                                                 const unsigned char* __restrict__ active) {
+                                                                 const unsigned char* __restrict__ active,
+                                                                 const unsigned char* __restrict__ restart) {
   __shared__ unsigned long long key[kCap];
   __shared__ long long ids[kCap];
   __shared__ int scan[kCap];
@@ -317,13 +329,14 @@ __global__ __launch_bounds__(512) void bank_cache_streams_kernel(float* __restri
     return;
   }
   // this stream's scores and ranking (as the serial kernel)
+  const bool decay_prev = has_prev && !restarted(restart, b);   // workgroup-uniform
   for (int a = tid; a < kCap; a += 512) {
     unsigned long long kv = 0ull;
     if (a < A) {
       const float s = sigmoidf(row_max(cls + ((size_t)b * A + a) * C, C));
       fresh_score[a] = s;
       float sc = s;
-      if (has_prev && a < T) sc = fmaxf(conf[(size_t)b * T + a] * decay, s);
+      if (decay_prev && a < T) sc = fmaxf(conf[(size_t)b * T + a] * decay, s);
       kv = sort_key(sc, (unsigned)a);
     }
     key[a] = kv;
@@ -397,9 +410,10 @@ __global__ __launch_bounds__(64) void bank_gather_kernel(float* __restrict__ out
 
 }  // namespace
 
-extern "C" int simpb_bank_get(float* anchor_out, unsigned char* mask_out, float* time_interval_out, const float* cached_anchor,
-                              const float* T_temp2cur, const float* time_interval, int batch_size, int num_temp,
-                              float max_time_interval, float default_time_interval, void* stream) {
+extern "C" int simpb_bank_get_restart(float* anchor_out, unsigned char* mask_out, float* time_interval_out,
+                                      const float* cached_anchor, const float* T_temp2cur, const float* time_interval,
+                                      int batch_size, int num_temp, float max_time_interval, float default_time_interval,
+                                      const unsigned char* restart, void* stream) {
   if (!anchor_out || !mask_out || !time_interval_out || !cached_anchor || !T_temp2cur || !time_interval || batch_size <= 0 ||
       num_temp <= 0)
     return SIMPB_EINVAL;
@@ -407,8 +421,15 @@ extern "C" int simpb_bank_get(float* anchor_out, unsigned char* mask_out, float*
   const int total = batch_size * num_temp;
   hipLaunchKernelGGL(bank_get_kernel, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), anchor_out,
                      mask_out, time_interval_out, cached_anchor, T_temp2cur, time_interval, batch_size, num_temp,
-                     max_time_interval, default_time_interval);
+                     max_time_interval, default_time_interval, restart);
   return simpb_check_launch();
+}
+
+extern "C" int simpb_bank_get(float* anchor_out, unsigned char* mask_out, float* time_interval_out, const float* cached_anchor,
+                              const float* T_temp2cur, const float* time_interval, int batch_size, int num_temp,
+                              float max_time_interval, float default_time_interval, void* stream) {
+  return simpb_bank_get_restart(anchor_out, mask_out, time_interval_out, cached_anchor, T_temp2cur, time_interval, batch_size,
+                                num_temp, max_time_interval, default_time_interval, nullptr, stream);
 }
 
 extern "C" int simpb_bank_update_rank(int* index_scratch, const float* cls, int batch_size, int num_anchors, int num_classes,
@@ -467,7 +488,7 @@ static int bank_cache_launch(float* confidence, float* cached_feature, float* ca
                              const float* anchor, const float* cls, int batch_size, int num_anchors, int num_classes,
                              int num_temp, int embed_dims, int has_previous, float confidence_decay, int has_threshold,
                              float threshold, const int* hold, int num_hold, int* sticky, unsigned* sync,
-                             const unsigned char* active, void* stream) {
+                             const unsigned char* active, const unsigned char* restart, void* stream) {
   if (!confidence || !cached_feature || !cached_anchor || !prev_id || !ids_out || !index_scratch || !feature || !anchor ||
       !cls || batch_size <= 0 || num_anchors <= 0 || num_anchors > kCap || num_classes <= 0 || num_temp <= 0 ||
       num_temp > num_anchors || embed_dims <= 0 || (embed_dims & 3) || batch_size > 65535 || num_hold < 0 ||
@@ -478,11 +499,11 @@ static int bank_cache_launch(float* confidence, float* cached_feature, float* ca
   if (sync && batch_size > 1 && batch_size <= 64)
     hipLaunchKernelGGL(bank_cache_streams_kernel, dim3(batch_size), dim3(512), 0, s, confidence, index_scratch, ids_out, instance_id,
                        prev_id, cls, batch_size, num_anchors, num_classes, num_temp, has_previous, confidence_decay, has_threshold,
-                       threshold, hold, num_hold, sticky, sync, active);
+                       threshold, hold, num_hold, sticky, sync, active, restart);
   else
     hipLaunchKernelGGL(bank_cache_kernel, dim3(1), dim3(512), 0, s, confidence, index_scratch, ids_out, instance_id, prev_id, cls,
                        batch_size, num_anchors, num_classes, num_temp, has_previous, confidence_decay, has_threshold, threshold, hold,
-                       num_hold, sticky, active);
+                       num_hold, sticky, active, restart);
   hipLaunchKernelGGL(bank_gather_kernel, dim3(num_temp, batch_size), dim3(64), 0, s, cached_feature, cached_anchor, feature,
                      anchor, index_scratch, num_anchors, num_temp, embed_dims, hold, num_hold, sticky, active);
   return simpb_check_launch();
@@ -495,7 +516,7 @@ extern "C" int simpb_bank_cache(float* confidence, float* cached_feature, float*
                                 float threshold, const int* hold, int num_hold, int* sticky, void* stream) {
   return bank_cache_launch(confidence, cached_feature, cached_anchor, instance_id, prev_id, ids_out, index_scratch, feature, anchor,
                            cls, batch_size, num_anchors, num_classes, num_temp, embed_dims, has_previous, confidence_decay,
-                           has_threshold, threshold, hold, num_hold, sticky, nullptr, nullptr, stream);
+                           has_threshold, threshold, hold, num_hold, sticky, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int simpb_bank_cache_streams(float* confidence, float* cached_feature, float* cached_anchor, long long* instance_id,
@@ -506,7 +527,7 @@ extern "C" int simpb_bank_cache_streams(float* confidence, float* cached_feature
                                         unsigned* sync_words, void* stream) {
   return bank_cache_launch(confidence, cached_feature, cached_anchor, instance_id, prev_id, ids_out, index_scratch, feature, anchor,
                            cls, batch_size, num_anchors, num_classes, num_temp, embed_dims, has_previous, confidence_decay,
-                           has_threshold, threshold, hold, num_hold, sticky, sync_words, nullptr, stream);
+                           has_threshold, threshold, hold, num_hold, sticky, sync_words, nullptr, nullptr, stream);
 }
 
 extern "C" int simpb_bank_cache_streams_active(float* confidence, float* cached_feature, float* cached_anchor,
@@ -518,5 +539,17 @@ extern "C" int simpb_bank_cache_streams_active(float* confidence, float* cached_
                                                const unsigned char* active, void* stream) {
   return bank_cache_launch(confidence, cached_feature, cached_anchor, instance_id, prev_id, ids_out, index_scratch, feature, anchor,
                            cls, batch_size, num_anchors, num_classes, num_temp, embed_dims, has_previous, confidence_decay,
-                           has_threshold, threshold, hold, num_hold, sticky, sync_words, active, stream);
+                           has_threshold, threshold, hold, num_hold, sticky, sync_words, active, nullptr, stream);
+}
+
+extern "C" int simpb_bank_cache_streams_restart(float* confidence, float* cached_feature, float* cached_anchor,
+                                                long long* instance_id, long long* prev_id, long long* ids_out,
+                                                int* index_scratch, const float* feature, const float* anchor, const float* cls,
+                                                int batch_size, int num_anchors, int num_classes, int num_temp, int embed_dims,
+                                                int has_previous, float confidence_decay, int has_threshold, float threshold,
+                                                const int* hold, int num_hold, int* sticky, unsigned* sync_words,
+                                                const unsigned char* active, const unsigned char* restart, void* stream) {
+  return bank_cache_launch(confidence, cached_feature, cached_anchor, instance_id, prev_id, ids_out, index_scratch, feature, anchor,
+                           cls, batch_size, num_anchors, num_classes, num_temp, embed_dims, has_previous, confidence_decay,
+                           has_threshold, threshold, hold, num_hold, sticky, sync_words, active, restart, stream);
 }

@@ -170,20 +170,35 @@ class SimPBHead(BaseModule):
         return out
 
     # ------------------------------------------------------------------ decoupled attention
-    def graph_model(self, index, query, key=None, value=None, query_pos=None, key_pos=None, **kwargs):
-        """simpb_head.py:298-310."""
+    def graph_model(self, index, query, key=None, value=None, query_pos=None, key_pos=None, restart=None, **kwargs):
+        """simpb_head.py:298-310. restart (u8 [bs] on the device, fused route only): batch rows with a non-zero byte are
+        served as the call with key = value = None serves them (layers.fused_graph_attention)."""
         layer = self.layers[index] if isinstance(index, int) else index
         kwargs.pop("attn_mask", None)
         if query.is_cuda and routes.R.dense:
-            out = fused_graph_attention(layer, self.fc_before, self.fc_after, query, query_pos, key, key_pos, value)
+            out = fused_graph_attention(layer, self.fc_before, self.fc_after, query, query_pos, key, key_pos, value,
+                                        restart=restart if key is not None else None)
             if out is not None:
                 return out
+        if restart is not None and key is not None:
+            raise ValueError("a per-stream restart needs the fused attention route (layers.fused_graph_attention)")
         query = torch.cat([query, query_pos], dim=-1)
         key = torch.cat([key, key_pos], dim=-1) if key is not None else None
         # fc_before (:303) is handed to the attention operator, which applies it on the value branch,
         # forked from the q/k projection branch (layers.run_parallel)
         pre = self.fc_before if value is not None else None
         return self.fc_after(layer(query, key, value, query_pos=None, key_pos=None, value_pre=pre, **kwargs))
+
+    def prepare_restart(self):
+        """The derived weights a frame with metas['restart'] uses beyond an ordinary warm frame's (the `temp_gnn` operators'
+        key / value fold without fc_before and its half split), built here so that a caller can capture such a frame
+        without having run one eagerly: weights first seen inside a capture take another kernel (dense._split_weights)."""
+        for op, layer in zip(self.operation_order, self.layers):
+            attn = getattr(layer, "attn", None)
+            if op == "temp_gnn" and isinstance(attn, nn.MultiheadAttention) and attn.in_proj_weight.is_cuda:
+                w, _ = dense.fold_mha_in(attn, None, "kv")
+                if routes.R.gemm_split_fp16:
+                    dense._split_weights(w)
 
     def graph_model2d(self, index, query, key=None, value=None, query_pos=None, key_pos=None, **kwargs):
         """simpb_head.py:312-321."""
@@ -281,6 +296,22 @@ class SimPBHead(BaseModule):
                 raise ValueError("metas['active'] must be a contiguous u8 [bs] tensor on the device")
             if not self.instance_bank._fusable(active):
                 raise ValueError("metas['active'] needs the fused bank route (static state, routes.fused_bank)")
+        restart = metas.get("restart")
+        if restart is not None:
+            # u8 [bs] on the device (static address): a stream with a non-zero byte is decoded as a fresh head decodes its first
+            # frame (InstanceBank.reset() + get() without history: no cached keys in temp_gnn, update() a no-op, no
+            # decay-maximum in cache(), ids -1, the default time step) while the others go on (csrc/bank.hip `restart`,
+            # layers.fused_graph_attention `restart`). Only meaningful on a frame with history; a cold frame ignores it.
+            if split:
+                raise NotImplementedError("forward_split cannot restart a stream: its single-frame part is already in flight "
+                                          "when the temporal part would have to start cold")
+            if self.static_capacity is None or (batch_size > 1 and not self.independent_streams):
+                raise ValueError("metas['restart'] needs a static capacity and, for a batch, independent_streams")
+            if (not torch.is_tensor(restart) or restart.dtype != torch.uint8 or restart.numel() != batch_size
+                    or not restart.is_cuda or not restart.is_contiguous()):
+                raise ValueError("metas['restart'] must be a contiguous u8 [bs] tensor on the device")
+            if not (self.instance_bank._fusable(restart) and routes.R.dense):
+                raise ValueError("metas['restart'] needs the fused bank route (static state, routes.fused_bank) and routes.dense")
         camera_valid = metas.get("camera_valid")
         if camera_valid is not None:
             # u8 [bs, cams] on the device (static address): a camera with 0 delivered no frame, and its stream is decoded as
@@ -300,6 +331,8 @@ class SimPBHead(BaseModule):
         else:
             instance_feature, anchor, temp_instance_feature, temp_anchor, time_interval = self.instance_bank.get(
                 batch_size, metas, dn_metas=None)
+        if temp_anchor is None:
+            restart = None   # a cold frame: every stream starts without history already
         if temp_anchor is not None and anchor.is_cuda:
             # one encoder launch over both anchor sets (the chain kernel is latency-bound per launch)
             both = self.anchor_encoder.forward(torch.cat([anchor, temp_anchor], dim=1))
@@ -442,7 +475,7 @@ class SimPBHead(BaseModule):
                 instance_feature = self.graph_model(i, instance_feature, value=instance_feature, query_pos=anchor_embed)
             elif op == "temp_gnn":
                 instance_feature = self.graph_model(i, instance_feature, temp_instance_feature, temp_instance_feature,
-                                                    query_pos=anchor_embed, key_pos=temp_anchor_embed)
+                                                    query_pos=anchor_embed, key_pos=temp_anchor_embed, restart=restart)
                 temp_attn_instance = instance_feature
             elif op == "deformable":
                 instance_feature = layer(instance_feature, anchor, anchor_embed, feature_maps, metas,
@@ -482,6 +515,8 @@ class SimPBHead(BaseModule):
                         instance_feature, anchor, merged_embed = self.instance_bank.update(
                             instance_feature, anchor, cls, rank=rank, embed=(cur_embed, temp_anchor_embed), hold=hold, sticky=sticky,
                             active=active)
+                    elif restart is not None:
+                        raise ValueError("metas['restart'] needs the fused bank route in InstanceBank.update")
                     else:
                         instance_feature, anchor = self.instance_bank.update(instance_feature, anchor, cls, active=active)
                 if merged_embed is not None:
@@ -502,7 +537,7 @@ class SimPBHead(BaseModule):
             "alloc_list": alloc_list, "overflow": overflow,
         }
         ids = self.instance_bank.cache_and_assign_ids(instance_feature, anchor, cls, metas, self.decoder.score_threshold,
-                                                      hold=hold, sticky=sticky, active=active)
+                                                      hold=hold, sticky=sticky, active=active, restart=restart)
         if ids is None:
             self.instance_bank.cache(instance_feature, anchor, cls, metas, feature_maps)
             ids = self.instance_bank.get_instance_id(cls, anchor, self.decoder.score_threshold)

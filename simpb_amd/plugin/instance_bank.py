@@ -154,12 +154,17 @@ class InstanceBank(nn.Module):
             self.mask = torch.empty(bs, dtype=torch.bool, device=stored.device)
             dt_out = torch.empty(bs, dtype=torch.float32, device=stored.device)
             lib = _lib.lib()
-            _lib.check(lib.simpb_bank_get(_ptr(warped), _ptr(self.mask), _ptr(dt_out), _ptr(stored),
-                                          _ptr(T_temp2cur.contiguous().float()), _ptr(dt.contiguous().float()), bs, t,
-                                          float(self.max_time_interval), float(self.default_time_interval), _stream()),
+            restart = metas.get("restart")   # u8 [bs]: streams that start this frame without history (csrc/bank.hip)
+            _lib.check(lib.simpb_bank_get_restart(_ptr(warped), _ptr(self.mask), _ptr(dt_out), _ptr(stored),
+                                                  _ptr(T_temp2cur.contiguous().float()), _ptr(dt.contiguous().float()), bs, t,
+                                                  float(self.max_time_interval), float(self.default_time_interval),
+                                                  _ptr(restart) if restart is not None else None, _stream()),
                        "simpb_bank_get")
             self.cached_anchor = warped
             return feature, anchor, self.cached_feature, self.cached_anchor, dt_out
+        if metas is not None and metas.get("restart") is not None:
+            # (the PyTorch statement below has no per-stream cold start: SimPBHead._forward refuses the flag on this route)
+            raise ValueError("metas['restart'] needs the fused bank route (static state, routes.fused_bank)")
         if static_warm:
             # T_temp2cur and the raw time step were prepared on the host by the caller (they depend on
             # metadata only) and already sit in device buffers
@@ -267,15 +272,16 @@ class InstanceBank(nn.Module):
                 and self.embed_dims % 4 == 0)
 
     def cache_and_assign_ids(self, instance_feature, anchor, confidence, metas=None, threshold=None, hold=None, sticky=None,
-                             active=None):
+                             active=None, restart=None):
         """cache() followed by get_instance_id() (simpb_head.py:744-747) on the persistent state, as two
         launches (csrc/bank.hip). Returns the instance ids, or None when the fused route does not apply
         (the caller then runs the two methods). `hold` (i32 flags on the device): when any is set the launches write
         nothing, i.e. the persistent state stays as the frame found it (an overflowed frame is re-run: runner.py). active
-        (u8 [bs] on the device): a stream with 0 keeps its state rows, gets ids -1 and takes no fresh ids."""
+        (u8 [bs] on the device): a stream with 0 keeps its state rows, gets ids -1 and takes no fresh ids. restart (u8 [bs] on
+        the device): a stream with a non-zero byte is ranked by its new scores alone, as cache() ranks with confidence None."""
         if not self._fusable(instance_feature) or instance_feature.shape[1] != self.num_anchor:
-            if active is not None:
-                raise ValueError("an activity mask needs the fused bank route (static state, routes.fused_bank)")
+            if active is not None or restart is not None:
+                raise ValueError("an activity mask / a restart needs the fused bank route (static state, routes.fused_bank)")
             return None
         st = self._static
         bs, a, c = instance_feature.shape
@@ -286,14 +292,15 @@ class InstanceBank(nn.Module):
         has_prev = self.confidence is not None
         # a batch of streams: one workgroup per stream (they meet once inside the launch); a batch of one: the serial kernel
         sync = self._sync if (bs > 1 and routes.R.bank_cache_per_stream and getattr(self, "_sync", None) is not None) else None
-        _lib.check(_lib.lib().simpb_bank_cache_streams_active(
+        _lib.check(_lib.lib().simpb_bank_cache_streams_restart(
             _ptr(st["confidence"]), _ptr(st["cached_feature"]), _ptr(st["cached_anchor"]), _ptr(st["instance_id"]),
             _ptr(st["prev_id"]), _ptr(ids_out), _ptr(scratch), _ptr(instance_feature.detach().contiguous().float()),
             _ptr(anchor.detach().contiguous().float()), _ptr(cls), bs, a, cls.shape[-1], t, c, 1 if has_prev else 0,
             float(self.confidence_decay), 0 if threshold is None else 1, 0.0 if threshold is None else float(threshold),
             _ptr(hold) if hold is not None else None, 0 if hold is None else hold.numel(),
             _ptr(sticky) if sticky is not None else None, _ptr(sync) if sync is not None else None,
-            _ptr(active) if active is not None else None, _stream()), "simpb_bank_cache")
+            _ptr(active) if active is not None else None, _ptr(restart) if restart is not None else None, _stream()),
+            "simpb_bank_cache")
         self.metas = metas
         self.confidence, self.cached_feature, self.cached_anchor = st["confidence"], st["cached_feature"], st["cached_anchor"]
         self.instance_id, self.prev_id = st["instance_id"], st["prev_id"]

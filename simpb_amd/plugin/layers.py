@@ -151,15 +151,22 @@ def mha_forward(attn, query, key, value, groups=None, same_qk=False, query_cam=N
 
 
 def fused_graph_attention(layer, pre, post, query, query_pos, key=None, key_pos=None, value=None, query_cam=None,
-                          group_start=None, m_live=None):
+                          group_start=None, m_live=None, restart=None):
     """graph_model / graph_model2d of the reference (simpb_head.py:298-321) around one attention
     operator, as three launches: a grouped GEMM for the q/k/v projections reading `query | query_pos`
     (and `key | key_pos`) in place with fc_before folded into the value rows, the flash attention
     core, and one GEMM for post(identity + out_proj(o)) reading `o | query | query_pos`
     (plugin/dense.py). Returns None when the call is not one of the forms the decoder uses, and the
-    caller takes the unfused route."""
+    caller takes the unfused route.
+
+    restart (u8 [bs] on the device, with a key only): a batch row with a non-zero byte is served as the call with
+    key = value = None serves it (the reference's cold frame, simpb_head.py:567-578: self-attention over its own `query`
+    rows with query_pos as key position, fc_before NOT applied) while the other rows attend `key`. A second key / value
+    projection -- the k and v rows of the fold without `pre` ("kv" = rows [E, 3E) of the cold frame's "qkv") over
+    `query | query_pos` -- is one more GEMM launch, and the attention core picks a set per row (ops.attention_select): a
+    restarted row reads nothing of `key`, and the other rows get the bits the call without `restart` gives them."""
     from . import dense
-    from .ops import attention_f32
+    from .ops import attention_f32, attention_select
     attn = getattr(layer, "attn", None)
     if (not isinstance(attn, nn.MultiheadAttention) or not getattr(layer, "batch_first", False)
             or not isinstance(post, nn.Linear) or post.bias is not None or query_pos is None
@@ -175,7 +182,7 @@ def fused_graph_attention(layer, pre, post, query, query_pos, key=None, key_pos=
     halfs = routes.R.attention_split_fp16
     qs = 1.0 / math.sqrt(64.0) if halfs else None
     if key is None:
-        if value is not None and value is not query:
+        if restart is not None or (value is not None and value is not query):
             return None
         w, b = dense.fold_mha_in(attn, pre if value is not None else None, "qkv", q_scale=qs)
         qkv = dense.linear([query, query_pos], w, b, m_live=m_live, split_halfs=halfs)
@@ -188,6 +195,15 @@ def fused_graph_attention(layer, pre, post, query, query_pos, key=None, key_pos=
         q, kv = dense.gemm(dense.job([query, query_pos], wq, bq, split_halfs=halfs),
                            dense.job([key, key_pos], wkv, bkv, split_halfs=halfs))
         k, v = kv[..., :e], kv[..., e:]
+        if restart is not None:
+            # A launch of its own, not a third job of the one above: the grouped GEMM picks its tile form from the tiles of
+            # the whole launch (csrc/gemm.hip), and another form sums in another order -- the streams that go on would part
+            # in the last bit from the frame without a restart.
+            wc, bc = dense.fold_mha_in(attn, None, "kv")   # (the k and v rows a cold frame's "qkv" fold projects with)
+            own = dense.linear([query, query_pos], wc, bc, split_halfs=halfs)
+            o = attention_select(q, k, v, own[..., :e], own[..., e:], restart, h, split=2 if halfs else 0)
+            wo, bo = dense.fold_mha_out(attn, post)
+            return dense.report(post, dense.linear([o, query, query_pos], wo, bo, m_live=m_live))
     o = attention_f32(q, k, v, h, query_cam, group_start, split=2 if halfs else 0)
     wo, bo = dense.fold_mha_out(attn, post)
     return dense.report(post, dense.linear([o, query, query_pos], wo, bo, m_live=m_live))

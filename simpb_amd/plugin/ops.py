@@ -399,6 +399,39 @@ def attention_f32(q, k, v, num_heads, query_cam=None, group_start=None, split=No
     return out
 
 
+def attention_select(q, k, v, k2, v2, select, num_heads, split=None):
+    """attention_f32 (ungrouped) with one of two key / value sets per batch row: row b attends (k, v) where select[b] == 0
+    and (k2, v2) otherwise (csrc/attention.hip simpb_attention_select). select: contiguous u8 [bs] on the device. Each
+    row's output is bit for bit attention_f32's on the set it selected; the other set is never read. split: as there."""
+    _require_gpu(q, k, v, k2, v2, select)
+    bs, nq, e = q.shape
+    hd = e // num_heads
+    if hd != 64 or e != num_heads * 64 or any(t.shape[2] != e or t.shape[0] != bs for t in (k, v, k2, v2)) \
+            or v.shape[1] != k.shape[1] or v2.shape[1] != k2.shape[1]:
+        raise ValueError("attention_select needs head_dim 64 and matching q/k/v widths")
+    if select.dtype != torch.uint8 or select.numel() != bs or not select.is_contiguous():
+        raise ValueError("attention_select: select must be a contiguous u8 [bs] tensor")
+
+    def rows(t):
+        n = t.shape[1]
+        if t.dtype != torch.float32:
+            t = t.float()
+        if t.stride(2) != 1 or (bs > 1 and t.stride(0) != n * t.stride(1)) or t.stride(1) % 4 or t.data_ptr() % 16:
+            t = t.contiguous()
+        return t, t.stride(1)
+
+    (q, ldq), (k, ldk), (v, ldv), (k2, ldk2), (v2, ldv2) = rows(q), rows(k), rows(v), rows(k2), rows(v2)
+    out = torch.empty(bs, nq, e, device=q.device, dtype=torch.float32)
+    if nq == 0:
+        return out
+    from . import routes
+    mode = (1 if routes.R.attention_split_fp16 else 0) if split is None else int(split)
+    _lib.check(_lib.lib().simpb_attention_select(mode, _ptr(out), _ptr(q), _ptr(k), _ptr(v), _ptr(k2), _ptr(v2), _ptr(select), bs,
+                                                 num_heads, hd, nq, k.shape[1], k2.shape[1], ldq, ldk, ldv, ldk2, ldv2, e,
+                                                 1.0 / (hd ** 0.5), _stream()), "simpb_attention_select")
+    return out
+
+
 def format_tokens(levels, bs, num_cams, biases=None):
     """feature_maps_format for channels_last level tensors [bs*cams, C, H, W] (f16 or f32), one
     pass (csrc/format.hip). Returns [col_feats, spatial_shape, scale_start_index] like

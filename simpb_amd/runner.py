@@ -72,6 +72,47 @@ def carry_inactive_metas(prev, metas, active):
     return out
 
 
+def restart_metas(prev, metas, restart):
+    """The `prev` a frame is staged against when some streams of the batch start over (step(..., restart=)). prev:
+    dict(img_metas=...) of the frame before; metas: this frame's; restart: one bool per stream. Returns a copy of `prev` in
+    which a restarted stream's img_metas entry is the stream's OWN current one: staged against it (stream_motion) the stream
+    gets dt = 0 and T_temp2cur = inv(T) @ T, and the pose and time stamp of whoever held the slot before are never read --
+    they may belong to another vehicle, in another global frame. Pure host function: nothing of `prev` or `metas` is modified."""
+    restart = [bool(r) for r in restart]
+    if len(restart) != len(metas["img_metas"]) or len(restart) != len(prev["img_metas"]):
+        raise ValueError(f"restart has {len(restart)} entries for {len(metas['img_metas'])} streams")
+    out = dict(prev)
+    out["img_metas"] = [m if r else p for r, m, p in zip(restart, metas["img_metas"], prev["img_metas"])]
+    return out
+
+
+def normalise_restart(restart, num_streams, active=None, cold=False, independent=True, supported=True):
+    """step / launch's `restart` -> None (no stream starts over: today's path) or a tuple of `num_streams` bools with a
+    True. restart: None, or one bool per stream; active: None or the frame's activity mask; cold: the frame is the runner's
+    first (every stream starts without history already: the flags are accepted and ignored); independent: the batch is a set
+    of independent streams (a batch of one always is); supported: the runner can restart a stream at all. Pure host function."""
+    if restart is None:
+        return None
+    flags = tuple(bool(r) for r in restart)
+    if len(flags) != num_streams:
+        raise ValueError(f"restart has {len(flags)} entries for {num_streams} streams")
+    if not any(flags):
+        return None
+    if not supported:
+        raise NotImplementedError("this runner cannot restart a stream: the single-frame part of the next frame is already in "
+                                  "flight when a restart would have to take effect (use FrameRunner or PipelinedRunner)")
+    if num_streams > 1 and not independent:
+        raise ValueError("restarting a stream of a batch needs independent_streams=True (the reference's batch pads the "
+                         "camera groups to the max over the batch: its streams are not independent)")
+    if active is not None:
+        if len(active) != num_streams:
+            raise ValueError(f"active has {len(active)} entries for {num_streams} streams")
+        both = [i for i, (r, a) in enumerate(zip(flags, active)) if r and not a]
+        if both:
+            raise ValueError(f"stream(s) {both} are paused and restarted in the same step: restart a stream in the step it resumes")
+    return None if cold else flags
+
+
 def normalise_cameras(cameras, num_streams, num_cams, active=None):
     """step / launch's `cameras` -> None (every camera of every stream that takes part delivered a frame: today's path) or
     a tuple of `num_streams` tuples of `num_cams` bools with a False somewhere. cameras: None, or one sequence of num_cams
@@ -108,6 +149,8 @@ class FrameInputs:
         active  u8 [bs]               1: the stream takes part
         cam     u8 [bs, cams]         1: the camera delivered a frame
         pose    f64 [bs, 14]          results.pose_row per stream; only with pose=True
+    and beside them `restart_host` / `restart_dev`, u8 [bs] (1: the stream starts over in this frame, restart_metas),
+    which are filled, uploaded and named in `metas` only on a warm frame that restarts a stream.
     The device buffers are allocated here and never replaced: captured graphs bake their addresses in. `fill` is pure host
     work, `upload` the frame's copies to the device, `metas` the dict the head reads them through."""
 
@@ -125,20 +168,29 @@ class FrameInputs:
             host = torch.full(shape, value, dtype=dtype)
             self.host[name] = host.pin_memory() if device.type == "cuda" else host
             self.dev[name] = torch.full(shape, value, dtype=dtype, device=device)
-        self.warm = self.masked = self.cam_masked = False   # of the frame last filled: what upload copies and metas names
+        host = torch.zeros(bs, dtype=torch.uint8)
+        self.restart_host = host.pin_memory() if device.type == "cuda" else host
+        self.restart_dev = torch.zeros(bs, dtype=torch.uint8, device=device)
+        self.warm = self.masked = self.cam_masked = self.restarting = False   # of the frame last filled: what upload copies and metas names
         self.uploaded = None                # event: the host buffers have been copied to the device and may be refilled
 
-    def fill(self, metas, prev, mask, cams, masked=False, cam_masked=False):
+    def fill(self, metas, prev, mask, cams, masked=False, cam_masked=False, restart=None):
         """One frame into the host buffers. metas: the frame's (paused streams already carried); prev: the metas of the
         frame before it (None: a cold frame, whose motion rows stay as they are); mask / cams: the frame's activity and
         camera masks (None: all ones); masked / cam_masked: the runner's graphs read the activity / camera buffer. A stream
-        whose img_metas entry lacks results.POSE_KEYS (a paused one) keeps the pose row it had."""
+        whose img_metas entry lacks results.POSE_KEYS (a paused one) keeps the pose row it had. restart: None or one bool
+        per stream with a True (normalise_restart); on a warm frame those streams' motion is staged against their own
+        metas (restart_metas) and the flags go to the head."""
         if self.uploaded is not None:
             self.uploaded.synchronize()     # the previous frame's copies out of these buffers (long done in practice)
         h = self.host
         proj = metas["projection_mat"]
         h["proj"].copy_(proj.cpu() if proj.is_cuda else proj)
         self.warm, self.masked, self.cam_masked = prev is not None, masked, cam_masked
+        self.restarting = self.warm and restart is not None
+        if self.restarting:
+            prev = restart_metas(prev, metas, restart)
+            self.restart_host.numpy()[:] = restart
         if self.warm:
             t, dt = stream_motion(metas, prev)
             h["t"].copy_(torch.from_numpy(t))
@@ -164,6 +216,8 @@ class FrameInputs:
             for name, dev in self.dev.items():
                 if live[name]:
                     dev.copy_(self.host[name], non_blocking=True)
+            if self.restarting:
+                self.restart_dev.copy_(self.restart_host, non_blocking=True)
             self.uploaded = torch.cuda.Event()
             self.uploaded.record(stream)
 
@@ -179,6 +233,8 @@ class FrameInputs:
             out["camera_valid"] = d["cam"]
         if "ti" in d:
             out["time_interval"] = d["ti"]
+        if self.restarting:
+            out["restart"] = self.restart_dev
         return out
 
 
@@ -265,9 +321,13 @@ class FrameRunner:
         self.prev_metas = None
         self.graph = None
         self.outputs = None
+        # the graph of a frame that restarts a stream (step(..., restart=)): the same frame with metas["restart"] read by the
+        # head. Captured at the first warm frame with a True, replayed on such frames only, dropped with the ordinary one
+        self.restart_graph = None
+        self.restart_outputs = None
         self.warm_frames = 0
         self.host3d = self.host2d = self.host_flag = None
-        self.stats = dict(eager=0, replay=0, overflow=0)
+        self.stats = dict(eager=0, replay=0, overflow=0)   # (+ "restart": frames that restarted a stream, from the first one on)
         self.last_rec3d = None      # device record f32 [bs, num_output, 15] of the frame last returned (dist.DetectionGather)
         self.last_rec2d = None      # ... and its 2D record f32 [bs, capacity, 8]
         # event after which those records may be overwritten (set by their consumer, if any). The records of a replayed
@@ -442,6 +502,7 @@ class FrameRunner:
         return bool(captured and routes.R.lean_refine2d)
 
     SUPPORTS_PAUSE = True
+    SUPPORTS_RESTART = True
 
     def _activity(self, active, cold):
         """step / launch's `active` -> None (every stream takes part: today's path) or a tuple of bs bools with a False."""
@@ -483,11 +544,12 @@ class FrameRunner:
             self.masked = True
         return carry_inactive_metas(dict(img_metas=prev["img_metas"], projection_mat=self.inputs.host["proj"]), metas, mask)
 
-    def _admit(self, prev, img, metas, active, cameras):
+    def _admit(self, prev, img, metas, active, cameras, restart=None):
         """What step / launch open with: the frame's activity mask, camera mask, metas (paused streams carried from `prev`,
-        the metas of the frame before) and checked frames. Everything that can refuse a frame does so here, before anything
-        is enqueued."""
+        the metas of the frame before), checked frames and restart flags. Everything that can refuse a frame does so here,
+        before anything is enqueued."""
         mask = self._activity(active, prev is None)
+        flags = normalise_restart(restart, self.bs, mask, prev is None, self.independent or self.bs == 1, self.SUPPORTS_RESTART)
         cams = self._camera_mask(cameras, mask)
         if mask is not None:
             metas = self._carry(prev, metas, mask)
@@ -495,21 +557,23 @@ class FrameRunner:
         if self.raw is not None:
             img = self._check_frames(img, mask, cams)   # (raw_surfaces: the tensors stay referenced until the frame is returned)
             self._ensure_plan(metas)
-        return mask, cams, metas, img
+        if flags is not None:
+            self.stats["restart"] = self.stats.get("restart", 0) + 1
+        return mask, cams, metas, img, flags
 
-    def _fill_inputs(self, inputs, metas, prev, mask, cams):
+    def _fill_inputs(self, inputs, metas, prev, mask, cams, restart=None):
         """The frame's decoder inputs into `inputs` (host side) -> the metas dict the head reads them through."""
         self.inputs = inputs
-        inputs.fill(metas, prev, mask, cams, self.masked, self.cam_masked)
+        inputs.fill(metas, prev, mask, cams, self.masked, self.cam_masked, restart)
         return inputs.metas(metas["img_metas"], self.wh, self.wh_host)
 
-    def _stage(self, img, metas, mask=None, cams=None):
+    def _stage(self, img, metas, mask=None, cams=None, restart=None):
         """Copy this frame's inputs into the static device buffers (a few small async copies); returns the head's metas."""
         if self.raw is None:
             self.img.copy_(img, non_blocking=True)
         else:
             self._stage_frames(self.raw, img, self.pin_table)
-        dmetas = self._fill_inputs(self.inputs, metas, self.prev_metas, mask, cams)
+        dmetas = self._fill_inputs(self.inputs, metas, self.prev_metas, mask, cams, restart)
         self.inputs.upload(torch.cuda.current_stream())
         return dmetas
 
@@ -542,7 +606,7 @@ class FrameRunner:
 
     # ------------------------------------------------------------------ capacity overflow
     def _drop_graphs(self):
-        self.graph = self.outputs = None
+        self.graph = self.outputs = self.restart_graph = self.restart_outputs = None
 
     def _drop_all_graphs(self):
         self._drop_graphs()
@@ -580,7 +644,7 @@ class FrameRunner:
 
     # ------------------------------------------------------------------ public
     @torch.no_grad()
-    def step(self, img, metas, force_eager=False, active=None, cameras=None):
+    def step(self, img, metas, force_eager=False, active=None, cameras=None, restart=None):
         """One frame for all streams: img f32 [bs, cams, 3, H, W] (device; u8 [bs, cams, Hs, Ws, 3] with raw_input, u8
         [bs, cams, Hs * 3 / 2, Ws] with raw_format "nv12" / "nv21"), metas as the reference's
         test pipeline collects them (projection_mat, timestamp, img_metas with T_global/T_global_inv/
@@ -596,21 +660,39 @@ class FrameRunner:
         anything; f32: anything finite -- the backbone still runs on it) and its projection_mat row are ignored, its 2D
         list is empty, and bank, track ids, ego-motion and time step go on as ever: a camera that comes back simply takes
         part again. A cold frame may have missing cameras. A stream that takes part needs at least one camera (ValueError:
-        pause it instead); a paused stream's row is not looked at. An overflowed frame is re-run with its own mask."""
-        mask, cams, metas, img = self._admit(self.prev_metas, img, metas, active, cameras)
+        pause it instead); a paused stream's row is not looked at. An overflowed frame is re-run with its own mask.
+
+        restart: None, or one bool per stream; a stream with True begins anew in this frame -- another vehicle takes the
+        slot. It is decoded exactly as a fresh runner decodes its first frame (no cached instances in the temporal attention,
+        no merge, no confidence decay, track ids -1 before the frame assigns fresh ones from the batch's running counter,
+        the default time step), nothing the slot held before -- bank rows, the previous pose and time stamp, NaN included --
+        reaches this frame's outputs or the state it leaves, and the following frames are warm against this one. Every other
+        stream is decoded as if nothing had happened (only the values of its fresh ids move with the ids the restarted
+        stream takes). A batch needs independent_streams=True; a stream cannot be paused and restarted in one step, but is
+        restarted in the step it resumes; on the runner's first frame the flags are ignored (everything is cold); all True
+        restarts the whole batch. Frames with a True replay a graph set of their own, captured at the first such frame
+        (stats["restart"] counts them); None or all False is the ordinary frame and stages nothing new."""
+        mask, cams, metas, img, flags = self._admit(self.prev_metas, img, metas, active, cameras, restart)
         aug = metas["img_metas"][0]["aug_config"]
-        dmetas = self._stage(img, metas, mask, cams)
+        dmetas = self._stage(img, metas, mask, cams, flags)
         warm = self.prev_metas is not None
-        if warm and self.use_graph and not force_eager and self.graph is None and self.warm_frames >= 1:
+        graph, outputs = (self.graph, self.outputs) if flags is None else (self.restart_graph, self.restart_outputs)
+        if warm and self.use_graph and not force_eager and graph is None and self.warm_frames >= 1:
             torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_MODE), self._capturing():
-                self.outputs = self._frame(dmetas, aug, captured=True)
-        if warm and self.graph is not None and not force_eager:
+            if flags is not None:
+                self.head.prepare_restart()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode=CAPTURE_MODE), self._capturing():
+                outputs = self._frame(dmetas, aug, captured=True)
+            if flags is None:
+                self.graph, self.outputs = graph, outputs
+            else:
+                self.restart_graph, self.restart_outputs = graph, outputs
+        if warm and graph is not None and not force_eager:
             if self.rec_consumed is not None:
                 torch.cuda.current_stream().wait_event(self.rec_consumed)
-            self.graph.replay()
-            rec = self.outputs
+            graph.replay()
+            rec = outputs
             self.stats["replay"] += 1
         else:
             rec = self._frame(dmetas, aug)
@@ -637,7 +719,7 @@ class FrameRunner:
 @dataclass
 class Job:
     """A decoder in flight. It keeps what a re-run (_finish) stages again: the frame's metas, the metas of the frame before
-    (None: a cold frame) and the frame's own activity and camera masks."""
+    (None: a cold frame) and the frame's own activity and camera masks and restart flags."""
     slot: int
     metas: dict
     prev: dict
@@ -646,6 +728,7 @@ class Job:
     active: tuple
     cameras: tuple
     surfaces: list      # raw_surfaces: the frame's tensors, held until its results have been returned
+    restart: tuple = None
 
 
 class PipelinedRunner(FrameRunner):
@@ -697,6 +780,8 @@ class PipelinedRunner(FrameRunner):
         self.head_graph = [None, None]
         self.head_out = [None, None]
         self.head_runs = [0, 0]
+        self.restart_graph = [None, None]   # per slot: the decoder graph of a frame that restarts a stream (FrameRunner.step)
+        self.restart_out = [None, None]
         self.count = 0
         n_alloc = sum(op == "allocation" for op in self.head.operation_order)
         self.flags = torch.zeros(2, n_alloc, dtype=torch.int32, device=dev)   # overflow flags, one row per feature slot
@@ -714,7 +799,7 @@ class PipelinedRunner(FrameRunner):
                 with torch.cuda.graph(g, stream=self.s_bb, capture_error_mode=CAPTURE_MODE), self._capturing():
                     self.bb_out[slot] = self._features(slot)
                 self.bb_graph[slot] = g
-                self.head_graph[slot] = None  # a decoder graph bound to the old buffer is stale
+                self.head_graph[slot] = self.restart_graph[slot] = None  # a decoder graph bound to the old buffer is stale
                 self.head_runs[slot] = 0
             if self.bb_graph[slot] is not None and not force_eager:
                 self.bb_graph[slot].replay()
@@ -739,6 +824,7 @@ class PipelinedRunner(FrameRunner):
 
     def _drop_graphs(self):
         self.head_graph, self.head_out, self.head_runs = [None, None], [None, None], [0, 0]
+        self.restart_graph, self.restart_out = [None, None], [None, None]
 
     def _drop_all_graphs(self):
         self._drop_graphs()
@@ -755,17 +841,21 @@ class PipelinedRunner(FrameRunner):
         with torch.cuda.stream(self.s_head):
             graph_ok = (self.use_graph and not force_eager and warm and self.bb_graph[slot] is not None
                         and self.fm[slot] is self.bb_out[slot])
-            if graph_ok and self.head_graph[slot] is None and self.head_runs[slot] >= 1:
+            # a frame that restarts a stream has a graph of its own per slot, captured at the first such frame of the slot
+            graphs, outs = (self.restart_graph, self.restart_out) if "restart" in dmetas else (self.head_graph, self.head_out)
+            if graph_ok and graphs[slot] is None and self.head_runs[slot] >= 1:
                 self.s_head.synchronize()
+                if "restart" in dmetas:
+                    self.head.prepare_restart()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=self.s_head, capture_error_mode=CAPTURE_MODE):
-                    self.head_out[slot] = self._decode(slot, dmetas, aug, inputs, captured=True)
-                self.head_graph[slot] = g
-            if graph_ok and self.head_graph[slot] is not None:
+                    outs[slot] = self._decode(slot, dmetas, aug, inputs, captured=True)
+                graphs[slot] = g
+            if graph_ok and graphs[slot] is not None:
                 if self.rec_consumed is not None:  # the record buffer of this graph may still be read by its consumer
                     self.s_head.wait_event(self.rec_consumed)
-                self.head_graph[slot].replay()
-                rec = self.head_out[slot]
+                graphs[slot].replay()
+                rec = outs[slot]
                 self.stats["replay"] += 1
             else:
                 rec = self._decode(slot, dmetas, aug, inputs)
@@ -786,20 +876,20 @@ class PipelinedRunner(FrameRunner):
             done.record(self.s_head)
         return done
 
-    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None, cams=None, surfaces=None):
+    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None, cams=None, surfaces=None, restart=None):
         """Stage the inputs of the frame whose features sit in `slot` and enqueue its decoder + read-back (_run_head)."""
         self.prev_metas = prev   # (what the base class's helpers look at)
         inputs = self.slot_inputs[slot]
-        dmetas = self._fill_inputs(inputs, metas, prev, mask, cams)
+        dmetas = self._fill_inputs(inputs, metas, prev, mask, cams, restart)
         rec = self._run_head(slot, inputs, dmetas, metas["img_metas"][0]["aug_config"], prev is not None, force_eager)
-        return Job(slot, metas, prev, rec, self._enqueue_readback(slot, rec), mask, cams, surfaces)
+        return Job(slot, metas, prev, rec, self._enqueue_readback(slot, rec), mask, cams, surfaces, restart)
 
     @torch.no_grad()
-    def launch(self, img, metas, force_eager=False, active=None, cameras=None):
+    def launch(self, img, metas, force_eager=False, active=None, cameras=None, restart=None):
         """Enqueue backbone(t) and decoder(t) without waiting for either (several runners -- several independent
-        camera streams on one GPU -- can be launched back to back and collected after). img, active, cameras: as
-        FrameRunner.step."""
-        mask, cams, metas, img = self._admit(self.last_metas, img, metas, active, cameras)
+        camera streams on one GPU -- can be launched back to back and collected after). img, active, cameras, restart: as
+        FrameRunner.step (an overflowed frame, and the one enqueued behind it, are re-run each with its own flags)."""
+        mask, cams, metas, img, flags = self._admit(self.last_metas, img, metas, active, cameras, restart)
         slot = self.count % 2
         cur = torch.cuda.current_stream()
         self.s_bb.wait_stream(cur)
@@ -819,7 +909,8 @@ class PipelinedRunner(FrameRunner):
         self.bb_done[slot].record(self.s_bb)
         self.s_head.wait_event(self.bb_done[slot])
         prev = dict(img_metas=self.last_metas["img_metas"]) if self.last_metas is not None else None
-        self.queue.append(self._enqueue_decoder(slot, metas, prev, force_eager, mask, cams, img[1] if self.surfaces else None))
+        self.queue.append(self._enqueue_decoder(slot, metas, prev, force_eager, mask, cams, img[1] if self.surfaces else None,
+                                                flags))
         self.last_metas = metas
         self.count += 1
 
@@ -853,7 +944,7 @@ class PipelinedRunner(FrameRunner):
 
     def _rerun(self, job):
         """The same frame again, eagerly, with its own masks (and its surfaces still held)."""
-        return self._enqueue_decoder(job.slot, job.metas, job.prev, True, job.active, job.cameras, job.surfaces)
+        return self._enqueue_decoder(job.slot, job.metas, job.prev, True, job.active, job.cameras, job.surfaces, job.restart)
 
     def _quiesce(self):
         self.s_head.synchronize()
@@ -869,9 +960,9 @@ class PipelinedRunner(FrameRunner):
             return None
         return self._finish(self.queue.pop(0))
 
-    def step(self, img, metas, force_eager=False, active=None, cameras=None):
+    def step(self, img, metas, force_eager=False, active=None, cameras=None, restart=None):
         """Feed frame t; returns the detections of frame t-1 (None on the very first call)."""
-        self.launch(img, metas, force_eager, active, cameras)
+        self.launch(img, metas, force_eager, active, cameras, restart)
         return self.collect()
 
     @torch.no_grad()
@@ -901,9 +992,12 @@ class SplitPipelinedRunner(PipelinedRunner):
         backbone stream, so no tensor of the caching allocator crosses streams.
 
     This is the single-stream form: it takes no paused streams (pausing its one stream means not calling step). It does
-    take `cameras`: the camera mask is one more per-frame decoder input with a device buffer per feature slot."""
+    take `cameras`: the camera mask is one more per-frame decoder input with a device buffer per feature slot. It cannot
+    restart its stream (`restart=` with a True raises NotImplementedError): part A of a frame starts from the learned anchors
+    and is in flight, with the time step staged for it, before the temporal part it would have to tell to start cold."""
 
     SUPPORTS_PAUSE = False
+    SUPPORTS_RESTART = False
     SLOT_INPUTS = True
 
     def __init__(self, *args, **kwargs):
