@@ -1,7 +1,7 @@
 // 1x1 convolution of the fp16 channels_last backbone with its whole epilogue in one launch:
 //   y[p, :] = relu?( x[pixel(p), :] . W^T + bias (+ residual[p, :]) )        fp16 in / out, fp32 accumulate
 // 36 of the 53 convolutions of ResNet50 and the four FPN lateral convolutions are 1x1
-// (/root/reference/projects/configs/simpb_nus_r50_img_704x256.py:79-99: mmdet ResNet style="pytorch" + FPN).
+// (mmdet ResNet style="pytorch" + FPN).
 // After conv-BN folding (tools/fuse_conv_bn.py:10-48) each is a vendor convolution (12-30 us at 6 x 256 x 704)
 // followed by an in-place bias / residual / ReLU pass over the activation map (csrc/bias_act.hip, 3-20 us):
 // the map is written, read again with the residual and written again. These layers are bound by exactly that
@@ -17,9 +17,8 @@
 // it measured faster (tools/bench_conv1x1.py); this kernel keeps the short ones and the input-side epilogue.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
-#include <type_traits>
 #include "../../include/simpb_hip.h"
-#include "mfma_f16.h"
+#include "conv_parts.h"
 
 extern "C" int simpb_check_launch(void);
 // csrc/conv3x3.hip: the same convolution through its staged pipeline (TAPS = 1)
@@ -29,21 +28,9 @@ extern "C" int simpb_conv_pointwise_staged(void* y, const void* x, const void* w
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using h16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using namespace simpb::conv;   // vector types, BN / BK / LDH / LDC / kThreads, pixel split, epilogue parts
 
-constexpr int BM = 128, BN = 64, BK = 64;
-constexpr int LDH = BK + 8;   // halfs per staged row (144 B): conflict-free 16-lane groups for ds_read_b128
-constexpr int LDC = BN + 1;   // floats per row of the epilogue tile
-constexpr int kThreads = 256;
-
-// pixel index of output pixel p = (n, ho, wo) in a residual map of HALF the size, read with nearest-neighbour 2x
-// upsampling (F.interpolate(mode="nearest") of an exact 2x: source = floor(dst / 2)): the FPN top-down path
-__device__ __forceinline__ int up2(int p, int Ho, int Wo) {
-  const int n = p / (Ho * Wo), rem = p - n * (Ho * Wo);
-  const int ho = rem / Wo, wo = rem - ho * Wo;
-  return (n * (Ho >> 1) + (ho >> 1)) * (Wo >> 1) + (wo >> 1);
-}
+constexpr int BM = 128;
 
 __global__ __launch_bounds__(kThreads) void conv1x1_f16_kernel(_Float16* __restrict__ y, const _Float16* __restrict__ x,
                                                                const _Float16* __restrict__ w, const _Float16* __restrict__ bias,
@@ -70,9 +57,8 @@ __global__ __launch_bounds__(kThreads) void conv1x1_f16_kernel(_Float16* __restr
   for (int i = 0; i < NA; ++i) {
     int p = min(p0 + sr + RS * i, P_out - 1);
     if (stride != 1) {  // output pixel (n, ho, wo) reads input pixel (n, ho * stride, wo * stride)
-      const int n = p / (Ho * Wo), rem = p - n * (Ho * Wo);
-      const int ho = rem / Wo, wo = rem - ho * Wo;
-      p = (n * H + ho * stride) * W + wo * stride;
+      const Pixel q = split_pixel(p, Ho, Wo);
+      p = (q.n * H + q.ho * stride) * W + q.wo * stride;
     }
     arow[i] = (size_t)p * Cin + sc;
   }
@@ -108,10 +94,7 @@ __global__ __launch_bounds__(kThreads) void conv1x1_f16_kernel(_Float16* __restr
   };
 
   f32x16 acc[2];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
+  zero_acc(acc);
 
   auto multiply = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -125,79 +108,50 @@ __global__ __launch_bounds__(kThreads) void conv1x1_f16_kernel(_Float16* __restr
     }
   };
 
-  // the residual pieces this thread will add in the epilogue are requested first, so that their round trip
-  // is over by the time the (short: Cin / 64 chunks) K loop ends
-  const bool full = c0 + BN <= Cout;
-  h16x8 rres[4];
-  if (residual && full) {
+  // the residual pieces this thread will add in the epilogue (piece lane + 64 * i of its wave's 32 rows, the map of
+  // tile_pieces) are requested first, so that their round trip is over by the time the (short: Cin / 64 chunks) K loop
+  // ends; zeros where there is no residual
+  const int pw = p0 + wave * 32;
+  const int cl = c0 + (lane & 7) * 8;   // 8 pieces to a row: every piece of this lane is the same eight channels
+  h16x8 rres[4] = {};
+  if (residual && cl < Cout) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int idx = tid + i * kThreads;
-      int p = min(p0 + (idx >> 3), P_out - 1);
-      if (res_up) p = up2(p, Ho, Wo);
-      rres[i] = *reinterpret_cast<const h16x8*>(residual + (size_t)p * Cout + c0 + (idx & 7) * 8);
+      int p = min(pw + ((lane + 64 * i) >> 3), P_out - 1);
+      if (res_up) p = up2_row(p, Ho, Wo);
+      rres[i] = *reinterpret_cast<const h16x8*>(residual + (size_t)p * Cout + cl);
     }
   }
 
-  fetch(std::integral_constant<int, 0>{}, 0);
-  fetch(std::integral_constant<int, 1>{}, 1);
+  fetch(IC<0>{}, 0);
+  fetch(IC<1>{}, 1);
   for (int c = 0; c < nchunks; c += 2) {
     __syncthreads();
-    stash(std::integral_constant<int, 0>{}, c);
+    stash(IC<0>{}, c);
     __syncthreads();
-    fetch(std::integral_constant<int, 0>{}, c + 2);
+    fetch(IC<0>{}, c + 2);
     multiply();
     if (c + 1 < nchunks) {
       __syncthreads();
-      stash(std::integral_constant<int, 1>{}, c + 1);
+      stash(IC<1>{}, c + 1);
       __syncthreads();
-      fetch(std::integral_constant<int, 1>{}, c + 3);
+      fetch(IC<1>{}, c + 3);
       multiply();
     }
   }
 
-  // accumulators -> LDS (C/D layout: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5))
+  // epilogue: each wave's 32 x 64 sums through its own fp32 tile, back as 16-byte pieces of rows (Cout is a multiple of 8:
+  // a piece lies inside the channels or outside them, never across)
+  float* mine = s_c + wave * 32 * LDC;
   __syncthreads();  // every wave is done reading the last staged chunk
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s_c[(wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * kb) * LDC + n * 32 + r32] = acc[n][r];
+  acc_to_tile<2, LDC>(mine, acc, r32, kb);
   __syncthreads();
-  // epilogue in 16-byte pieces: 128 rows x 8 pieces -> 4 per thread
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int idx = tid + i * kThreads;
-    const int r = idx >> 3, c8 = (idx & 7) * 8;
-    const int p = p0 + r;
-    if (p >= P_out) continue;
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = s_c[r * LDC + c8 + e];
-    if (full) {
-      const h16x8 bv = *reinterpret_cast<const h16x8*>(bias + c0 + c8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] += (float)bv[e];
-      if (residual) {
-        const h16x8 rv = rres[i];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += (float)rv[e];
-      }
-      h16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (_Float16)(relu ? fmaxf(v[e], 0.f) : v[e]);
-      *reinterpret_cast<h16x8*>(y + (size_t)p * Cout + c0 + c8) = o;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int c = c0 + c8 + e;
-        if (c < Cout) {
-          float t = v[e] + (float)bias[c];
-          if (residual) t += (float)residual[(size_t)(res_up ? up2(p, Ho, Wo) : p) * Cout + c];
-          y[(size_t)p * Cout + c] = (_Float16)(relu ? fmaxf(t, 0.f) : t);
-        }
-      }
-    }
-  }
+  if (cl >= Cout) return;
+  const h16x8 bv = *reinterpret_cast<const h16x8*>(bias + cl);
+  tile_pieces<2, LDC>(mine, 0, lane, [&](int i, int r, int, const float (&v)[8]) __attribute__((always_inline)) {
+    const int p = pw + r;
+    if (p < P_out) *reinterpret_cast<h16x8*>(y + (size_t)p * Cout + cl) = finish_piece(v, bv, rres[i], relu);
+  });
 }
 
 }  // namespace

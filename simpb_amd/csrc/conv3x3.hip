@@ -1,48 +1,59 @@
 // 3x3 convolution (padding 1, stride 1 or 2) of the fp16 channels_last backbone as an implicit GEMM with its epilogue in
 // the launch:   y[n, ho, wo, :] = relu?( sum_{dy,dx} x[n, ho*s + dy - 1, wo*s + dx - 1, :] . W[:, dy, dx, :]^T + bias )
-// These are conv2 of every ResNet bottleneck and the four output convolutions of the FPN
-// (/root/reference/projects/configs/simpb_nus_r50_img_704x256.py:79-99: mmdet ResNet style="pytorch" + FPN), after conv-BN
-// folding (tools/fuse_conv_bn.py:10-48). Round 1 left them to the vendor library. Round 2 found two reasons not to:
-//  * MIOpen's fastest choice for several of these shapes is a composable-kernel XDL kernel built on the gfx950 double-K FP16
-//    matrix instruction, which makes other kernels' vector arithmetic go wrong while it runs; with those
-//    solvers off it falls back to split-K assembly kernels that need a zero-fill launch in front and a bias/ReLU pass behind;
-//  * the FPN's output convolutions can write the decoder's fp32 token buffer themselves (`tokens` below), which removes the
-//    separate format pass (46 MB read + 92 MB written per frame).
+// These are conv2 of every ResNet bottleneck and the four output convolutions of the FPN (mmdet ResNet style="pytorch" + FPN)
+// after conv-BN folding (tools/fuse_conv_bn.py). The FPN's output convolutions write the decoder's token buffer themselves
+// (`tok`, `tok16` below): no separate format pass.
 //
 // GEMM view: M = output pixels, N = output channels, K = 9 taps x Cin walked tap by tap in chunks of 64 input channels.
-// The MFMA contraction does not care WHICH eight k-values a lane brings as long as both operands agree, so lane
-// (row r32, half kb) of a wave takes channels [32*kb, 32*kb + 32) of the chunk: its four 16-byte loads are 64 contiguous
-// bytes of ITS pixel's row, and the A operand goes global -> registers directly -- no staging of the (nine times re-read)
-// activations through LDS, no barrier for them; a tap outside the image is read from the pixel's own centre (always in
-// bounds) and zeroed when it is consumed. Weights as PyTorch keeps a channels_last convolution weight: [Cout][3][3][Cin], i.e.
-// row-major [Cout][K] in exactly this chunk order. Two ways to share the work among the 4 waves of a workgroup:
-//  * MSPLIT (large maps): waves tile M (32*AF pixels x 64 channels each); the 64 x 64 weight chunk is shared through a
-//    double-buffered LDS stage (one barrier per chunk), three register sets of A in flight;
-//  * KSPLIT (small maps, long K: stages 3-4, coarse FPN levels): all four waves own the SAME 32*AF x 64 tile and take every
-//    fourth chunk; both operands straight from global memory, no LDS and no barrier in the loop, one LDS meeting at the end.
-//    M = 1 056 pixels (8 x 22 x 6 cameras) still yields 264 workgroups.
-// Both direct forms are bound by their load instructions (32 lines each); with Cin >= 256 the small maps run the staged
-// pipeline below at 64 x 64, K split over groups of waves inside the workgroup where the grid is small (KS).
-// The large maps run the staged pipeline, and at stride 1 with Cin 64 / 128 / 256 its resident form: the 2-D tile of input
-// pixels with its halo goes to LDS once and the taps are addresses into it (conv_resident_tile, further below).
-// FP16 matrix step = two v_mfma_f32_32x32x8f16 (csrc/mfma_f16.h; never the gfx950 double-K instruction).
+// Weights as PyTorch keeps a channels_last convolution weight: [Cout][3][3][Cin], i.e. row-major [Cout][K] in this chunk order.
+//
+//  variant  kernel                                       tile px x ch   waves    variant 0 runs it                  its bits are those of
+//  1        conv3x3_f16_kernel<1, false>                 128 x 64       4 (M)    choose_variant                     1, 2, 9
+//  2        conv3x3_f16_kernel<2, false>                 256 x 64       4 (M)    never (tests, tuning tools)        1, 2, 9
+//  3        conv3x3_f16_kernel<1, true>                  32 x 64        4 (K)    choose_variant, the smallest maps  3, 4, 11
+//  4        conv3x3_f16_kernel<2, true>                  64 x 64        4 (K)    choose_variant                     3, 4, 11
+//  5        conv_staged_kernel<128, 64, 4, 1>            128 x 64       4 x 1    never                              5-8, 12, 13
+//  6        conv_staged_kernel<128, 128, 2, 2>           128 x 128      2 x 2    choose_variant, >= 2048 tiles      5-8, 12, 13
+//  7        conv_staged_kernel<96, 64, 3, 1>             96 x 64        3 x 1    choose_variant                     5-8, 12, 13
+//  8        conv_staged_kernel<96, 128, 1, 4>            96 x 128       1 x 4    choose_variant; the group launch   5-8, 12, 13
+//  9        conv_staged_ksplit_kernel<64, 64, 2, 2, 1>   64 x 64        2 x 2    choose_variant, Cin, Cout >= 256   1, 2, 9
+//  10       conv_staged_ksplit_kernel<64, 64, 2, 2, 2>   64 x 64        2 x 2 x 2  never                            its own
+//  11       conv_staged_ksplit_kernel<64, 64, 2, 2, 4>   64 x 64        2 x 2 x 4  choose_variant, Cin, Cout >= 512 3, 4, 11
+//  12       conv_resident_kernel<Cin, 4, 64, 2, 2, 2>    4 x 16 x 64    2 x 2    choose_resident                    5-8, 12, 13
+//  13       conv_resident_kernel<Cin, 8, 128, 4, 2, 3>   8 x 16 x 128   4 x 2    choose_resident; the group launch  5-8, 12, 13
+// (the forms are stated once, as V1 .. V13 below; 1x1 convolutions run conv_staged_kernel with one tap: P0 .. P2.) Forms whose
+// bits agree add the same products in the same order with the same eight k-values in every matrix instruction, so variant 0's
+// choice between them changes no output.
+//
+// The direct forms (1-4): the MFMA contraction does not care WHICH eight k-values a lane brings as long as both operands agree,
+// so lane (row r32, half kb) of a wave takes channels [32*kb, 32*kb + 32) of the chunk: its four 16-byte loads are 64 contiguous
+// bytes of ITS pixel's row, and the A operand goes global -> registers directly; a tap outside the image is read from the
+// pixel's own centre (always in bounds) and zeroed when it is consumed. The 4 waves of a workgroup share the work two ways:
+//  * M split: waves tile M (32*AF pixels x 64 channels each); the 64 x 64 weight chunk is shared through a double-buffered
+//    LDS stage (one barrier per chunk), three register sets of A in flight;
+//  * K split: all four waves own the SAME 32*AF x 64 tile and take every fourth chunk; both operands straight from global
+//    memory, no LDS and no barrier in the loop, one LDS meeting at the end.
+// Both are bound by their load instructions (a wave-instruction touches 32 different lines); the staged and resident forms
+// further below load whole lines.
+//
+// No double-K MFMA: the FP16 matrix step is two v_mfma_f32_32x32x8f16 (csrc/mfma_f16.h). The gfx950 double-K FP16 instruction
+// makes other kernels' vector arithmetic go wrong while it runs, which is also why these convolutions
+// are not left to the vendor library, whose fastest kernels for these shapes are built on it.
+// Loads are pinned where they are written (sched_barrier): left to itself the scheduler sinks them to the end of the matrix
+// work in front of their use, and the wait for them then drains the queue.
+// LDS pitches: a staged chunk row is LDH = 72 halfs (144 B, an odd number of 16-byte slots: conflict-free 16-lane groups for
+// ds_read_b128); a wave's fp32 epilogue tile has an odd pitch in floats (LDC, 32 * NF + 1); the resident halo: see there.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
-#include <type_traits>
 #include "../../include/simpb_hip.h"
-#include "mfma_f16.h"
+#include "conv_parts.h"
 
 extern "C" int simpb_check_launch(void);
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using h16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using namespace simpb::conv;   // vector types, BN / BK / LDH / LDC / kThreads, pixel split, epilogue parts
 
-constexpr int BN = 64, BK = 64;
-constexpr int LDH = BK + 8;   // halfs per staged weight row (144 B): conflict-free 16-lane groups for ds_read_b128
-constexpr int LDC = BN + 1;   // floats per row of the epilogue tile
-constexpr int kThreads = 256;
 constexpr int kStageBytes = 2 * BN * LDH * 2;        // two weight chunks
 constexpr int kTileBytes = 4 * 32 * LDC * 4;         // one 32 x 64 fp32 tile per wave
 constexpr int kSmemBytes = kStageBytes > kTileBytes ? kStageBytes : kTileBytes;
@@ -60,70 +71,51 @@ struct ConvArgs {
   int tiles_w, tiles_h;   // resident form: 2-D tiles across and down one image (gx = images x tiles_h x tiles_w)
 };
 
-template <int S>
-using IC = std::integral_constant<int, S>;
+// Several convolutions of one form in ONE launch (the FPN's four output convolutions: 240 us as four launches, of which
+// the three small levels -- 352, 88 and 22 tiles -- leave most of the chip idle for 97 us; in one launch their tiles fill
+// the last round of the large level's 1 408). Problem j owns the tiles [start[j], start[j + 1]) of one XCD-contiguous walk.
+constexpr int kMaxConvGroup = 4;
+struct ConvGroup {
+  ConvArgs a[kMaxConvGroup];
+  int start[kMaxConvGroup + 1];
+  int n, per_xcd;
+};
+__device__ __forceinline__ int group_problem(const ConvGroup& g, int gt) {
+  int j = 0;
+#pragma unroll
+  for (int t = 1; t < kMaxConvGroup; ++t)
+    if (t < g.n && gt >= g.start[t]) j = t;
+  return j;
+}
 
-// one 16-byte piece of an output row: bias, ReLU, one rounding to fp16; to the f16 map or, widened, to the token buffer.
+// one 16-byte piece of an output row (channels c0 + c8 .. + 7 of pixel p; Cout is a multiple of 8, so a piece lies inside
+// the channels or outside them, never across): the epilogue element, then to the f16 map or, widened, to the token buffer.
 // TOK16 (a kernel's template argument): the launch writes the f16 token rows alone (tok == NULL, tok16 set) -- the fp32
 // conversions and stores are not in that kernel at all
 template <bool TOK16>
-__device__ __forceinline__ void emit_piece(const ConvArgs& a, int c0, bool full, int p, int c8, const float (&v)[8]) {
-  if (p >= a.P_out) return;
-  size_t trow = 0;
-  if (TOK16 || a.tok) {   // the FPN's output convolution writes the decoder's token row itself: the fp16 result, widened to fp32 or (TOK16) as it is
+__device__ __forceinline__ void emit_piece(const ConvArgs& a, int c0, int p, int c8, const float (&v)[8]) {
+  const int c = c0 + c8;
+  if (p >= a.P_out || c >= a.Cout) return;
+  const bool to_tokens = TOK16 || a.tok;   // the FPN's output convolution writes the decoder's token row itself
+  size_t row = p;                         // the piece's row in the map, or in the token buffer
+  if (to_tokens) {
     const int hw = a.Ho * a.Wo;
     const int n = p / hw, pix = p - n * hw;
-    trow = ((size_t)n * a.tokens_per_cam + a.level_start + pix) * a.Cout;
+    row = (size_t)n * a.tokens_per_cam + a.level_start + pix;
   }
-  size_t rrow = 0;
-  if (a.residual) {
-    int rp = p;
-    if (a.res_up) {   // F.interpolate(mode="nearest") of an exact 2x: source = floor(dst / 2) (the FPN top-down path)
-      const int hw = a.Ho * a.Wo;
-      const int n = p / hw, rem = p - n * hw;
-      const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
-      rp = (n * (a.Ho >> 1) + (ho >> 1)) * (a.Wo >> 1) + (wo >> 1);
+  const size_t at = row * a.Cout + c;
+  const h16x8 bv = *reinterpret_cast<const h16x8*>(a.bias + c);
+  h16x8 rv = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (a.residual) rv = *reinterpret_cast<const h16x8*>(a.residual + (size_t)(a.res_up ? up2_row(p, a.Ho, a.Wo) : p) * a.Cout + c);
+  const h16x8 o = finish_piece(v, bv, rv, a.relu);
+  if (!to_tokens) {
+    *reinterpret_cast<h16x8*>(a.y + at) = o;
+  } else {   // the fp16 result, widened to fp32 or (TOK16) as it is
+    if constexpr (!TOK16) {
+      *reinterpret_cast<float4*>(a.tok + at) = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
+      *reinterpret_cast<float4*>(a.tok + at + 4) = make_float4((float)o[4], (float)o[5], (float)o[6], (float)o[7]);
     }
-    rrow = (size_t)rp * a.Cout;
-  }
-  if (full) {
-    const h16x8 bv = *reinterpret_cast<const h16x8*>(a.bias + c0 + c8);
-    h16x8 rv = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (a.residual) rv = *reinterpret_cast<const h16x8*>(a.residual + rrow + c0 + c8);
-    h16x8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float t = v[e] + (float)bv[e] + (float)rv[e];
-      o[e] = (_Float16)(a.relu ? fmaxf(t, 0.f) : t);
-    }
-    if constexpr (TOK16) {
-      *reinterpret_cast<h16x8*>(a.tok16 + trow + c0 + c8) = o;
-    } else if (a.tok) {
-      float* d = a.tok + trow + c0 + c8;
-      *reinterpret_cast<float4*>(d) = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
-      *reinterpret_cast<float4*>(d + 4) = make_float4((float)o[4], (float)o[5], (float)o[6], (float)o[7]);
-      if (a.tok16) *reinterpret_cast<h16x8*>(a.tok16 + trow + c0 + c8) = o;
-    } else {
-      *reinterpret_cast<h16x8*>(a.y + (size_t)p * a.Cout + c0 + c8) = o;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int c = c0 + c8 + e;
-      if (c < a.Cout) {
-        float t = v[e] + (float)a.bias[c];
-        if (a.residual) t += (float)a.residual[rrow + c];
-        const _Float16 o = (_Float16)(a.relu ? fmaxf(t, 0.f) : t);
-        if constexpr (TOK16) {
-          a.tok16[trow + c] = o;
-        } else if (a.tok) {
-          a.tok[trow + c] = (float)o;
-          if (a.tok16) a.tok16[trow + c] = o;
-        } else {
-          a.y[(size_t)p * a.Cout + c] = o;
-        }
-      }
-    }
+    if (TOK16 || a.tok16) *reinterpret_cast<h16x8*>(a.tok16 + at) = o;
   }
 }
 
@@ -135,10 +127,9 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs
   constexpr int WROWS = 32 * AF;
   constexpr int BMt = KSPLIT ? WROWS : 4 * WROWS;
 
-  // each XCD (blockIdx % 8) walks a contiguous range of tiles, channel blocks of one pixel block next to each other:
-  // neighbouring tiles share their activation rows in that XCD's L2
-  const int tile = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= a.per_xcd || tile >= a.gx * a.gy) return;
+  // channel blocks of one pixel block are next to each other in an XCD's range: neighbouring tiles share their activation rows
+  const int tile = simpb::xcd_tile(a.per_xcd, a.gx * a.gy);
+  if (tile < 0) return;
   const int tx = tile / a.gy, ty = tile - tx * a.gy;
 
   const int tid = threadIdx.x;
@@ -156,12 +147,9 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs
   unsigned amask[AF];
 #pragma unroll
   for (int f = 0; f < AF; ++f) {
-    const int p = min(p0 + row0 + 32 * f + r32, a.P_out - 1);
-    const int hw = a.Ho * a.Wo;
-    const int n = p / hw, rem = p - n * hw;
-    const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
-    const int hc = ho * a.stride, wc = wo * a.stride;
-    actr[f] = a.x + ((size_t)(n * H + hc) * W + wc) * Cin + 32 * kb;
+    const Pixel q = split_pixel(min(p0 + row0 + 32 * f + r32, a.P_out - 1), a.Ho, a.Wo);
+    const int hc = q.ho * a.stride, wc = q.wo * a.stride;
+    actr[f] = a.x + ((size_t)(q.n * H + hc) * W + wc) * Cin + 32 * kb;
     unsigned m = 0;
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
@@ -222,12 +210,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs
   };
 
   f32x16 acc[AF][2];
-#pragma unroll
-  for (int f = 0; f < AF; ++f)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[f][n][r] = 0.f;
+  zero_acc(acc);
 
   auto multiply = [&](auto set_c, int buf) __attribute__((always_inline)) {
     constexpr int s = decltype(set_c)::value;
@@ -249,45 +232,32 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs
     }
   };
 
-  // the loads are pinned where they are written (sched_barrier): left to itself the scheduler sinks them to the end of the
-  // matrix work in front of their use, and the wait for them then drains the queue
   if constexpr (KSPLIT) {
     // wave w takes chunks w, w + 4, ...; three register sets in flight; chunks past the end are loaded from the last one
     // and contribute zeros (alive = 0)
     const int mine_n = (nchunks + 3) / 4;
+    auto step = [&](auto cur, auto nxt, int chunk) __attribute__((always_inline)) {
+      load_a(nxt, chunk);
+      load_b(nxt, chunk);
+      __builtin_amdgcn_sched_barrier(0);
+      multiply(cur, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    load_a(IC<0>{}, wave);
+    load_b(IC<0>{}, wave);
     if constexpr (AF == 1) {
-      const int iters = (mine_n + 2) / 3 * 3;
-      load_a(IC<0>{}, wave);
-      load_b(IC<0>{}, wave);
       load_a(IC<1>{}, wave + 4);
       load_b(IC<1>{}, wave + 4);
-      auto step = [&](auto cur, auto nxt2, int i) __attribute__((always_inline)) {
-        load_a(nxt2, wave + 4 * (i + 2));
-        load_b(nxt2, wave + 4 * (i + 2));
-        __builtin_amdgcn_sched_barrier(0);
-        multiply(cur, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      for (int i = 0; i < iters; i += 3) {
-        step(IC<0>{}, IC<2>{}, i);
-        step(IC<1>{}, IC<0>{}, i + 1);
-        step(IC<2>{}, IC<1>{}, i + 2);
+      for (int i = 0; i < (mine_n + 2) / 3 * 3; i += 3) {
+        step(IC<0>{}, IC<2>{}, wave + 4 * (i + 2));
+        step(IC<1>{}, IC<0>{}, wave + 4 * (i + 3));
+        step(IC<2>{}, IC<1>{}, wave + 4 * (i + 4));
       }
     } else {
       // 64 x 64 tile per wave: two register sets (a chunk is 16 matrix steps of cover)
-      const int iters = (mine_n + 1) / 2 * 2;
-      load_a(IC<0>{}, wave);
-      load_b(IC<0>{}, wave);
-      auto step = [&](auto cur, auto nxt, int i) __attribute__((always_inline)) {
-        load_a(nxt, wave + 4 * (i + 1));
-        load_b(nxt, wave + 4 * (i + 1));
-        __builtin_amdgcn_sched_barrier(0);
-        multiply(cur, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      for (int i = 0; i < iters; i += 2) {
-        step(IC<0>{}, IC<1>{}, i);
-        step(IC<1>{}, IC<0>{}, i + 1);
+      for (int i = 0; i < (mine_n + 1) / 2 * 2; i += 2) {
+        step(IC<0>{}, IC<1>{}, wave + 4 * (i + 1));
+        step(IC<1>{}, IC<0>{}, wave + 4 * (i + 2));
       }
     }
   } else {
@@ -317,54 +287,35 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs
     }
   }
 
-  // epilogue, one A fragment at a time: accumulators -> LDS (C/D layout: column = lane & 31,
-  // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)), then 16-byte pieces of full rows: bias, ReLU, one rounding to fp16
-  const bool full = c0 + BN <= a.Cout;
-  auto emit = [&](int p, int c8, const float (&v)[8]) __attribute__((always_inline)) { emit_piece<TOK16>(a, c0, full, p, c8, v); };
+  // epilogue, one A fragment at a time through the waves' fp32 tiles
   float* mine = s_c + wave * 32 * LDC;
 #pragma unroll
   for (int f = 0; f < AF; ++f) {
     __syncthreads();   // the weight stage (or the previous fragment's tile) is no longer read
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * kb) * LDC + n * 32 + r32] = acc[f][n][r];
+    acc_to_tile<2, LDC>(mine, acc[f], r32, kb);
     __syncthreads();
     if constexpr (KSPLIT) {
+      // the meeting of the K split: every thread adds one piece of the four waves' tiles, in a fixed order. (Not
+      // tile_pieces: there a WAVE walks all 32 rows; here the four waves share them.)
       const int r = tid >> 3, c8 = (tid & 7) * 8;
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         float s = 0.f;
 #pragma unroll
-        for (int w4 = 0; w4 < 4; ++w4) s += s_c[(w4 * 32 + r) * LDC + c8 + e];   // fixed order: deterministic
+        for (int w4 = 0; w4 < 4; ++w4) s += s_c[(w4 * 32 + r) * LDC + c8 + e];
         v[e] = s;
       }
-      emit(p0 + 32 * f + r, c8, v);
+      emit_piece<TOK16>(a, c0, p0 + 32 * f + r, c8, v);
     } else {
-#pragma unroll
-      for (int pass = 0; pass < 4; ++pass) {
-        const int r = (lane >> 3) + 8 * pass, c8 = (lane & 7) * 8;
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = mine[r * LDC + c8 + e];
-        emit(p0 + row0 + 32 * f + r, c8, v);
-      }
+      tile_pieces<2, LDC>(mine, 0, lane, [&](int, int r, int c8, const float (&v)[8]) __attribute__((always_inline)) {
+        emit_piece<TOK16>(a, c0, p0 + row0 + 32 * f + r, c8, v);
+      });
     }
   }
 }
 
-template <int AF, bool KSPLIT, bool TOK16>
-void launch(ConvArgs& a, hipStream_t stream) {
-  constexpr int BMt = KSPLIT ? 32 * AF : 128 * AF;
-  a.gx = (a.P_out + BMt - 1) / BMt;
-  a.gy = (a.Cout + BN - 1) / BN;
-  const long long total = (long long)a.gx * a.gy;
-  a.per_xcd = (int)((total + 7) / 8);
-  hipLaunchKernelGGL((conv3x3_f16_kernel<AF, KSPLIT, TOK16>), dim3((unsigned)(a.per_xcd * 8)), dim3(kThreads), 0, stream, a);
-}
-
-// ---- large maps: both operands staged through LDS with coalesced loads ------------------------------------------------------
+// ---- both operands staged through LDS with coalesced loads (variants 5-11, the 1x1 tilings) ------------------------------------
 // Reading A straight into the MFMA layout costs a wave-instruction 32 different 128-byte lines (one per pixel row, two lanes
 // each), and the texture path takes them a quad of lanes at a time: the direct kernels above top out near 430 TFLOP/s on the
 // 64 x 176 maps with the matrix cores half idle. Here 8 consecutive lanes load the 8 pieces of one pixel row (a
@@ -400,7 +351,7 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
   const int tid = threadIdx.x - grp * NT;
   const int lane = tid & 63, wave = tid >> 6;
   const int r32 = lane & 31, kb = lane >> 5;
-  const int wm = wave / WGN, wn = wave - wm * WGN;
+  const int wm = WGM == 1 ? 0 : wave / WGN, wn = wave - wm * WGN;   // (said outright for one row of waves: a register less)
   const int p0 = tx * BMt, c0 = ty * BNt;
   const int Cin = a.Cin, W = a.W, H = a.H;
   const int per_tap = Cin / BK, nchunks = TAPS * per_tap;
@@ -415,12 +366,9 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
   static_assert(NA <= 5, "6 mask bits per staged row in one register");
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
-    const int p = min(p0 + ((tid + NT * i) >> 3), a.P_out - 1);
-    const int hw = a.Ho * a.Wo;
-    const int n = p / hw, rem = p - n * hw;
-    const int ho = rem / a.Wo, wo = rem - ho * a.Wo;
-    const int hc = ho * a.stride, wc = wo * a.stride;
-    actr[i] = a.x + ((size_t)(n * H + hc) * W + wc) * Cin + sc;
+    const Pixel q = split_pixel(min(p0 + ((tid + NT * i) >> 3), a.P_out - 1), a.Ho, a.Wo);
+    const int hc = q.ho * a.stride, wc = q.wo * a.stride;
+    actr[i] = a.x + ((size_t)(q.n * H + hc) * W + wc) * Cin + sc;
     const unsigned rows = (hc > 0 ? 1u : 0u) | 2u | (hc + 1 < H ? 4u : 0u), cols = (wc > 0 ? 1u : 0u) | 2u | (wc + 1 < W ? 4u : 0u);
     amask |= (rows | (cols << 3)) << (6 * i);
   }
@@ -478,12 +426,7 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
   };
 
   f32x16 acc[AF][NF];
-#pragma unroll
-  for (int f = 0; f < AF; ++f)
-#pragma unroll
-    for (int n = 0; n < NF; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[f][n][r] = 0.f;
+  zero_acc(acc);
 
   auto multiply = [&](int buf) __attribute__((always_inline)) {
     constexpr int KLANE = DIRECTK ? 32 : 8, KSTEP = DIRECTK ? 8 : 16;   // halfs between the lane halves / the matrix steps
@@ -524,102 +467,52 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
     if ((TAPS == 9 && KS == 1) || c + 2 < nsteps) step(IC<2>{}, IC<0>{}, c + 2);
   }
 
-  // epilogue, one A fragment at a time through the wave's own 32 x (32 * NF) fp32 tile: 16-byte pieces of output rows
+  // epilogue, one A fragment at a time through the wave's own 32 x (32 * NF) fp32 tile
   float* mine = s_c + (grp * WGM * WGN + wave) * 32 * LDW;
   const int cw = c0 + wn * NF * 32;
-  const bool full = cw + 32 * NF <= a.Cout;
 #pragma unroll
   for (int f = 0; f < AF; ++f) {
     if (f) __syncthreads();
-#pragma unroll
-    for (int n = 0; n < NF; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * kb) * LDW + n * 32 + r32] = acc[f][n][r];
+    acc_to_tile<NF, LDW>(mine, acc[f], r32, kb);
     __syncthreads();
-    constexpr int PR = 4 * NF;            // pieces per row
     if (KS > 1 && grp) continue;          // K split: group 0 adds the partial tiles of its wave's place in every group
-#pragma unroll
-    for (int pass = 0; pass < 32 * PR / 64; ++pass) {
-      const int idx = lane + 64 * pass;
-      const int r = idx / PR, c8 = (idx % PR) * 8;
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = mine[r * LDW + c8 + e];
-      if constexpr (KS > 1) {
-#pragma unroll
-        for (int g = 1; g < KS; ++g)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += mine[(g * WGM * WGN * 32 + r) * LDW + c8 + e];
-      }
-      emit_piece<TOK16>(a, cw, full, p0 + (wm * AF + f) * 32 + r, c8, v);
-    }
+    tile_pieces<NF, LDW, KS>(mine, WGM * WGN * 32 * LDW, lane, [&](int, int r, int c8, const float (&v)[8]) __attribute__((always_inline)) {
+      emit_piece<TOK16>(a, cw, p0 + (wm * AF + f) * 32 + r, c8, v);
+    });
   }
 }
 
 template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
 __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 3 ? 3 : 2) void conv_staged_kernel(const ConvArgs a) {
-  // each XCD (blockIdx % 8) walks a contiguous range of tiles
-  const int tile = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= a.per_xcd || tile >= a.gx * a.gy) return;
+  const int tile = simpb::xcd_tile(a.per_xcd, a.gx * a.gy);
+  if (tile < 0) return;
   conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16>(a, tile);
 }
 
 // the small maps with long K (3x3 variants 9-11): KS groups of waves, the direct kernels' k map (their sums, bit for bit)
 template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16, int KS>
 __global__ __launch_bounds__(64 * WGM * WGN * KS, 2) void conv_staged_ksplit_kernel(const ConvArgs a) {
-  const int tile = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= a.per_xcd || tile >= a.gx * a.gy) return;
+  const int tile = simpb::xcd_tile(a.per_xcd, a.gx * a.gy);
+  if (tile < 0) return;
   conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16, KS, true>(a, tile);
 }
 
-// Several convolutions of one tile shape in ONE launch (the FPN's four output convolutions: 240 us as four launches, of which
-// the three small levels -- 352, 88 and 22 tiles -- leave most of the chip idle for 97 us; in one launch their tiles fill
-// the last round of the large level's 1 408). Problem j owns the tiles [start[j], start[j + 1]) of one XCD-contiguous walk.
-constexpr int kMaxConvGroup = 4;
-struct ConvGroup {
-  ConvArgs a[kMaxConvGroup];
-  int start[kMaxConvGroup + 1];
-  int n, per_xcd;
-};
 template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
 __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 3 ? 3 : 2) void conv_staged_group_kernel(const ConvGroup g) {
-  const int gt = (blockIdx.x & 7) * g.per_xcd + (blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= g.per_xcd || gt >= g.start[g.n]) return;
-  int j = 0;
-#pragma unroll
-  for (int t = 1; t < kMaxConvGroup; ++t)
-    if (t < g.n && gt >= g.start[t]) j = t;
+  const int gt = simpb::xcd_tile(g.per_xcd, g.start[g.n]);
+  if (gt < 0) return;
+  const int j = group_problem(g, gt);
   conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16>(g.a[j], gt - g.start[j]);
 }
 
-template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
-void launch_staged(ConvArgs& a, hipStream_t stream) {
-  a.gx = (a.P_out + BMt - 1) / BMt;
-  a.gy = (a.Cout + BNt - 1) / BNt;
-  const long long total = (long long)a.gx * a.gy;
-  a.per_xcd = (int)((total + 7) / 8);
-  hipLaunchKernelGGL((conv_staged_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16>), dim3((unsigned)(a.per_xcd * 8)), dim3(64 * WGM * WGN), 0,
-                     stream, a);
-}
-
-template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16, int KS>
-void launch_staged_ksplit(ConvArgs& a, hipStream_t stream) {
-  a.gx = (a.P_out + BMt - 1) / BMt;
-  a.gy = (a.Cout + BNt - 1) / BNt;
-  const long long total = (long long)a.gx * a.gy;
-  a.per_xcd = (int)((total + 7) / 8);
-  hipLaunchKernelGGL((conv_staged_ksplit_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16, KS>), dim3((unsigned)(a.per_xcd * 8)),
-                     dim3(64 * WGM * WGN * KS), 0, stream, a);
-}
-
-// ---- large maps, stride 1: the input tile stays in LDS (3x3 variants 12, 13) --------------------------------------------------
+// ---- stride 1: the input tile stays in LDS (3x3 variants 12, 13) --------------------------------------------------------------
 // The staged pipeline above stages the A tile once per chunk: nine taps x Cin / 64 times the same pixels, shifted by one tap.
 // Here a workgroup owns a 2-D tile of TH x 16 output pixels of ONE image (clipped at the image's border) and loads the
 // (TH + 2) x 18 input pixels under it, all Cin channels, into LDS once, with the same coalesced 16-byte loads (8 lanes per 128
 // bytes of a pixel's row); a pixel outside the image is written as zeros -- that is the padding, there are no per-tap masks.
 // A tap is then an address: fragment row r32 of a wave is output pixel (2 * fragment + r32 / 16, r32 % 16) of the tile, and
 // tap (dy, dx) reads input pixel (row + dy, column + dx) of the halo. Only the 64-channel weight chunks still go through an
-// LDS stage, one barrier per chunk as before (1 + 9 * Cin / 64 per tile of 128 pixels, the count of the 96-pixel staged tile).
+// LDS stage, one barrier per chunk (1 + 9 * Cin / 64 per tile of 128 pixels, the count of the 96-pixel staged tile).
 //  * All loads of the halo are issued at once, 64 channels (what one chunk reads) per slice; slice 0 is written to LDS in
 //    front of the first barrier, slice s > 0 during chunk s - 1: the first Cin / 64 chunks run while the rest is in flight.
 //  * The weight stage is a ring of THREE chunks: chunk c + 2 is written during chunk c, so chunk c + 1 is complete and
@@ -741,12 +634,7 @@ __device__ __forceinline__ void conv_resident_tile(const ConvArgs& a, const int 
   __syncthreads();
 
   f32x16 acc[AF][NF];
-#pragma unroll
-  for (int f = 0; f < AF; ++f)
-#pragma unroll
-    for (int n = 0; n < NF; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[f][n][r] = 0.f;
+  zero_acc(acc);
 
   // this lane's pixel of fragment 0 at tap (0, 0) and its weight row, its half of a 16-deep step
   const unsigned char* a_lane = smem + (wm * AF * 2 + (r32 >> 4)) * ROW + (r32 & 15) * PIX + 16 * kb;
@@ -819,36 +707,28 @@ __device__ __forceinline__ void conv_resident_tile(const ConvArgs& a, const int 
     step(S2{}, c + 2, true, true);
   }
 
-  // epilogue as in conv_staged_tile, the wave's fp32 tile over the halo (nobody reads it after the last barrier)
+  // epilogue as in conv_staged_tile, the wave's fp32 tile over the halo (nobody reads it after the last barrier); tile row r
+  // is output pixel (2 * fragment + r / 16, r % 16) of the 2-D tile
   float* mine = s_c + wave * 32 * LDW;
   const int cw = c0 + wn * NF * 32;
-  const bool full = cw + 32 * NF <= a.Cout;
 #pragma unroll
   for (int f = 0; f < AF; ++f) {
     if (f) __syncthreads();
-#pragma unroll
-    for (int n = 0; n < NF; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * kb) * LDW + n * 32 + r32] = acc[f][n][r];
+    acc_to_tile<NF, LDW>(mine, acc[f], r32, kb);
     __syncthreads();
-    constexpr int PR = 4 * NF;
-#pragma unroll
-    for (int pass = 0; pass < 32 * PR / 64; ++pass) {
-      const int idx = lane + 64 * pass;
-      const int r = idx / PR, c8 = (idx % PR) * 8;
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = mine[r * LDW + c8 + e];
+    tile_pieces<NF, LDW>(mine, 0, lane, [&](int, int r, int c8, const float (&v)[8]) __attribute__((always_inline)) {
       const int oy = y0 + (wm * AF + f) * 2 + (r >> 4), ox = x0 + (r & 15);
       const int p = oy < H && ox < W ? (img * H + oy) * W + ox : a.P_out;   // a clipped tile: nothing to write
-      emit_piece<TOK16>(a, cw, full, p, c8, v);
-    }
+      emit_piece<TOK16>(a, cw, p, c8, v);
+    });
   }
 }
 
 template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
 __global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char resident_smem[];
+  // simpb::xcd_tile, written out: through the function the Cin 64 form of variant 12 takes 66 registers for 64 and loses a
+  // wave per SIMD (profiles/conv_shared_parts.md, "What went back")
   const int tile = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
   if ((int)(blockIdx.x >> 3) >= a.per_xcd || tile >= a.gx * a.gy) return;
   conv_resident_tile<CIN, TH, BNt, WGM, WGN, RING, TOK16>(a, tile, resident_smem);
@@ -857,65 +737,156 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_kernel(const Con
 template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
 __global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_group_kernel(const ConvGroup g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char resident_smem[];
-  const int gt = (blockIdx.x & 7) * g.per_xcd + (blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= g.per_xcd || gt >= g.start[g.n]) return;
-  int j = 0;
-#pragma unroll
-  for (int t = 1; t < kMaxConvGroup; ++t)
-    if (t < g.n && gt >= g.start[t]) j = t;
+  const int gt = simpb::xcd_tile(g.per_xcd, g.start[g.n]);
+  if (gt < 0) return;
+  const int j = group_problem(g, gt);
   conv_resident_tile<CIN, TH, BNt, WGM, WGN, RING, TOK16>(g.a[j], gt - g.start[j], resident_smem);
 }
 
+// ---- host: the forms, each stated once ------------------------------------------------------------------------------------------
+// A form knows its tile count on a shape (what the choose_* rules ask), its grid (what the kernel walks), its threads and its
+// kernels; the entry points below take all of them from V1 .. V13 / P0 .. P2 and restate none.
+inline long long ceil_div(long long a, int b) { return (a + b - 1) / b; }
+
+// workgroups of the XCD walk over the gx x gy tiles of `a`
+inline unsigned xcd_blocks(ConvArgs& a) {
+  a.per_xcd = (int)(((long long)a.gx * a.gy + 7) / 8);
+  return (unsigned)(a.per_xcd * 8);
+}
+
+// a tile of BMt consecutive output pixels x BNt output channels (the direct and the staged forms)
+template <int BMt, int BNt>
+struct FlatTile {
+  static long long tiles(long long p_out, int cout) { return ceil_div(p_out, BMt) * ceil_div(cout, BNt); }
+  static void grid(ConvArgs& a) {
+    a.gx = (int)ceil_div(a.P_out, BMt);
+    a.gy = (int)ceil_div(a.Cout, BNt);
+  }
+};
+
+template <int AF, bool KSPLIT>
+struct Direct : FlatTile<(KSPLIT ? 32 : 128) * AF, BN> {
+  template <int TAPS, bool TOK16>
+  static void launch(ConvArgs& a, hipStream_t stream) {
+    static_assert(TAPS == 9, "the direct forms are 3x3 only");
+    Direct::grid(a);
+    hipLaunchKernelGGL((conv3x3_f16_kernel<AF, KSPLIT, TOK16>), dim3(xcd_blocks(a)), dim3(kThreads), 0, stream, a);
+  }
+};
+
+// KS = 0: conv_staged_kernel (the pipeline's own k map); KS >= 1: conv_staged_ksplit_kernel with KS groups of waves
+template <int BMt, int BNt, int WGM, int WGN, int KS = 0>
+struct Staged : FlatTile<BMt, BNt> {
+  static constexpr int threads = 64 * WGM * WGN * (KS ? KS : 1);
+  template <int TAPS, bool TOK16>
+  static void launch(ConvArgs& a, hipStream_t stream) {
+    Staged::grid(a);
+    const dim3 blocks(xcd_blocks(a));
+    if constexpr (KS == 0) hipLaunchKernelGGL((conv_staged_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16>), blocks, dim3(threads), 0, stream, a);
+    else hipLaunchKernelGGL((conv_staged_ksplit_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16, KS>), blocks, dim3(threads), 0, stream, a);
+  }
+  template <bool TOK16>
+  static void launch_group(const ConvGroup& g, hipStream_t stream) {
+    hipLaunchKernelGGL((conv_staged_group_kernel<BMt, BNt, WGM, WGN, 9, TOK16>), dim3((unsigned)(g.per_xcd * 8)), dim3(threads), 0, stream, g);
+  }
+};
+
 inline bool resident_shape(int cin, int stride) { return stride == 1 && (cin == 64 || cin == 128 || cin == 256); }
 
-// the tile grid of the resident form: whole 2-D tiles per image, channel blocks of one tile next to each other
-template <int TH, int BNt>
-void resident_grid(ConvArgs& a) {
-  a.tiles_w = (a.Wo + RTW - 1) / RTW;
-  a.tiles_h = (a.Ho + TH - 1) / TH;
-  a.gx = a.P_out / (a.Ho * a.Wo) * a.tiles_w * a.tiles_h;
-  a.gy = (a.Cout + BNt - 1) / BNt;
-}
-
 // a kernel is allowed its dynamic LDS (more than 64 KB where Cin = 256) once
-template <typename KernelT>
-bool allow_resident_lds(KernelT kernel, size_t bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-}
-
-template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
-void launch_resident_cin(ConvArgs& a, hipStream_t stream) {
-  constexpr size_t lds = resident_lds<CIN, TH, BNt, WGM, WGN, RING>();
-  auto kernel = conv_resident_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>;
-  static const bool allowed = allow_resident_lds(kernel, lds);
+template <auto kernel, class Arg>
+void launch_with_lds(size_t lds, unsigned blocks, int threads, const Arg& arg, hipStream_t stream) {
+  static const bool allowed =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
   (void)allowed;
-  resident_grid<TH, BNt>(a);
-  const long long total = (long long)a.gx * a.gy;
-  a.per_xcd = (int)((total + 7) / 8);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(a.per_xcd * 8)), dim3(64 * WGM * WGN), lds, stream, a);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, stream, arg);
 }
 
-template <int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
-void launch_resident(ConvArgs& a, hipStream_t stream) {
-  if (a.Cin == 64) launch_resident_cin<64, TH, BNt, WGM, WGN, RING, TOK16>(a, stream);
-  else if (a.Cin == 128) launch_resident_cin<128, TH, BNt, WGM, WGN, RING, TOK16>(a, stream);
-  else launch_resident_cin<256, TH, BNt, WGM, WGN, RING, TOK16>(a, stream);
-}
+// whole 2-D tiles of TH x RTW output pixels per image x BNt output channels, channel blocks of one tile next to each other
+template <int TH, int BNt, int WGM, int WGN, int RING>
+struct Resident {
+  static constexpr int threads = 64 * WGM * WGN;
+  static long long tiles(long long images, int ho, int wo, int cout) {
+    return images * ceil_div(ho, TH) * ceil_div(wo, RTW) * ceil_div(cout, BNt);
+  }
+  static void grid(ConvArgs& a) {
+    a.tiles_w = (int)ceil_div(a.Wo, RTW);
+    a.tiles_h = (int)ceil_div(a.Ho, TH);
+    a.gx = a.P_out / (a.Ho * a.Wo) * a.tiles_w * a.tiles_h;
+    a.gy = (int)ceil_div(a.Cout, BNt);
+  }
+  // Cin is a template argument of the kernels (64, 128 or 256: resident_shape): the one place that makes it one, for the
+  // launch of one problem (Arg = ConvArgs) and of a group (Arg = ConvGroup)
+  template <bool TOK16, class Arg>
+  static void launch_cin(int cin, unsigned blocks, const Arg& arg, hipStream_t stream) {
+    auto go = [&](auto cin_c) {
+      constexpr int CIN = decltype(cin_c)::value;
+      constexpr size_t lds = resident_lds<CIN, TH, BNt, WGM, WGN, RING>();
+      if constexpr (std::is_same_v<Arg, ConvGroup>)
+        launch_with_lds<conv_resident_group_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>>(lds, blocks, threads, arg, stream);
+      else
+        launch_with_lds<conv_resident_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>>(lds, blocks, threads, arg, stream);
+    };
+    if (cin == 64) go(IC<64>{});
+    else if (cin == 128) go(IC<128>{});
+    else go(IC<256>{});
+  }
+  template <int TAPS, bool TOK16>
+  static void launch(ConvArgs& a, hipStream_t stream) {
+    static_assert(TAPS == 9, "the resident form is 3x3 only");
+    grid(a);
+    launch_cin<TOK16>(a.Cin, xcd_blocks(a), a, stream);
+  }
+  template <bool TOK16>
+  static void launch_group(const ConvGroup& g, hipStream_t stream) {
+    launch_cin<TOK16>(g.a[0].Cin, (unsigned)(g.per_xcd * 8), g, stream);
+  }
+};
 
-template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
-void launch_resident_group_cin(const ConvGroup& g, hipStream_t stream) {
-  constexpr size_t lds = resident_lds<CIN, TH, BNt, WGM, WGN, RING>();
-  auto kernel = conv_resident_group_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>;
-  static const bool allowed = allow_resident_lds(kernel, lds);
-  (void)allowed;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(g.per_xcd * 8)), dim3(64 * WGM * WGN), lds, stream, g);
-}
+// THE statement of every form's shape: 3x3 variants 1-13 (the table at the head of the file) ...
+using V1 = Direct<1, false>;                 // 128 pixels x 64 channels, weights through LDS
+using V2 = Direct<2, false>;                 // 256 x 64
+using V3 = Direct<1, true>;                  // 32 x 64, K split over the waves
+using V4 = Direct<2, true>;                  // 64 x 64, K split over the waves
+using V5 = Staged<128, 64, 4, 1>;            // 128 x 64, operands staged through LDS
+using V6 = Staged<128, 128, 2, 2>;           // 128 x 128
+using V7 = Staged<96, 64, 3, 1>;             // 96 x 64, three waves: 704 workgroups for 67 584 pixels
+using V8 = Staged<96, 128, 1, 4>;            // 96 x 128, waves side by side along the channels
+using V9 = Staged<64, 64, 2, 2, 1>;          // 64 x 64, four waves of 32 x 32: the sums of 1
+using V10 = Staged<64, 64, 2, 2, 2>;         // 64 x 64, K split over 2 groups of four waves
+using V11 = Staged<64, 64, 2, 2, 4>;         // 64 x 64, K split over 4 groups (16 waves): the sums of 3 / 4
+using V12 = Resident<4, 64, 2, 2, 2>;        // resident 4 x 16 pixels x 64 channels, four waves of 32 x 32, weight ring of two
+using V13 = Resident<8, 128, 4, 2, 3>;       // resident 8 x 16 x 128, eight waves of 32 x 64, weight ring of three
+// ... and the tilings of a 1x1 convolution through the staged pipeline (conv1x1 variants 2-4)
+using P0 = V5;                               // 128 x 64
+using P1 = V6;                               // 128 x 128
+using P2 = Staged<64, 64, 2, 2>;             // 64 x 64 (four waves, 32 x 32 each): the sums of P0 bit for bit
 
-template <int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
-void launch_resident_group(const ConvGroup& g, hipStream_t stream) {
-  if (g.a[0].Cin == 64) launch_resident_group_cin<64, TH, BNt, WGM, WGN, RING, TOK16>(g, stream);
-  else if (g.a[0].Cin == 128) launch_resident_group_cin<128, TH, BNt, WGM, WGN, RING, TOK16>(g, stream);
-  else launch_resident_group_cin<256, TH, BNt, WGM, WGN, RING, TOK16>(g, stream);
+// 3x3 variant v is kVariant[v - 1] (TOK16: the kernels that write the f16 token rows alone)
+using Launch = void (*)(ConvArgs&, hipStream_t);
+template <bool TOK16>
+constexpr Launch kVariant[13] = {V1::launch<9, TOK16>,  V2::launch<9, TOK16>,  V3::launch<9, TOK16>, V4::launch<9, TOK16>, V5::launch<9, TOK16>,
+                                 V6::launch<9, TOK16>,  V7::launch<9, TOK16>,  V8::launch<9, TOK16>, V9::launch<9, TOK16>, V10::launch<9, TOK16>,
+                                 V11::launch<9, TOK16>, V12::launch<9, TOK16>, V13::launch<9, TOK16>};
+
+// The arguments every entry point fills the same way; where the output goes (y / tok / tok16, tokens_per_cam, level_start)
+// and the residual are set by name where they exist. The grid is the form's to fill.
+ConvArgs conv_args(const void* x, const void* weight, const void* bias, long long p_out, int in_channels, int out_channels, int relu,
+                   int stride, int ho, int wo, int in_h, int in_w) {
+  ConvArgs a = {};
+  a.x = static_cast<const _Float16*>(x);
+  a.w = static_cast<const _Float16*>(weight);
+  a.bias = static_cast<const _Float16*>(bias);
+  a.P_out = (int)p_out;
+  a.Cin = in_channels;
+  a.Cout = out_channels;
+  a.relu = relu;
+  a.stride = stride;
+  a.Ho = ho;
+  a.Wo = wo;
+  a.H = in_h;
+  a.W = in_w;
+  return a;
 }
 
 }  // namespace
@@ -925,17 +896,15 @@ extern "C" int simpb_conv3x3_choose_variant(long long p_out, int in_channels, in
   // measured on the ResNet50 / FPN shapes at 6 x 256 x 704 (tools/bench_conv3x3.py): the LDS-staged 96-row tilings while
   // they fill the chip (96 divides the pixel counts of a 6-camera rig and leaves no nearly empty last round of
   // workgroups), then the direct ones, K split inside the workgroup for the smallest maps
-  const long long ny = (out_channels + BN - 1) / BN;
-  const long long t96 = (p_out + 95) / 96, t128 = (p_out + 127) / 128, t64 = (p_out + 63) / 64;
-  if (out_channels >= 128 && t128 * ((out_channels + 127) / 128) >= 2048) return 6;   // many rounds: the larger tile wins
-  if (out_channels >= 128 && t96 * ((out_channels + 127) / 128) >= 160) return 8;
-  if (t96 * ny >= 256) return 7;
+  if (out_channels >= 128 && V6::tiles(p_out, out_channels) >= 2048) return 6;   // many rounds: the larger tile wins
+  if (out_channels >= 128 && V8::tiles(p_out, out_channels) >= 160) return 8;
+  if (V7::tiles(p_out, out_channels) >= 256) return 7;
   // Cin >= 256 on the small maps (tools/bench_conv_small_maps.py, profiles/conv3x3_small_maps.md): the direct forms are
   // bound by their 16-byte loads of 32 different rows per wave-instruction, not by latency (8 or 16 waves on the same loads
   // were no faster); the staged 64 x 64 tile wins, with K split over 16 waves where 64 x 64 tiles leave half the chip empty.
   // 9 gives the bits of 1 and 11 the bits of 4 (DIRECTK above), so neither choice changes an output
-  if (t128 * ny >= 128) return in_channels >= 256 && out_channels >= 256 ? 9 : 1;
-  if (t64 * ny >= 128) return in_channels >= 512 && out_channels >= 512 ? 11 : 4;
+  if (V1::tiles(p_out, out_channels) >= 128) return in_channels >= 256 && out_channels >= 256 ? 9 : 1;
+  if (V4::tiles(p_out, out_channels) >= 128) return in_channels >= 512 && out_channels >= 512 ? 11 : 4;
   return 3;
 }
 
@@ -950,11 +919,9 @@ extern "C" int simpb_conv3x3_choose_resident(long long p_out, int in_h, int in_w
     return 0;
   const int staged = simpb_conv3x3_choose_variant(p_out, in_channels, out_channels);
   if (staged != 7 && staged != 8) return 0;
-  const long long images = p_out / ((long long)in_h * in_w), across = (in_w + RTW - 1) / RTW;
-  const long long t13 = images * ((in_h + 7) / 8) * across * ((out_channels + 127) / 128);
-  const long long t12 = images * ((in_h + 3) / 4) * across * ((out_channels + 63) / 64);
-  if (in_channels == 256 && t13 >= 1024) return 13;   // four rounds of one eight-wave workgroup per CU
-  if (t12 >= 512) return 12;
+  const long long images = p_out / ((long long)in_h * in_w);
+  if (in_channels == 256 && V13::tiles(images, in_h, in_w, out_channels) >= 1024) return 13;   // four rounds of one eight-wave workgroup per CU
+  if (V12::tiles(images, in_h, in_w, out_channels) >= 512) return 12;
   return 0;
 }
 
@@ -967,7 +934,7 @@ extern "C" int simpb_conv3x3_group_choose_resident(int num_levels, int num_image
   long long tiles = 0;
   for (int j = 0; j < num_levels; ++j) {
     if (in_h[j] <= 0 || in_w[j] <= 0) return 0;
-    tiles += (long long)num_images * ((in_h[j] + 7) / 8) * ((in_w[j] + RTW - 1) / RTW) * 2;
+    tiles += V13::tiles(num_images, in_h[j], in_w[j], out_channels);
   }
   return tiles >= 1024 ? 13 : 0;
 }
@@ -990,9 +957,12 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
   if (p_out > (1ll << 30) || in_elems > (1ll << 31) - 1) return SIMPB_EINVAL;   // tap offsets are 32-bit
   if (to_tokens && (tokens_per_cam < ho * wo || level_start < 0 || level_start + ho * wo > tokens_per_cam)) return SIMPB_EINVAL;
   (void)hipGetLastError();
-  ConvArgs a{static_cast<_Float16*>(y), tokens, static_cast<_Float16*>(tokens_f16), static_cast<const _Float16*>(x), static_cast<const _Float16*>(weight),
-             static_cast<const _Float16*>(bias), nullptr, 0, (int)p_out, in_channels, out_channels, relu, stride, ho, wo, in_h, in_w,
-             tokens_per_cam, level_start, 0, 0, 0};
+  ConvArgs a = conv_args(x, weight, bias, p_out, in_channels, out_channels, relu, stride, ho, wo, in_h, in_w);
+  a.y = static_cast<_Float16*>(y);
+  a.tok = tokens;
+  a.tok16 = static_cast<_Float16*>(tokens_f16);
+  a.tokens_per_cam = tokens_per_cam;
+  a.level_start = level_start;
   if (variant == 0) {
     variant = simpb_conv3x3_choose_variant(p_out, in_channels, out_channels);
     if (variant == 7 || variant == 8) {   // the same bits either way: the resident form where it measured faster
@@ -1000,27 +970,8 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
       if (resident) variant = resident;
     }
   }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  auto dispatch = [&](auto tok16_c) {
-    constexpr bool T = decltype(tok16_c)::value;
-    switch (variant) {
-      case 1: launch<1, false, T>(a, s); break;   // 128 pixels x 64 channels, weights through LDS
-      case 2: launch<2, false, T>(a, s); break;   // 256 x 64
-      case 3: launch<1, true, T>(a, s); break;    // 32 x 64, K split over the waves
-      case 4: launch<2, true, T>(a, s); break;    // 64 x 64, K split over the waves
-      case 5: launch_staged<128, 64, 4, 1, 9, T>(a, s); break;    // 128 x 64, operands staged through LDS
-      case 6: launch_staged<128, 128, 2, 2, 9, T>(a, s); break;  // 128 x 128
-      case 7: launch_staged<96, 64, 3, 1, 9, T>(a, s); break;     // 96 x 64, three waves: 704 workgroups for 67 584 pixels
-      case 8: launch_staged<96, 128, 1, 4, 9, T>(a, s); break;    // 96 x 128, waves side by side along the channels
-      case 9: launch_staged_ksplit<64, 64, 2, 2, 9, T, 1>(a, s); break;    // 64 x 64, four waves of 32 x 32: the sums of 1
-      case 10: launch_staged_ksplit<64, 64, 2, 2, 9, T, 2>(a, s); break;   // 64 x 64, K split over 2 groups of four waves
-      case 11: launch_staged_ksplit<64, 64, 2, 2, 9, T, 4>(a, s); break;   // 64 x 64, K split over 4 groups (16 waves): the sums of 3 / 4
-      case 12: launch_resident<4, 64, 2, 2, 2, T>(a, s); break;     // resident 4 x 16 pixels x 64 channels, four waves of 32 x 32, weight ring of two
-      default: launch_resident<8, 128, 4, 2, 3, T>(a, s); break;    // resident 8 x 16 x 128, eight waves of 32 x 64, weight ring of three
-    }
-  };
-  if (!tokens && tokens_f16) dispatch(std::true_type{});   // the f16 token rows alone: kernels without the fp32 stores
-  else dispatch(std::false_type{});
+  const bool tok16_alone = !tokens && tokens_f16;   // the f16 token rows alone: kernels without the fp32 stores
+  (tok16_alone ? kVariant<true> : kVariant<false>)[variant - 1](a, static_cast<hipStream_t>(stream));
   return simpb_check_launch();
 }
 
@@ -1036,7 +987,7 @@ extern "C" int simpb_conv3x3_group_tokens_forms_f16(int num_levels, float* token
       num_images <= 0 || in_channels <= 0 || out_channels <= 0 || in_channels % BK != 0 || out_channels % 8 != 0 ||
       ((reinterpret_cast<size_t>(tokens) | reinterpret_cast<size_t>(tokens_f16)) & 15))
     return SIMPB_EINVAL;
-  // the levels of one form share a launch: form[0] the 96 x 128 staged tiles, form[1] the resident 8 x 16 x 128 tiles
+  // the levels of one form share a launch: form[0] the staged tiles of variant 8, form[1] the resident tiles of variant 13
   ConvGroup form[2] = {};
   long long total[2] = {0, 0};
   const int rule = variant ? 0 : simpb_conv3x3_group_choose_resident(num_levels, num_images, in_h, in_w, in_channels, out_channels);
@@ -1054,16 +1005,13 @@ extern "C" int simpb_conv3x3_group_tokens_forms_f16(int num_levels, float* token
     const int f = v == 13;
     ConvGroup& g = form[f];
     ConvArgs& a = g.a[g.n];
-    a = ConvArgs{nullptr, tokens, static_cast<_Float16*>(tokens_f16), static_cast<const _Float16*>(x[j]),
-                 static_cast<const _Float16*>(weight[j]), static_cast<const _Float16*>(bias[j]), nullptr, 0, (int)p_out,
-                 in_channels, out_channels, relu, 1, in_h[j], in_w[j], in_h[j], in_w[j], tokens_per_cam, level_start[j],
-                 0, 0, 0, 0, 0};
-    if (f == 1) {
-      resident_grid<8, 128>(a);
-    } else {
-      a.gx = (int)((p_out + 95) / 96);
-      a.gy = (out_channels + 127) / 128;
-    }
+    a = conv_args(x[j], weight[j], bias[j], p_out, in_channels, out_channels, relu, 1, in_h[j], in_w[j], in_h[j], in_w[j]);
+    a.tok = tokens;
+    a.tok16 = static_cast<_Float16*>(tokens_f16);
+    a.tokens_per_cam = tokens_per_cam;
+    a.level_start = level_start[j];
+    if (f == 1) V13::grid(a);
+    else V8::grid(a);
     g.start[g.n++] = (int)total[f];
     total[f] += (long long)a.gx * a.gy;
   }
@@ -1074,14 +1022,9 @@ extern "C" int simpb_conv3x3_group_tokens_forms_f16(int num_levels, float* token
   }
   (void)hipGetLastError();
   hipStream_t s = static_cast<hipStream_t>(stream);
-  auto launches = [&](auto tok16_c) {
-    constexpr bool T = decltype(tok16_c)::value;
-    if (form[1].n) launch_resident_group<8, 128, 4, 2, 3, T>(form[1], s);   // the large levels first: the staged launch is the short one
-    if (form[0].n)
-      hipLaunchKernelGGL((conv_staged_group_kernel<96, 128, 1, 4, 9, T>), dim3((unsigned)(form[0].per_xcd * 8)), dim3(256), 0, s, form[0]);
-  };
-  if (!tokens) launches(std::true_type{});   // the f16 token rows alone
-  else launches(std::false_type{});
+  // the large levels first: the staged launch is the short one; tokens == NULL: the f16 token rows alone
+  if (form[1].n) (tokens ? V13::launch_group<false> : V13::launch_group<true>)(form[1], s);
+  if (form[0].n) (tokens ? V8::launch_group<false> : V8::launch_group<true>)(form[0], s);
   return simpb_check_launch();
 }
 
@@ -1094,18 +1037,18 @@ extern "C" int simpb_conv3x3_group_tokens_f16(int num_levels, float* tokens, voi
                                               in_h, in_w, in_channels, out_channels, relu, nullptr, stream);
 }
 
-// 1x1 convolutions through the same staged pipeline (TAPS = 1): csrc/conv1x1.hip validates and forwards here.
-// tiling 0: 128 x 64 per workgroup, 1: 128 x 128, 2: 64 x 64 (four waves, 32 x 32 each: twice the workgroups of tiling 0 for
-// the small maps of stages 3-4; the sums of tiling 0 bit for bit: the same chunks in the same order through the same k map).
+// 1x1 convolutions through the same staged pipeline (TAPS = 1): csrc/conv1x1.hip validates and forwards here; `tiling` picks
+// P0 .. P2 above.
 extern "C" int simpb_conv_pointwise_staged(void* y, const void* x, const void* weight, const void* bias, const void* residual,
                                            int p_out, int in_h, int in_w, int ho, int wo, int in_channels, int out_channels,
                                            int stride, int relu, int residual_upsample2x, int tiling, void* stream) {
-  ConvArgs a{static_cast<_Float16*>(y), nullptr, nullptr, static_cast<const _Float16*>(x), static_cast<const _Float16*>(weight),
-             static_cast<const _Float16*>(bias), static_cast<const _Float16*>(residual), residual_upsample2x ? 1 : 0,
-             p_out, in_channels, out_channels, relu, stride, ho, wo, in_h, in_w, 0, 0, 0, 0, 0};
+  ConvArgs a = conv_args(x, weight, bias, p_out, in_channels, out_channels, relu, stride, ho, wo, in_h, in_w);
+  a.y = static_cast<_Float16*>(y);
+  a.residual = static_cast<const _Float16*>(residual);
+  a.res_up = residual_upsample2x ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (tiling == 0) launch_staged<128, 64, 4, 1, 1, false>(a, s);
-  else if (tiling == 1) launch_staged<128, 128, 2, 2, 1, false>(a, s);
-  else launch_staged<64, 64, 2, 2, 1, false>(a, s);
+  if (tiling == 0) P0::launch<1, false>(a, s);
+  else if (tiling == 1) P1::launch<1, false>(a, s);
+  else P2::launch<1, false>(a, s);
   return simpb_check_launch();
 }
