@@ -651,6 +651,32 @@ int simpb_bank_cache_streams_restart(float* confidence, float* cached_feature, f
                                      float threshold, const int* hold, int num_hold, int* sticky, unsigned* sync_words,
                                      const unsigned char* active, const unsigned char* restart, void* stream);
 
+/* One stream of the bank as a STREAM RECORD: a contiguous u8 buffer that holds everything the persistent state keeps for
+ * batch row `stream`, so that the stream can go on in another slot, another bank of the same model or another process.
+ * Every section starts at a multiple of 16 bytes from the record's first byte; padding is zero:
+ *   header         64 bytes: i32 magic 0x42504D53, i32 layout version 1, i32 num_temp (T), i32 num_anchor (N),
+ *                  i32 embed_dims (C), i32 anchor_dims (D), i64 largest id of the id row (-1: none), zeros
+ *   confidence     f32 [T]
+ *   cached_anchor  f32 [T, D]
+ *   cached_feature f32 [T, C]
+ *   instance_id    i64 [N]
+ * so its size is 64 + pad16(4 T) + pad16(4 T D) + pad16(4 T C) + pad16(8 N) bytes. Bank tensors as in simpb_bank_cache:
+ * confidence [bs, T], cached_feature [bs, T, C], cached_anchor [bs, T, D], instance_id i64 [bs, N], prev_id i64 [1]. `blob`
+ * is device memory at a multiple of 8 bytes (16-byte accesses are used where record and rows both sit at multiples of 16).
+ *   simpb_bank_export_stream: one launch writes the whole record (header included) from the stream's rows; the bank is
+ *     only read.
+ *   simpb_bank_import_stream: one launch writes the record's four sections into the stream's rows and raises prev_id, the
+ *     next id to issue, to max(prev_id, 1 + largest id of the record's id row) -- computed from the row: the header is
+ *     neither read nor trusted here, the caller checks it. Importing the same record twice leaves what importing it once
+ *     leaves. Nothing but the stream's rows and prev_id is written.
+ * Both return SIMPB_EINVAL for a NULL pointer, `stream` outside [0, batch_size), a non-positive size or a misaligned blob. */
+int simpb_bank_export_stream(unsigned char* blob, const float* confidence, const float* cached_feature,
+                             const float* cached_anchor, const long long* instance_id, int stream, int batch_size, int num_temp,
+                             int num_anchor, int embed_dims, int anchor_dims, void* stream_handle);
+int simpb_bank_import_stream(float* confidence, float* cached_feature, float* cached_anchor, long long* instance_id,
+                             long long* prev_id, const unsigned char* blob, int stream, int batch_size, int num_temp,
+                             int num_anchor, int embed_dims, int anchor_dims, void* stream_handle);
+
 /* Fixed-shape detection records of SparseBox3DDecoder.decode_with2d (models/detection3d/decoder.py:124-252).
  * 3D (:133-167 with squeezed classes + decode_box :23-34), one workgroup per sample:
  *   score = max_c sigmoid(cls), label = the first class whose fp32 sigmoid reaches it (torch.max on the sigmoids: not the

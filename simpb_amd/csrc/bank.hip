@@ -408,7 +408,179 @@ __global__ __launch_bounds__(64) void bank_gather_kernel(float* __restrict__ out
   if (lane < 11) out_a[((size_t)b * T + r) * 11 + lane] = src_a[((size_t)b * A + src) * 11 + lane];
 }
 
+// ---- one stream's rows <-> one contiguous record (include/simpb_hip.h "stream record"). blockIdx.y picks the section:
+// 0 confidence, 1 cached_anchor, 2 cached_feature (the only large one: blockIdx.x strides over it), 3 the id row, which ONE
+// workgroup owns: it reduces the largest id while it copies, so the header word (export) and the prev_id floor (import)
+// need no meeting of workgroups. Copies move bits, never floats: NaN payloads and denormals travel as they are.
+constexpr int kRecMagic = 0x42504D53;   // "SMPB"
+constexpr int kRecVersion = 1;
+constexpr int kRecHeader = 64;
+constexpr int kRecThreads = 256;
+
+// n 32-bit words from src to dst by the `stride` threads of a section, `first` being this thread's rank: 16-byte accesses
+// where both addresses allow them, single words for the tail or throughout; loads retired before stores, stores before the
+// next trip's loads (store_fence.h)
+__device__ __forceinline__ void rec_copy_words(unsigned* __restrict__ dst, const unsigned* __restrict__ src, size_t n,
+                                               size_t first, size_t stride) {
+  size_t done = 0;
+  if ((((uintptr_t)dst | (uintptr_t)src) & 15) == 0) {
+    const size_t n4 = n >> 2;
+    for (size_t i = first; i < n4; i += stride) {
+      const uint4 v = reinterpret_cast<const uint4*>(src)[i];
+      simpb::loads_retired();
+      reinterpret_cast<uint4*>(dst)[i] = v;
+      simpb::stores_retired();
+    }
+    done = n4 << 2;
+  }
+  for (size_t i = done + first; i < n; i += stride) {
+    const unsigned v = src[i];
+    simpb::loads_retired();
+    dst[i] = v;
+    simpb::stores_retired();
+  }
+}
+
+// the id row (n ids) from src to dst by one workgroup -> the largest id of the row (-1: none), in every thread
+__device__ __forceinline__ long long rec_copy_ids(long long* __restrict__ dst, const long long* __restrict__ src, int n) {
+  __shared__ long long s_max[kRecThreads / 64];
+  const int tid = threadIdx.x;
+  long long m = -1;
+  for (int i = tid; i < n; i += kRecThreads) {
+    const long long v = src[i];
+    simpb::loads_retired();
+    dst[i] = v;
+    simpb::stores_retired();
+    m = v > m ? v : m;
+  }
+#pragma unroll
+  for (int k = 32; k >= 1; k >>= 1) {
+    const long long o = __shfl_xor(m, k);
+    m = o > m ? o : m;
+  }
+  if ((tid & 63) == 0) s_max[tid >> 6] = m;
+  __syncthreads();
+  m = s_max[0];
+#pragma unroll
+  for (int w = 1; w < kRecThreads / 64; ++w) m = s_max[w] > m ? s_max[w] : m;
+  return m;
+}
+
+struct RecLayout {
+  size_t conf, anchor, feature, ids, size;   // byte offsets of the sections, and the record's size
+};
+__host__ __device__ __forceinline__ RecLayout rec_layout(int T, int N, int C, int D) {
+  RecLayout l;
+  l.conf = kRecHeader;
+  l.anchor = l.conf + (((size_t)T * 4 + 15) & ~(size_t)15);
+  l.feature = l.anchor + (((size_t)T * D * 4 + 15) & ~(size_t)15);
+  l.ids = l.feature + (((size_t)T * C * 4 + 15) & ~(size_t)15);
+  l.size = l.ids + (((size_t)N * 8 + 15) & ~(size_t)15);
+  return l;
+}
+
+__global__ __launch_bounds__(kRecThreads) void bank_export_stream_kernel(unsigned char* __restrict__ blob,
+                                                                         const float* __restrict__ conf,
+                                                                         const float* __restrict__ feature,
+                                                                         const float* __restrict__ anchor,
+                                                                         const long long* __restrict__ instance_id, int b,
+                                                                         int T, int N, int C, int D) {
+  const RecLayout l = rec_layout(T, N, C, D);
+  const int section = blockIdx.y, tid = threadIdx.x;
+  if (section == 3) {
+    if (blockIdx.x != 0) return;
+    long long* dst = reinterpret_cast<long long*>(blob + l.ids);
+    const long long largest = rec_copy_ids(dst, instance_id + (size_t)b * N, N);
+    if (tid == 0 && (N & 1)) dst[N] = 0;   // the section's padding
+    // the header: sixteen 32-bit words, the largest id in words 6-7
+    if (tid < 16) {
+      const unsigned long long big = (unsigned long long)largest;
+      unsigned w = 0;
+      if (tid == 0) w = (unsigned)kRecMagic;
+      else if (tid == 1) w = (unsigned)kRecVersion;
+      else if (tid == 2) w = (unsigned)T;
+      else if (tid == 3) w = (unsigned)N;
+      else if (tid == 4) w = (unsigned)C;
+      else if (tid == 5) w = (unsigned)D;
+      else if (tid == 6) w = (unsigned)(big & 0xFFFFFFFFull);
+      else if (tid == 7) w = (unsigned)(big >> 32);
+      reinterpret_cast<unsigned*>(blob)[tid] = w;
+    }
+    return;
+  }
+  const size_t words = section == 0 ? (size_t)T : section == 1 ? (size_t)T * D : (size_t)T * C;
+  const size_t at = section == 0 ? l.conf : section == 1 ? l.anchor : l.feature;
+  const float* src = section == 0 ? conf + (size_t)b * T : section == 1 ? anchor + (size_t)b * T * D : feature + (size_t)b * T * C;
+  unsigned* dst = reinterpret_cast<unsigned*>(blob + at);
+  rec_copy_words(dst, reinterpret_cast<const unsigned*>(src), words, (size_t)blockIdx.x * kRecThreads + tid,
+                 (size_t)gridDim.x * kRecThreads);
+  const int pad = (int)((4 - (words & 3)) & 3);   // zero words up to the next 16-byte boundary
+  if (blockIdx.x == 0 && tid < pad) dst[words + tid] = 0u;
+}
+
+__global__ __launch_bounds__(kRecThreads) void bank_import_stream_kernel(float* __restrict__ conf, float* __restrict__ feature,
+                                                                         float* __restrict__ anchor,
+                                                                         long long* __restrict__ instance_id,
+                                                                         long long* __restrict__ prev_id,
+                                                                         const unsigned char* __restrict__ blob, int b, int T,
+                                                                         int N, int C, int D) {
+  const RecLayout l = rec_layout(T, N, C, D);
+  const int section = blockIdx.y, tid = threadIdx.x;
+  if (section == 3) {
+    if (blockIdx.x != 0) return;
+    const long long largest = rec_copy_ids(instance_id + (size_t)b * N, reinterpret_cast<const long long*>(blob + l.ids), N);
+    // the next id to issue never falls at or below an id the adopted stream carries (this workgroup alone writes prev_id;
+    // launches of one stream are ordered, so the frame's commit kernel reads the raised value)
+    if (tid == 0) {
+      const long long cur = *prev_id;
+      simpb::loads_retired();
+      if (largest + 1 > cur) *prev_id = largest + 1;
+    }
+    return;
+  }
+  const size_t words = section == 0 ? (size_t)T : section == 1 ? (size_t)T * D : (size_t)T * C;
+  const size_t at = section == 0 ? l.conf : section == 1 ? l.anchor : l.feature;
+  float* dst = section == 0 ? conf + (size_t)b * T : section == 1 ? anchor + (size_t)b * T * D : feature + (size_t)b * T * C;
+  rec_copy_words(reinterpret_cast<unsigned*>(dst), reinterpret_cast<const unsigned*>(blob + at), words,
+                 (size_t)blockIdx.x * kRecThreads + tid, (size_t)gridDim.x * kRecThreads);
+}
+
+// workgroups along x: one per 4 KiB of the feature section, at most 64 (the small sections stride over the same grid)
+inline int rec_grid_x(int T, int C) {
+  const size_t chunks = ((size_t)T * C * 4 + 4095) / 4096;
+  return (int)(chunks < 1 ? 1 : chunks > 64 ? 64 : chunks);
+}
+inline bool rec_sizes_ok(int stream, int batch_size, int T, int N, int C, int D) {
+  return stream >= 0 && batch_size > 0 && stream < batch_size && T > 0 && N > 0 && C > 0 && D > 0;
+}
+
 }  // namespace
+
+extern "C" int simpb_bank_export_stream(unsigned char* blob, const float* confidence, const float* cached_feature,
+                                        const float* cached_anchor, const long long* instance_id, int stream, int batch_size,
+                                        int num_temp, int num_anchor, int embed_dims, int anchor_dims, void* stream_handle) {
+  if (!blob || !confidence || !cached_feature || !cached_anchor || !instance_id ||
+      !rec_sizes_ok(stream, batch_size, num_temp, num_anchor, embed_dims, anchor_dims) || ((uintptr_t)blob & 7))
+    return SIMPB_EINVAL;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(bank_export_stream_kernel, dim3(rec_grid_x(num_temp, embed_dims), 4), dim3(kRecThreads), 0,
+                     static_cast<hipStream_t>(stream_handle), blob, confidence, cached_feature, cached_anchor, instance_id, stream,
+                     num_temp, num_anchor, embed_dims, anchor_dims);
+  return simpb_check_launch();
+}
+
+extern "C" int simpb_bank_import_stream(float* confidence, float* cached_feature, float* cached_anchor, long long* instance_id,
+                                        long long* prev_id, const unsigned char* blob, int stream, int batch_size, int num_temp,
+                                        int num_anchor, int embed_dims, int anchor_dims, void* stream_handle) {
+  if (!blob || !confidence || !cached_feature || !cached_anchor || !instance_id || !prev_id ||
+      !rec_sizes_ok(stream, batch_size, num_temp, num_anchor, embed_dims, anchor_dims) || ((uintptr_t)blob & 7))
+    return SIMPB_EINVAL;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(bank_import_stream_kernel, dim3(rec_grid_x(num_temp, embed_dims), 4), dim3(kRecThreads), 0,
+                     static_cast<hipStream_t>(stream_handle), confidence, cached_feature, cached_anchor, instance_id, prev_id, blob,
+                     stream, num_temp, num_anchor, embed_dims, anchor_dims);
+  return simpb_check_launch();
+}
 
 extern "C" int simpb_bank_get_restart(float* anchor_out, unsigned char* mask_out, float* time_interval_out,
                                       const float* cached_anchor, const float* T_temp2cur, const float* time_interval,

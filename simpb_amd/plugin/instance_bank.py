@@ -21,6 +21,59 @@ from . import routes
 
 _STATE_FIELDS = ("cached_feature", "cached_anchor", "confidence", "instance_id", "prev_id")
 
+# The stream record (include/simpb_hip.h): one stream's rows of the state as one u8 buffer, every section at a multiple of 16
+RECORD_MAGIC, RECORD_VERSION, RECORD_HEADER = 0x42504D53, 1, 64
+
+
+def record_layout(num_temp, num_anchor, embed_dims, anchor_dims):
+    """Byte offsets of a stream record's sections and its size: dict(confidence, cached_anchor, cached_feature,
+    instance_id, size). A pure function of (T, N, C, D)."""
+    pad16 = lambda n: (n + 15) // 16 * 16  # noqa: E731
+    t, n, c, d = int(num_temp), int(num_anchor), int(embed_dims), int(anchor_dims)
+    if min(t, n, c, d) <= 0:
+        raise ValueError(f"a stream record needs positive sizes, got (T, N, C, D) = {(t, n, c, d)}")
+    out = dict(confidence=RECORD_HEADER)
+    out["cached_anchor"] = out["confidence"] + pad16(4 * t)
+    out["cached_feature"] = out["cached_anchor"] + pad16(4 * t * d)
+    out["instance_id"] = out["cached_feature"] + pad16(4 * t * c)
+    out["size"] = out["instance_id"] + pad16(8 * n)
+    return out
+
+
+def record_header(blob):
+    """The header of a stream record (u8 tensor on any device, bytes or numpy u8; at least 64 bytes) -> dict(magic, version,
+    num_temp, num_anchor, embed_dims, anchor_dims, largest_id). Reads 64 bytes on the host."""
+    if torch.is_tensor(blob):
+        blob = blob[:RECORD_HEADER].cpu().numpy()
+    raw = np.frombuffer(bytes(blob[:RECORD_HEADER]), np.uint8)
+    if raw.size < RECORD_HEADER:
+        raise ValueError(f"a stream record begins with a {RECORD_HEADER}-byte header; this one has {raw.size} bytes")
+    words = raw[:24].view("<i4")
+    names = ("magic", "version", "num_temp", "num_anchor", "embed_dims", "anchor_dims")
+    return dict(zip(names, (int(w) for w in words)), largest_id=int(raw[24:32].view("<i8")[0]))
+
+
+def check_record(blob, num_temp, num_anchor, embed_dims, anchor_dims):
+    """Refuse, in words, a stream record that is not one of a bank with these sizes (header and length; host side)."""
+    size = len(blob) if not torch.is_tensor(blob) else blob.numel()
+    if torch.is_tensor(blob) and (blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous()):
+        raise ValueError(f"a stream record is a contiguous 1-d u8 tensor, got {blob.dtype} {tuple(blob.shape)}")
+    if size < RECORD_HEADER:
+        raise ValueError(f"a stream record begins with a {RECORD_HEADER}-byte header; this one has {size} bytes")
+    h = record_header(blob)
+    if h["magic"] != RECORD_MAGIC:
+        raise ValueError(f"not a stream record: magic {h['magic'] & 0xFFFFFFFF:#010x}, expected {RECORD_MAGIC:#010x}")
+    if h["version"] != RECORD_VERSION:
+        raise ValueError(f"stream record of layout version {h['version']}; this build reads version {RECORD_VERSION}")
+    got = (h["num_temp"], h["num_anchor"], h["embed_dims"], h["anchor_dims"])
+    want = (int(num_temp), int(num_anchor), int(embed_dims), int(anchor_dims))
+    if got != want:
+        raise ValueError(f"stream record of a bank with (T, N, C, D) = {got}; this bank has {want}")
+    need = record_layout(*want)["size"]
+    if size != need:
+        raise ValueError(f"stream record of {size} bytes; (T, N, C, D) = {want} makes {need}")
+    return h
+
 
 def topk(confidence, k, *inputs):
     """Rows of every input at the k largest confidences per batch row (instance_bank.py:13-20)."""
@@ -111,6 +164,96 @@ class InstanceBank(nn.Module):
             self._static[name].copy_(value)
             value = self._static[name]
         setattr(self, name, value)
+
+    # ------------------------------------------------------------------ one stream in and out
+    def record_dims(self):
+        """(T, N, C, D) of this bank's stream record."""
+        return self.num_temp_instances, self.num_anchor, self.embed_dims, int(self.anchor.shape[-1])
+
+    def _stream_state(self, b, fused):
+        """The four state tensors one stream is moved from / to, and whether the move runs as a csrc/bank.hip launch."""
+        src = self._static if self._static is not None else {k: getattr(self, k) for k in _STATE_FIELDS}
+        if fused and self._static is None:
+            raise ValueError("the HIP route of export_stream / import_stream works on the persistent state: enable_static first")
+        if any(not torch.is_tensor(src[k]) for k in _STATE_FIELDS[:4]):
+            raise ValueError("this bank holds no temporal state (nothing decoded since reset, and no persistent buffers)")
+        bs = src["cached_feature"].shape[0]
+        if not 0 <= int(b) < bs:
+            raise ValueError(f"stream {b} of a bank with {bs} streams")
+        if fused is None:
+            fused = self._static is not None and routes.R.fused_bank and src["cached_feature"].is_cuda
+        elif fused and not src["cached_feature"].is_cuda:
+            raise ValueError("the HIP route of export_stream / import_stream needs the state on the GPU")
+        return src, bs, bool(fused)
+
+    def export_stream(self, b, out=None, fused=None):
+        """Stream b's rows of the temporal state as one stream record (include/simpb_hip.h): a u8 tensor of
+        record_layout(T, N, C, D)["size"] bytes on the state's device, written into `out` if given. The bank is only read.
+        fused: None picks the csrc/bank.hip launch where the persistent state is on the GPU (routes.fused_bank) and the
+        PyTorch statement below otherwise; True / False ask for one of them."""
+        src, bs, fused = self._stream_state(b, fused)
+        t, n, c, d = dims = self.record_dims()
+        lay = record_layout(*dims)
+        dev = src["cached_feature"].device
+        if out is None:
+            out = torch.empty(lay["size"], dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() != lay["size"] or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out: a contiguous u8 [{lay['size']}] tensor on {dev}")
+        if fused:
+            _lib.check(_lib.lib().simpb_bank_export_stream(
+                _ptr(out), _ptr(src["confidence"]), _ptr(src["cached_feature"]), _ptr(src["cached_anchor"]),
+                _ptr(src["instance_id"]), int(b), bs, t, n, c, d, _stream()), "simpb_bank_export_stream")
+            return out
+        ids = src["instance_id"][b].contiguous()
+        out.zero_()
+        head = torch.tensor([RECORD_MAGIC, RECORD_VERSION, t, n, c, d], dtype=torch.int32, device=dev)
+        out[:24].copy_(head.view(torch.uint8))
+        out[24:32].copy_(ids.max().clamp(min=-1).reshape(1).view(torch.uint8))
+        for name, rows in (("confidence", src["confidence"][b]), ("cached_anchor", src["cached_anchor"][b]),
+                           ("cached_feature", src["cached_feature"][b]), ("instance_id", ids)):
+            raw = rows.contiguous().view(-1).view(torch.uint8)
+            out[lay[name]: lay[name] + raw.numel()].copy_(raw)
+        return out
+
+    def import_stream(self, b, blob, fused=None, header=None):
+        """Write a stream record into slot b of the temporal state and raise the running id counter to
+        max(prev_id, 1 + largest id of the record), so that no id issued here afterwards equals one the adopted stream
+        carries. Nothing of the slot's previous content survives and no other slot changes; importing twice is importing
+        once. The header is checked on the host (check_record: 64 bytes are read back) before anything is written; a caller
+        that knows the record's (T, N, C, D) on the host passes them as `header` and nothing is read back (the runners: a
+        record in flight is not waited for). fused: as export_stream."""
+        src, bs, fused = self._stream_state(b, fused)
+        t, n, c, d = dims = self.record_dims()
+        lay = record_layout(*dims)
+        if header is None:
+            check_record(blob, *dims)
+        elif tuple(header) != dims or not torch.is_tensor(blob) or blob.dtype != torch.uint8 or blob.numel() != lay["size"]:
+            raise ValueError(f"stream record of a bank with (T, N, C, D) = {tuple(header)}; this bank has {dims}")
+        dev = src["cached_feature"].device
+        if not torch.is_tensor(blob) or blob.device != dev:
+            raise ValueError(f"the stream record must be a u8 tensor on the bank's device {dev}")
+        if fused:
+            _lib.check(_lib.lib().simpb_bank_import_stream(
+                _ptr(src["confidence"]), _ptr(src["cached_feature"]), _ptr(src["cached_anchor"]), _ptr(src["instance_id"]),
+                _ptr(src["prev_id"]), _ptr(blob), int(b), bs, t, n, c, d, _stream()), "simpb_bank_import_stream")
+        else:
+            for name, dtype in (("confidence", torch.float32), ("cached_anchor", torch.float32),
+                                ("cached_feature", torch.float32), ("instance_id", torch.long)):
+                dst = src[name][b]
+                size = dst.numel() * dst.element_size()
+                # (a section may sit at an address the element type cannot be viewed at: through a copy of the bytes)
+                dst.copy_(blob[lay[name]: lay[name] + size].clone().view(dtype).view(dst.shape))
+            floor = src["instance_id"][b].max() + 1
+            if torch.is_tensor(src["prev_id"]):
+                src["prev_id"].copy_(torch.maximum(src["prev_id"], floor.to(src["prev_id"].device)))
+            else:
+                self.prev_id = torch.maximum(torch.as_tensor(src["prev_id"], dtype=torch.long, device=dev), floor)
+        if self._static is not None:
+            # the state a frame finds is the persistent one from here on, as behind a committed frame
+            st = self._static
+            self.confidence, self.cached_feature, self.cached_anchor = st["confidence"], st["cached_feature"], st["cached_anchor"]
+            self.instance_id, self.prev_id = st["instance_id"], st["prev_id"]
+            self.has_history = True
 
     # ------------------------------------------------------------------ frame start
     def _ego_motion(self, metas):

@@ -113,6 +113,138 @@ def normalise_restart(restart, num_streams, active=None, cold=False, independent
     return None if cold else flags
 
 
+STATE_META_KEYS = ("T_global", "T_global_inv", "timestamp")   # what stream_motion reads of a previous frame's entry
+_META_BYTES = (16 + 16 + 1) * 8
+
+
+class StreamState:
+    """One stream's temporal state, ready to go on in another slot, another runner or another process: the bank's stream
+    record (include/simpb_hip.h; a u8 tensor on a device or on the host) and, of the img_metas entry of the stream's last
+    ACTIVE frame -- the frame its bank rows belong to --, what stream_motion reads: T_global, T_global_inv (f64 [4, 4]) and
+    timestamp (f64). `dims` = the record's (T, N, C, D), known on the host. export_stream of the runners makes one; `adopt=`
+    of step / launch takes one. A state exported behind a frame still in flight (PipelinedRunner) is sealed when that frame's
+    results are returned; touching it earlier raises RuntimeError."""
+
+    def __init__(self, record, dims, T_global, T_global_inv, timestamp, sealed=True):
+        from .plugin.instance_bank import record_layout
+        self.dims = tuple(int(x) for x in dims)
+        size = record_layout(*self.dims)["size"]
+        if not torch.is_tensor(record) or record.dtype != torch.uint8 or record.dim() != 1 or record.numel() != size:
+            raise ValueError(f"a stream record of (T, N, C, D) = {self.dims} is a u8 [{size}] tensor")
+        self._record = record
+        self.T_global = np.array(T_global, np.float64).reshape(4, 4)
+        self.T_global_inv = np.array(T_global_inv, np.float64).reshape(4, 4)
+        self.timestamp = float(timestamp)
+        self._sealed = bool(sealed)
+        self._ready = None      # event behind the launch that wrote the record last (None: nothing to wait for)
+
+    @property
+    def sealed(self):
+        return self._sealed
+
+    def _need_sealed(self):
+        if not self._sealed:
+            raise RuntimeError("this stream state was exported behind a frame whose results have not been returned yet: "
+                               "collect() / step() / flush() the runner it came from first")
+
+    @property
+    def record(self):
+        """The stream record (u8 tensor). On the device it may still be being written: order reads behind `wait(stream)`."""
+        self._need_sealed()
+        return self._record
+
+    def wait(self, stream=None):
+        """Order `stream` (None: the host) behind the launch that wrote the record."""
+        self._need_sealed()
+        if self._ready is not None:
+            if stream is None:
+                self._ready.synchronize()
+            else:
+                stream.wait_event(self._ready)
+
+    def img_meta(self):
+        """The img_metas entry of the stream's last active frame, reduced to STATE_META_KEYS."""
+        return dict(T_global=self.T_global, T_global_inv=self.T_global_inv, timestamp=self.timestamp)
+
+    def to(self, device):
+        """The same state with its record on `device` (self if it is there already)."""
+        device = torch.device(device)
+        rec = self.record
+        if rec.device == device or (rec.device.type == device.type == "cuda" and device.index is None):
+            return self
+        self.wait()
+        return StreamState(rec.to(device), self.dims, self.T_global, self.T_global_inv, self.timestamp)
+
+    def to_bytes(self):
+        """One flat host byte string: the record, then T_global, T_global_inv and timestamp as little-endian f64."""
+        self.wait()
+        tail = np.concatenate([self.T_global.ravel(), self.T_global_inv.ravel(), [self.timestamp]]).astype("<f8")
+        return self.record.cpu().numpy().tobytes() + tail.tobytes()
+
+    @classmethod
+    def from_bytes(cls, data):
+        """The state `to_bytes` wrote (record on the host); a string that is not one is refused in words."""
+        from .plugin.instance_bank import RECORD_HEADER, check_record, record_header
+        data = bytes(data)
+        if len(data) < RECORD_HEADER + _META_BYTES:
+            raise ValueError(f"a stream state has at least {RECORD_HEADER + _META_BYTES} bytes; this string has {len(data)}")
+        h = record_header(data)
+        dims = (h["num_temp"], h["num_anchor"], h["embed_dims"], h["anchor_dims"])
+        if min(dims) <= 0:
+            raise ValueError(f"not a stream state: header sizes (T, N, C, D) = {dims}")
+        body = data[:len(data) - _META_BYTES]
+        check_record(body, *dims)
+        tail = np.frombuffer(data[len(body):], "<f8")
+        record = torch.from_numpy(np.frombuffer(body, np.uint8).copy())
+        return cls(record, dims, tail[:16], tail[16:32], tail[32])
+
+
+def adopt_metas(prev, adopt):
+    """The `prev` a frame is staged against when some slots adopt a stream that ran elsewhere (step(..., adopt=)). prev:
+    dict(img_metas=...) of the frame before; adopt: {slot: StreamState}. Returns a copy of `prev` in which an adopted slot's
+    img_metas entry is the state's own (StreamState.img_meta): staged against it (stream_motion) the stream gets its own
+    time step and ego-motion, and nothing of whoever held the slot before is read. Pure host function: nothing of `prev` or
+    of the states is modified."""
+    entries = list(prev["img_metas"])
+    for slot, state in adopt.items():
+        if not 0 <= int(slot) < len(entries):
+            raise ValueError(f"adopt: slot {slot} of {len(entries)} streams")
+        entries[int(slot)] = state.img_meta()
+    out = dict(prev)
+    out["img_metas"] = entries
+    return out
+
+
+def normalise_adopt(adopt, num_streams, dims, active=None, restart=None, independent=True, supported=True):
+    """step / launch's `adopt` -> None (no slot adopts a stream: today's path) or a dict {slot: StreamState} in slot order.
+    dims: the bank's (T, N, C, D); active / restart: the frame's masks as given (None or one bool per stream). Everything that
+    can refuse an adoption does so here. Pure host function."""
+    if adopt is None or len(adopt) == 0:
+        return None
+    if not supported:
+        raise NotImplementedError("this runner cannot adopt a stream: the single-frame part of the next frame is already in "
+                                  "flight when an adoption would have to take effect (use FrameRunner or PipelinedRunner)")
+    if num_streams > 1 and not independent:
+        raise ValueError("adopting a stream into a batch needs independent_streams=True (the reference's batch pads the "
+                         "camera groups to the max over the batch: its streams are not independent)")
+    out = {}
+    for slot in sorted(adopt, key=int):
+        state = adopt[slot]
+        if int(slot) != slot or not 0 <= int(slot) < num_streams:
+            raise ValueError(f"adopt: slot {slot!r} of {num_streams} streams")
+        if not isinstance(state, StreamState):
+            raise ValueError(f"adopt[{slot}] is a {type(state).__name__}, not a StreamState")
+        state._need_sealed()
+        if state.dims != tuple(dims):
+            raise ValueError(f"adopt[{slot}]: stream record of a bank with (T, N, C, D) = {state.dims}; this bank has {tuple(dims)}")
+        if active is not None and len(active) == num_streams and not active[int(slot)]:
+            raise ValueError(f"stream {slot} is paused and adopted in the same step: adopt a stream in the step it runs")
+        if restart is not None and len(restart) == num_streams and restart[int(slot)]:
+            raise ValueError(f"stream {slot} is adopted and restarted in the same step: it either goes on or starts over")
+        out[int(slot)] = state
+    return out
+
+
 def normalise_cameras(cameras, num_streams, num_cams, active=None):
     """step / launch's `cameras` -> None (every camera of every stream that takes part delivered a frame: today's path) or
     a tuple of `num_streams` tuples of `num_cams` bools with a False somewhere. cameras: None, or one sequence of num_cams
@@ -328,6 +460,7 @@ class FrameRunner:
         self.warm_frames = 0
         self.host3d = self.host2d = self.host_flag = None
         self.stats = dict(eager=0, replay=0, overflow=0)   # (+ "restart": frames that restarted a stream, from the first one on)
+        self.decoded = [False] * batch_size   # per slot: it has taken part in a frame here (export_stream needs that)
         self.last_rec3d = None      # device record f32 [bs, num_output, 15] of the frame last returned (dist.DetectionGather)
         self.last_rec2d = None      # ... and its 2D record f32 [bs, capacity, 8]
         # event after which those records may be overwritten (set by their consumer, if any). The records of a replayed
@@ -544,11 +677,23 @@ class FrameRunner:
             self.masked = True
         return carry_inactive_metas(dict(img_metas=prev["img_metas"], projection_mat=self.inputs.host["proj"]), metas, mask)
 
-    def _admit(self, prev, img, metas, active, cameras, restart=None):
+    def _admit(self, prev, img, metas, active, cameras, restart=None, adopt=None):
         """What step / launch open with: the frame's activity mask, camera mask, metas (paused streams carried from `prev`,
-        the metas of the frame before), checked frames and restart flags. Everything that can refuse a frame does so here,
-        before anything is enqueued."""
+        the metas of the frame before), checked frames, restart flags, the adoptions and the dict(img_metas=...) the frame
+        is staged against (None: a cold frame). Everything that can refuse a frame does so here, before anything is enqueued.
+
+        A frame with adoptions is staged against adopt_metas(prev, adopt). In a runner that has not decoded a frame yet it
+        runs as a WARM frame in which every active slot without an adoption is restarted: `prev` is then the frame's own
+        metas (what restart_metas puts there anyway) with the adopted states' entries."""
+        adopt = normalise_adopt(adopt, self.bs, self.head.instance_bank.record_dims(), active, restart,
+                                self.independent or self.bs == 1, self.SUPPORTS_RESTART)
+        first = prev is None and adopt is not None
+        if first:
+            prev = dict(img_metas=list(metas["img_metas"]))
         mask = self._activity(active, prev is None)
+        if first:
+            given = [False] * self.bs if restart is None else [bool(r) for r in restart]
+            restart = [r or (i not in adopt and (mask is None or mask[i])) for i, r in enumerate(given)]
         flags = normalise_restart(restart, self.bs, mask, prev is None, self.independent or self.bs == 1, self.SUPPORTS_RESTART)
         cams = self._camera_mask(cameras, mask)
         if mask is not None:
@@ -559,7 +704,68 @@ class FrameRunner:
             self._ensure_plan(metas)
         if flags is not None:
             self.stats["restart"] = self.stats.get("restart", 0) + 1
-        return mask, cams, metas, img, flags
+        staged = dict(img_metas=prev["img_metas"]) if prev is not None else None
+        if adopt is not None:
+            self.stats["adopt"] = self.stats.get("adopt", 0) + 1
+            staged = adopt_metas(staged, adopt)
+        for i in range(self.bs):
+            self.decoded[i] = self.decoded[i] or mask is None or mask[i]
+        return mask, cams, metas, img, flags, adopt, staged
+
+    def _import(self, adopt, stream):
+        """The import launches of a frame's adoptions on `stream`, in front of its decoder -> the records as they sit on this
+        device (kept by the caller until the frame is through). Importing again (a re-run) changes nothing."""
+        held = []
+        here = self.head.instance_bank._static["cached_feature"].device
+        for slot, state in adopt.items():
+            rec = state.record
+            with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+                if rec.device != here:
+                    state.wait()
+                    rec = rec.to(here)
+                elif rec.is_cuda:
+                    state.wait(torch.cuda.current_stream())
+                self.head.instance_bank.import_stream(slot, rec, header=state.dims)
+            held.append(rec)
+        return held
+
+    def _check_export(self, s):
+        """export_stream's refusals, before anything is enqueued."""
+        if not self.SUPPORTS_RESTART:
+            raise NotImplementedError("this runner cannot export a stream: the single-frame part of the next frame is already "
+                                      "in flight when an export would have to take effect (use FrameRunner or PipelinedRunner)")
+        if int(s) != s or not 0 <= int(s) < self.bs:
+            raise ValueError(f"export_stream: stream {s!r} of {self.bs}")
+        if self.bs > 1 and not self.independent:
+            raise ValueError("exporting a stream of a batch needs independent_streams=True (the reference's batch pads the "
+                             "camera groups to the max over the batch: its streams are not independent)")
+        if not self.decoded[int(s)]:
+            raise ValueError(f"stream {s} has not decoded a frame in this runner: there is nothing to export")
+        return int(s)
+
+    def _export(self, s, metas, stream=None, into=None):
+        """Enqueue the export launch of stream s on `stream` (None: the current one) -> StreamState (into: take it again
+        into this state's record). metas: the img_metas list of the frame the bank rows belong to."""
+        bank = self.head.instance_bank
+        with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+            rec = bank.export_stream(s, out=into._record if into is not None else None)
+            ready = None
+            if rec.is_cuda:
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream())
+        if into is None:
+            m = metas[s]
+            into = StreamState(rec, bank.record_dims(), m["T_global"], m["T_global_inv"], m["timestamp"])
+        into._ready = ready
+        return into
+
+    def export_stream(self, s):
+        """The state of stream s behind the last step as a StreamState: its bank rows (one launch, csrc/bank.hip) and the
+        pose and time stamp of its last active frame. The slot itself does not change: pause it, restart it or adopt another
+        stream into it next. Refused for a stream that has not decoded a frame here, for a batch without independent_streams
+        and by the split runner."""
+        s = self._check_export(s)
+        return self._export(s, self.prev_metas["img_metas"])
 
     def _fill_inputs(self, inputs, metas, prev, mask, cams, restart=None):
         """The frame's decoder inputs into `inputs` (host side) -> the metas dict the head reads them through."""
@@ -567,13 +773,16 @@ class FrameRunner:
         inputs.fill(metas, prev, mask, cams, self.masked, self.cam_masked, restart)
         return inputs.metas(metas["img_metas"], self.wh, self.wh_host)
 
-    def _stage(self, img, metas, mask=None, cams=None, restart=None):
-        """Copy this frame's inputs into the static device buffers (a few small async copies); returns the head's metas."""
+    def _stage(self, img, metas, mask=None, cams=None, restart=None, prev="last"):
+        """Copy this frame's inputs into the static device buffers (a few small async copies); returns the head's metas.
+        prev: what the frame is staged against (None: a cold frame); by default the metas of the frame last returned."""
+        if prev == "last":
+            prev = self.prev_metas
         if self.raw is None:
             self.img.copy_(img, non_blocking=True)
         else:
             self._stage_frames(self.raw, img, self.pin_table)
-        dmetas = self._fill_inputs(self.inputs, metas, self.prev_metas, mask, cams, restart)
+        dmetas = self._fill_inputs(self.inputs, metas, prev, mask, cams, restart)
         self.inputs.upload(torch.cuda.current_stream())
         return dmetas
 
@@ -644,7 +853,7 @@ class FrameRunner:
 
     # ------------------------------------------------------------------ public
     @torch.no_grad()
-    def step(self, img, metas, force_eager=False, active=None, cameras=None, restart=None):
+    def step(self, img, metas, force_eager=False, active=None, cameras=None, restart=None, adopt=None):
         """One frame for all streams: img f32 [bs, cams, 3, H, W] (device; u8 [bs, cams, Hs, Ws, 3] with raw_input, u8
         [bs, cams, Hs * 3 / 2, Ws] with raw_format "nv12" / "nv21"), metas as the reference's
         test pipeline collects them (projection_mat, timestamp, img_metas with T_global/T_global_inv/
@@ -671,11 +880,21 @@ class FrameRunner:
         stream takes). A batch needs independent_streams=True; a stream cannot be paused and restarted in one step, but is
         restarted in the step it resumes; on the runner's first frame the flags are ignored (everything is cold); all True
         restarts the whole batch. Frames with a True replay a graph set of their own, captured at the first such frame
-        (stats["restart"] counts them); None or all False is the ordinary frame and stages nothing new."""
-        mask, cams, metas, img, flags = self._admit(self.prev_metas, img, metas, active, cameras, restart)
+        (stats["restart"] counts them); None or all False is the ordinary frame and stages nothing new.
+
+        adopt: None, or {slot: StreamState}; the slot takes over a stream that ran elsewhere (export_stream of any runner of
+        the same model) and decodes this frame WARM against that stream's own history: its record is written into the slot's
+        bank rows by one launch in front of the frame (the batch's id counter is raised above every id the record carries),
+        and its time step and ego-motion are measured from the state's own last frame (adopt_metas). Nothing of the slot's
+        previous occupant is read. The slot must take part in the frame and cannot be restarted in it. In a runner that has
+        not decoded a frame yet, the frame runs warm with every other active slot restarted. No graph changes or is captured
+        anew because of an adoption (stats["adopt"] counts the frames that had one)."""
+        mask, cams, metas, img, flags, adopt, prev = self._admit(self.prev_metas, img, metas, active, cameras, restart, adopt)
         aug = metas["img_metas"][0]["aug_config"]
-        dmetas = self._stage(img, metas, mask, cams, flags)
-        warm = self.prev_metas is not None
+        dmetas = self._stage(img, metas, mask, cams, flags, prev)
+        warm = prev is not None
+        if adopt is not None:   # eager launches between replays, in front of the frame: no graph knows of them
+            self._import(adopt, None)
         graph, outputs = (self.graph, self.outputs) if flags is None else (self.restart_graph, self.restart_outputs)
         if warm and self.use_graph and not force_eager and graph is None and self.warm_frames >= 1:
             torch.cuda.synchronize()
@@ -729,6 +948,9 @@ class Job:
     cameras: tuple
     surfaces: list      # raw_surfaces: the frame's tensors, held until its results have been returned
     restart: tuple = None
+    adopt: dict = None      # {slot: StreamState} imported in front of this frame (a re-run imports them again)
+    records: list = None    # ... and their records as they sit on this device, held until the frame is through
+    exports: list = None    # [(stream, StreamState)] taken behind this frame: sealed when its results are returned
 
 
 class PipelinedRunner(FrameRunner):
@@ -876,20 +1098,38 @@ class PipelinedRunner(FrameRunner):
             done.record(self.s_head)
         return done
 
-    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None, cams=None, surfaces=None, restart=None):
-        """Stage the inputs of the frame whose features sit in `slot` and enqueue its decoder + read-back (_run_head)."""
+    def _enqueue_decoder(self, slot, metas, prev, force_eager, mask=None, cams=None, surfaces=None, restart=None, adopt=None):
+        """Stage the inputs of the frame whose features sit in `slot` and enqueue its decoder + read-back (_run_head); a
+        frame's adoptions are imported on the decoder stream right in front of it."""
         self.prev_metas = prev   # (what the base class's helpers look at)
         inputs = self.slot_inputs[slot]
         dmetas = self._fill_inputs(inputs, metas, prev, mask, cams, restart)
+        records = self._import(adopt, self.s_head) if adopt is not None else None
         rec = self._run_head(slot, inputs, dmetas, metas["img_metas"][0]["aug_config"], prev is not None, force_eager)
-        return Job(slot, metas, prev, rec, self._enqueue_readback(slot, rec), mask, cams, surfaces, restart)
+        return Job(slot, metas, prev, rec, self._enqueue_readback(slot, rec), mask, cams, surfaces, restart, adopt, records)
+
+    def export_stream(self, s):
+        """FrameRunner.export_stream behind the frame launched last: the export launch is enqueued on the decoder stream
+        behind that frame's decoder, with no host wait, and the state is SEALED when that frame's results are returned
+        (collect, step or flush) -- the lifetime rule of raw_surfaces; using it earlier raises RuntimeError. If the frame
+        (or the one in front of it) overflowed, its bank commit was held back: the export is taken again behind its re-run,
+        into the same record. With nothing in flight the state is sealed at once."""
+        s = self._check_export(s)
+        state = self._export(s, self.last_metas["img_metas"], self.s_head)
+        if self.queue:
+            job = self.queue[-1]
+            job.exports = (job.exports or []) + [(s, state)]
+            state._sealed = False
+        return state
 
     @torch.no_grad()
-    def launch(self, img, metas, force_eager=False, active=None, cameras=None, restart=None):
+    def launch(self, img, metas, force_eager=False, active=None, cameras=None, restart=None, adopt=None):
         """Enqueue backbone(t) and decoder(t) without waiting for either (several runners -- several independent
-        camera streams on one GPU -- can be launched back to back and collected after). img, active, cameras, restart: as
-        FrameRunner.step (an overflowed frame, and the one enqueued behind it, are re-run each with its own flags)."""
-        mask, cams, metas, img, flags = self._admit(self.last_metas, img, metas, active, cameras, restart)
+        camera streams on one GPU -- can be launched back to back and collected after). img, active, cameras, restart, adopt:
+        as FrameRunner.step (an overflowed frame, and the one enqueued behind it, are re-run each with its own flags and
+        adoptions). A launch with an adoption waits for the decoder still in flight, behind enqueuing its own backbone: the
+        slot's previous occupant must have committed its last frame before the adopted rows replace its own."""
+        mask, cams, metas, img, flags, adopt, prev = self._admit(self.last_metas, img, metas, active, cameras, restart, adopt)
         slot = self.count % 2
         cur = torch.cuda.current_stream()
         self.s_bb.wait_stream(cur)
@@ -908,15 +1148,36 @@ class PipelinedRunner(FrameRunner):
         self._run_backbone(slot, force_eager)
         self.bb_done[slot].record(self.s_bb)
         self.s_head.wait_event(self.bb_done[slot])
-        prev = dict(img_metas=self.last_metas["img_metas"]) if self.last_metas is not None else None
+        if adopt is not None and self.queue:
+            # the import replaces the slot's rows for good: the frame in flight has to have committed first -- were it to
+            # overflow, its re-run would decode the slot's previous occupant against the adopted rows. The one host wait an
+            # adoption costs (the backbone of this frame is enqueued already); frames without one never come here
+            settled = []
+            while self.queue:
+                settled.append(self._settle(self.queue.pop(0)))
+            self.queue.extend(settled)
         self.queue.append(self._enqueue_decoder(slot, metas, prev, force_eager, mask, cams, img[1] if self.surfaces else None,
-                                                flags))
+                                                flags, adopt))
         self.last_metas = metas
         self.count += 1
 
     def _finish(self, job):
         """Wait for a decoder in flight, re-run it (and whatever was enqueued behind it) if its 2D set overflowed,
         return its detections."""
+        job = self._settle(job)
+        h = self.host[job.slot]
+        for _, state in job.exports or ():
+            state._sealed = True
+        self.last_rec3d, self.last_rec2d = job.rec[0], job.rec[1]
+        self.prev_metas = dict(img_metas=job.metas["img_metas"])
+        if self.world_output is None:
+            return self._results(h[0], h[1], job.active)
+        self.last_world, self.last_world_count = job.rec[3], job.rec[4]
+        return self._results(h[0], h[1], job.active, h[3], h[4])
+
+    def _settle(self, job):
+        """Wait for a decoder in flight and, if its 2D set overflowed, re-run it and whatever was enqueued behind it -> the
+        job whose records hold (the same one where nothing overflowed; settling it again is a no-op)."""
         job.done.synchronize()
         h = self.host[job.slot]
         if bool(h[2].any()):
@@ -935,16 +1196,17 @@ class PipelinedRunner(FrameRunner):
                 job.done.synchronize()
                 h = self.host[job.slot]
             self.queue.extend(self._rerun(b) for b in behind)
-        self.last_rec3d, self.last_rec2d = job.rec[0], job.rec[1]
-        self.prev_metas = dict(img_metas=job.metas["img_metas"])
-        if self.world_output is None:
-            return self._results(h[0], h[1], job.active)
-        self.last_world, self.last_world_count = job.rec[3], job.rec[4]
-        return self._results(h[0], h[1], job.active, h[3], h[4])
+        return job
 
     def _rerun(self, job):
-        """The same frame again, eagerly, with its own masks (and its surfaces still held)."""
-        return self._enqueue_decoder(job.slot, job.metas, job.prev, True, job.active, job.cameras, job.surfaces, job.restart)
+        """The same frame again, eagerly, with its own masks and adoptions (and its surfaces still held); an export taken
+        behind the first attempt found the state that attempt did not commit, and is taken again into the same record."""
+        again = self._enqueue_decoder(job.slot, job.metas, job.prev, True, job.active, job.cameras, job.surfaces, job.restart,
+                                      job.adopt)
+        again.exports = job.exports
+        for s, state in job.exports or ():
+            self._export(s, job.metas["img_metas"], self.s_head, into=state)
+        return again
 
     def _quiesce(self):
         self.s_head.synchronize()
@@ -960,9 +1222,9 @@ class PipelinedRunner(FrameRunner):
             return None
         return self._finish(self.queue.pop(0))
 
-    def step(self, img, metas, force_eager=False, active=None, cameras=None, restart=None):
+    def step(self, img, metas, force_eager=False, active=None, cameras=None, restart=None, adopt=None):
         """Feed frame t; returns the detections of frame t-1 (None on the very first call)."""
-        self.launch(img, metas, force_eager, active, cameras, restart)
+        self.launch(img, metas, force_eager, active, cameras, restart, adopt)
         return self.collect()
 
     @torch.no_grad()
