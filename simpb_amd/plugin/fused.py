@@ -1,7 +1,7 @@
 """Host side of csrc/mlp_chain.hip: turns the reference's nn.Sequential stacks ([Linear, ReLU]*,
 LayerNorm, ..., Linear, Scale) into the argument block of simpb_mlp_chain_forward. The module tree
-(and so the state_dict) is untouched; the kernel reads the Linear weights through transposed
-copies that are refreshed whenever a parameter is replaced or modified in place."""
+(and so the state_dict) is untouched; where a form of the kernel wants another weight layout it reads
+repacked copies, which are refreshed whenever a parameter is replaced or modified in place."""
 import ctypes
 
 import torch
@@ -14,15 +14,53 @@ from .ops import _stream
 
 MAX_OPS, MAX_CHAINS = 12, 8
 POST_NONE, POST_REFINE3D, POST_REFINE2D, POST_SIGMOID = 0, 1, 2, 3
-# routes.chain_rows4 (shipped): 4-row workgroups on the 4x4 matrix blocks, weights k4-packed [in/4][out][4]
-# (csrc/mlp_chain.hip: mlp_chain_r4_kernel): 225 workgroups for 900 rows instead of 57. Off: the 16-row matrix-core kernel
-# on the weights as stored, or (routes.chain_transposed) the VALU kernel on transposed copies.
-# Launches with at least WIDE_ROWS rows (a batch of camera streams: runner independent_streams) take the 32-row kernel on the
-# 32x32 matrix tiles (mlp_chain_r32_kernel, fragment-packed weights): at ~9 k rows the 4-row kernel sits at the issue rate of
-# its 4x4 matrix instruction, a quarter of the fp32 matrix rate.
 WIDE_ROWS = 4096
 LINEAR, LAYERNORM = 0, 1
 IN_ROWS, IN_SINE2D, IN_ROWS_LN = 0, 1, 2
+# The forms of the kernel (csrc/mlp_chain.hip, table kForms): the value is simpb_mlp_args.weights_transposed.
+R16, VALU, R4, R32 = 0, 1, 2, 3
+LEAD_NORM = (R4, R32)   # the forms that have the IN_ROWS_LN prologue
+
+
+def launch_form(num_rows, sine, r=None):
+    """The form that a launch of `num_rows` rows takes (sine: any of its jobs has the sine input stage), under the routes `r`
+    (default: routes.R now) and WIDE_ROWS as they are at the time of the call.
+    routes.chain_rows4 (shipped): R4, 4-row workgroups on the 4x4 matrix blocks: 225 workgroups for 900 rows instead of 57.
+    Off: R16, the 16-row matrix-core kernel, or (routes.chain_transposed) VALU.
+    Launches with at least WIDE_ROWS rows (a batch of camera streams: runner independent_streams) take R32, the 32-row kernel
+    on the 32x32 matrix tiles: at ~9 k rows the 4-row kernel sits at the issue rate of its 4x4 matrix instruction, a quarter
+    of the fp32 matrix rate. Not the sine chains: their prologue is transcendental work per element, which 32-row workgroups
+    serialise in front of the matrix work -- 2D encoder at 8.9 k rows: 84 us against 64 us on the 4-row kernel."""
+    r = routes.R if r is None else r
+    if not r.chain_rows4:
+        return VALU if r.chain_transposed else R16
+    return R32 if int(num_rows) >= WIDE_ROWS and not sine else R4
+
+
+def pack_transposed(w):
+    """Wt[k][n] = W[n][k] (f32, contiguous)."""
+    return w.t().contiguous().float()
+
+
+def pack_k4(w):
+    """Wp[k // 4][n][k % 4] = W[n][k] (f32, contiguous); in_dim % 4 == 0."""
+    n, k = w.shape
+    return w.float().t().reshape(k // 4, 4, n).permute(0, 2, 1).contiguous()
+
+
+def pack_fragments(w):
+    """Wq[t][c][q][32 h + r][e] = W[32 t + r][32 c + 16 h + 4 q + e] (f32, zeros past out_dim; in_dim % 32 == 0): the B operand
+    of v_mfma_f32_32x32x2f32 for tile t and 32-deep chunk c as four coalesced 1-KiB wave loads (csrc/mlp_chain.hip)."""
+    n, k = w.shape
+    tiles = -(-n // 32)
+    full = torch.zeros(tiles * 32, k, device=w.device, dtype=torch.float32)
+    full[:n] = w.float()
+    # [t, r, c, h, q, e] -> [t, c, q, h, r, e]
+    return full.reshape(tiles, 32, k // 32, 2, 4, 4).permute(0, 2, 4, 3, 1, 5).contiguous()
+
+
+# form -> (K divisor of its packed layout, packer): which Linear layers a form reads through a repacked copy of the weight
+LAYOUTS = {R16: (1, None), VALU: (1, pack_transposed), R4: (4, pack_k4), R32: (32, pack_fragments)}
 
 
 class _Op(ctypes.Structure):
@@ -76,73 +114,33 @@ class ChainPlan:
         self.in_dim = self.ops[0][1]
         self.out_dim = self.ops[-1][2]
 
-    def _transposed(self, lin):
-        key = id(lin)
+    def _cached(self, kind, lin, make):
+        """make(lin.weight) kept under (kind, lin), refreshed when the parameter is replaced or modified in place."""
         w = lin.weight
         tag = (w.data_ptr(), w._version, w.device)
-        hit = self._wt.get(key)
+        hit = self._wt.get((kind, id(lin)))
         if hit is None or hit[0] != tag:
-            hit = (tag, w.detach().t().contiguous().float())
-            self._wt[key] = hit
+            hit = (tag, make(w.detach()))
+            self._wt[kind, id(lin)] = hit
         return hit[1]
 
-    def _packed(self, lin):
-        """Wp[k // 4][n][k % 4] = W[n][k] (f32, contiguous), refreshed when the parameter is replaced or modified."""
-        key = ("k4", id(lin))
-        w = lin.weight
-        tag = (w.data_ptr(), w._version, w.device)
-        hit = self._wt.get(key)
-        if hit is None or hit[0] != tag:
-            n, k = w.shape
-            hit = (tag, w.detach().float().t().reshape(k // 4, 4, n).permute(0, 2, 1).contiguous())
-            self._wt[key] = hit
-        return hit[1]
-
-    def _fragments(self, lin):
-        """Wq[t][c][q][32 h + r][e] = W[32 t + r][32 c + 16 h + 4 q + e] (f32, zeros past out_dim): the B operand of
-        v_mfma_f32_32x32x2f32 for tile t and 32-deep chunk c as four coalesced 1-KiB wave loads (csrc/mlp_chain.hip)."""
-        key = ("frag", id(lin))
-        w = lin.weight
-        tag = (w.data_ptr(), w._version, w.device)
-        hit = self._wt.get(key)
-        if hit is None or hit[0] != tag:
-            n, k = w.shape
-            tiles = -(-n // 32)
-            full = torch.zeros(tiles * 32, k, device=w.device, dtype=torch.float32)
-            full[:n] = w.detach().float()
-            # [t, r, c, h, q, e] -> [t, c, q, h, r, e]
-            hit = (tag, full.reshape(tiles, 32, k // 32, 2, 4, 4).permute(0, 2, 4, 3, 1, 5).contiguous())
-            self._wt[key] = hit
-        return hit[1]
-
-    def fill(self, chain, keep, wide=False):
+    def fill(self, chain, keep, form):
+        """The ops of this chain for a launch of `form`: a Linear whose in_dim the form's divisor divides is read through the
+        form's packed copy, every other one in nn.Linear's own layout, in place."""
+        divisor, pack = LAYOUTS[form]
         chain.n_ops = len(self.ops)
         for j, (typ, din, dout, relu, m) in enumerate(self.ops):
             op = chain.ops[j]
             op.type, op.in_dim, op.out_dim, op.relu = typ, din, dout, relu
             if typ == LINEAR:
-                if wide and din % 32 == 0:
-                    wq = self._fragments(m)
-                    keep.append(wq)
-                    op.w = wq.data_ptr()
-                elif wide:
-                    w = m.weight
-                    if not w.is_contiguous() or w.dtype != torch.float32:
-                        raise ValueError("mlp_chain reads nn.Linear weights in place: contiguous f32 expected")
-                    op.w = w.data_ptr()
-                elif routes.R.chain_rows4 and din % 4 == 0:
-                    wp = self._packed(m)
-                    keep.append(wp)
-                    op.w = wp.data_ptr()
-                elif routes.R.chain_transposed and not routes.R.chain_rows4:
-                    wt = self._transposed(m)
-                    keep.append(wt)
-                    op.w = wt.data_ptr()
+                if pack is not None and din % divisor == 0:
+                    w = self._cached(form, m, pack)
+                    keep.append(w)
                 else:
                     w = m.weight
                     if not w.is_contiguous() or w.dtype != torch.float32:
                         raise ValueError("mlp_chain reads nn.Linear weights in place: contiguous f32 expected")
-                    op.w = w.data_ptr()
+                op.w = w.data_ptr()
                 op.b = m.bias.data_ptr() if m.bias is not None else None
             else:
                 op.w, op.b = m.weight.data_ptr(), m.bias.data_ptr()
@@ -184,10 +182,8 @@ def run_chains(jobs, num_rows, device, m_live=None):
     args = _Args()
     args.num_rows, args.num_chains = int(num_rows), len(jobs)
     args.m_live = m_live.data_ptr() if m_live is not None else None
-    # (not the sine chains: their prologue is transcendental work per element, which 32-row workgroups serialise in front
-    # of the matrix work -- 2D encoder at 8.9 k rows: 84 us against 64 us on the 4-row kernel)
-    wide = routes.R.chain_rows4 and int(num_rows) >= WIDE_ROWS and not any(j.get("sine") for j in jobs)
-    args.weights_transposed = 3 if wide else 2 if routes.R.chain_rows4 else (1 if routes.R.chain_transposed else 0)
+    form = launch_form(num_rows, any(j.get("sine") for j in jobs))
+    args.weights_transposed = form
     keep = []
     for c, job in enumerate(jobs):
         ch = args.chain[c]
@@ -212,7 +208,7 @@ def run_chains(jobs, num_rows, device, m_live=None):
         ch.in_dim = plan.in_dim if plan is not None else job["ln"][0].normalized_shape[0]
         if job.get("ln") is not None:
             ln, ln_out = job["ln"]
-            if not routes.R.chain_rows4 or ln.normalized_shape != (ch.in_dim,) or abs(ln.eps - 1e-5) > 1e-12 or job.get("sine"):
+            if form not in LEAD_NORM or ln.normalized_shape != (ch.in_dim,) or abs(ln.eps - 1e-5) > 1e-12 or job.get("sine"):
                 raise ValueError("a leading LayerNorm needs the 4-row chain kernel and a norm of the chain's input width")
             ch.in_mode = IN_ROWS_LN
             ch.ln_w, ch.ln_b = ln.weight.data_ptr(), ln.bias.data_ptr()
@@ -230,7 +226,7 @@ def run_chains(jobs, num_rows, device, m_live=None):
                 ch.div, ch.div_rows, ch.div_col0 = post["div"].data_ptr(), post["div_rows"], post["div_col0"]
                 keep.append(post["div"])
         if plan is not None:
-            plan.fill(ch, keep, wide)
+            plan.fill(ch, keep, form)
         else:
             ch.n_ops, ch.out_scale = 0, None
         keep.append(xt)

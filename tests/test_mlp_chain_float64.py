@@ -559,6 +559,12 @@ def _m_live_names(kernel):
     return ["w3"] + (["enc2d_sine"] if kernel != "r32" else []) + (["lnlead100", "ref2d_norm"] if kernel in ("r4", "r32") else [])
 
 
+def _m_live_values(kernel):
+    """The *m_live values of test_m_live_inside_and_outside_a_tile (also dumped by tools/chain_bits.py)."""
+    R = KERNELS[kernel]["R"]
+    return sorted({0, 1, R - 1, R, R + 1, N, 72})
+
+
 @gpu
 @pytest.mark.parametrize("kernel", list(KERNELS))
 def test_m_live_inside_and_outside_a_tile(kernel):
@@ -569,7 +575,7 @@ def test_m_live_inside_and_outside_a_tile(kernel):
     for name in _m_live_names(kernel):
         kind = _launches()[name].kinds[0]
         refs = _reference(name, kind)
-        for i, live in enumerate(sorted({0, 1, R - 1, R, R + 1, N, 72})):
+        for i, live in enumerate(_m_live_values(kernel)):
             out, spans, ln_bufs = _run(kernel, name, _operands(name, kind), N, i % 2, live=live)
             what = (kernel, name, "m_live", live)
             _assert_unowned(out, spans, N, what)
