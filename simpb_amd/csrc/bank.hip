@@ -8,7 +8,7 @@
 #include "../../include/simpb_hip.h"
 #include "store_fence.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
 
 namespace {
 

@@ -7,7 +7,7 @@
 #include <hip/hip_fp16.h>
 #include "../../include/simpb_hip.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
 
 namespace {
 

@@ -20,7 +20,7 @@
 #include "../../include/simpb_hip.h"
 #include "conv_parts.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
 // csrc/conv3x3.hip: the same convolution through its staged pipeline (TAPS = 1)
 extern "C" int simpb_conv_pointwise_staged(void* y, const void* x, const void* weight, const void* bias, const void* residual,
                                            int p_out, int in_h, int in_w, int ho, int wo, int in_channels, int out_channels,

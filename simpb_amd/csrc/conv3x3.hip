@@ -48,7 +48,7 @@
 #include "../../include/simpb_hip.h"
 #include "conv_parts.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
 
 namespace {
 

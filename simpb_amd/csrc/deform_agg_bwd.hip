@@ -15,12 +15,13 @@
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
+#include "sampler_parts.h"
 
 namespace {
 
-constexpr int kWaves = 4;
-constexpr int kThreads = kWaves * 64;
+using namespace simpb::sampler;
+
 constexpr int kMaxPK = 128;
 constexpr int kNJ = 4;  // channels per lane: c = lane + 64*j
 
@@ -43,12 +44,7 @@ __global__ __launch_bounds__(kThreads) void daf_bwd_rows(
   for (int i = threadIdx.x; i < kWaves * kMaxPK * 2; i += kThreads) (&s_gl[0][0][0])[i] = 0.f;
   __syncthreads();
 
-  const float2* loc2 = reinterpret_cast<const float2*>(loc) + row * PK;
-  float2 l0 = make_float2(-1.f, -1.f), l1 = make_float2(-1.f, -1.f);
-  if (lane < PK) l0 = loc2[lane];
-  if (lane + 64 < PK) l1 = loc2[lane + 64];
-  const unsigned long long m0 = __ballot(l0.x > 0.f && l0.x < 1.f && l0.y > 0.f && l0.y < 1.f);
-  const unsigned long long m1 = __ballot(l1.x > 0.f && l1.x < 1.f && l1.y > 0.f && l1.y < 1.f);
+  const RowLocations r = load_locations(reinterpret_cast<const float2*>(loc) + row * PK, lane, PK);
 
   float go[kNJ];
   int grp[kNJ];
@@ -63,24 +59,20 @@ __global__ __launch_bounds__(kThreads) void daf_bwd_rows(
   const float* wrow = weights + row * PK * L * G;
 
   for (int lvl = wave; lvl < L; lvl += kWaves) {
-    unsigned long long ma = m0, mb = m1;
+    unsigned long long ma = r.m0, mb = r.m1;
     while (ma | mb) {
-      int i0;
-      if (ma) { i0 = __builtin_ctzll(ma); ma &= ma - 1; } else { i0 = 64 + __builtin_ctzll(mb); mb &= mb - 1; }
-      const float lx = i0 < 64 ? __shfl(l0.x, i0) : __shfl(l1.x, i0 - 64);
-      const float ly = i0 < 64 ? __shfl(l0.y, i0) : __shfl(l1.y, i0 - 64);
+      const int i0 = pop_sample(ma, mb);
+      const float2 l = sample_location(r, i0);
       const int cam = i0 % num_cams;
       const int cs = cam * L + lvl;
       const int H = spatial_shape[2 * cs], W = spatial_shape[2 * cs + 1];
       const size_t base = (size_t)scale_start[cs] * C;
-      const float h_im = (float)((double)(ly * (float)H) - 0.5);
-      const float w_im = (float)((double)(lx * (float)W) - 0.5);
-      const float hf = floorf(h_im), wf = floorf(w_im);
-      const int h0 = (int)hf, w0 = (int)wf;
-      const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
-      const bool y0 = h0 >= 0, y1 = h0 + 1 <= H - 1, x0 = w0 >= 0, x1 = w0 + 1 <= W - 1;
-      const bool t1 = y0 && x0, t2 = y0 && x1, t3 = y1 && x0, t4 = y1 && x1;
-      const size_t p1 = base + (size_t)(h0 * W + w0) * C, p2 = p1 + C, p3 = p1 + (size_t)W * C, p4 = p3 + C;
+      const Bilinear t = taps_gated(l.x, l.y, H, W);
+      const float lh = t.lh, lw = t.lw, hh = t.hh, hw = t.hw;
+      const bool t1 = t.in[0], t2 = t.in[1], t3 = t.in[2], t4 = t.in[3];
+      // (a valid tap's clamped corner is the corner itself)
+      const size_t p1 = base + (size_t)t.pixel(0, W) * C, p2 = base + (size_t)t.pixel(1, W) * C;
+      const size_t p3 = base + (size_t)t.pixel(2, W) * C, p4 = base + (size_t)t.pixel(3, W) * C;
       const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
       float gx = 0.f, gy = 0.f;
       float gwp[kNJ];

@@ -4,7 +4,8 @@
 // (ops/src/deformable_aggregation_cuda.cu:129-187). What csrc/dfa_prep.hip + csrc/deform_agg.hip do in three launches
 // through two HBM tensors (loc 0.56 MB, weights 9 MB written and read back per layer), here in one: the workgroup that
 // aggregates anchor `a` computes that anchor's 13 x 6 sampling locations in registers and its 312 x 8 softmax weights
-// in LDS first. Same arithmetic, statement for statement, as the three kernels (tests compare them).
+// in LDS first. Key point, projection, gate, tap rule and gather walk are the same functions as in the three kernels
+// (csrc/sampler_parts.h); the weight softmax is this kernel's own (tests compare the two routes).
 //
 // Mapping as daf_fwd_rows: one workgroup of 4 waves per (batch, anchor), wave w = level w, lane = 4 channels, a tap = one
 // coalesced row per wave-instruction, sums in registers, one LDS meeting, one store. FEAT = float reads the decoder's
@@ -14,56 +15,14 @@
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
 #include "store_fence.h"
-
-extern "C" int simpb_check_launch(void);
-extern "C" int simpb_timing_begin(int kernel_id, void* stream);
-extern "C" void simpb_timing_end(int slot, void* stream);
+#include "launch.h"
+#include "sampler_parts.h"
 
 namespace {
 
-constexpr int kWaves = 4;
-constexpr int kThreads = kWaves * 64;
+using namespace simpb::sampler;
+
 constexpr int kMaxW = 4096;   // floats of LDS for the softmax weights: cams * L * P * G
-
-struct Tap4 {
-  float4 v00, v01, v10, v11;
-  float w00, w01, w10, w11;
-};
-
-__device__ __forceinline__ float4 ld_row(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 ld_row(const _Float16* p) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  const h4 v = *reinterpret_cast<const h4*>(p);
-  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
-
-template <class FEAT>
-__device__ __forceinline__ void issue_taps(Tap4& t, const FEAT* __restrict__ base, int H, int W, int C, float lx, float ly,
-                                           int coff) {
-  const float h_im = (float)((double)(ly * (float)H) - 0.5);
-  const float w_im = (float)((double)(lx * (float)W) - 0.5);
-  const float hf = floorf(h_im), wf = floorf(w_im);
-  const int h0 = (int)hf, w0 = (int)wf;
-  const float lh = h_im - hf, lw = w_im - wf;
-  const float hh = 1.f - lh, hw = 1.f - lw;
-  const bool y0 = h0 >= 0, y1 = h0 + 1 <= H - 1, x0 = w0 >= 0, x1 = w0 + 1 <= W - 1;
-  const int yc0 = max(h0, 0), yc1 = min(h0 + 1, H - 1), xc0 = max(w0, 0), xc1 = min(w0 + 1, W - 1);
-  t.w00 = (y0 && x0) ? hh * hw : 0.f;
-  t.w01 = (y0 && x1) ? hh * lw : 0.f;
-  t.w10 = (y1 && x0) ? lh * hw : 0.f;
-  t.w11 = (y1 && x1) ? lh * lw : 0.f;
-  t.v00 = ld_row(base + (size_t)(yc0 * W + xc0) * C + coff);
-  t.v01 = ld_row(base + (size_t)(yc0 * W + xc1) * C + coff);
-  t.v10 = ld_row(base + (size_t)(yc1 * W + xc0) * C + coff);
-  t.v11 = ld_row(base + (size_t)(yc1 * W + xc1) * C + coff);
-}
-
-__device__ __forceinline__ void accumulate(float4& acc, const Tap4& t, float wgt) {
-  acc.x += wgt * (t.w00 * t.v00.x + t.w01 * t.v01.x + t.w10 * t.v10.x + t.w11 * t.v11.x);
-  acc.y += wgt * (t.w00 * t.v00.y + t.w01 * t.v01.y + t.w10 * t.v10.y + t.w11 * t.v11.y);
-  acc.z += wgt * (t.w00 * t.v00.z + t.w01 * t.v01.z + t.w10 * t.v10.z + t.w11 * t.v11.z);
-  acc.w += wgt * (t.w00 * t.v00.w + t.w01 * t.v01.w + t.w10 * t.v10.w + t.w11 * t.v11.w);
-}
 
 struct DfaArgs {
   float* out;                 // [bs, A, C]
@@ -93,9 +52,8 @@ struct PointOps {
 
 // vmask (masked form): bit c = camera c of this stream is valid; `spare` a valid camera (or 0). The rows of a masked camera
 // are not read: its loads go to the spare camera's rows and their results are dropped.
-template <int CAMS, int NUM_FIX, int NUM_LEARN, bool MASKED = false>
-__device__ __forceinline__ void fetch_point(PointOps& o, const DfaArgs& k, size_t row, int b, int i, unsigned vmask = 0,
-                                            int spare = 0) {
+template <int CAMS, int NUM_FIX, int NUM_LEARN, bool MASKED>
+__device__ __forceinline__ void fetch_point(PointOps& o, const DfaArgs& k, size_t row, int b, int i, unsigned vmask, int spare) {
   const int p = i / CAMS;
   int cam = i - p * CAMS;
   if (MASKED) cam = ((vmask >> cam) & 1u) ? cam : spare;
@@ -107,27 +65,6 @@ __device__ __forceinline__ void fetch_point(PointOps& o, const DfaArgs& k, size_
   for (int j = 0; j < 12; ++j) o.m[j] = M[j];
   const float* wh = k.image_wh + ((size_t)b * CAMS + cam) * 2;
   o.w0 = wh[0]; o.w1 = wh[1];
-}
-
-// dfa_points_kernel's arithmetic (csrc/dfa_prep.hip), statement for statement
-__device__ __forceinline__ float2 project_point(const PointOps& o, const float* av) {
-  const float sw = expf(av[3]), sl = expf(av[4]), sh = expf(av[5]);
-  float kx, ky, kz;
-  if (o.fixed) {
-    kx = o.f0 * sw; ky = o.f1 * sl; kz = o.f2 * sh;
-  } else {
-    kx = (1.f / (1.f + expf(-o.f0)) - 0.5f) * sw;
-    ky = (1.f / (1.f + expf(-o.f1)) - 0.5f) * sl;
-    kz = (1.f / (1.f + expf(-o.f2)) - 0.5f) * sh;
-  }
-  const float sn = av[6], cs = av[7];
-  const float px = cs * kx - sn * ky + av[0];
-  const float py = sn * kx + cs * ky + av[1];
-  const float pz = kz + av[2];
-  const float u = o.m[0] * px + o.m[1] * py + o.m[2] * pz + o.m[3];
-  const float v = o.m[4] * px + o.m[5] * py + o.m[6] * pz + o.m[7];
-  const float d = fmaxf(o.m[8] * px + o.m[9] * py + o.m[10] * pz + o.m[11], 1e-5f);
-  return make_float2(u / d / o.w0, v / d / o.w1);
 }
 
 // CAMS / L / NUM_FIX / NUM_LEARN / G / C are compile-time: the index arithmetic of the prologue (entry -> (cam, level, point))
@@ -172,8 +109,7 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
     for (int j = 0; j < 8; ++j) av[j] = an[j];
   }
   PointOps op;   // thread i < PK computes sampling location i = p * cams + cam, once per workgroup
-  if (MASKED) fetch_point<CAMS, NUM_FIX, NUM_LEARN, true>(op, k, row, b, min(tid, PK - 1), vmask, spare);
-  else fetch_point<CAMS, NUM_FIX, NUM_LEARN>(op, k, row, b, min(tid, PK - 1));
+  fetch_point<CAMS, NUM_FIX, NUM_LEARN, MASKED>(op, k, row, b, min(tid, PK - 1), vmask, spare);
   // softmax entries of this thread: group g_sm, (level, point) pairs lp = slice + j * slices, every camera
   constexpr int NJ = (LP + slices - 1) / slices;
   float lg[NJ][CAMS];
@@ -197,17 +133,14 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
     }
   }
 
-  // ---- sampling locations (dfa_points_kernel's arithmetic), published through LDS
-  if (MASKED) {
-    const bool on = (vmask >> (min(tid, PK - 1) % CAMS)) & 1u;
-    if (tid < PK) s_loc[tid] = on ? project_point(op, av) : make_float2(-1.f, -1.f);
-    else if (tid < 128) s_loc[tid] = make_float2(-1.f, -1.f);
-  } else {
-    if (tid < PK) s_loc[tid] = project_point(op, av);
+  // ---- sampling locations (the functions of dfa_points_kernel), published through LDS
+  {
+    const bool on = !MASKED || ((vmask >> (min(tid, PK - 1) % CAMS)) & 1u);
+    if (tid < PK) s_loc[tid] = on ? project(op.m, key_point(av, op.f0, op.f1, op.f2, op.fixed), op.w0, op.w1) : make_float2(-1.f, -1.f);
     else if (tid < 128) s_loc[tid] = make_float2(-1.f, -1.f);
   }
 
-  // ---- softmax over the cams * L * P entries of each group (dfa_weights_kernel's arithmetic): thread -> (group, slice);
+  // ---- softmax over the cams * L * P entries of each group (dfa_weights_kernel's result by another tree): thread -> (group, slice);
   // lanes of one group sit G apart inside a wave, so a group's reduction is xor shuffles + one LDS meeting. The division
   // by the sum is applied once to the finished channel sums (every channel belongs to one group).
   float inv_sum;
@@ -255,66 +188,33 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
     if (MASKED && vmask == 0u) inv_sum = 0.f;   // no valid camera: zeros out, not 0 x inf
   }
   // lane i (and i + 64) of EVERY wave holds location i
-  const float2 l0 = s_loc[lane], l1 = s_loc[lane + 64];
+  // (masked form: location i belongs to camera i % cams; a masked camera's bit is cleared whatever its location holds)
+  const RowLocations r = load_locations(s_loc, lane, 128, !MASKED || ((vmask >> (lane % CAMS)) & 1u),
+                                        !MASKED || ((vmask >> ((lane + 64) % CAMS)) & 1u));
   if (k.loc_out && wave == 0) {
     float2* lo = reinterpret_cast<float2*>(k.loc_out) + row * PK;
-    if (lane < PK) lo[lane] = l0;
-    if (lane + 64 < PK) lo[lane + 64] = l1;
+    if (lane < PK) lo[lane] = r.l0;
+    if (lane + 64 < PK) lo[lane + 64] = r.l1;
     simpb::stores_retired();   // (measurement-only output: nothing of it in flight beside the gather's counted waits)
   }
-  // (masked form: location i belongs to camera i % cams; a masked camera's bit is cleared whatever its location holds)
-  const bool on0 = !MASKED || ((vmask >> (lane % CAMS)) & 1u), on1 = !MASKED || ((vmask >> ((lane + 64) % CAMS)) & 1u);
-  const unsigned long long m0 = __ballot(on0 && l0.x > 0.f && l0.x < 1.f && l0.y > 0.f && l0.y < 1.f);
-  const unsigned long long m1 = __ballot(on1 && l1.x > 0.f && l1.x < 1.f && l1.y > 0.f && l1.y < 1.f);
 
-  // ---- the aggregation itself (daf_fwd_rows' loop with the weights in LDS)
+  // ---- the aggregation itself (daf_fwd_rows' walk with the weights in LDS), four samples at a time
   const int coff = lane * 4;
   const int ld_off = coff < C ? coff : 0;
   const int g = ld_off / (C / G);
-  const FEAT* featb = static_cast<const FEAT*>(k.feat) + (size_t)b * k.num_feat * C;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  constexpr int kBatch = 4;   // samples (x 4 taps) requested before any is consumed: a trip of the loop is one memory round trip
-  for (int lvl = wave; lvl < L; lvl += kWaves) {
-    unsigned long long ma = m0, mb = m1;
-    while (ma | mb) {
-      int idx[kBatch];
-#pragma unroll
-      for (int j = 0; j < kBatch; ++j) {
-        idx[j] = -1;
-        if (ma) { idx[j] = __builtin_ctzll(ma); ma &= ma - 1; }
-        else if (mb) { idx[j] = 64 + __builtin_ctzll(mb); mb &= mb - 1; }
-      }
-      Tap4 t[kBatch];
-      float wg[kBatch];
-#pragma unroll
-      for (int j = 0; j < kBatch; ++j) {
-        wg[j] = 0.f;
-        if (idx[j] >= 0) {   // wave-uniform
-          const int i = idx[j];
-          const float x = i < 64 ? __shfl(l0.x, i) : __shfl(l1.x, i - 64);
-          const float y = i < 64 ? __shfl(l0.y, i) : __shfl(l1.y, i - 64);
-          const int cs = (i % cams) * L + lvl;
-          issue_taps(t[j], featb + (size_t)k.scale_start[cs] * C, k.spatial_shape[2 * cs], k.spatial_shape[2 * cs + 1], C, x, y,
-                     ld_off);
-          wg[j] = s_w[(i * L + lvl) * G + g];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < kBatch; ++j)
-        if (idx[j] >= 0) accumulate(acc, t[j], wg[j]);
-    }
-  }
+  gather_levels<4>(acc, r, static_cast<const FEAT*>(k.feat) + (size_t)b * k.num_feat * C, k.spatial_shape, k.scale_start, cams, L,
+                   C, ld_off, wave, [&](int i, int lvl) { return s_w[(i * L + lvl) * G + g]; });
   __syncthreads();   // every wave has read the sums out of s_red
   acc.x *= inv_sum; acc.y *= inv_sum; acc.z *= inv_sum; acc.w *= inv_sum;
-  s_red[wave][lane] = acc;
-  __syncthreads();
-  if (tid < C) {
-    const float* r = reinterpret_cast<const float*>(s_red);
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) s += r[w * 256 + tid];
-    k.out[row * C + tid] = s;
-  }
+  meet_and_store(s_red, acc, wave, lane, k.out + row * C, 0, C);
+}
+
+// the shipped layout (config :221-238: 6 cameras, 4 levels, 7 fixed + 6 learnable key points, 8 groups of 32 channels)
+template <class FEAT>
+void launch_fused(bool masked, dim3 grid, hipStream_t s, const DfaArgs& k) {
+  if (masked) hipLaunchKernelGGL((daf_fused_rows<FEAT, 6, 4, 7, 6, 8, 256, true>), grid, dim3(kThreads), 0, s, k);
+  else hipLaunchKernelGGL((daf_fused_rows<FEAT, 6, 4, 7, 6, 8, 256, false>), grid, dim3(kThreads), 0, s, k);
 }
 
 }  // namespace
@@ -345,17 +245,8 @@ extern "C" int simpb_dfa_fused_forward_cams(
   hipStream_t s = static_cast<hipStream_t>(stream);
   dim3 grid(num_anchors, batch_size);
   const int tslot = simpb_timing_begin(SIMPB_KERNEL_DAF, stream);
-  // the shipped layout (config :221-238: 6 cameras, 4 levels, 7 fixed + 6 learnable key points, 8 groups of 32 channels)
-  if (cam_valid) {
-    if (feat_is_f16)
-      hipLaunchKernelGGL((daf_fused_rows<_Float16, 6, 4, 7, 6, 8, 256, true>), grid, dim3(kThreads), 0, s, k);
-    else
-      hipLaunchKernelGGL((daf_fused_rows<float, 6, 4, 7, 6, 8, 256, true>), grid, dim3(kThreads), 0, s, k);
-  } else if (feat_is_f16) {
-    hipLaunchKernelGGL((daf_fused_rows<_Float16, 6, 4, 7, 6, 8, 256, false>), grid, dim3(kThreads), 0, s, k);
-  } else {
-    hipLaunchKernelGGL((daf_fused_rows<float, 6, 4, 7, 6, 8, 256, false>), grid, dim3(kThreads), 0, s, k);
-  }
+  if (feat_is_f16) launch_fused<_Float16>(cam_valid != nullptr, grid, s, k);
+  else launch_fused<float>(cam_valid != nullptr, grid, s, k);
   simpb_timing_end(tslot, stream);
   return simpb_check_launch();
 }

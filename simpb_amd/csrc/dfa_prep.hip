@@ -13,13 +13,17 @@
 #include "../../include/simpb_hip.h"
 #include "store_fence.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
+#include "sampler_parts.h"
 
 namespace {
 
+using simpb::sampler::key_point;
+using simpb::sampler::project;
+
 // thread per (b, a, p): computes the key point once, projects it into every camera. MASKED: a camera with
 // cam_valid[b, cam] = 0 (u8 [bs, cams]) delivered no frame: its location is (-1, -1), which the aggregation kernel skips
-// (csrc/deform_agg.hip: outside (0, 1)), and neither its matrix nor its image_wh row is read.
+// (csrc/sampler_parts.h in_image: outside (0, 1)), and neither its matrix nor its image_wh row is read.
 template <bool MASKED>
 __global__ void dfa_points_kernel(float* __restrict__ loc, float* __restrict__ key_points,
                                   const float* __restrict__ anchor, const float* __restrict__ learn,
@@ -45,19 +49,8 @@ __global__ void dfa_points_kernel(float* __restrict__ loc, float* __restrict__ k
     f0 = l[0]; f1 = l[1]; f2 = l[2];
   }
   simpb::loads_retired();
-  const float sw = expf(av[3]), sl = expf(av[4]), sh = expf(av[5]);
-  float kx, ky, kz;
-  if (p < num_fix) {
-    kx = f0 * sw; ky = f1 * sl; kz = f2 * sh;
-  } else {
-    kx = (1.f / (1.f + expf(-f0)) - 0.5f) * sw;
-    ky = (1.f / (1.f + expf(-f1)) - 0.5f) * sl;
-    kz = (1.f / (1.f + expf(-f2)) - 0.5f) * sh;
-  }
-  const float sn = av[6], cs = av[7];
-  float px = cs * kx - sn * ky + av[0];
-  float py = sn * kx + cs * ky + av[1];
-  float pz = kz + av[2];
+  const float3 kpt = key_point(av, f0, f1, f2, p < num_fix);
+  float px = kpt.x, py = kpt.y, pz = kpt.z;
   if (key_points) {
     simpb::pin(px); simpb::pin(py); simpb::pin(pz);
     float* kp = key_points + (size_t)idx * 3;
@@ -83,10 +76,8 @@ __global__ void dfa_points_kernel(float* __restrict__ loc, float* __restrict__ k
     for (int k = 0; k < 12; ++k) m[k] = M[k];
     const float w0 = wh[0], w1 = wh[1];
     simpb::loads_retired();  // also retires the previous camera's stores
-    const float u = m[0] * px + m[1] * py + m[2] * pz + m[3];
-    const float v = m[4] * px + m[5] * py + m[6] * pz + m[7];
-    const float d = fmaxf(m[8] * px + m[9] * py + m[10] * pz + m[11], 1e-5f);
-    float r0 = u / d / w0, r1 = v / d / w1;
+    const float2 uv = project(m, make_float3(px, py, pz), w0, w1);
+    float r0 = uv.x, r1 = uv.y;
     simpb::pin(r0); simpb::pin(r1);
     float* o = loc + ((size_t)idx * cams + c) * 2;
     o[0] = r0;

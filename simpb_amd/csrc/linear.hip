@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
 
 namespace {
 

@@ -24,7 +24,7 @@
 #include "../../include/simpb_hip.h"
 #include "mfma_f16.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
 
 namespace {
 

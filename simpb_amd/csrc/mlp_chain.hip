@@ -23,7 +23,7 @@
 #include <type_traits>
 #include "../../include/simpb_hip.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
 
 #ifdef SIMPB_CHAIN_STAMPS
 // diagnostic build only (tools/chain_stamps.py): s_memtime of workgroup (0, 0), wave 0 at the walk's phase boundaries:

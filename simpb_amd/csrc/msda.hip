@@ -5,7 +5,7 @@
 // slot q samples the value map of camera query_cam[q]. Per (query, head):
 //   out[q, head, :] = sum over (lvl, pt) of attn[q,head,lvl,pt] * bilinear(value[cam, lvl, :, head, :], loc)
 // Sampling rule = mmcv's CUDA op = grid_sample(bilinear, padding zeros, align_corners=False):
-// pixel = loc*size - 0.5, each tap zero outside the map.
+// pixel = loc*size - 0.5, each tap zero outside the map (csrc/sampler_parts.h: taps_free).
 //
 // Mapping: one workgroup of 4 waves per (batch, query); wave w takes levels w, w+4, ...; a lane
 // owns 4 consecutive channels of one head, so one wave-instruction fetches, for every head, the
@@ -14,17 +14,12 @@
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
 
-extern "C" int simpb_check_launch(void);
-extern "C" int simpb_timing_begin(int kernel_id, void* stream);
-extern "C" void simpb_timing_end(int slot, void* stream);
+#include "launch.h"
+#include "sampler_parts.h"
 
 namespace {
 
-constexpr int kWaves = 4;
-constexpr int kThreads = kWaves * 64;
-constexpr int kMaxPts = 8;
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+using namespace simpb::sampler;
 
 template <int PTS>
 __device__ __forceinline__ void level_points(float4& acc, const float* __restrict__ vbase, int H, int W, int HC,
@@ -36,25 +31,10 @@ __device__ __forceinline__ void level_points(float4& acc, const float* __restric
   for (int pt = 0; pt < PTS; ++pt) {
     const float2 l = locp[pt];
     const float aw = attp[pt];
-    const float h_im = l.y * (float)H - 0.5f;
-    const float w_im = l.x * (float)W - 0.5f;
-    const float hf = floorf(h_im), wf = floorf(w_im);
-    // far-away locations: keep the int conversion defined, every tap ends up invalid anyway
-    const int h0 = (int)fminf(fmaxf(hf, -2.f), (float)H);
-    const int w0 = (int)fminf(fmaxf(wf, -2.f), (float)W);
-    const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
-    const bool y0 = h0 >= 0 && h0 <= H - 1, y1 = h0 + 1 >= 0 && h0 + 1 <= H - 1;
-    const bool x0 = w0 >= 0 && w0 <= W - 1, x1 = w0 + 1 >= 0 && w0 + 1 <= W - 1;
-    const int yc0 = min(max(h0, 0), H - 1), yc1 = min(max(h0 + 1, 0), H - 1);
-    const int xc0 = min(max(w0, 0), W - 1), xc1 = min(max(w0 + 1, 0), W - 1);
-    tw[pt][0] = (y0 && x0) ? aw * hh * hw : 0.f;
-    tw[pt][1] = (y0 && x1) ? aw * hh * lw : 0.f;
-    tw[pt][2] = (y1 && x0) ? aw * lh * hw : 0.f;
-    tw[pt][3] = (y1 && x1) ? aw * lh * lw : 0.f;
-    v[pt][0] = ld4(vbase + (size_t)(yc0 * W + xc0) * HC + coff);
-    v[pt][1] = ld4(vbase + (size_t)(yc0 * W + xc1) * HC + coff);
-    v[pt][2] = ld4(vbase + (size_t)(yc1 * W + xc0) * HC + coff);
-    v[pt][3] = ld4(vbase + (size_t)(yc1 * W + xc1) * HC + coff);
+    const Bilinear t = taps_free(l.x, l.y, H, W);
+    tap_weights(tw[pt], t, aw);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[pt][k] = ld_row(vbase + (size_t)t.pixel(k, W) * HC + coff);
   }
 #pragma unroll
   for (int pt = 0; pt < PTS; ++pt)
@@ -104,16 +84,7 @@ __global__ __launch_bounds__(kThreads) void msda_grouped_fwd(
       }
     }
     if (cbase) __syncthreads();
-    s_red[wave][lane] = acc;
-    __syncthreads();
-    const int c = cbase + threadIdx.x;
-    if (c < HC) {
-      const float* r = reinterpret_cast<const float*>(s_red);
-      float s = 0.f;
-#pragma unroll
-      for (int w = 0; w < kWaves; ++w) s += r[w * 256 + threadIdx.x];
-      out[qrow * HC + c] = s;
-    }
+    meet_and_store(s_red, acc, wave, lane, out + qrow * HC, cbase, HC);
   }
 }
 

@@ -11,15 +11,14 @@
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
+#include "sampler_parts.h"
 
 namespace {
 
-constexpr int kWaves = 4;
-constexpr int kThreads = kWaves * 64;
+using namespace simpb::sampler;
 
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void atomic_add4(float* p, const float4& v, float s) {
   atomicAdd(p + 0, v.x * s); atomicAdd(p + 1, v.y * s); atomicAdd(p + 2, v.z * s); atomicAdd(p + 3, v.w * s);
 }
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(kThreads) void msda_grouped_bwd(
   const size_t cam_off = ((size_t)b * num_cams + min(cam, num_cams - 1)) * num_value * HC;
   const float* vcam = value + cam_off;
   float* gvcam = g_value + cam_off;
-  const float4 go = ld4(g_out + qrow * HC + coff);
+  const float4 go = ld_row(g_out + qrow * HC + coff);
   const float2* locq = reinterpret_cast<const float2*>(loc) + (qrow * heads + head) * L * P;
   const float* attq = attn + (qrow * heads + head) * L * P;
 
@@ -60,17 +59,15 @@ __global__ __launch_bounds__(kThreads) void msda_grouped_bwd(
     for (int pt = 0; pt < P; ++pt) {
       const float2 l = locq[lvl * P + pt];
       const float aw = attq[lvl * P + pt];
-      const float h_im = l.y * (float)H - 0.5f, w_im = l.x * (float)W - 0.5f;
-      const float hf = floorf(h_im), wf = floorf(w_im);
-      const int h0 = (int)fminf(fmaxf(hf, -2.f), (float)H), w0 = (int)fminf(fmaxf(wf, -2.f), (float)W);
-      const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
-      const bool y0 = h0 >= 0 && h0 <= H - 1, y1 = h0 + 1 >= 0 && h0 + 1 <= H - 1;
-      const bool x0 = w0 >= 0 && w0 <= W - 1, x1 = w0 + 1 >= 0 && w0 + 1 <= W - 1;
-      const bool t1 = y0 && x0, t2 = y0 && x1, t3 = y1 && x0, t4 = y1 && x1;
-      const size_t p1 = lbase + (size_t)(h0 * W + w0) * HC + coff, p2 = p1 + HC, p3 = p1 + (size_t)W * HC, p4 = p3 + HC;
+      const Bilinear t = taps_free(l.x, l.y, H, W);
+      const float lh = t.lh, lw = t.lw, hh = t.hh, hw = t.hw;
+      const bool t1 = t.in[0], t2 = t.in[1], t3 = t.in[2], t4 = t.in[3];
+      // (a valid tap's clamped corner is the corner itself)
+      const size_t p1 = lbase + (size_t)t.pixel(0, W) * HC + coff, p2 = lbase + (size_t)t.pixel(1, W) * HC + coff;
+      const size_t p3 = lbase + (size_t)t.pixel(2, W) * HC + coff, p4 = lbase + (size_t)t.pixel(3, W) * HC + coff;
       const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float4 v1 = t1 ? ld4(vcam + p1) : z, v2 = t2 ? ld4(vcam + p2) : z;
-      const float4 v3 = t3 ? ld4(vcam + p3) : z, v4 = t4 ? ld4(vcam + p4) : z;
+      const float4 v1 = t1 ? ld_row(vcam + p1) : z, v2 = t2 ? ld_row(vcam + p2) : z;
+      const float4 v3 = t3 ? ld_row(vcam + p3) : z, v4 = t4 ? ld_row(vcam + p4) : z;
       if (t1) atomic_add4(gvcam + p1, go, aw * hh * hw);
       if (t2) atomic_add4(gvcam + p2, go, aw * hh * lw);
       if (t3) atomic_add4(gvcam + p3, go, aw * lh * hw);

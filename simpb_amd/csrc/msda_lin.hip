@@ -10,26 +10,26 @@
 // rows per (query, head) and writes agg[q] = [8 heads x 256 | 8 tap-weight sums | pad] (2 176 floats); the projection
 // with W_h -- folded with output_proj into ONE [256 x 2 176] matrix on the host (plugin/dense.py: fold_msda_linear) --
 // is the small query-sized GEMM that follows (1.2 GFLOP instead of 11.8 + 0.15). Softmax of the attention logits,
-// reference point + offset / (W_l, H_l) (group_attn.py:181-201; csrc/rowops.hip msda_prep) ride in the prologue.
+// reference point + offset / (W_l, H_l) (group_attn.py:181-201; msda_operand of csrc/sampler_parts.h, as msda_prep) ride in the prologue.
 //
 // Mapping: one workgroup of 4 waves per (batch, query slot); a HALF-wave owns one head (wave w: heads 2w, 2w + 1), a
 // lane 8 consecutive channels, so a tap is one 16-byte load per lane and a half-wave fetches one whole 512-byte f16 token
 // row (two rows per wave-instruction). Per level all 4 points x 4 taps are requested before any is consumed (16 loads in
 // flight per lane); the 8 x 256 sums live in registers, no cross-wave reduction. TOK = float serves callers whose tokens
 // are not f16 numbers (1 KiB rows, two 16-byte loads per tap).
-// Sampling rule = mmcv's CUDA op = grid_sample(bilinear, zeros, align_corners=False), as csrc/msda.hip.
+// Sampling rule = mmcv's CUDA op = grid_sample(bilinear, zeros, align_corners=False), as csrc/msda.hip (taps_free).
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
 #include "store_fence.h"
 
-extern "C" int simpb_check_launch(void);
-extern "C" int simpb_timing_begin(int kernel_id, void* stream);
-extern "C" void simpb_timing_end(int slot, void* stream);
+#include "launch.h"
+#include "sampler_parts.h"
 
 namespace {
 
+using namespace simpb::sampler;
+
 constexpr int kHeads = 8, kL = 4, kP = 4, kC = 256, kLP = kL * kP;
-constexpr int kThreads = 256;
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(kThreads) void msda_linear_fwd(
   cam = min(cam, num_cams - 1);
   const size_t qrow = (size_t)b * nq + q;
 
-  // ---- prologue (msda_prep's arithmetic): thread t < 128 -> (head t / 16, level (t % 16) / 4, point t % 4)
+  // ---- prologue (msda_prep_kernel's msda_operand): thread t < 128 -> (head t / 16, level (t % 16) / 4, point t % 4)
   if (tid < kHeads * kLP) {
     const float* r = raw + qrow * ldraw;
     const float2 o = *reinterpret_cast<const float2*>(r + 2 * tid);
@@ -70,16 +70,10 @@ __global__ __launch_bounds__(kThreads) void msda_linear_fwd(
     const float rx = ref[qrow * ldref], ry = ref[qrow * ldref + 1];
     const int l = (tid % kLP) / kP;
     const float hl = (float)spatial_shapes[2 * l], wl = (float)spatial_shapes[2 * l + 1];
-    float mx = lg;
-#pragma unroll
-    for (int m = kLP / 2; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-    const float ex = expf(lg - mx);
-    float sum = ex;
-#pragma unroll
-    for (int m = kLP / 2; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
-    s_x[tid] = rx + o.x / wl;
-    s_y[tid] = ry + o.y / hl;
-    s_a[tid] = ex / sum;
+    const MsdaOperand op = msda_operand<kLP>(lg, o.x, o.y, rx, ry, wl, hl);
+    s_x[tid] = op.x;
+    s_y[tid] = op.y;
+    s_a[tid] = op.a;
   }
   __syncthreads();
 
@@ -102,24 +96,10 @@ __global__ __launch_bounds__(kThreads) void msda_linear_fwd(
     for (int p = 0; p < PB; ++p) {
       const int t = head * kLP + l * kP + p0 + p;
       const float lx = s_x[t], ly = s_y[t], aw = s_a[t];
-      const float h_im = ly * (float)H - 0.5f;
-      const float w_im = lx * (float)W - 0.5f;
-      const float hf = floorf(h_im), wf = floorf(w_im);
-      const int h0 = (int)fminf(fmaxf(hf, -2.f), (float)H);   // far-away locations: keep the conversion defined
-      const int w0 = (int)fminf(fmaxf(wf, -2.f), (float)W);
-      const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
-      const bool y0 = h0 >= 0 && h0 <= H - 1, y1 = h0 + 1 >= 0 && h0 + 1 <= H - 1;
-      const bool x0 = w0 >= 0 && w0 <= W - 1, x1 = w0 + 1 >= 0 && w0 + 1 <= W - 1;
-      const int yc0 = min(max(h0, 0), H - 1), yc1 = min(max(h0 + 1, 0), H - 1);
-      const int xc0 = min(max(w0, 0), W - 1), xc1 = min(max(w0 + 1, 0), W - 1);
-      tw[p][0] = (y0 && x0) ? aw * hh * hw : 0.f;
-      tw[p][1] = (y0 && x1) ? aw * hh * lw : 0.f;
-      tw[p][2] = (y1 && x0) ? aw * lh * hw : 0.f;
-      tw[p][3] = (y1 && x1) ? aw * lh * lw : 0.f;
-      v[p][0].load(base + (size_t)(yc0 * W + xc0) * kC);
-      v[p][1].load(base + (size_t)(yc0 * W + xc1) * kC);
-      v[p][2].load(base + (size_t)(yc1 * W + xc0) * kC);
-      v[p][3].load(base + (size_t)(yc1 * W + xc1) * kC);
+      const Bilinear b4 = taps_free(lx, ly, H, W);
+      tap_weights(tw[p], b4, aw);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[p][k].load(base + (size_t)b4.pixel(k, W) * kC);
     }
 #pragma unroll
     for (int p = 0; p < PB; ++p)

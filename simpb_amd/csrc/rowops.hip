@@ -5,7 +5,8 @@
 #include "../../include/simpb_hip.h"
 #include "store_fence.h"
 
-extern "C" int simpb_check_launch(void);
+#include "launch.h"
+#include "sampler_parts.h"
 
 namespace {
 
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void anchor_projection_kernel(float* __restric
 
 // ---- operands of the grouped multi-scale deformable attention from the fused projection
 // (group_attn.py:181-201): one thread per (query slot, head, level*point) element, coalesced; the
-// softmax over the L*P (= 16 shipped) logits of a head is a 16-lane reduction. raw row = [offsets
+// softmax over the L*P (= 16 shipped) logits of a head is a 16-lane reduction (msda_operand, csrc/sampler_parts.h). raw row = [offsets
 // heads*L*P*2 | logits heads*L*P]; location = reference point + offset / (W_l, H_l).
 template <int LP>
 __global__ __launch_bounds__(256) void msda_prep_kernel(float* __restrict__ loc, float* __restrict__ attn,
@@ -80,17 +81,11 @@ __global__ __launch_bounds__(256) void msda_prep_kernel(float* __restrict__ loc,
     const int l = (e % LP) / P;
     hl = (float)spatial_shapes[2 * l]; wl = (float)spatial_shapes[2 * l + 1];
   }
-  float mx = lg;
-#pragma unroll
-  for (int m = LP / 2; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-  const float ex = alive ? expf(lg - mx) : 0.f;
-  float sum = ex;
-#pragma unroll
-  for (int m = LP / 2; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
+  const simpb::sampler::MsdaOperand op = simpb::sampler::msda_operand<LP>(lg, ox, oy, rx, ry, wl, hl, alive);   // (a dead lane's exp counts as 0)
   if (!in) return;
   const size_t o = (size_t)q * per_row + e;
-  reinterpret_cast<float2*>(loc)[o] = alive ? make_float2(rx + ox / wl, ry + oy / hl) : make_float2(0.f, 0.f);
-  attn[o] = alive ? ex / sum : 0.f;
+  reinterpret_cast<float2*>(loc)[o] = alive ? make_float2(op.x, op.y) : make_float2(0.f, 0.f);
+  attn[o] = alive ? op.a : 0.f;
 }
 
 // ---- ReWeight.alpha (aggregation.py:23-24): one wave per row
