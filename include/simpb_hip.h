@@ -274,6 +274,41 @@ int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, const void* i
 /* Bytes of one row of the `mid` scratch above (whole groups of 4 pixels, rounded up to 16); 0 for a width outside 1..2048. */
 int simpb_preprocess_mid_pitch(int out_width);
 
+/* The same ingest for a RIG of cameras that differ: each camera has its own source size, format, surface layout, resize,
+ * crop and flip, and all of them give one output size. Image n belongs to camera n % num_cams (images in (stream, camera)
+ * order, num_images a multiple of num_cams). Two launches for the whole rig, whatever its cameras are; each output block
+ * equals simpb_preprocess_surface_nhwc4_f16 of that camera alone bit for bit.
+ *   simpb_rig_camera  one camera: format .. chroma_offset, src_row0 .. flip and yoff .. ibu mean what the arguments of that
+ *                 name mean above (the chroma fields and yoff .. ibu are not looked at for _BGR), for this camera's images.
+ *     kx_offset   ints from `kx` to this camera's [out_width][taps_x] coefficients;  x_offset: entries from `xlo` / `xn` to
+ *                 its out_width entries;  ky_offset / y_offset: the same for [out_height][taps_y] and out_height
+ *     mid_row     the camera's first row inside one stream's block of the intermediate (it takes src_rows rows)
+ *   cams          HOST array of num_cams <= SIMPB_RIG_MAX_CAMS descriptors. They travel to the kernels by value: a captured
+ *                 launch keeps the rig it was captured with, and only image_table is read at replay.
+ *   kx, xlo, xn, ky, ylo, yn   device int32 arrays of kx_len, x_len, x_len, ky_len, y_len, y_len entries: the cameras'
+ *                 tables, concatenated;  lut: one table for all cameras
+ *   mid           scratch of (num_images / num_cams) * mid_rows * simpb_preprocess_mid_pitch(out_width) bytes, 16-byte aligned
+ *   image_table   device array of num_images 64-bit addresses (8-byte aligned), read when the kernels run. An address of 0
+ *                 skips that image: none of its source bytes is read and its output block is written as f16 zeros (a paused
+ *                 stream, a camera that delivered nothing); every other image is unaffected.
+ * The horizontal grid spans the largest src_rows of the rig; a workgroup past its camera's rows leaves at once. Its LDS is
+ * sized for the rig's widest cameras (at most 34832 bytes), not for the widest source this file takes.
+ * SIMPB_EINVAL, and nothing launched or written: num_cams outside 1..16; num_images no multiple of num_cams; for any camera,
+ * whatever simpb_preprocess_surface_nhwc4_f16 refuses in its address-table form; a table range or an intermediate range
+ * that leaves its array or overlaps another camera's. Two launches on `stream`; no allocation, no synchronisation. */
+#define SIMPB_RIG_MAX_CAMS 16
+typedef struct simpb_rig_camera {
+  int format, src_height, src_width;
+  int src_row0, src_rows, taps_x, taps_y, flip;
+  long long pitch, chroma_pitch, chroma_offset;
+  int kx_offset, x_offset, ky_offset, y_offset, mid_row;
+  int yoff, iy, irv, igu, igv, ibu;
+} simpb_rig_camera;
+int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table, void* mid, const int* kx, const int* xlo, const int* xn,
+                                   const int* ky, const int* ylo, const int* yn, const void* lut, const simpb_rig_camera* cams,
+                                   int num_cams, int num_images, int out_height, int out_width, int kx_len, int x_len, int ky_len,
+                                   int y_len, int mid_rows, int swap_rb, void* stream);
+
 /* Grouped small GEMM of the decoder: up to 4 independent problems per launch, each
  *   y[M, 0:N] (row stride ldy) = relu?( [x0 | x1 | ...][M, K] . w[N, K]^T (row stride ldw) + bias[N] )
  * where x is given as up to 4 column segments (pointer, row stride, width; widths sum to K). This is
@@ -705,6 +740,18 @@ int simpb_decode2d_record_ragged(float* rec2d, const float* cls2d, const float* 
                                  const int* group_start, const int* rank_of_anchor, int batch_size, int rows_per_stream,
                                  int num_cams, int num_classes, int num_anchors, float crop_w, float crop_h, float crop_y0,
                                  float resize, void* stream);
+
+/* Both 2D records for a rig whose cameras differ in crop and resize (simpb_preprocess_rig_nhwc4_f16): cam_rule, device f32
+ * [num_cams, 4], 16-byte aligned, holds (crop_w, crop_h, crop_y0, 1 / resize) per camera in place of the four scalars, and
+ * a slot's box is decoded with the row of the slot's own camera (query_cam; counted within the stream in the ragged form).
+ * The arithmetic is the scalar entry points': a table of equal rows, 1 / resize rounded to fp32, gives their bits. */
+int simpb_decode2d_record_cams(float* rec2d, const float* cls2d, const float* box2d, const int* q2a, const int* query_cam,
+                               const int* rank_of_anchor, int batch_size, int num_query2d, int num_classes, int num_anchors,
+                               const float* cam_rule, int num_cams, void* stream);
+int simpb_decode2d_record_ragged_cams(float* rec2d, const float* cls2d, const float* box2d, const int* q2a,
+                                      const int* query_cam, const int* group_start, const int* rank_of_anchor, int batch_size,
+                                      int rows_per_stream, int num_cams, int num_classes, int num_anchors, const float* cam_rule,
+                                      void* stream);
 
 /* Exchange form of a 2D record (simpb_amd/dist.py): out f32 [bs, rows_out, 8] = the rows of rec2d [bs, rows_in, 8] that
  * decode_with2d returns (rank >= 0 and camera >= 0: slots of the kept 3D boxes, decoder.py:176-251) in their order, pad rows

@@ -19,6 +19,13 @@ class WorldTables(ctypes.Structure):
                 ("threshold", _F), ("has_threshold", _I), ("num_output", _I)]
 
 
+class RigCamera(ctypes.Structure):
+    """simpb_rig_camera of include/simpb_hip.h: one camera of a rig (simpb_preprocess_rig_nhwc4_f16 takes a host array of them)."""
+    _fields_ = ([(n, _I) for n in ("format", "src_height", "src_width", "src_row0", "src_rows", "taps_x", "taps_y", "flip")] +
+                [(n, _LL) for n in ("pitch", "chroma_pitch", "chroma_offset")] +
+                [(n, _I) for n in ("kx_offset", "x_offset", "ky_offset", "y_offset", "mid_row", "yoff", "iy", "irv", "igu", "igv", "ibu")])
+
+
 SIGNATURES = {
     "simpb_abi_version": ([], _I),
     "simpb_last_error": ([], ctypes.c_char_p),
@@ -51,6 +58,7 @@ SIGNATURES = {
     "simpb_preprocess_yuv420sp_nhwc4_f16": ([_P] * 10 + [_I] * 18 + [_P], _I),
     "simpb_preprocess_surface_nhwc4_f16": ([_P] * 11 + [_I] * 12 + [_LL] * 4 + [_I] * 6 + [_P], _I),
     "simpb_preprocess_mid_pitch": ([_I], _I),
+    "simpb_preprocess_rig_nhwc4_f16": ([_P] * 10 + [ctypes.POINTER(RigCamera)] + [_I] * 10 + [_P], _I),
     "simpb_linear_f16in_split": ([_P] * 5 + [_I] * 3 + [_P], _I),
     "simpb_format_tokens": ([_P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
     "simpb_attention_f32": ([_P] * 6 + [_I] * 9 + [_F, _P], _I),
@@ -74,6 +82,8 @@ SIGNATURES = {
     "simpb_decode2d_record": ([_P] * 6 + [_I] * 4 + [_F] * 4 + [_P], _I),
     "simpb_record2d_compact": ([_P, _LL, _P, _LL, _I, _I, _I, _P], _I),
     "simpb_decode2d_record_ragged": ([_P] * 7 + [_I] * 5 + [_F] * 4 + [_P], _I),
+    "simpb_decode2d_record_cams": ([_P] * 6 + [_I] * 4 + [_P, _I, _P], _I),
+    "simpb_decode2d_record_ragged_cams": ([_P] * 7 + [_I] * 5 + [_P, _P], _I),
     "simpb_world_record": ([_P] * 5 + [WorldTables, _I, _P], _I),
     "simpb_topk_rows": ([_P, _P, _P, _I, _I, _I, _P], _I),
     "simpb_rowdot_sigmoid": ([_P, _P, _I, _P, _P, _I, _I, _P, _P], _I),

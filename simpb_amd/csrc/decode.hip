@@ -125,6 +125,16 @@ __global__ __launch_bounds__(512) void decode3d_kernel(float* __restrict__ rec3d
   }
 }
 
+// decode_box2d (:36-51): a normalised (cx, cy, w, h) box of the cropped image -> xyxy in the camera's source pixels.
+__device__ __forceinline__ void box2d_pixels(float* r, const float* __restrict__ bx, float crop_w, float crop_h, float crop_y0,
+                                             float inv_resize) {
+  const float cx = bx[0], cy = bx[1], w = bx[2], h = bx[3];
+  r[0] = fminf(fmaxf((cx - 0.5f * w) * crop_w, 0.f), crop_w) * inv_resize;
+  r[1] = (fminf(fmaxf((cy - 0.5f * h) * crop_h, 0.f), crop_h) + crop_y0) * inv_resize;
+  r[2] = fminf(fmaxf((cx + 0.5f * w) * crop_w, 0.f), crop_w) * inv_resize;
+  r[3] = (fminf(fmaxf((cy + 0.5f * h) * crop_h, 0.f), crop_h) + crop_y0) * inv_resize;
+}
+
 // 2D half (:168-175, decode_box2d :36-51), one thread per 2D slot.
 __global__ __launch_bounds__(256) void decode2d_kernel(float* __restrict__ rec2d, const float* __restrict__ cls2d,
                                                        const float* __restrict__ box2d, const int* __restrict__ q2a,
@@ -138,12 +148,8 @@ __global__ __launch_bounds__(256) void decode2d_kernel(float* __restrict__ rec2d
   int arg;
   const float m = best_class(row, C, arg);
   const float* bx = box2d + (size_t)i * 4;
-  const float cx = bx[0], cy = bx[1], w = bx[2], h = bx[3];
   float r[8];
-  r[0] = fminf(fmaxf((cx - 0.5f * w) * crop_w, 0.f), crop_w) * inv_resize;
-  r[1] = (fminf(fmaxf((cy - 0.5f * h) * crop_h, 0.f), crop_h) + crop_y0) * inv_resize;
-  r[2] = fminf(fmaxf((cx + 0.5f * w) * crop_w, 0.f), crop_w) * inv_resize;
-  r[3] = (fminf(fmaxf((cy + 0.5f * h) * crop_h, 0.f), crop_h) + crop_y0) * inv_resize;
+  box2d_pixels(r, bx, crop_w, crop_h, crop_y0, inv_resize);
   r[4] = m;
   r[5] = (float)arg;
   const int a = q2a[i];
@@ -179,17 +185,85 @@ __global__ __launch_bounds__(256) void decode2d_ragged_kernel(float* __restrict_
   int arg;
   const float m = best_class(row, C, arg);
   const float* bx = box2d + (size_t)j * 4;
-  const float cx = bx[0], cy = bx[1], w = bx[2], h = bx[3];
   float r[8];
-  r[0] = fminf(fmaxf((cx - 0.5f * w) * crop_w, 0.f), crop_w) * inv_resize;
-  r[1] = (fminf(fmaxf((cy - 0.5f * h) * crop_h, 0.f), crop_h) + crop_y0) * inv_resize;
-  r[2] = fminf(fmaxf((cx + 0.5f * w) * crop_w, 0.f), crop_w) * inv_resize;
-  r[3] = (fminf(fmaxf((cy + 0.5f * h) * crop_h, 0.f), crop_h) + crop_y0) * inv_resize;
+  box2d_pixels(r, bx, crop_w, crop_h, crop_y0, inv_resize);
   r[4] = m;
   r[5] = (float)arg;
   const int a = q2a[j];
   r[6] = (a >= 0 && a < bs * A) ? (float)rank_of_anchor[a] : -1.f;
   r[7] = (float)(query_cam[j] - b * cams);
+  if (!live) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) r[k] = 0.f;
+    r[6] = r[7] = -1.f;
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) simpb::pin(r[k]);
+  simpb::loads_retired();  // store_fence.h
+  float* o = rec2d + (size_t)i * 8;
+  *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
+  *reinterpret_cast<float4*>(o + 4) = make_float4(r[4], r[5], r[6], r[7]);
+}
+
+// Both 2D kernels for a RIG whose cameras differ in crop and resize: the four numbers of box2d_pixels come from row
+// `cam` of cam_rule f32 [cams][4] = (crop_w, crop_h, crop_y0, 1 / resize), cam the slot's own camera (clamped into the
+// table: an empty slot's box is never looked at). Everything else is the scalar kernel's, so equal rows give its bits.
+__device__ __forceinline__ float4 camera_rule(const float* __restrict__ cam_rule, int cam, int cams) {
+  return *reinterpret_cast<const float4*>(cam_rule + 4 * min(max(cam, 0), cams - 1));
+}
+
+__global__ __launch_bounds__(256) void decode2d_cams_kernel(float* __restrict__ rec2d, const float* __restrict__ cls2d,
+                                                            const float* __restrict__ box2d, const int* __restrict__ q2a,
+                                                            const int* __restrict__ query_cam, const int* __restrict__ rank_of_anchor,
+                                                            int bs, int N2, int C, int A, const float* __restrict__ cam_rule,
+                                                            int cams) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= bs * N2) return;
+  const int b = i / N2, slot = i - b * N2;
+  const float* row = cls2d + (size_t)i * C;
+  int arg;
+  const float m = best_class(row, C, arg);
+  const int cam = query_cam[slot];
+  const float4 rule = camera_rule(cam_rule, cam, cams);
+  float r[8];
+  box2d_pixels(r, box2d + (size_t)i * 4, rule.x, rule.y, rule.z, rule.w);
+  r[4] = m;
+  r[5] = (float)arg;
+  const int a = q2a[i];
+  r[6] = (a >= 0 && a < A) ? (float)rank_of_anchor[(size_t)b * A + a] : -1.f;
+  r[7] = (float)cam;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) simpb::pin(r[k]);
+  simpb::loads_retired();  // store_fence.h
+  float* o = rec2d + (size_t)i * 8;
+  *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
+  *reinterpret_cast<float4*>(o + 4) = make_float4(r[4], r[5], r[6], r[7]);
+}
+
+__global__ __launch_bounds__(256) void decode2d_ragged_cams_kernel(float* __restrict__ rec2d, const float* __restrict__ cls2d,
+                                                                   const float* __restrict__ box2d, const int* __restrict__ q2a,
+                                                                   const int* __restrict__ query_cam,
+                                                                   const int* __restrict__ group_start,
+                                                                   const int* __restrict__ rank_of_anchor, int bs, int rows, int cams,
+                                                                   int C, int A, const float* __restrict__ cam_rule) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= bs * rows) return;
+  const int b = i / rows, r_in = i - b * rows;
+  const int lo = group_start[b * cams], hi = group_start[(b + 1) * cams];
+  const bool live = lo + r_in < hi;
+  const int j = live ? lo + r_in : 0;   // (as decode2d_ragged_kernel)
+  const float* row = cls2d + (size_t)j * C;
+  int arg;
+  const float m = best_class(row, C, arg);
+  const int cam = query_cam[j] - b * cams;
+  const float4 rule = camera_rule(cam_rule, cam, cams);
+  float r[8];
+  box2d_pixels(r, box2d + (size_t)j * 4, rule.x, rule.y, rule.z, rule.w);
+  r[4] = m;
+  r[5] = (float)arg;
+  const int a = q2a[j];
+  r[6] = (a >= 0 && a < bs * A) ? (float)rank_of_anchor[a] : -1.f;
+  r[7] = (float)cam;
   if (!live) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) r[k] = 0.f;
@@ -290,6 +364,35 @@ extern "C" int simpb_decode2d_record_ragged(float* rec2d, const float* cls2d, co
   hipLaunchKernelGGL(decode2d_ragged_kernel, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), rec2d,
                      cls2d, box2d, q2a, query_cam, group_start, rank_of_anchor, batch_size, rows_per_stream, num_cams,
                      num_classes, num_anchors, crop_w, crop_h, crop_y0, 1.f / resize);
+  return simpb_check_launch();
+}
+
+extern "C" int simpb_decode2d_record_cams(float* rec2d, const float* cls2d, const float* box2d, const int* q2a,
+                                          const int* query_cam, const int* rank_of_anchor, int batch_size, int num_query2d,
+                                          int num_classes, int num_anchors, const float* cam_rule, int num_cams, void* stream) {
+  if (!rec2d || !cls2d || !box2d || !q2a || !query_cam || !rank_of_anchor || batch_size <= 0 || num_query2d <= 0 ||
+      num_classes <= 0 || num_anchors <= 0 || !cam_rule || (reinterpret_cast<size_t>(cam_rule) & 15) || num_cams <= 0)
+    return SIMPB_EINVAL;
+  (void)hipGetLastError();
+  const int total = batch_size * num_query2d;
+  hipLaunchKernelGGL(decode2d_cams_kernel, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), rec2d, cls2d,
+                     box2d, q2a, query_cam, rank_of_anchor, batch_size, num_query2d, num_classes, num_anchors, cam_rule, num_cams);
+  return simpb_check_launch();
+}
+
+extern "C" int simpb_decode2d_record_ragged_cams(float* rec2d, const float* cls2d, const float* box2d, const int* q2a,
+                                                 const int* query_cam, const int* group_start, const int* rank_of_anchor,
+                                                 int batch_size, int rows_per_stream, int num_cams, int num_classes,
+                                                 int num_anchors, const float* cam_rule, void* stream) {
+  if (!rec2d || !cls2d || !box2d || !q2a || !query_cam || !group_start || !rank_of_anchor || batch_size <= 0 ||
+      rows_per_stream <= 0 || num_cams <= 0 || num_classes <= 0 || num_anchors <= 0 || !cam_rule ||
+      (reinterpret_cast<size_t>(cam_rule) & 15) || (long long)batch_size * rows_per_stream > 0x7fffffffll / 8)
+    return SIMPB_EINVAL;
+  (void)hipGetLastError();
+  const int total = batch_size * rows_per_stream;
+  hipLaunchKernelGGL(decode2d_ragged_cams_kernel, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), rec2d,
+                     cls2d, box2d, q2a, query_cam, group_start, rank_of_anchor, batch_size, rows_per_stream, num_cams,
+                     num_classes, num_anchors, cam_rule);
   return simpb_check_launch();
 }
 

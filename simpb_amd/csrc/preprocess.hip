@@ -23,6 +23,10 @@
 // source format (BGR, NV12, NV21, and P010 in u16): row pitch, chroma pitch and offset and the image stride are arguments,
 // and the images are either one contiguous batch or a device table of one address per image. It reads no byte outside a
 // needed row's samples and shares filter, store and the vertical pass with the other two, which keep the tight forms.
+// A RIG of cameras that differ (simpb_preprocess_rig_nhwc4_f16) is two launches as well: image n belongs to camera n % cams,
+// each camera has its own descriptor (format, size, layout, row range, taps, tables), passed by value, and both rig kernels
+// are the surface path's device functions (stage_bgr_row, filter_row_and_store, resample_cols_lut_row) behind a
+// per-workgroup choice of the descriptor; address 0 in the table skips an image, whose output block is written as zeros.
 // Every load of a thread is retired before its stores are issued (store_fence.h).
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
@@ -176,35 +180,29 @@ __device__ __forceinline__ void stage_row(unsigned char* s_dst, const unsigned c
   }
 }
 
-// The horizontal pass over a surface, one workgroup per (needed source row, image), for every source format:
-//   mid[n][r][j][c] = clip8(2^21 + sum_t bgr[n][row0 + r][xlo[jj] + t][c] * kx[jj][t]),  jj = flip ? w - 1 - j : j
-// kBgr: bgr is the surface's own interleaved row. 4:2:0 semi-planar (kNv12: (Cb, Cr) pairs, kNv21: (Cr, Cb), u8; kP010: (Cb,
-// Cr), u16 little-endian with the 10-bit sample in the high bits): chroma sample (i, j) covers luma rows 2i, 2i + 1 and
-// columns 2j, 2j + 1 (replicated). The luma row and the chroma row under it are staged and converted once into the (B, G,
-// R) row, with S = 16 fractional bits, chroma centre C = 128 for u8 and S = 18, C = 512, yoff * 4 for 10-bit samples:
+// One source row of a surface as the (B, G, R) row the filter reads, for every source format. `image` is the image's first
+// byte, luma (or BGR) row r at + r * pitch, chroma row i at + chroma_offset + i * chroma_pitch.
+// kBgr: the surface's own interleaved row, staged where the filter reads it (s_luma / s_chroma are not looked at). 4:2:0
+// semi-planar (kNv12: (Cb, Cr) pairs, kNv21: (Cr, Cb), u8; kP010: (Cb, Cr), u16 little-endian with the 10-bit sample in the high
+// bits): chroma sample (i, j) covers luma rows 2i, 2i + 1 and columns 2j, 2j + 1 (replicated). The luma row and the chroma row
+// under it are staged (Ws samples each in s_luma / s_chroma) and converted once into the (B, G, R) row, with S = 16 fractional
+// bits, chroma centre C = 128 for u8 and S = 18, C = 512, yoff * 4 for 10-bit samples:
 //   c = iy * (Y - yoff) + 2^(S-1),  R = clamp((c + irv * (Cr - C)) >> S),  G = clamp((c + igu * (Cb - C) + igv * (Cr - C)) >> S),
 //   B = clamp((c + ibu * (Cb - C)) >> S)     (int32, arithmetic shift, clamp to 0..255)
-// Chroma rows that lie under no needed luma row are never read.
+// Chroma rows that lie under no needed luma row are never read. Returns with s_src complete (synchronised).
 template <int F>
-__global__ __launch_bounds__(kThreads) void resample_rows_surface_kernel(unsigned char* __restrict__ mid, Surface sf,
-                                                                         const int* __restrict__ kx, const int* __restrict__ xlo,
-                                                                         const int* __restrict__ xn, int Ws, int row0, int rows, int w,
-                                                                         int taps, int flip, int pitch, YuvCoeffs q) {
-  __shared__ __attribute__((aligned(16))) unsigned char s_src[kMaxSrcW * 3];
-  __shared__ __attribute__((aligned(16))) unsigned char s_out[kMaxOutW * 3 + 16];
-  const int tid = threadIdx.x, r = blockIdx.x, n = blockIdx.y;
-  const int row = row0 + r;
-  const unsigned char* image = sf.table ? reinterpret_cast<const unsigned char*>(sf.table[n]) : sf.src + (size_t)n * sf.image_stride;
+__device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned char* s_luma, unsigned char* s_chroma,
+                                              const unsigned char* __restrict__ image, long long pitch, long long chroma_offset,
+                                              long long chroma_pitch, int row, int Ws, const YuvCoeffs& q) {
+  const int tid = threadIdx.x;
   if constexpr (F == kBgr) {
-    stage_row(s_src, image + (size_t)row * sf.pitch, Ws * 3);
+    stage_row(s_src, image + (size_t)row * pitch, Ws * 3);
     __syncthreads();
   } else {
     constexpr int kSample = F == kP010 ? 2 : 1;   // bytes per sample
-    __shared__ __attribute__((aligned(16))) unsigned char s_luma[kMaxSrcW * kSample];   // (a BGR row is staged where the filter reads it)
-    __shared__ __attribute__((aligned(16))) unsigned char s_chroma[kMaxSrcW * kSample];
     constexpr int kShift = F == kP010 ? 18 : 16, kCentre = F == kP010 ? 512 : 128, kVu = F == kNv21 ? 1 : 0;
-    stage_row(s_luma, image + (size_t)row * sf.pitch, Ws * kSample);
-    stage_row(s_chroma, image + sf.chroma_offset + (size_t)(row >> 1) * sf.chroma_pitch, Ws * kSample);
+    stage_row(s_luma, image + (size_t)row * pitch, Ws * kSample);
+    stage_row(s_chroma, image + chroma_offset + (size_t)(row >> 1) * chroma_pitch, Ws * kSample);
     __syncthreads();
     const int yoff = F == kP010 ? 4 * q.yoff : q.yoff;
     for (int x = 2 * tid; x < Ws; x += 2 * kThreads) {   // a chroma pair and its two luma samples (Ws is even)
@@ -229,25 +227,88 @@ __global__ __launch_bounds__(kThreads) void resample_rows_surface_kernel(unsigne
     }
     __syncthreads();
   }
+}
+
+// The horizontal pass over a surface, one workgroup per (needed source row, image), for every source format (stage_bgr_row):
+//   mid[n][r][j][c] = clip8(2^21 + sum_t bgr[n][row0 + r][xlo[jj] + t][c] * kx[jj][t]),  jj = flip ? w - 1 - j : j
+template <int F>
+__global__ __launch_bounds__(kThreads) void resample_rows_surface_kernel(unsigned char* __restrict__ mid, Surface sf,
+                                                                         const int* __restrict__ kx, const int* __restrict__ xlo,
+                                                                         const int* __restrict__ xn, int Ws, int row0, int rows, int w,
+                                                                         int taps, int flip, int pitch, YuvCoeffs q) {
+  __shared__ __attribute__((aligned(16))) unsigned char s_src[kMaxSrcW * 3];
+  __shared__ __attribute__((aligned(16))) unsigned char s_out[kMaxOutW * 3 + 16];
+  constexpr int kPlane = F == kBgr ? 16 : kMaxSrcW * (F == kP010 ? 2 : 1);   // (a BGR row is staged where the filter reads it)
+  __shared__ __attribute__((aligned(16))) unsigned char s_luma[kPlane];
+  __shared__ __attribute__((aligned(16))) unsigned char s_chroma[kPlane];
+  const int r = blockIdx.x, n = blockIdx.y;
+  const unsigned char* image = sf.table ? reinterpret_cast<const unsigned char*>(sf.table[n]) : sf.src + (size_t)n * sf.image_stride;
+  stage_bgr_row<F>(s_src, s_luma, s_chroma, image, sf.pitch, sf.chroma_offset, sf.chroma_pitch, row0 + r, Ws, q);
   filter_row_and_store(mid + ((size_t)n * rows + r) * pitch, s_src, s_out, kx, xlo, xn, Ws, w, taps, flip, pitch);
 }
 
-// out[n][y][x][c] = lut[c][clip8(2^21 + sum_t mid[n][ylo[y] - row0 + t][x][swap ? 2 - c : c] * ky[y][t])], out[..][3] = 0
-__global__ __launch_bounds__(kThreads) void resample_cols_lut_kernel(_Float16* __restrict__ out, const unsigned char* __restrict__ mid,
-                                                                     const int* __restrict__ ky, const int* __restrict__ ylo,
-                                                                     const int* __restrict__ yn, const _Float16* __restrict__ lut,
-                                                                     int row0, int rows, int h, int w, int taps, int swap_rb, int pitch) {
+// A RIG (simpb_preprocess_rig_nhwc4_f16): image n belongs to camera n % num_cams, and every camera has its own size, format,
+// layout and tables (simpb_rig_camera, handed over by value: a captured launch keeps its rig and reads nothing but the
+// address table at replay). The descriptor is chosen by blockIdx alone, i.e. it is uniform over the workgroup and is read
+// through scalar loads.
+struct Rig { simpb_rig_camera cam[SIMPB_RIG_MAX_CAMS]; };
+
+// The horizontal pass of a rig: the grid spans the tallest camera's rows, and a workgroup past its own camera's rows -- or
+// whose image has address 0 (the image is skipped: the vertical pass writes zeros) -- leaves before any barrier. Stream
+// n / num_cams keeps its cameras' rows one behind the other in a block of `mid_rows` rows, camera c from row mid_row on.
+// LDS is dynamic, sized by the entry point for the rig at hand (RigLds: the widest camera's (B, G, R) row, the resampled row,
+// and the widest YCbCr camera's luma and chroma rows), not for the widest source the file takes: a rig of 1600-wide NV12
+// cameras holds 10 KB per workgroup where the static arrays of the surface kernel hold 26 KB, and a BGR rig has no planes.
+struct RigLds { int src_bytes, out_bytes, plane_bytes; };   // each a multiple of 16
+
+__global__ __launch_bounds__(kThreads) void resample_rows_rig_kernel(unsigned char* __restrict__ mid,
+                                                                     const unsigned long long* __restrict__ table, Rig rig,
+                                                                     int num_cams, const int* __restrict__ kx,
+                                                                     const int* __restrict__ xlo, const int* __restrict__ xn, int w,
+                                                                     int pitch, int mid_rows, RigLds lds) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_rig[];
+  unsigned char* s_src = s_rig;
+  unsigned char* s_out = s_src + lds.src_bytes;
+  unsigned char* s_luma = s_out + lds.out_bytes;
+  unsigned char* s_chroma = s_luma + lds.plane_bytes;
+  const int r = blockIdx.x, n = blockIdx.y;
+  const int stream = n / num_cams;
+  const simpb_rig_camera& c = rig.cam[n - stream * num_cams];
+  if (r >= c.src_rows) return;
+  const unsigned char* image = reinterpret_cast<const unsigned char*>(table[n]);
+  if (image == nullptr) return;
+  const YuvCoeffs q = {c.yoff, c.iy, c.irv, c.igu, c.igv, c.ibu};
+  const int row = c.src_row0 + r, Ws = c.src_width;
+  switch (c.format) {
+    case kBgr: stage_bgr_row<kBgr>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, row, Ws, q); break;
+    case kNv12: stage_bgr_row<kNv12>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, row, Ws, q); break;
+    case kNv21: stage_bgr_row<kNv21>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, row, Ws, q); break;
+    default: stage_bgr_row<kP010>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, row, Ws, q); break;
+  }
+  filter_row_and_store(mid + ((size_t)stream * mid_rows + c.mid_row + r) * pitch, s_src, s_out, kx + c.kx_offset, xlo + c.x_offset,
+                       xn + c.x_offset, Ws, w, c.taps_x, c.flip, pitch);
+}
+
+// One output row of one image, the vertical pass + table: `out_image` f16 [h][w][4], `mid_image` the image's `rows`
+// intermediate rows (source rows row0 ..), ky / ylo / yn the image's own tables; y = blockIdx.y, the groups of 4 pixels along
+// blockIdx.x.
+//   out[y][x][c] = lut[c][clip8(2^21 + sum_t mid[ylo[y] - row0 + t][x][swap ? 2 - c : c] * ky[y][t])], out[..][3] = 0
+// zero (uniform over the workgroup): nothing of mid_image is read and the row is written as f16 zeros.
+__device__ __forceinline__ void resample_cols_lut_row(_Float16* __restrict__ out_image, const unsigned char* __restrict__ mid_image,
+                                                      const int* __restrict__ ky, const int* __restrict__ ylo,
+                                                      const int* __restrict__ yn, const _Float16* __restrict__ lut, int row0, int rows,
+                                                      int w, int taps, int swap_rb, int pitch, bool zero) {
   __shared__ _Float16 s_lut[3 * 256];
   __shared__ int s_k[kMaxTaps];
-  const int tid = threadIdx.x, y = blockIdx.y, n = blockIdx.z;
+  const int tid = threadIdx.x, y = blockIdx.y;
   for (int i = tid; i < 3 * 256; i += kThreads) s_lut[i] = lut[i];
-  const int cnt = min(min(yn[y], taps), rows);
+  const int cnt = zero ? 0 : min(min(yn[y], taps), rows);
   if (tid < cnt) s_k[tid] = ky[(size_t)y * taps + tid];
   __syncthreads();
   const int g = blockIdx.x * kThreads + tid;   // group of 4 output pixels
   if (4 * g >= w) return;
-  const int first = min(max(ylo[y] - row0, 0), rows - cnt);   // (clamped like the horizontal pass: never outside `mid`)
-  const unsigned int* p = reinterpret_cast<const unsigned int*>(mid + ((size_t)n * rows + first) * pitch) + 3 * g;
+  const int first = zero ? 0 : min(max(ylo[y] - row0, 0), rows - cnt);   // (clamped like the horizontal pass: never outside `mid`)
+  const unsigned int* p = reinterpret_cast<const unsigned int*>(mid_image + (size_t)first * pitch) + 3 * g;
   const int pitch4 = pitch >> 2;
   int acc[12];
 #pragma unroll
@@ -269,14 +330,14 @@ __global__ __launch_bounds__(kThreads) void resample_cols_lut_kernel(_Float16* _
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int ci = swap_rb ? 2 - c : c;
-      v[px >> 1][(px & 1) * 4 + c] = s_lut[c * 256 + clip8(acc[px * 3 + ci])];
+      v[px >> 1][(px & 1) * 4 + c] = zero ? (_Float16)0.f : s_lut[c * 256 + clip8(acc[px * 3 + ci])];
     }
     v[px >> 1][(px & 1) * 4 + 3] = (_Float16)0.f;
   }
   simpb::pin(v[0]);
   simpb::pin(v[1]);
   simpb::loads_retired();
-  _Float16* o = out + (((size_t)n * h + y) * w + 4 * g) * 4;
+  _Float16* o = out_image + ((size_t)y * w + 4 * g) * 4;
   if (4 * g + 4 <= w) {
     *reinterpret_cast<h8*>(o) = v[0];
     *reinterpret_cast<h8*>(o + 8) = v[1];
@@ -288,6 +349,31 @@ __global__ __launch_bounds__(kThreads) void resample_cols_lut_kernel(_Float16* _
         for (int c = 0; c < 4; ++c) o[px * 4 + c] = v[px >> 1][(px & 1) * 4 + c];
       }
   }
+}
+
+// out[n][y][x][c] = lut[c][clip8(2^21 + sum_t mid[n][ylo[y] - row0 + t][x][swap ? 2 - c : c] * ky[y][t])], out[..][3] = 0
+__global__ __launch_bounds__(kThreads) void resample_cols_lut_kernel(_Float16* __restrict__ out, const unsigned char* __restrict__ mid,
+                                                                     const int* __restrict__ ky, const int* __restrict__ ylo,
+                                                                     const int* __restrict__ yn, const _Float16* __restrict__ lut,
+                                                                     int row0, int rows, int h, int w, int taps, int swap_rb, int pitch) {
+  const int n = blockIdx.z;
+  resample_cols_lut_row(out + (size_t)n * h * w * 4, mid + (size_t)n * rows * pitch, ky, ylo, yn, lut, row0, rows, w, taps, swap_rb,
+                        pitch, false);
+}
+
+// The vertical pass of a rig: image n reads its camera's ky / ylo / yn, row range and taps, and its own rows of its stream's
+// intermediate block; an image whose address is 0 is written as zeros.
+__global__ __launch_bounds__(kThreads) void resample_cols_lut_rig_kernel(_Float16* __restrict__ out, const unsigned char* __restrict__ mid,
+                                                                         const unsigned long long* __restrict__ table, Rig rig,
+                                                                         int num_cams, const int* __restrict__ ky,
+                                                                         const int* __restrict__ ylo, const int* __restrict__ yn,
+                                                                         const _Float16* __restrict__ lut, int h, int w, int swap_rb,
+                                                                         int pitch, int mid_rows) {
+  const int n = blockIdx.z;
+  const int stream = n / num_cams;
+  const simpb_rig_camera& c = rig.cam[n - stream * num_cams];
+  resample_cols_lut_row(out + (size_t)n * h * w * 4, mid + ((size_t)stream * mid_rows + c.mid_row) * pitch, ky + c.ky_offset,
+                        ylo + c.y_offset, yn + c.y_offset, lut, c.src_row0, c.src_rows, w, c.taps_y, swap_rb, pitch, table[n] == 0ull);
 }
 
 }  // namespace
@@ -423,4 +509,78 @@ extern "C" int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, co
                       chroma_offset, pitch, chroma_pitch};
   return launch_surface(format, out, sf, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_width, out_height, out_width, taps_x, taps_y,
                         src_row0, src_rows, flip, swap_rb, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream);
+}
+
+// [lo, lo + len) of two cameras overlap
+static bool ranges_overlap(long long a, long long alen, long long b, long long blen) { return a < b + blen && b < a + alen; }
+
+extern "C" int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table, void* mid, const int* kx, const int* xlo,
+                                              const int* xn, const int* ky, const int* ylo, const int* yn, const void* lut,
+                                              const simpb_rig_camera* cams, int num_cams, int num_images, int out_height,
+                                              int out_width, int kx_len, int x_len, int ky_len, int y_len, int mid_rows, int swap_rb,
+                                              void* stream) {
+  if (!cams || num_cams <= 0 || num_cams > SIMPB_RIG_MAX_CAMS || num_images <= 0 || num_images % num_cams) return SIMPB_EINVAL;
+  if (kx_len <= 0 || x_len <= 0 || ky_len <= 0 || y_len <= 0 || mid_rows <= 0) return SIMPB_EINVAL;
+  if (reinterpret_cast<size_t>(image_table) & 7) return SIMPB_EINVAL;
+  constexpr long long kMaxPitch = 1LL << 30;
+  int max_rows = 0;
+  for (int i = 0; i < num_cams; ++i) {
+    const simpb_rig_camera& c = cams[i];
+    // (the rules of simpb_preprocess_surface_nhwc4_f16 in its address-table form, camera by camera)
+    if (bad_arguments(out, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, c.src_height, c.src_width, out_height, out_width,
+                      c.taps_x, c.taps_y, c.src_row0, c.src_rows))
+      return SIMPB_EINVAL;
+    if (c.format != kBgr && c.format != kNv12 && c.format != kNv21 && c.format != kP010) return SIMPB_EINVAL;
+    const long long sample = c.format == kP010 ? 2 : 1;
+    const long long row = (long long)c.src_width * (c.format == kBgr ? 3 : sample);
+    if (c.pitch < row || c.pitch > kMaxPitch) return SIMPB_EINVAL;
+    if (c.format != kBgr) {
+      const long long luma_end = (long long)(c.src_height - 1) * c.pitch + row;
+      if ((c.src_height & 1) || (c.src_width & 1) || c.iy <= 0) return SIMPB_EINVAL;
+      if (c.chroma_pitch < row || c.chroma_pitch > kMaxPitch) return SIMPB_EINVAL;
+      if (c.chroma_offset < luma_end || c.chroma_offset > (1LL << 40)) return SIMPB_EINVAL;
+      if (c.format == kP010 && ((c.pitch | c.chroma_pitch | c.chroma_offset) & 1)) return SIMPB_EINVAL;
+    }
+    // the camera's tables and intermediate rows lie inside the arrays given ...
+    if (c.kx_offset < 0 || c.x_offset < 0 || c.ky_offset < 0 || c.y_offset < 0 || c.mid_row < 0) return SIMPB_EINVAL;
+    if ((long long)c.kx_offset + (long long)out_width * c.taps_x > kx_len || (long long)c.x_offset + out_width > x_len ||
+        (long long)c.ky_offset + (long long)out_height * c.taps_y > ky_len || (long long)c.y_offset + out_height > y_len ||
+        (long long)c.mid_row + c.src_rows > mid_rows)
+      return SIMPB_EINVAL;
+    // ... and apart from every other camera's
+    for (int j = 0; j < i; ++j) {
+      const simpb_rig_camera& d = cams[j];
+      if (ranges_overlap(c.kx_offset, (long long)out_width * c.taps_x, d.kx_offset, (long long)out_width * d.taps_x) ||
+          ranges_overlap(c.x_offset, out_width, d.x_offset, out_width) ||
+          ranges_overlap(c.ky_offset, (long long)out_height * c.taps_y, d.ky_offset, (long long)out_height * d.taps_y) ||
+          ranges_overlap(c.y_offset, out_height, d.y_offset, out_height) || ranges_overlap(c.mid_row, c.src_rows, d.mid_row, d.src_rows))
+        return SIMPB_EINVAL;
+    }
+    max_rows = c.src_rows > max_rows ? c.src_rows : max_rows;
+  }
+  Rig rig = {};
+  for (int i = 0; i < num_cams; ++i) {
+    rig.cam[i] = cams[i];
+    rig.cam[i].flip = cams[i].flip ? 1 : 0;
+  }
+  const int pitch = mid_pitch(out_width);
+  // LDS for the rig at hand (validated above: at most kMaxSrcW * 3 + kMaxOutW * 3 + 16 + 2 * kMaxSrcW * 2 = 34832 bytes)
+  int src_bytes = 0, plane_bytes = 0;
+  for (int i = 0; i < num_cams; ++i) {
+    const int planes = cams[i].format == kBgr ? 0 : cams[i].src_width * (cams[i].format == kP010 ? 2 : 1);
+    src_bytes = cams[i].src_width * 3 > src_bytes ? cams[i].src_width * 3 : src_bytes;
+    plane_bytes = planes > plane_bytes ? planes : plane_bytes;
+  }
+  const RigLds lds = {(src_bytes + 15) / 16 * 16, pitch + 16, (plane_bytes + 15) / 16 * 16};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  (void)hipGetLastError();
+  const unsigned long long* table = static_cast<const unsigned long long*>(image_table);
+  hipLaunchKernelGGL(resample_rows_rig_kernel, dim3(max_rows, num_images), dim3(kThreads),
+                     (size_t)(lds.src_bytes + lds.out_bytes + 2 * lds.plane_bytes), s, static_cast<unsigned char*>(mid), table, rig,
+                     num_cams, kx, xlo, xn, out_width, pitch, mid_rows, lds);
+  const int groups = (out_width + 3) / 4;
+  hipLaunchKernelGGL(resample_cols_lut_rig_kernel, dim3((groups + kThreads - 1) / kThreads, out_height, num_images), dim3(kThreads), 0, s,
+                     static_cast<_Float16*>(out), static_cast<const unsigned char*>(mid), table, rig, num_cams, ky, ylo, yn,
+                     static_cast<const _Float16*>(lut), out_height, out_width, swap_rb ? 1 : 0, pitch, mid_rows);
+  return simpb_check_launch();
 }

@@ -322,6 +322,9 @@ class SparseBox3DDecoder(object):
         return torch.cat([box[:, X:Z + 1], box[:, W:H + 1].exp(), yaw[:, None], box[:, VX:]], dim=-1)
 
     def decode_box2d(self, box, aug_config):
+        if not isinstance(aug_config, dict):
+            raise NotImplementedError("a rig of cameras that differ (preprocess.RigPlan) is decoded by the device kernels "
+                                      "(csrc/decode.hip: simpb_decode2d_record_cams) only")
         crop = aug_config["crop"]
         scale_factor = aug_config["resize"]
         crop_img_size = (crop[2] - crop[0], crop[3] - crop[1])
@@ -422,7 +425,9 @@ class SparseBox3DDecoder(object):
                                              _stream()), "simpb_decode3d_record")
         cls2d, box2d = cls2d.contiguous().float(), box2d.contiguous().float()
         n2 = cls2d.shape[1]
-        crop, resize = aug_config["crop"], aug_config["resize"]
+        # a rig (preprocess.RigPlan in place of the aug_config dict): (crop_w, crop_h, crop_y0, 1 / resize) per camera
+        rig = None if isinstance(aug_config, dict) else aug_config.box2d_device(dev)
+        crop, resize = (aug_config["crop"], aug_config["resize"]) if rig is None else (None, None)
         if getattr(alloc, "streams", 0):
             # independent streams: the flat slot array [1, bs * capacity] back to one record per stream, as a batch of one
             # writes it (its slots first, cameras counted within the stream, pad rows behind)
@@ -431,13 +436,25 @@ class SparseBox3DDecoder(object):
             rows = n2 // bs
             rec2d = torch.empty(bs, rows, 8, device=dev)
             cams = (alloc.group_start.numel() - 1) // bs
+            if rig is not None:
+                if rig.shape[0] != cams:
+                    raise ValueError(f"decode: the rig has {rig.shape[0]} cameras, the allocation {cams}")
+                _lib.check(lib.simpb_decode2d_record_ragged_cams(
+                    _ptr(rec2d), _ptr(cls2d), _ptr(box2d), _ptr(alloc.q2a.contiguous()), _ptr(alloc.query_cam.contiguous()),
+                    _ptr(alloc.group_start), _ptr(rank), bs, rows, cams, cls2d.shape[-1], num_anchor, _ptr(rig), _stream()),
+                    "simpb_decode2d_record_ragged_cams")
+                return rec3d, rec2d
             _lib.check(lib.simpb_decode2d_record_ragged(
                 _ptr(rec2d), _ptr(cls2d), _ptr(box2d), _ptr(alloc.q2a.contiguous()), _ptr(alloc.query_cam.contiguous()),
                 _ptr(alloc.group_start), _ptr(rank), bs, rows, cams, cls2d.shape[-1], num_anchor, float(crop[2] - crop[0]),
                 float(crop[3] - crop[1]), float(crop[1]), float(resize), _stream()), "simpb_decode2d_record_ragged")
             return rec3d, rec2d
         rec2d = torch.empty(bs, n2, 8, device=dev)
-        if n2:
+        if n2 and rig is not None:
+            _lib.check(lib.simpb_decode2d_record_cams(_ptr(rec2d), _ptr(cls2d), _ptr(box2d), _ptr(alloc.q2a.contiguous()),
+                                                      _ptr(alloc.query_cam.contiguous()), _ptr(rank), bs, n2, cls2d.shape[-1],
+                                                      num_anchor, _ptr(rig), rig.shape[0], _stream()), "simpb_decode2d_record_cams")
+        elif n2:
             _lib.check(lib.simpb_decode2d_record(_ptr(rec2d), _ptr(cls2d), _ptr(box2d), _ptr(alloc.q2a.contiguous()),
                                                  _ptr(alloc.query_cam.contiguous()), _ptr(rank), bs, n2, cls2d.shape[-1],
                                                  num_anchor, float(crop[2] - crop[0]), float(crop[3] - crop[1]),

@@ -13,7 +13,11 @@ Frames may also arrive as 4:2:0 semi-planar YCbCr (NV12 / NV21), the form hardwa
 `yuv_coefficients` defines the integer conversion to the (B, G, R) bytes above that the horizontal pass applies while it
 stages a row; everything behind it is the BGR route's own. `SurfaceLayout` describes how a decoder lays such an image out
 in memory (padded row pitch, aligned plane height, the chroma plane's own pitch and offset, tail padding) and adds P010, the
-10-bit form of NV12 (`p010_coefficients`); `ResamplePlan.run_surfaces` takes one allocation per image."""
+10-bit form of NV12 (`p010_coefficients`); `ResamplePlan.run_surfaces` takes one allocation per image.
+
+A ResamplePlan describes all its images as one layout. `CameraSource` / `RigPlan` describe a rig whose cameras differ (source
+size, format, layout, resize, crop, flip): per camera the tables of that camera's own ResamplePlan, one output size, two
+launches for the whole rig, and the per-camera numbers the 2D record and the intrinsics need (`box2d_table`, `image_transforms`)."""
 import ctypes
 import math
 
@@ -494,4 +498,204 @@ class ResamplePlan:
             p(out), p(src) if table is None else null, null if table is None else p(table), *tables, *ints,
             SURFACE_FORMAT[self.frame_format], sf.pitch, sf.chroma_pitch, sf.chroma_offset, sf.image_bytes, *yuv, stream),
             "simpb_preprocess_surface_nhwc4_f16")
+        return out
+
+
+# ---------------------------------------------------------------------- a rig of cameras that differ
+RIG_MAX_CAMS = 16     # SIMPB_RIG_MAX_CAMS of include/simpb_hip.h
+
+
+class CameraSource:
+    """One camera of a rig (RigPlan): what a ResamplePlan takes for that camera alone, with the same checks. A camera of a
+    rig gives its scale as the reference's scalar `resize` (with `crop` and `flip`): the 2D boxes are mapped back to source
+    pixels by that scalar (decoder.py:36-51), so an explicit, possibly anisotropic `resize_dims` is refused."""
+
+    def __init__(self, src_hw, aug_config=None, frame_format="bgr", colour="jfif", layout=None):
+        self.src_hw = (int(src_hw[0]), int(src_hw[1]))
+        self.aug_config = dict(aug_config or {})
+        if self.aug_config.get("resize_dims") is not None:
+            raise ValueError("a camera of a rig gives its scale as `resize` (with crop / flip): resize_dims is not taken, the 2D "
+                             "boxes are mapped back to source pixels by the reference's isotropic rule")
+        _check_format(frame_format, colour)
+        self.frame_format, self.colour = frame_format, colour
+        self.surface = SurfaceLayout.make(layout, self.src_hw, frame_format)
+        self.resize = float(self.aug_config.get("resize", 1))
+        self.resize_dims, self.crop, self.flip = resolve_aug(self.src_hw, self.aug_config)
+        self.out_hw = (self.crop[3] - self.crop[1], self.crop[2] - self.crop[0])
+        self.key = plan_key(self.src_hw, self.aug_config, frame_format, colour, self.surface) + (self.resize,)
+
+    def plan(self, img_norm_cfg=None):
+        """The ResamplePlan of this camera alone."""
+        return ResamplePlan(self.src_hw, self.aug_config, img_norm_cfg, self.frame_format, self.colour, self.surface)
+
+    def describe(self):
+        return f"{self.frame_format} {self.src_hw[1]} x {self.src_hw[0]} -> {self.out_hw[1]} x {self.out_hw[0]}"
+
+
+class RigPlan:
+    """Tables of a rig of 1 .. 16 cameras that may differ in source size, format, colour standard, surface layout, resize, crop
+    and flip, and give one output size: per camera exactly what its own ResamplePlan holds (`plans`), concatenated camera
+    by camera for the device, and one normalisation table. A rig takes surfaces only -- one device u8 tensor per image, in
+    (stream, camera) order -- since images of different sizes have no common tensor; None in place of a tensor (address 0 in
+    the table) skips that image: nothing is read for it and its output block is zeros."""
+
+    TABLES = ("kx", "xlo", "xn", "ky", "ylo", "yn")
+
+    def __init__(self, sources, img_norm_cfg=None):
+        sources = list(sources)
+        if not 1 <= len(sources) <= RIG_MAX_CAMS:
+            raise ValueError(f"a rig has 1 .. {RIG_MAX_CAMS} cameras, got {len(sources)}")
+        for i, s in enumerate(sources):
+            if not isinstance(s, CameraSource):
+                raise ValueError(f"camera {i} of the rig is a {type(s).__name__}: a rig is a list of preprocess.CameraSource")
+        if len({s.out_hw for s in sources}) != 1:
+            sizes = ", ".join(f"camera {i}: {s.out_hw[1]} x {s.out_hw[0]}" for i, s in enumerate(sources))
+            raise ValueError(f"the cameras of a rig give one output size (the backbone takes one), got {sizes}")
+        self.sources = tuple(sources)
+        self.num_cams = len(sources)
+        self.plans = tuple(s.plan(img_norm_cfg) for s in sources)
+        p0 = self.plans[0]
+        self.out_hw, self.img_norm_cfg, self.swap_rb, self.lut = p0.out_hw, p0.img_norm_cfg, p0.swap_rb, p0.lut
+        self.key = ("rig",) + tuple(s.key for s in sources)
+        # per camera: the plan's own arrays and numbers
+        for name in self.TABLES:
+            setattr(self, name, tuple(getattr(p, name) for p in self.plans))
+        for name in ("taps_x", "taps_y", "src_row0", "src_rows", "flip"):
+            setattr(self, name, tuple(getattr(p, name) for p in self.plans))
+        self.yuv = tuple(p.yuv for p in self.plans)
+        self.surfaces = tuple(p.surface for p in self.plans)
+        # where each camera's tables start in the concatenation, and its rows in one stream's intermediate block
+        ends = lambda sizes: [int(v) for v in np.concatenate([[0], np.cumsum(sizes)])]   # noqa: E731
+        self.kx_offset, self.x_offset = ends([k.size for k in self.kx]), ends([v.size for v in self.xlo])
+        self.ky_offset, self.y_offset = ends([k.size for k in self.ky]), ends([v.size for v in self.ylo])
+        self.mid_row = ends(self.src_rows)
+        self.mid_rows = self.mid_row[-1]
+        self._dev = None
+
+    # ------------------------------------------------------------------ what a caller multiplies / hands on
+    def image_transforms(self):
+        """float64 [cams, 3, 3]: per camera the matrix `ResizeCropFlipImage._img_transform` returns (augment.py:111-118 with
+        rotate = 0): resize on the diagonal, minus the crop origin, then the flip. A caller multiplies it into the camera's
+        intrinsics, as the reference's pipeline does."""
+        out = np.zeros((self.num_cams, 3, 3), np.float64)
+        for i, s in enumerate(self.sources):
+            m = np.eye(3)
+            m[:2, :2] *= s.aug_config.get("resize", 1)
+            m[:2, 2] -= np.array(s.crop[:2])
+            if s.flip:
+                m = np.array([[-1, 0, s.crop[2] - s.crop[0]], [0, 1, 0], [0, 0, 1]]) @ m
+            out[i] = m
+        return out
+
+    def box2d_table(self):
+        """float32 [cams, 4] = (crop_w, crop_h, crop_y0, 1 / resize) per camera: what the 2D record kernels take as four
+        scalars for a uniform rig (1 / resize in fp32, as simpb_decode2d_record computes it)."""
+        out = np.zeros((self.num_cams, 4), np.float32)
+        for i, s in enumerate(self.sources):
+            x0, y0, x1, y1 = s.crop
+            out[i] = (x1 - x0, y1 - y0, y0, np.float32(1.0) / np.float32(s.resize))
+        return out
+
+    def box2d_device(self, device):
+        """`box2d_table` on the device (resident: a captured 2D record reads it)."""
+        if self._dev is None or self._dev["device"] != _device(device):
+            self.upload(device)
+        return self._dev["box2d"]
+
+    def descriptors(self):
+        """The rig as the host array of simpb_rig_camera that simpb_preprocess_rig_nhwc4_f16 takes."""
+        from . import _lib
+        cams = (_lib.RigCamera * self.num_cams)()
+        for i, (p, c) in enumerate(zip(self.plans, cams)):
+            sf = p.surface
+            c.format, c.src_height, c.src_width = SURFACE_FORMAT[p.frame_format], p.src_hw[0], p.src_hw[1]
+            c.src_row0, c.src_rows, c.taps_x, c.taps_y, c.flip = p.src_row0, p.src_rows, p.taps_x, p.taps_y, int(p.flip)
+            c.pitch, c.chroma_pitch, c.chroma_offset = sf.pitch, sf.chroma_pitch, sf.chroma_offset
+            c.kx_offset, c.x_offset, c.ky_offset, c.y_offset = self.kx_offset[i], self.x_offset[i], self.ky_offset[i], self.y_offset[i]
+            c.mid_row = self.mid_row[i]
+            c.yoff, c.iy, c.irv, c.igu, c.igv, c.ibu = p.yuv if p.yuv is not None else (0, 1, 0, 0, 0, 0)
+        return cams
+
+    # ------------------------------------------------------------------ device
+    def upload(self, device):
+        import torch
+        from . import _lib
+        for p in self.plans:
+            if p.taps_x > 64 or p.taps_y > 64 or p.src_hw[1] > 4096 or p.out_hw[1] > 2048:
+                raise ValueError(f"ingest of {p.src_hw} -> {p.resize_dims} is outside the kernel's limits "
+                                 "(source width 4096, output width 2048, 64 taps)")
+        device = _device(device)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)   # noqa: E731
+        cat = lambda name: t(np.concatenate([a.reshape(-1) for a in getattr(self, name)]))   # noqa: E731
+        self._dev = dict(device=device, lut=t(self.lut), box2d=t(self.box2d_table()), mid=None, table=None, cams=self.descriptors(),
+                         pitch=int(_lib.lib().simpb_preprocess_mid_pitch(self.out_hw[1])), **{n: cat(n) for n in self.TABLES})
+        return self
+
+    def reserve(self, num_images, device):
+        """Allocate the intermediate buffer for `num_images` (whole streams) now (a runner does this before any capture)."""
+        import torch
+        if num_images <= 0 or num_images % self.num_cams:
+            raise ValueError(f"a rig of {self.num_cams} cameras takes whole streams: {num_images} images")
+        if self._dev is None or self._dev["device"] != _device(device):
+            self.upload(device)
+        d = self._dev
+        need = num_images // self.num_cams * self.mid_rows * d["pitch"]
+        if d["mid"] is None or d["mid"].numel() < need:
+            d["mid"] = torch.empty(need, dtype=torch.uint8, device=d["device"])
+        return self
+
+    def surface_table(self, tensors):
+        """(addresses, device) of a flat list of streams * cams device u8 tensors in (stream, camera) order, each checked by
+        `check_surfaces` against its own camera's layout; None gives address 0 (the image is skipped)."""
+        tensors = list(tensors)
+        if not tensors or len(tensors) % self.num_cams:
+            raise ValueError(f"a rig of {self.num_cams} cameras takes whole streams of surfaces, got {len(tensors)}")
+        device = None
+        for c, p in enumerate(self.plans):
+            mine = [t for t in tensors[c::self.num_cams] if t is not None]
+            if not mine:
+                continue
+            try:
+                dev = check_surfaces(mine, p.surface)
+            except (ValueError, RuntimeError) as e:
+                raise type(e)(f"camera {c} of the rig: {e}") from None
+            device = dev if device is None else device
+            if dev != device:
+                raise ValueError(f"camera {c} of the rig: its surfaces are on {dev}, the others on {device}")
+        if device is None:
+            raise ValueError("ingest of a rig without a single surface")
+        return [0 if t is None else t.data_ptr() for t in tensors], device
+
+    def run_surfaces(self, tensors, out=None):
+        """One device u8 tensor (or None) per image, streams * cams of them -> f16 [N, h, w, 4]. The addresses go into a
+        resident int64 table that the launch reads; the tensors must stay alive and unchanged until the launch has run."""
+        import torch
+        ptrs, device = self.surface_table(tensors)
+        n = len(ptrs)
+        self.reserve(n, device)
+        d = self._dev
+        if d["table"] is None or d["table"].numel() < n:
+            d["table"] = torch.zeros(n, dtype=torch.int64, device=d["device"])
+        d["table"][:n].copy_(torch.tensor(ptrs, dtype=torch.int64))
+        return self.run_table(d["table"][:n], out)
+
+    def run_table(self, table, out=None):
+        """table: device int64 [...], contiguous, streams * cams addresses (as `surface_table` checks them; 0 skips the image).
+        The launch reads the table when it runs, so a captured launch follows the addresses written before each replay."""
+        import torch
+        from . import _lib
+        if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.numel() == 0:
+            raise ValueError("the surface table is a contiguous device int64 tensor with one address per image")
+        n, (h, w) = int(table.numel()), self.out_hw
+        self.reserve(n, table.device)
+        d = self._dev
+        if out is None:
+            out = torch.empty(n, h, w, 4, dtype=torch.float16, device=table.device)
+        elif out.dtype != torch.float16 or tuple(out.shape) != (n, h, w, 4) or not out.is_contiguous():
+            raise ValueError(f"ingest writes f16 [{n}, {h}, {w}, 4]")
+        p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
+        _lib.check(_lib.lib().simpb_preprocess_rig_nhwc4_f16(
+            p(out), p(table), p(d["mid"]), *(p(d[name]) for name in self.TABLES), p(d["lut"]), d["cams"], self.num_cams, n, h, w,
+            d["kx"].numel(), d["xlo"].numel(), d["ky"].numel(), d["ylo"].numel(), self.mid_rows, int(self.swap_rb),
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "simpb_preprocess_rig_nhwc4_f16")
         return out

@@ -377,7 +377,7 @@ class FrameRunner:
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
                  raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
-                 raw_layout=None, raw_surfaces=False):
+                 raw_layout=None, raw_surfaces=False, raw_rig=None):
         """independent_streams: the batch is a set of independent camera streams, each decoded exactly as a batch of one
         would be (`capacity` 2D slots per stream; SimPBHead.independent_streams) -- the throughput form of BASELINE config
         #3. False: the reference's batch semantics (camera groups padded to the max over the batch).
@@ -396,6 +396,11 @@ class FrameRunner:
         bs * cams addresses per frame. A surface stays valid and unchanged until the results of its frame have been returned
         (step's return, the collect that yields the frame, or flush); the runner holds a reference to each until then. A
         paused stream or a masked camera takes None in place of a tensor.
+        raw_rig=[preprocess.CameraSource, ...], one per camera of the model (instead of raw_input and everything that goes with
+        it): the cameras differ in source size, format, colour standard, layout, resize, crop or flip and give the runner's
+        image size. `img` is the nested list [bs][cams] of raw_surfaces, with the same lifetime rule; a None (paused stream,
+        masked camera) is an image the ingest skips. metas["img_metas"][0]["aug_config"] is not read: the ingest and the 2D
+        record both follow the rig (preprocess.RigPlan); `set_raw_rig` changes it between frames.
 
         world_output=dict(classes=..., tracking=bool, threshold=float | None): a second output per frame, the WORLD RECORD
         (csrc/world.hip, results.py): boxes in the global frame, threshold and class ranges applied, kept rows packed, a
@@ -420,7 +425,17 @@ class FrameRunner:
         self.raw_layout = None              # preprocess.SurfaceLayout of every image (raw_layout=; None: the tight form)
         self.surfaces = bool(raw_surfaces)  # img is a nested list of device tensors; self.raw is then the int64 address table
         self.pin_table = None               # raw_surfaces: the pinned host side of that table
-        if self.raw_input is None:
+        self.rig = None                     # raw_rig: the cameras' preprocess.CameraSource; self.plan is then their RigPlan
+        if raw_rig is not None:
+            if raw_input is not None or (raw_format, raw_colour) != ("bgr", "jfif") or raw_layout is not None or raw_surfaces:
+                raise ValueError("raw_rig describes every camera by itself: raw_input / raw_format / raw_colour / raw_layout / "
+                                 "raw_surfaces must not be given with it")
+            self.img, self.surfaces = None, True
+            self.plan = self._rig_plan(raw_rig)
+            self.rig = self.plan.sources
+            self.raw = self._raw_buffer()
+            self.pin_table = torch.zeros(batch_size, cams, dtype=torch.int64).pin_memory()
+        elif self.raw_input is None:
             if (raw_format, raw_colour) != ("bgr", "jfif"):
                 raise ValueError(f"raw_format={raw_format!r} / raw_colour={raw_colour!r} describe raw frames: they need raw_input=(Hs, Ws)")
             if raw_layout is not None or raw_surfaces:
@@ -532,6 +547,38 @@ class FrameRunner:
     def _new_raw_buffers(self):
         self.raw = self._raw_buffer()
 
+    def _rig_plan(self, sources):
+        """raw_rig: the RigPlan of `sources`, refused unless it has one camera per camera of the model and the runner's size."""
+        from .preprocess import RigPlan
+        sources = list(sources)
+        if len(sources) != self.head.num_cams:
+            raise ValueError(f"raw_rig has {len(sources)} cameras, the model {self.head.num_cams}")
+        plan = RigPlan(sources, self.img_norm_cfg)
+        if plan.out_hw != self.image_hw:
+            raise ValueError(f"raw_rig turns its frames into {plan.out_hw} images; this runner was built for {self.image_hw}")
+        return plan
+
+    def set_raw_rig(self, sources):
+        """The rig changes (a camera was replaced, a decoder reconfigured) from the next frame on, by set_raw_layout's rules:
+        refused with frames in flight, nothing happens for an equal key, otherwise every graph is dropped (they hold the old
+        rig by value and the old tables' addresses) and the plan is made anew."""
+        if self.rig is None:
+            raise ValueError("set_raw_rig changes the rig of a raw_rig runner")
+        if self._in_flight():
+            raise RuntimeError(f"set_raw_rig with {self._in_flight()} frame(s) in flight: flush() the runner first (their results "
+                               "have not been returned)")
+        plan = self._rig_plan(sources)
+        if plan.key == self.plan.key:
+            return
+        torch.cuda.synchronize(self.device)   # nothing in flight reads the old tables
+        self._drop_all_graphs()
+        self.plan, self.rig = plan, plan.sources
+
+    def _aug(self, metas):
+        """What the decoder maps its 2D boxes back to source pixels with: the frame's aug_config, or with raw_rig the rig's
+        plan (its per-camera table)."""
+        return self.plan if self.rig is not None else metas["img_metas"][0]["aug_config"]
+
     def _in_flight(self):
         """Frames fed whose results have not been returned (a step of this runner returns its own frame's)."""
         return 0
@@ -542,6 +589,9 @@ class FrameRunner:
         new plan, and every captured graph is dropped first (they bake the old tables' addresses and the decoder's crop /
         resize in): a frame never runs on stale tables."""
         from .preprocess import ResamplePlan, plan_key
+        if self.rig is not None:   # (the rig's plan does not follow the metas; reserve allocates on the first frame only)
+            self.plan.reserve(self.bs * self.head.num_cams, self.device)
+            return
         aug = metas["img_metas"][0]["aug_config"]
         if self.plan is not None and self.plan.key == plan_key(self.raw_input, aug, self.raw_format, self.raw_colour, self.raw_layout):
             return
@@ -587,6 +637,12 @@ class FrameRunner:
                     raise ValueError(f"raw_surfaces: stream {i} camera {c} has no surface, and is neither paused nor masked")
             rows.append(list(row))
             held += [t for t in row if t is not None]
+        if self.rig is not None:   # each surface against its own camera's layout; a None is address 0: the ingest skips it
+            ptrs, device = self.plan.surface_table([t for row in rows for t in row])
+            if device != torch.device(self.raw.device):
+                raise ValueError(f"raw_rig: the surfaces are on {device}, the runner on {self.raw.device}")
+            n = num_cams
+            return [ptrs[i * n:(i + 1) * n] for i in range(self.bs)], held
         if not held:
             raise ValueError("raw_surfaces: this step brings no surface at all (every camera of every active stream is masked): "
                              "the address table needs one live surface")
@@ -890,7 +946,7 @@ class FrameRunner:
         not decoded a frame yet, the frame runs warm with every other active slot restarted. No graph changes or is captured
         anew because of an adoption (stats["adopt"] counts the frames that had one)."""
         mask, cams, metas, img, flags, adopt, prev = self._admit(self.prev_metas, img, metas, active, cameras, restart, adopt)
-        aug = metas["img_metas"][0]["aug_config"]
+        aug = self._aug(metas)
         dmetas = self._stage(img, metas, mask, cams, flags, prev)
         warm = prev is not None
         if adopt is not None:   # eager launches between replays, in front of the frame: no graph knows of them
@@ -1105,7 +1161,7 @@ class PipelinedRunner(FrameRunner):
         inputs = self.slot_inputs[slot]
         dmetas = self._fill_inputs(inputs, metas, prev, mask, cams, restart)
         records = self._import(adopt, self.s_head) if adopt is not None else None
-        rec = self._run_head(slot, inputs, dmetas, metas["img_metas"][0]["aug_config"], prev is not None, force_eager)
+        rec = self._run_head(slot, inputs, dmetas, self._aug(metas), prev is not None, force_eager)
         return Job(slot, metas, prev, rec, self._enqueue_readback(slot, rec), mask, cams, surfaces, restart, adopt, records)
 
     def export_stream(self, s):

@@ -24,9 +24,17 @@
       tight tensor, as a padded tensor (raw_layout) and as a pointer list (raw_surfaces) whose surfaces alternate between
       two pools -- the tensor forms pay the 13 / 14.5 MB device-to-device staging copy per frame, the pointer list 48 bytes.
 
+  (e) `rig` (--only-rig; not part of a plain run): a rig of cameras that differ (RigPlan, simpb_preprocess_rig_nhwc4_f16).
+      `launch`: the two ingest launches, --launches per block, in --blocks alternating blocks: the uniform six-camera rig
+      (1600 x 900 NV12 at pitch 1792 -> 704 x 256) through the rig entry point and, as the yardstick, the same surfaces
+      through simpb_preprocess_surface_nhwc4_f16 in pointer mode; and the mixed rig (three such cameras beside three 1920 x
+      1080 P010 cameras at pitch 4096), which has no yardstick of equal work: the share of its horizontal workgroups that
+      leave at once (the grid is padded to the tallest camera) stands beside it. `runner`: SplitPipelinedRunner frames/s
+      with the uniform rig (raw_rig) beside the raw_surfaces runner on the same surface pools, in alternating blocks.
+
 A run that finds no GPU fails.
 
-    python tools/bench_preprocess.py [--launches 200] [--blocks 5] [--block-steps 40] [--only-surface | --skip-surface]
+    python tools/bench_preprocess.py [--launches 200] [--blocks 5] [--block-steps 40] [--only-surface | --skip-surface | --only-rig]
 """
 import argparse
 import json
@@ -306,6 +314,102 @@ def surface_runner_leg(torch, args):
     return out
 
 
+def rig_sources():
+    """(uniform, mixed): six 1600 x 900 NV12 cameras on the padded layout; three of them beside three 1920 x 1080 P010 ones."""
+    from simpb_amd.preprocess import CameraSource
+    nus = CameraSource((900, 1600), CONFIGS["r50_704x256"], "nv12", layout=PADDED)
+    hd = CameraSource((1080, 1920), dict(resize=0.44, crop=(70, 140, 774, 396)), "p010", "bt709", dict(pitch=4096, luma_rows=1088))
+    return [nus] * 6, [nus] * 3 + [hd] * 3
+
+
+def rig_launch_leg(torch, args):
+    from simpb_amd.preprocess import RigPlan
+    uniform, mixed = rig_sources()
+    padded = pack_nv12(torch, nv12_frames(torch, 0)[0][0], uniform[0].surface)          # [6, image_bytes]
+    gen = torch.Generator().manual_seed(0)
+    out = {}
+    for bs in (1, 8):
+        n = bs * 6
+        nus = [padded[i % 6].cuda().clone() for i in range(n)]
+        # (integer arithmetic without a data-dependent branch: noise times like a picture)
+        hd = [torch.randint(0, 256, (mixed[3].surface.image_bytes,), dtype=torch.uint8, generator=gen).cuda() for _ in range(n)]
+        dst = torch.empty(n, 256, 704, 4, dtype=torch.float16, device="cuda")
+        rig, alone, both = RigPlan(uniform).reserve(n, "cuda"), uniform[0].plan().reserve(n, "cuda"), RigPlan(mixed).reserve(n, "cuda")
+        t_rig = torch.tensor(rig.surface_table(nus)[0], dtype=torch.int64, device="cuda")
+        t_mixed = torch.tensor(both.surface_table([nus[i] if i % 6 < 3 else hd[i] for i in range(n)])[0], dtype=torch.int64, device="cuda")
+        forms = {"uniform_rig": lambda: rig.run_table(t_rig, out=dst), "surface_pointer_table": lambda: alone.run_table(t_rig, out=dst),
+                 "mixed_rig": lambda: both.run_table(t_mixed, out=dst)}
+        alone.run_table(t_rig, out=dst)
+        ref = dst.clone()
+        rig.run_table(t_rig, out=dst)
+        assert torch.equal(dst, ref)      # the yardstick and the rig decode the same pictures to the same operand
+        blocks = {k: [] for k in forms}
+        for go in forms.values():
+            for _ in range(20):
+                go()
+        torch.cuda.synchronize()
+        for _ in range(args.blocks):
+            for name, go in forms.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.launches):
+                    go()
+                e1.record()
+                e1.synchronize()
+                blocks[name].append(e0.elapsed_time(e1) / args.launches)
+        res = {k: dict(ms=round(float(np.mean(v)), 5), block_ms=[round(x, 5) for x in v], spread_ms=round(max(v) - min(v), 5), images=n,
+                       launches=args.launches * args.blocks) for k, v in blocks.items()}
+        res["uniform_rig_minus_yardstick_ms"] = round(res["uniform_rig"]["ms"] - res["surface_pointer_table"]["ms"], 5)
+        res["yardstick_spread_ms"] = res["surface_pointer_table"]["spread_ms"]
+        rows = both.src_rows
+        res["mixed_rig"]["src_rows"] = list(rows)
+        res["mixed_rig"]["workgroups_leaving_early"] = round(1.0 - sum(rows) / (max(rows) * len(rows)), 5)
+        res["uniform_rig"]["workgroups_leaving_early"] = 0.0
+        out[f"bs{bs}"] = res
+    return out
+
+
+def rig_runner_leg(torch, args):
+    from simpb_amd import synth
+    from simpb_amd.runner import SplitPipelinedRunner
+    ring = 4
+    uniform, _ = rig_sources()
+    layout = uniform[0].surface
+    padded = [pack_nv12(torch, nv12_frames(torch, f)[0], layout) for f in range(ring)]
+    dev = torch.device("cuda")
+    make = lambda **kw: SplitPipelinedRunner(build_model(torch), 1, (256, 704), capacity=1536, device=dev, use_graph=True, **kw)   # noqa: E731
+    pools = [[[padded[f][0, c].cuda().clone() for c in range(6)] for f in range(ring)] for _ in range(2)]
+    runners = {"raw_surfaces": make(raw_input=(900, 1600), raw_format="nv12", raw_layout=layout, raw_surfaces=True),
+               "uniform_rig": make(raw_rig=uniform)}
+    count = dict.fromkeys(runners, 0)
+
+    def run(name, steps):
+        for _ in range(steps):
+            f = count[name]
+            runners[name].step([pools[f % 2][f % ring]], synth.frame_metas(1, f))
+            count[name] = f + 1
+
+    for name in runners:
+        run(name, 12)
+    torch.cuda.synchronize()
+    blocks = {k: [] for k in runners}
+    for _ in range(args.blocks):
+        for name in runners:
+            run(name, 4)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(name, args.block_steps)
+            torch.cuda.synchronize()
+            blocks[name].append((time.perf_counter() - t0) / args.block_steps * 1e3)
+    out = {}
+    for name, ms in blocks.items():
+        mean = float(np.mean(ms))
+        out[name] = dict(ms_per_step=round(mean, 4), frames_per_s=round(1e3 / mean, 1), block_ms=[round(v, 4) for v in ms],
+                         spread_ms=round(max(ms) - min(ms), 4), timed_frames=args.blocks * args.block_steps, replays=runners[name].stats["replay"])
+    out["rig_minus_raw_surfaces_ms"] = round(out["uniform_rig"]["ms_per_step"] - out["raw_surfaces"]["ms_per_step"], 4)
+    return out
+
+
 def cpu_leg(frames=3):
     try:
         from PIL import Image
@@ -341,6 +445,7 @@ def main():
     ap.add_argument("--skip-runner", action="store_true")
     ap.add_argument("--skip-surface", action="store_true", help="leave out the decoder-surface leg (d)")
     ap.add_argument("--only-surface", action="store_true", help="the decoder-surface leg (d) alone")
+    ap.add_argument("--only-rig", action="store_true", help="the rig leg (e) alone")
     ap.add_argument("--profile-raw", action="store_true",
                     help="only the runner leg's raw form: the program to put behind `rocprofv3 --kernel-trace --stats --`")
     args = ap.parse_args()
@@ -349,6 +454,11 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_preprocess.py needs a GPU: nothing here is measured on a CPU in its place")
+    if args.only_rig:
+        with torch.no_grad():
+            rig = dict(launch=rig_launch_leg(torch, args), runner=None if args.skip_runner else rig_runner_leg(torch, args))
+        print(json.dumps(dict(tool="bench_preprocess", device=torch.cuda.get_device_name(0), rig=rig)))
+        return
     with torch.no_grad():
         surface = None
         if not (args.skip_surface or args.profile_raw):
