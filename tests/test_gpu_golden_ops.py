@@ -39,7 +39,7 @@ def test_token_format_vs_reference_vectors():
 
 
 def test_allocation_vs_reference_vectors():
-    """A2, allocation.py:27-144 on the reference's known-answer case: index tables bit-exact, reference points to 1e-6."""
+    """A2, allocation.py:27-144 on the reference's known-answer case: index tables bit-exact, reference points to 2.4e-7."""
     from simpb_amd.plugin.allocation import DynamicQueryAllocation
     g = load_golden("ops.npz")
     layer = DynamicQueryAllocation().eval()
@@ -51,8 +51,12 @@ def test_allocation_vs_reference_vectors():
     assert np.array_equal(tmask.cpu().numpy(), g["alloc.trans_mask"])
     assert np.array_equal(tshape.cpu().numpy(), g["alloc.trans_shape"])
     assert np.array_equal(np.asarray(groups), g["alloc.query_groups"])
-    assert np.abs(pts.cpu().numpy() - g["alloc.ref_pts2d"]).max() <= 1e-6
-    assert np.abs(depth.cpu().numpy() - g["alloc.ref_depth2d"]).max() <= 1e-5
+    err_pts = float(np.abs(pts.cpu().numpy() - g["alloc.ref_pts2d"]).max())
+    err_depth = float(np.abs(depth.cpu().numpy() - g["alloc.ref_depth2d"]).max())
+    print(f"FIG ops.npz alloc ref_pts2d abs {err_pts:.4g}\nFIG ops.npz alloc ref_depth2d abs {err_depth:.4g}")
+    # four times what was measured against these vectors (5.96e-8 = one float32 ulp below 1; profiles/allocation_vs_float64.md);
+    # the depth came out bit-equal, and 1e-5 is already only five float32 ulps of the 19.5 m it compares
+    assert err_pts <= 2.4e-7 and err_depth <= 1e-5
     # the static-capacity form of the same call: same tables in the live slots, pads marked
     layer(torch.from_numpy(g["alloc.anchor"]).cuda(), metas, dense=False, capacity=8)
     s = layer.last
@@ -214,7 +218,7 @@ def test_daf_kernel_vs_reference_fallback_vectors():
 
 def test_allocation_tables_r50_frame0_position_by_position():
     """The first allocation layer of the shipped R50 704x256 stream at frame 0 (900 learned anchors, 6 cameras): every
-    integer table equals the reference's element by element (no set-wise comparison), reference points to 1e-5, in the
+    integer table equals the reference's element by element (no set-wise comparison), reference points to 7.2e-7, in the
     exact-size form and in the static-capacity form the runners use."""
     g = load_golden("head_r50.npz")
     spec = spec_of(g)
@@ -229,7 +233,9 @@ def test_allocation_tables_r50_frame0_position_by_position():
         assert np.array_equal(a.q2a.cpu().numpy(), G("q2a")) and np.array_equal(a.is_center.cpu().numpy(), G("is_center"))
         assert np.array_equal(tmask.cpu().numpy().astype(np.uint8), G("trans_mask"))
         assert np.array_equal(tshape.cpu().numpy(), G("trans_shape")) and np.array_equal(np.asarray(groups), G("query_groups"))
-        assert np.abs(pts.cpu().numpy() - G("ref_pts2d")).max() <= 1e-5
+        err_pts = float(np.abs(pts.cpu().numpy() - G("ref_pts2d")).max())
+        print(f"FIG r50 frame 0 allocation ref_pts2d abs {err_pts:.4g}")
+        assert err_pts <= 7.2e-7     # four times the 1.79e-7 measured (profiles/allocation_vs_float64.md); was 1e-5
         n2 = G("q2a").shape[1]
         layer(anchor, metas, dense=False, capacity=1536)
         s = layer.last
