@@ -271,15 +271,52 @@ int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, const void* i
                                        long long image_stride, int yoff, int iy, int irv, int igu, int igv, int ibu,
                                        void* stream);
 
+/* The same ingest for the frames of the other producers in a vehicle: a software decoder's planar 4:2:0, the packed 4:2:2 of
+ * a camera that reaches the host without a codec, and the RGB-order and 4-byte pixels of loaders, ISPs and compositors. The
+ * arguments are those of simpb_preprocess_surface_nhwc4_f16 plus chroma2_offset, and formats 0..3 ARE that entry point (the
+ * same kernels, the same refusals, the same bits). The further formats:
+ *   _YUV420P      three planes, u8: src_height luma rows at `pitch`, src_height / 2 Cb rows of src_width / 2 bytes at
+ *                 chroma_offset + i * chroma_pitch, and as many Cr rows at chroma2_offset + i * chroma_pitch. I420 has the Cb
+ *                 plane first in memory and YV12 the Cr plane: that is said by the two offsets alone. Even sizes.
+ *   _YUYV / _UYVY one plane, rows of src_width / 2 groups (Y0, Cb, Y1, Cr) / (Cb, Y0, Cr, Y1), 2 bytes per pixel; the chroma
+ *                 pair belongs to columns 2j, 2j + 1 of its own row. Even src_width, any src_height.
+ *   _RGB          one plane, 3 bytes per pixel, R first
+ *   _BGRA / _RGBA one plane, 4 bytes per pixel; byte 3 of a pixel is read and ignored
+ * YCbCr samples are converted by the 8-bit rule of simpb_preprocess_yuv420sp_nhwc4_f16 (16 fractional bits, chroma replicated,
+ * not interpolated); the RGB-order formats are a byte permutation into the (B, G, R) row, and yoff .. ibu are not looked at
+ * for them. So `out` equals simpb_preprocess_u8_nhwc4_f16 on the converted / permuted frames bit for bit. chroma_pitch and
+ * chroma_offset are not looked at for the one-plane formats, chroma2_offset for every format but _YUV420P. The promise about
+ * the bytes read is that of the entry point above: of a needed row exactly its sample bytes (all four of a 4-byte pixel), no
+ * chroma row under no needed luma row, 16-byte chunks only for a row that starts on a 16-byte boundary.
+ * SIMPB_EINVAL, and nothing launched: whatever simpb_preprocess_surface_nhwc4_f16 refuses; a format outside {0..3, 8..13}; an
+ * odd src_width for a YCbCr format, an odd src_height for _YUV420P; iy <= 0 for a YCbCr format; a pitch below the row's
+ * sample bytes (src_width * 1, 2, 2, 3, 4, 4 in the order above), a chroma_pitch below src_width / 2; a chroma plane that
+ * starts before the luma samples end; Cb and Cr planes that overlap; with src, an image_stride below the image's last
+ * sample. Two launches on `stream`; no allocation, no synchronisation (graph capture safe). */
+#define SIMPB_SURFACE_YUV420P 8
+#define SIMPB_SURFACE_YUYV 9
+#define SIMPB_SURFACE_UYVY 10
+#define SIMPB_SURFACE_RGB 11
+#define SIMPB_SURFACE_BGRA 12
+#define SIMPB_SURFACE_RGBA 13
+int simpb_preprocess_planes_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
+                                      const int* xlo, const int* xn, const int* ky, const int* ylo, const int* yn,
+                                      const void* lut, int num_images, int src_height, int src_width, int out_height,
+                                      int out_width, int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb,
+                                      int format, long long pitch, long long chroma_pitch, long long chroma_offset,
+                                      long long chroma2_offset, long long image_stride, int yoff, int iy, int irv, int igu,
+                                      int igv, int ibu, void* stream);
+
 /* Bytes of one row of the `mid` scratch above (whole groups of 4 pixels, rounded up to 16); 0 for a width outside 1..2048. */
 int simpb_preprocess_mid_pitch(int out_width);
 
 /* The same ingest for a RIG of cameras that differ: each camera has its own source size, format, surface layout, resize,
  * crop and flip, and all of them give one output size. Image n belongs to camera n % num_cams (images in (stream, camera)
  * order, num_images a multiple of num_cams). Two launches for the whole rig, whatever its cameras are; each output block
- * equals simpb_preprocess_surface_nhwc4_f16 of that camera alone bit for bit.
- *   simpb_rig_camera  one camera: format .. chroma_offset, src_row0 .. flip and yoff .. ibu mean what the arguments of that
- *                 name mean above (the chroma fields and yoff .. ibu are not looked at for _BGR), for this camera's images.
+ * equals simpb_preprocess_planes_nhwc4_f16 of that camera alone bit for bit.
+ *   simpb_rig_camera  one camera: format .. chroma_offset, chroma2_offset, src_row0 .. flip and yoff .. ibu mean what the
+ *                 arguments of that name mean above (any of the ten formats; a field a format does not look at is not looked
+ *                 at here), for this camera's images.
  *     kx_offset   ints from `kx` to this camera's [out_width][taps_x] coefficients;  x_offset: entries from `xlo` / `xn` to
  *                 its out_width entries;  ky_offset / y_offset: the same for [out_height][taps_y] and out_height
  *     mid_row     the camera's first row inside one stream's block of the intermediate (it takes src_rows rows)
@@ -292,9 +329,11 @@ int simpb_preprocess_mid_pitch(int out_width);
  *                 skips that image: none of its source bytes is read and its output block is written as f16 zeros (a paused
  *                 stream, a camera that delivered nothing); every other image is unaffected.
  * The horizontal grid spans the largest src_rows of the rig; a workgroup past its camera's rows leaves at once. Its LDS is
- * sized for the rig's widest cameras (at most 34832 bytes), not for the widest source this file takes.
+ * sized for the rig's widest cameras, not for the widest source this file takes: at most 34832 bytes, reached by a 4096-wide
+ * _P010 camera (two planes of 8192 bytes) and equally by a 4096-wide _BGRA / _RGBA one (its row of 16384 bytes is staged
+ * before it is compacted), each beside the 12288-byte (B, G, R) row and the 6160-byte resampled row.
  * SIMPB_EINVAL, and nothing launched or written: num_cams outside 1..16; num_images no multiple of num_cams; for any camera,
- * whatever simpb_preprocess_surface_nhwc4_f16 refuses in its address-table form; a table range or an intermediate range
+ * whatever simpb_preprocess_planes_nhwc4_f16 refuses in its address-table form; a table range or an intermediate range
  * that leaves its array or overlaps another camera's. Two launches on `stream`; no allocation, no synchronisation. */
 #define SIMPB_RIG_MAX_CAMS 16
 typedef struct simpb_rig_camera {
@@ -303,6 +342,7 @@ typedef struct simpb_rig_camera {
   long long pitch, chroma_pitch, chroma_offset;
   int kx_offset, x_offset, ky_offset, y_offset, mid_row;
   int yoff, iy, irv, igu, igv, ibu;
+  long long chroma2_offset;
 } simpb_rig_camera;
 int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table, void* mid, const int* kx, const int* xlo, const int* xn,
                                    const int* ky, const int* ylo, const int* yn, const void* lut, const simpb_rig_camera* cams,

@@ -23,7 +23,8 @@ class RigCamera(ctypes.Structure):
     """simpb_rig_camera of include/simpb_hip.h: one camera of a rig (simpb_preprocess_rig_nhwc4_f16 takes a host array of them)."""
     _fields_ = ([(n, _I) for n in ("format", "src_height", "src_width", "src_row0", "src_rows", "taps_x", "taps_y", "flip")] +
                 [(n, _LL) for n in ("pitch", "chroma_pitch", "chroma_offset")] +
-                [(n, _I) for n in ("kx_offset", "x_offset", "ky_offset", "y_offset", "mid_row", "yoff", "iy", "irv", "igu", "igv", "ibu")])
+                [(n, _I) for n in ("kx_offset", "x_offset", "ky_offset", "y_offset", "mid_row", "yoff", "iy", "irv", "igu", "igv", "ibu")] +
+                [("chroma2_offset", _LL)])
 
 
 SIGNATURES = {
@@ -57,6 +58,7 @@ SIGNATURES = {
     "simpb_preprocess_u8_nhwc4_f16": ([_P] * 10 + [_I] * 11 + [_P], _I),
     "simpb_preprocess_yuv420sp_nhwc4_f16": ([_P] * 10 + [_I] * 18 + [_P], _I),
     "simpb_preprocess_surface_nhwc4_f16": ([_P] * 11 + [_I] * 12 + [_LL] * 4 + [_I] * 6 + [_P], _I),
+    "simpb_preprocess_planes_nhwc4_f16": ([_P] * 11 + [_I] * 12 + [_LL] * 5 + [_I] * 6 + [_P], _I),
     "simpb_preprocess_mid_pitch": ([_I], _I),
     "simpb_preprocess_rig_nhwc4_f16": ([_P] * 10 + [ctypes.POINTER(RigCamera)] + [_I] * 10 + [_P], _I),
     "simpb_linear_f16in_split": ([_P] * 5 + [_I] * 3 + [_P], _I),

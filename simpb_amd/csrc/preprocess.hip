@@ -27,6 +27,9 @@
 // each camera has its own descriptor (format, size, layout, row range, taps, tables), passed by value, and both rig kernels
 // are the surface path's device functions (stage_bgr_row, filter_row_and_store, resample_cols_lut_row) behind a
 // per-workgroup choice of the descriptor; address 0 in the table skips an image, whose output block is written as zeros.
+// What other producers deliver (simpb_preprocess_planes_nhwc4_f16, and per camera of a rig) are further branches of
+// stage_bgr_row and nothing else: planar 4:2:0 (three planes: a software decoder), packed 4:2:2 (YUYV / UYVY: a camera without
+// a codec) by the same integer rule with replicated chroma, and RGB / BGRA / RGBA as a byte permutation into the (B, G, R) row.
 // Every load of a thread is retired before its stores are issued (store_fence.h).
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
@@ -152,15 +155,28 @@ __global__ __launch_bounds__(kThreads) void resample_rows_yuv420sp_kernel(unsign
 
 // One image as a decoder delivers it (include/simpb_hip.h, simpb_preprocess_surface_nhwc4_f16): image n starts at
 // src + n * image_stride, or at table[n] when `table` is given; luma (or BGR) row r at + r * pitch, chroma row i at
-// + chroma_offset + i * chroma_pitch. The table is read by the kernel: a captured launch follows the addresses written
-// into it before each replay.
+// + chroma_offset + i * chroma_pitch (planar 4:2:0: the Cb row there, the Cr row at + chroma2_offset + i * chroma_pitch). The
+// table is read by the kernel: a captured launch follows the addresses written into it before each replay.
 struct Surface {
   const unsigned char* src;
   const unsigned long long* table;
-  long long image_stride, chroma_offset, pitch, chroma_pitch;
+  long long image_stride, chroma_offset, pitch, chroma_pitch, chroma2_offset;
 };
 
 constexpr int kBgr = SIMPB_SURFACE_BGR, kNv12 = SIMPB_SURFACE_NV12, kNv21 = SIMPB_SURFACE_NV21, kP010 = SIMPB_SURFACE_P010;
+constexpr int kYuv420p = SIMPB_SURFACE_YUV420P, kYuyv = SIMPB_SURFACE_YUYV, kUyvy = SIMPB_SURFACE_UYVY, kRgb = SIMPB_SURFACE_RGB;
+constexpr int kBgra = SIMPB_SURFACE_BGRA, kRgba = SIMPB_SURFACE_RGBA;
+
+// LDS bytes of the two staging planes of a source `width` wide, s_luma and s_chroma (one plane each; a multiple of 16). A
+// packed row that is converted or compacted on its way into the (B, G, R) row (4:2:2: 2 bytes per pixel, BGRA / RGBA: 4) is
+// staged from s_luma on and runs through into s_chroma, which lies right behind it; the two chroma rows of planar 4:2:0 share
+// s_chroma, the Cr row in its second half. BGR and RGB rows are staged where the filter reads them.
+__host__ __device__ constexpr int plane_bytes(int format, int width) {
+  return format == kBgr || format == kRgb ? 0
+         : format == kP010 || format == kBgra || format == kRgba ? (2 * width + 15) / 16 * 16
+         : format == kYuv420p ? 2 * ((width / 2 + 15) / 16 * 16)
+                              : (width + 15) / 16 * 16;   // (NV12 / NV21: a luma and a chroma row; 4:2:2: the halves of its row)
+}
 
 // Exactly `bytes` of one source row into LDS, never a byte past them (a surface may end at its last sample, and what lies
 // between two rows is not the caller's to read). A row that starts on a 16-byte boundary goes as floor(bytes / 16) chunks and
@@ -190,13 +206,73 @@ __device__ __forceinline__ void stage_row(unsigned char* s_dst, const unsigned c
 //   c = iy * (Y - yoff) + 2^(S-1),  R = clamp((c + irv * (Cr - C)) >> S),  G = clamp((c + igu * (Cb - C) + igv * (Cr - C)) >> S),
 //   B = clamp((c + ibu * (Cb - C)) >> S)     (int32, arithmetic shift, clamp to 0..255)
 // Chroma rows that lie under no needed luma row are never read. Returns with s_src complete (synchronised).
+// What follows is the 8-bit rule (S = 16, C = 128) on other arrangements of the same samples, and byte permutations:
+// kYuv420p (I420 / YV12): three planes, the Cb row i of Ws / 2 bytes at + chroma_offset + i * chroma_pitch and the Cr row at
+// + chroma2_offset + i * chroma_pitch; which plane comes first in memory is the caller's to say through the two offsets.
+// kYuyv / kUyvy (packed 4:2:2): one plane, a row is Ws / 2 groups (Y0, Cb, Y1, Cr) / (Cb, Y0, Cr, Y1); the pair belongs to
+// columns 2j, 2j + 1 of its own row. kRgb: the BGR row with bytes 0 and 2 of every pixel exchanged. kBgra / kRgba: 4 bytes per
+// pixel, byte 3 is dropped whatever it holds.
+__device__ __forceinline__ void yuv_pair_to_bgr(unsigned char* d, int y0, int y1, int cb, int cr, const YuvCoeffs& q) {
+  cb -= 128; cr -= 128;
+  const int dr = q.irv * cr, dg = q.igu * cb + q.igv * cr, db = q.ibu * cb;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = q.iy * ((i ? y1 : y0) - q.yoff) + (1 << 15);
+    d[3 * i] = (unsigned char)clamp8((c + db) >> 16);
+    d[3 * i + 1] = (unsigned char)clamp8((c + dg) >> 16);
+    d[3 * i + 2] = (unsigned char)clamp8((c + dr) >> 16);
+  }
+}
+
 template <int F>
 __device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned char* s_luma, unsigned char* s_chroma,
                                               const unsigned char* __restrict__ image, long long pitch, long long chroma_offset,
-                                              long long chroma_pitch, int row, int Ws, const YuvCoeffs& q) {
+                                              long long chroma_pitch, long long chroma2_offset, int row, int Ws, const YuvCoeffs& q) {
   const int tid = threadIdx.x;
   if constexpr (F == kBgr) {
     stage_row(s_src, image + (size_t)row * pitch, Ws * 3);
+    __syncthreads();
+  } else if constexpr (F == kRgb) {   // permuted where it lies: a thread exchanges the ends of its own pixels
+    stage_row(s_src, image + (size_t)row * pitch, Ws * 3);
+    __syncthreads();
+    for (int x = tid; x < Ws; x += kThreads) {
+      unsigned char* d = s_src + x * 3;
+      const unsigned char r = d[0];
+      d[0] = d[2];
+      d[2] = r;
+    }
+    __syncthreads();
+  } else if constexpr (F == kBgra || F == kRgba) {   // the row of dwords (LDS is 16-byte aligned), compacted
+    stage_row(s_luma, image + (size_t)row * pitch, Ws * 4);
+    __syncthreads();
+    const unsigned int* px = reinterpret_cast<const unsigned int*>(s_luma);
+    for (int x = tid; x < Ws; x += kThreads) {
+      const unsigned int v = px[x];
+      unsigned char* d = s_src + x * 3;
+      d[F == kRgba ? 2 : 0] = (unsigned char)(v & 255u);
+      d[1] = (unsigned char)((v >> 8) & 255u);
+      d[F == kRgba ? 0 : 2] = (unsigned char)((v >> 16) & 255u);
+    }
+    __syncthreads();
+  } else if constexpr (F == kYuyv || F == kUyvy) {   // one dword = one chroma pair and its two luma samples (Ws is even)
+    stage_row(s_luma, image + (size_t)row * pitch, Ws * 2);
+    __syncthreads();
+    const unsigned int* group = reinterpret_cast<const unsigned int*>(s_luma);
+    constexpr int kY = F == kYuyv ? 0 : 8, kC = 8 - kY;   // bit of Y0 and of Cb inside the group
+    for (int j = tid; 2 * j < Ws; j += kThreads) {
+      const unsigned int v = group[j];
+      yuv_pair_to_bgr(s_src + j * 6, (int)((v >> kY) & 255u), (int)((v >> (kY + 16)) & 255u), (int)((v >> kC) & 255u),
+                      (int)((v >> (kC + 16)) & 255u), q);
+    }
+    __syncthreads();
+  } else if constexpr (F == kYuv420p) {
+    unsigned char* s_cr = s_chroma + (((Ws >> 1) + 15) & ~15);   // (plane_bytes: the second half of s_chroma)
+    stage_row(s_luma, image + (size_t)row * pitch, Ws);
+    stage_row(s_chroma, image + chroma_offset + (size_t)(row >> 1) * chroma_pitch, Ws >> 1);
+    stage_row(s_cr, image + chroma2_offset + (size_t)(row >> 1) * chroma_pitch, Ws >> 1);
+    __syncthreads();
+    for (int j = tid; 2 * j < Ws; j += kThreads)
+      yuv_pair_to_bgr(s_src + j * 6, (int)s_luma[2 * j], (int)s_luma[2 * j + 1], (int)s_chroma[j], (int)s_cr[j], q);
     __syncthreads();
   } else {
     constexpr int kSample = F == kP010 ? 2 : 1;   // bytes per sample
@@ -238,12 +314,14 @@ __global__ __launch_bounds__(kThreads) void resample_rows_surface_kernel(unsigne
                                                                          int taps, int flip, int pitch, YuvCoeffs q) {
   __shared__ __attribute__((aligned(16))) unsigned char s_src[kMaxSrcW * 3];
   __shared__ __attribute__((aligned(16))) unsigned char s_out[kMaxOutW * 3 + 16];
-  constexpr int kPlane = F == kBgr ? 16 : kMaxSrcW * (F == kP010 ? 2 : 1);   // (a BGR row is staged where the filter reads it)
-  __shared__ __attribute__((aligned(16))) unsigned char s_luma[kPlane];
-  __shared__ __attribute__((aligned(16))) unsigned char s_chroma[kPlane];
+  // (a BGR / RGB row is staged where the filter reads it; a packed 4:2:2 or 4-byte row lies in s_luma as a whole)
+  constexpr bool kPacked = F == kYuyv || F == kUyvy || F == kBgra || F == kRgba;
+  constexpr int kPlane = plane_bytes(F, kMaxSrcW) == 0 ? 16 : plane_bytes(F, kMaxSrcW);
+  __shared__ __attribute__((aligned(16))) unsigned char s_luma[kPacked ? 2 * kPlane : kPlane];
+  __shared__ __attribute__((aligned(16))) unsigned char s_chroma[kPacked ? 16 : kPlane];
   const int r = blockIdx.x, n = blockIdx.y;
   const unsigned char* image = sf.table ? reinterpret_cast<const unsigned char*>(sf.table[n]) : sf.src + (size_t)n * sf.image_stride;
-  stage_bgr_row<F>(s_src, s_luma, s_chroma, image, sf.pitch, sf.chroma_offset, sf.chroma_pitch, row0 + r, Ws, q);
+  stage_bgr_row<F>(s_src, s_luma, s_chroma, image, sf.pitch, sf.chroma_offset, sf.chroma_pitch, sf.chroma2_offset, row0 + r, Ws, q);
   filter_row_and_store(mid + ((size_t)n * rows + r) * pitch, s_src, s_out, kx, xlo, xn, Ws, w, taps, flip, pitch);
 }
 
@@ -257,7 +335,7 @@ struct Rig { simpb_rig_camera cam[SIMPB_RIG_MAX_CAMS]; };
 // whose image has address 0 (the image is skipped: the vertical pass writes zeros) -- leaves before any barrier. Stream
 // n / num_cams keeps its cameras' rows one behind the other in a block of `mid_rows` rows, camera c from row mid_row on.
 // LDS is dynamic, sized by the entry point for the rig at hand (RigLds: the widest camera's (B, G, R) row, the resampled row,
-// and the widest YCbCr camera's luma and chroma rows), not for the widest source the file takes: a rig of 1600-wide NV12
+// and the widest staging planes of any camera, plane_bytes), not for the widest source the file takes: a rig of 1600-wide NV12
 // cameras holds 10 KB per workgroup where the static arrays of the surface kernel hold 26 KB, and a BGR rig has no planes.
 struct RigLds { int src_bytes, out_bytes, plane_bytes; };   // each a multiple of 16
 
@@ -279,12 +357,21 @@ __global__ __launch_bounds__(kThreads) void resample_rows_rig_kernel(unsigned ch
   if (image == nullptr) return;
   const YuvCoeffs q = {c.yoff, c.iy, c.irv, c.igu, c.igv, c.ibu};
   const int row = c.src_row0 + r, Ws = c.src_width;
+#define SIMPB_STAGE(F) \
+  case F: stage_bgr_row<F>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, c.chroma2_offset, row, Ws, q); break
   switch (c.format) {
-    case kBgr: stage_bgr_row<kBgr>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, row, Ws, q); break;
-    case kNv12: stage_bgr_row<kNv12>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, row, Ws, q); break;
-    case kNv21: stage_bgr_row<kNv21>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, row, Ws, q); break;
-    default: stage_bgr_row<kP010>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, row, Ws, q); break;
+    SIMPB_STAGE(kBgr);
+    SIMPB_STAGE(kNv12);
+    SIMPB_STAGE(kNv21);
+    SIMPB_STAGE(kYuv420p);
+    SIMPB_STAGE(kYuyv);
+    SIMPB_STAGE(kUyvy);
+    SIMPB_STAGE(kRgb);
+    SIMPB_STAGE(kBgra);
+    SIMPB_STAGE(kRgba);
+    default: stage_bgr_row<kP010>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, c.chroma2_offset, row, Ws, q); break;
   }
+#undef SIMPB_STAGE
   filter_row_and_store(mid + ((size_t)stream * mid_rows + c.mid_row + r) * pitch, s_src, s_out, kx + c.kx_offset, xlo + c.x_offset,
                        xn + c.x_offset, Ws, w, c.taps_x, c.flip, pitch);
 }
@@ -428,6 +515,12 @@ static int launch_surface(int format, void* out, const Surface& sf, void* mid, c
     case kBgr: SIMPB_ROWS(kBgr); break;
     case kNv12: SIMPB_ROWS(kNv12); break;
     case kNv21: SIMPB_ROWS(kNv21); break;
+    case kYuv420p: SIMPB_ROWS(kYuv420p); break;
+    case kYuyv: SIMPB_ROWS(kYuyv); break;
+    case kUyvy: SIMPB_ROWS(kUyvy); break;
+    case kRgb: SIMPB_ROWS(kRgb); break;
+    case kBgra: SIMPB_ROWS(kBgra); break;
+    case kRgba: SIMPB_ROWS(kRgba); break;
     default: SIMPB_ROWS(kP010); break;
   }
 #undef SIMPB_ROWS
@@ -472,33 +565,55 @@ extern "C" int simpb_preprocess_yuv420sp_nhwc4_f16(void* out, const void* src, v
   return finish_vertical(out, mid, ky, ylo, yn, lut, num_images, out_height, out_width, taps_y, src_row0, src_rows, swap_rb, pitch, s);
 }
 
-extern "C" int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
-                                                  const int* xlo, const int* xn, const int* ky, const int* ylo, const int* yn,
-                                                  const void* lut, int num_images, int src_height, int src_width, int out_height,
-                                                  int out_width, int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb,
-                                                  int format, long long pitch, long long chroma_pitch, long long chroma_offset,
-                                                  long long image_stride, int yoff, int iy, int irv, int igu, int igv, int ibu,
-                                                  void* stream) {
+// [lo, lo + len) of two ranges overlap
+static bool ranges_overlap(long long a, long long alen, long long b, long long blen) { return a < b + blen && b < a + alen; }
+
+static bool known_format(int format) { return (format >= kBgr && format <= kP010) || (format >= kYuv420p && format <= kRgba); }
+
+// The layout rules of one surface of a known format, shared by every entry point that takes one: the offset one past the
+// image's last sample, or -1 for a layout that is refused. The fields a format does not look at are set to 0.
+static long long surface_extent(int format, int src_height, int src_width, long long pitch, long long& chroma_pitch,
+                                long long& chroma_offset, long long& chroma2_offset, int iy) {
+  constexpr long long kMaxPitch = 1LL << 30, kMaxOffset = 1LL << 40;   // (keeps every offset below far inside 63 bits)
+  const bool planar = format == kYuv420p, semi = format == kNv12 || format == kNv21 || format == kP010;
+  const bool ycbcr = planar || semi || format == kYuyv || format == kUyvy;
+  const long long pixel = format == kBgr || format == kRgb ? 3 : format == kBgra || format == kRgba ? 4
+                          : format == kP010 || format == kYuyv || format == kUyvy ? 2 : 1;
+  const long long row = (long long)src_width * pixel;   // sample bytes of a luma (packed) row
+  if (pitch < row || pitch > kMaxPitch) return -1;
+  if (ycbcr && ((src_width & 1) || iy <= 0)) return -1;
+  const long long luma_end = (long long)(src_height - 1) * pitch + row;
+  if (!planar) chroma2_offset = 0;
+  if (!planar && !semi) {
+    chroma_pitch = chroma_offset = 0;
+    return luma_end;
+  }
+  if (src_height & 1) return -1;
+  const long long chroma_row = planar ? src_width / 2 : row;   // sample bytes of a chroma row
+  if (chroma_pitch < chroma_row || chroma_pitch > kMaxPitch) return -1;
+  const long long span = (long long)(src_height / 2 - 1) * chroma_pitch + chroma_row;
+  if (chroma_offset < luma_end || chroma_offset > kMaxOffset) return -1;   // a chroma plane lies behind the luma plane
+  if (format == kP010 && ((pitch | chroma_pitch | chroma_offset) & 1)) return -1;
+  if (!planar) return chroma_offset + span;
+  if (chroma2_offset < luma_end || chroma2_offset > kMaxOffset) return -1;
+  if (ranges_overlap(chroma_offset, span, chroma2_offset, span)) return -1;
+  return (chroma_offset > chroma2_offset ? chroma_offset : chroma2_offset) + span;
+}
+
+// what both surface entry points do behind their own check of `format`
+static int preprocess_surface(void* out, const void* src, const void* image_table, void* mid, const int* kx, const int* xlo,
+                              const int* xn, const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
+                              int src_height, int src_width, int out_height, int out_width, int taps_x, int taps_y, int src_row0,
+                              int src_rows, int flip, int swap_rb, int format, long long pitch, long long chroma_pitch,
+                              long long chroma_offset, long long chroma2_offset, long long image_stride, const YuvCoeffs& q,
+                              void* stream) {
   if ((src != nullptr) == (image_table != nullptr)) return SIMPB_EINVAL;   // exactly one form of the images
   if (bad_arguments(out, src ? src : image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height,
                     out_width, taps_x, taps_y, src_row0, src_rows))
     return SIMPB_EINVAL;
-  if (format != kBgr && format != kNv12 && format != kNv21 && format != kP010) return SIMPB_EINVAL;
   if (reinterpret_cast<size_t>(image_table) & 7) return SIMPB_EINVAL;
-  constexpr long long kMaxPitch = 1LL << 30;   // (keeps every offset below far inside 63 bits)
-  const long long sample = format == kP010 ? 2 : 1;
-  const long long row = (long long)src_width * (format == kBgr ? 3 : sample);   // sample bytes of a luma (BGR) and of a chroma row
-  if (pitch < row || pitch > kMaxPitch) return SIMPB_EINVAL;
-  long long end = (long long)(src_height - 1) * pitch + row;   // one past the image's last sample
-  if (format == kBgr) {
-    chroma_pitch = chroma_offset = 0;   // (not looked at)
-  } else {
-    if ((src_height & 1) || (src_width & 1) || iy <= 0) return SIMPB_EINVAL;
-    if (chroma_pitch < row || chroma_pitch > kMaxPitch) return SIMPB_EINVAL;
-    if (chroma_offset < end || chroma_offset > (1LL << 40)) return SIMPB_EINVAL;   // the chroma plane lies behind the luma plane
-    end = chroma_offset + (long long)(src_height / 2 - 1) * chroma_pitch + row;
-    if (format == kP010 && ((pitch | chroma_pitch | chroma_offset) & 1)) return SIMPB_EINVAL;
-  }
+  const long long end = surface_extent(format, src_height, src_width, pitch, chroma_pitch, chroma_offset, chroma2_offset, q.iy);
+  if (end < 0) return SIMPB_EINVAL;
   if (src) {
     if (image_stride < end || image_stride > (1LL << 40)) return SIMPB_EINVAL;
     if (format == kP010 && ((image_stride | (long long)reinterpret_cast<size_t>(src)) & 1)) return SIMPB_EINVAL;
@@ -506,13 +621,36 @@ extern "C" int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, co
     image_stride = 0;   // (not looked at)
   }
   const Surface sf = {static_cast<const unsigned char*>(src), static_cast<const unsigned long long*>(image_table), image_stride,
-                      chroma_offset, pitch, chroma_pitch};
+                      chroma_offset, pitch, chroma_pitch, chroma2_offset};
   return launch_surface(format, out, sf, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_width, out_height, out_width, taps_x, taps_y,
-                        src_row0, src_rows, flip, swap_rb, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream);
+                        src_row0, src_rows, flip, swap_rb, q, stream);
 }
 
-// [lo, lo + len) of two cameras overlap
-static bool ranges_overlap(long long a, long long alen, long long b, long long blen) { return a < b + blen && b < a + alen; }
+extern "C" int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
+                                                  const int* xlo, const int* xn, const int* ky, const int* ylo, const int* yn,
+                                                  const void* lut, int num_images, int src_height, int src_width, int out_height,
+                                                  int out_width, int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb,
+                                                  int format, long long pitch, long long chroma_pitch, long long chroma_offset,
+                                                  long long image_stride, int yoff, int iy, int irv, int igu, int igv, int ibu,
+                                                  void* stream) {
+  if (format != kBgr && format != kNv12 && format != kNv21 && format != kP010) return SIMPB_EINVAL;
+  return preprocess_surface(out, src, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height,
+                            out_width, taps_x, taps_y, src_row0, src_rows, flip, swap_rb, format, pitch, chroma_pitch, chroma_offset, 0,
+                            image_stride, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream);
+}
+
+extern "C" int simpb_preprocess_planes_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
+                                                 const int* xlo, const int* xn, const int* ky, const int* ylo, const int* yn,
+                                                 const void* lut, int num_images, int src_height, int src_width, int out_height,
+                                                 int out_width, int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb,
+                                                 int format, long long pitch, long long chroma_pitch, long long chroma_offset,
+                                                 long long chroma2_offset, long long image_stride, int yoff, int iy, int irv, int igu,
+                                                 int igv, int ibu, void* stream) {
+  if (!known_format(format)) return SIMPB_EINVAL;
+  return preprocess_surface(out, src, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height,
+                            out_width, taps_x, taps_y, src_row0, src_rows, flip, swap_rb, format, pitch, chroma_pitch, chroma_offset,
+                            chroma2_offset, image_stride, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream);
+}
 
 extern "C" int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table, void* mid, const int* kx, const int* xlo,
                                               const int* xn, const int* ky, const int* ylo, const int* yn, const void* lut,
@@ -522,7 +660,6 @@ extern "C" int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table
   if (!cams || num_cams <= 0 || num_cams > SIMPB_RIG_MAX_CAMS || num_images <= 0 || num_images % num_cams) return SIMPB_EINVAL;
   if (kx_len <= 0 || x_len <= 0 || ky_len <= 0 || y_len <= 0 || mid_rows <= 0) return SIMPB_EINVAL;
   if (reinterpret_cast<size_t>(image_table) & 7) return SIMPB_EINVAL;
-  constexpr long long kMaxPitch = 1LL << 30;
   int max_rows = 0;
   for (int i = 0; i < num_cams; ++i) {
     const simpb_rig_camera& c = cams[i];
@@ -530,17 +667,10 @@ extern "C" int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table
     if (bad_arguments(out, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, c.src_height, c.src_width, out_height, out_width,
                       c.taps_x, c.taps_y, c.src_row0, c.src_rows))
       return SIMPB_EINVAL;
-    if (c.format != kBgr && c.format != kNv12 && c.format != kNv21 && c.format != kP010) return SIMPB_EINVAL;
-    const long long sample = c.format == kP010 ? 2 : 1;
-    const long long row = (long long)c.src_width * (c.format == kBgr ? 3 : sample);
-    if (c.pitch < row || c.pitch > kMaxPitch) return SIMPB_EINVAL;
-    if (c.format != kBgr) {
-      const long long luma_end = (long long)(c.src_height - 1) * c.pitch + row;
-      if ((c.src_height & 1) || (c.src_width & 1) || c.iy <= 0) return SIMPB_EINVAL;
-      if (c.chroma_pitch < row || c.chroma_pitch > kMaxPitch) return SIMPB_EINVAL;
-      if (c.chroma_offset < luma_end || c.chroma_offset > (1LL << 40)) return SIMPB_EINVAL;
-      if (c.format == kP010 && ((c.pitch | c.chroma_pitch | c.chroma_offset) & 1)) return SIMPB_EINVAL;
-    }
+    if (!known_format(c.format)) return SIMPB_EINVAL;
+    long long chroma_pitch = c.chroma_pitch, chroma_offset = c.chroma_offset, chroma2_offset = c.chroma2_offset;
+    if (surface_extent(c.format, c.src_height, c.src_width, c.pitch, chroma_pitch, chroma_offset, chroma2_offset, c.iy) < 0)
+      return SIMPB_EINVAL;
     // the camera's tables and intermediate rows lie inside the arrays given ...
     if (c.kx_offset < 0 || c.x_offset < 0 || c.ky_offset < 0 || c.y_offset < 0 || c.mid_row < 0) return SIMPB_EINVAL;
     if ((long long)c.kx_offset + (long long)out_width * c.taps_x > kx_len || (long long)c.x_offset + out_width > x_len ||
@@ -564,14 +694,15 @@ extern "C" int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table
     rig.cam[i].flip = cams[i].flip ? 1 : 0;
   }
   const int pitch = mid_pitch(out_width);
-  // LDS for the rig at hand (validated above: at most kMaxSrcW * 3 + kMaxOutW * 3 + 16 + 2 * kMaxSrcW * 2 = 34832 bytes)
-  int src_bytes = 0, plane_bytes = 0;
+  // LDS for the rig at hand (validated above: at most kMaxSrcW * 3 + kMaxOutW * 3 + 16 + 2 * kMaxSrcW * 2 = 34832 bytes; a 4-byte
+  // row of the widest source is as long as the two P010 planes of one)
+  int src_bytes = 0, planes = 0;
   for (int i = 0; i < num_cams; ++i) {
-    const int planes = cams[i].format == kBgr ? 0 : cams[i].src_width * (cams[i].format == kP010 ? 2 : 1);
+    const int plane = plane_bytes(cams[i].format, cams[i].src_width);
     src_bytes = cams[i].src_width * 3 > src_bytes ? cams[i].src_width * 3 : src_bytes;
-    plane_bytes = planes > plane_bytes ? planes : plane_bytes;
+    planes = plane > planes ? plane : planes;
   }
-  const RigLds lds = {(src_bytes + 15) / 16 * 16, pitch + 16, (plane_bytes + 15) / 16 * 16};
+  const RigLds lds = {(src_bytes + 15) / 16 * 16, pitch + 16, planes};
   hipStream_t s = static_cast<hipStream_t>(stream);
   (void)hipGetLastError();
   const unsigned long long* table = static_cast<const unsigned long long*>(image_table);

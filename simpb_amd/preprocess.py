@@ -17,7 +17,13 @@ in memory (padded row pitch, aligned plane height, the chroma plane's own pitch 
 
 A ResamplePlan describes all its images as one layout. `CameraSource` / `RigPlan` describe a rig whose cameras differ (source
 size, format, layout, resize, crop, flip): per camera the tables of that camera's own ResamplePlan, one output size, two
-launches for the whole rig, and the per-camera numbers the 2D record and the intrinsics need (`box2d_table`, `image_transforms`)."""
+launches for the whole rig, and the per-camera numbers the 2D record and the intrinsics need (`box2d_table`, `image_transforms`).
+
+Frames of the other producers in a vehicle are taken as they lie as well: a software decoder's planar 4:2:0 ("yuv420p" = I420,
+"yvu420p" = YV12), the packed 4:2:2 of a camera that reaches the host without a codec ("yuyv", "uyvy"), and the RGB-order and
+4-byte pixels of loaders, ISPs and compositors ("rgb", "bgra", "rgba"). The YCbCr ones follow `yuv_coefficients` with
+replicated chroma, the others are a byte permutation: no new arithmetic, and the output equals the BGR plan's on the
+host-converted frames bit for bit."""
 import ctypes
 import math
 
@@ -28,8 +34,15 @@ PRECISION_BITS = 22   # Pillow: 32 - 8 - 2
 IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 
 
-FRAME_FORMATS = ("bgr", "nv12", "nv21", "p010")
-SURFACE_FORMAT = {"bgr": 0, "nv12": 1, "nv21": 2, "p010": 3}   # SIMPB_SURFACE_* of include/simpb_hip.h
+FRAME_FORMATS = ("bgr", "nv12", "nv21", "p010", "yuv420p", "yvu420p", "yuyv", "uyvy", "rgb", "bgra", "rgba")
+# SIMPB_SURFACE_* of include/simpb_hip.h (the two planar names differ in their default plane order alone)
+SURFACE_FORMAT = {"bgr": 0, "nv12": 1, "nv21": 2, "p010": 3, "yuv420p": 8, "yvu420p": 8, "yuyv": 9, "uyvy": 10, "rgb": 11, "bgra": 12,
+                  "rgba": 13}
+SEMI_PLANAR = ("nv12", "nv21", "p010")      # a luma plane and one plane of interleaved chroma pairs
+PLANAR = ("yuv420p", "yvu420p")             # a luma plane, a Cb plane and a Cr plane
+PACKED_422 = ("yuyv", "uyvy")               # one plane: (Y0, Cb, Y1, Cr) / (Cb, Y0, Cr, Y1)
+PIXEL_BYTES = {"bgr": 3, "rgb": 3, "bgra": 4, "rgba": 4, "yuyv": 2, "uyvy": 2}   # the one-plane formats
+RGB_ORDER = ("bgr", "rgb", "bgra", "rgba")  # no YCbCr conversion: the colour standard says nothing about them
 YUV_BITS = 16         # fractional bits of the YCbCr -> BGR coefficients
 # standard -> (Kr, Kb, full range)
 YUV_STANDARDS = {"jfif": (0.299, 0.114, True), "bt601": (0.299, 0.114, False), "bt709": (0.2126, 0.0722, False)}
@@ -82,9 +95,13 @@ def p010_coefficients(standard):
     return yoff, iy, irv, igu, igv, ibu
 
 
+def _unknown_format(frame_format):
+    return ValueError(f"frame format {frame_format!r}: one of {FRAME_FORMATS} (planar I420 is 'yuv420p', YV12 is 'yvu420p')")
+
+
 def _check_format(frame_format, colour):
     if frame_format not in FRAME_FORMATS:
-        raise ValueError(f"frame format {frame_format!r}: one of {FRAME_FORMATS}")
+        raise _unknown_format(frame_format)
     if colour not in YUV_STANDARDS:
         raise ValueError(f"colour standard {colour!r}: one of {sorted(YUV_STANDARDS)}")
     if frame_format == "p010":
@@ -94,10 +111,14 @@ def _check_format(frame_format, colour):
 def frame_shape(src_hw, frame_format="bgr"):
     """Trailing dimensions of one tightly packed image of `src_hw` = (Hs, Ws): (Hs, Ws, 3) interleaved BGR, or (Hs * 3 / 2, Ws) for
     NV12 / NV21 (Hs luma rows, then Hs / 2 rows of interleaved chroma pairs; row pitch Ws), or (Hs * 3 / 2, Ws * 2) for P010 (the
-    bytes of u16 little-endian samples in the NV12 arrangement)."""
+    bytes of u16 little-endian samples in the NV12 arrangement). "yuv420p" / "yvu420p": (Hs * 3 / 2, Ws) as NV12 -- the same
+    bytes count, so a caller's buffers carry over: Hs luma rows, then the Cb (yvu420p: Cr) plane of Hs / 2 rows of Ws / 2 bytes,
+    then the other one. "yuyv" / "uyvy": (Hs, Ws, 2). "rgb": (Hs, Ws, 3). "bgra" / "rgba": (Hs, Ws, 4)."""
     hs, ws = int(src_hw[0]), int(src_hw[1])
-    if frame_format == "bgr":
-        return (hs, ws, 3)
+    if frame_format in PIXEL_BYTES:
+        if frame_format in PACKED_422 and ws % 2:
+            raise ValueError(f"{frame_format} frames have an even width (one chroma pair per two luma samples), got {ws} x {hs}")
+        return (hs, ws, PIXEL_BYTES[frame_format])
     if hs % 2 or ws % 2:
         raise ValueError(f"{frame_format} frames have even sizes (one chroma pair per 2 x 2 luma samples), got {ws} x {hs}")
     return (hs * 3 // 2, ws * (2 if frame_format == "p010" else 1))
@@ -107,59 +128,93 @@ class SurfaceLayout:
     """Where the samples of one image lie in a decoder's surface; the same for all images of a plan or runner.
 
     frame_format "bgr": one plane of Hs rows, 3 bytes per pixel. "nv12" / "nv21" / "p010": a luma plane of Hs rows, 1 byte per
-    sample (2 for p010), and a chroma plane of Hs / 2 rows of interleaved pairs of the same row width.
-      pitch          bytes from one luma (BGR) row to the next; at least the row's sample bytes (3 Ws, Ws, 2 Ws: the default)
+    sample (2 for p010), and a chroma plane of Hs / 2 rows of interleaved pairs of the same row width. "yuv420p" / "yvu420p": a
+    luma plane of Hs rows and two chroma planes of Hs / 2 rows of Ws / 2 bytes each. "yuyv" / "uyvy" (2 bytes per pixel), "rgb"
+    (3), "bgra" / "rgba" (4): one plane, like "bgr".
+      pitch          bytes from one luma (packed) row to the next; at least the row's sample bytes (the default)
       luma_rows      the plane height the decoder allocated, >= Hs (default Hs)
-      chroma_pitch   bytes from one chroma row to the next (default: pitch)
-      chroma_offset  bytes from the image's first byte to chroma row 0 (default: luma_rows * pitch)
+      chroma_pitch   bytes from one chroma row to the next (default: pitch; planar: pitch // 2, shared by both chroma planes)
+      chroma_offset  bytes from the image's first byte to chroma row 0 (default: luma_rows * pitch); planar: to row 0 of the
+                     Cb plane, whichever name the format has
+      chroma2_offset planar only: bytes to row 0 of the Cr plane. The two planar names differ in these two defaults alone:
+                     "yuv420p" has Cb at luma_rows * pitch and Cr behind Cb's Hs / 2 rows, "yvu420p" Cr first and Cb behind it
       image_bytes    the extent of one image and the stride between the images of a contiguous batch (default: the end of the
-                     last chroma / BGR row; larger = tail padding)
+                     last chroma / packed row; larger = tail padding)
     ValueError for rows or planes that overlap, a sample outside image_bytes, and odd offsets of 16-bit samples.
     `.tight`: every field has its default (for bgr / nv12 / nv21 the form a ResamplePlan without a layout takes). `.key`:
     what enters `plan_key` (None when tight)."""
 
-    def __init__(self, src_hw, frame_format, pitch=None, luma_rows=None, chroma_pitch=None, chroma_offset=None, image_bytes=None):
+    def __init__(self, src_hw, frame_format, pitch=None, luma_rows=None, chroma_pitch=None, chroma_offset=None, image_bytes=None,
+                 chroma2_offset=None):
         if frame_format not in FRAME_FORMATS:
-            raise ValueError(f"frame format {frame_format!r}: one of {FRAME_FORMATS}")
+            raise _unknown_format(frame_format)
         hs, ws = int(src_hw[0]), int(src_hw[1])
         if hs <= 0 or ws <= 0:
             raise ValueError(f"source {ws} x {hs}")
         self.src_hw, self.frame_format = (hs, ws), frame_format
-        self.tight = all(v is None for v in (pitch, luma_rows, chroma_pitch, chroma_offset, image_bytes))
+        self.tight = all(v is None for v in (pitch, luma_rows, chroma_pitch, chroma_offset, image_bytes, chroma2_offset))
         self.sample_bytes = 2 if frame_format == "p010" else 1
-        self.row_bytes = ws * (3 if frame_format == "bgr" else self.sample_bytes)   # the samples of a luma (BGR) or chroma row
+        self.row_bytes = ws * PIXEL_BYTES.get(frame_format, self.sample_bytes)   # the samples of a luma (packed) row
+        self.chroma_row_bytes = 0 if frame_format in PIXEL_BYTES else ws // 2 if frame_format in PLANAR else self.row_bytes
         self.pitch = self.row_bytes if pitch is None else int(pitch)
-        if frame_format == "bgr":
-            given = [n for n, v in (("luma_rows", luma_rows), ("chroma_pitch", chroma_pitch), ("chroma_offset", chroma_offset)) if v is not None]
+        self.chroma2_offset = 0
+        if frame_format in PIXEL_BYTES:
+            given = [n for n, v in (("luma_rows", luma_rows), ("chroma_pitch", chroma_pitch), ("chroma_offset", chroma_offset),
+                                    ("chroma2_offset", chroma2_offset)) if v is not None]
             if given:
-                raise ValueError(f"a bgr surface is one plane: {', '.join(given)} must not be given")
+                raise ValueError(f"a {frame_format} surface is one plane: {', '.join(given)} must not be given")
+            frame_shape((hs, ws), frame_format)   # (an even width for 4:2:2)
             self.luma_rows, self.chroma_pitch, self.chroma_offset = hs, 0, 0
             self.sample_end = (hs - 1) * self.pitch + self.row_bytes
-        else:
+        elif frame_format in SEMI_PLANAR:
+            if chroma2_offset is not None:
+                raise ValueError(f"a {frame_format} surface has one chroma plane of interleaved pairs: chroma2_offset must not be given")
             frame_shape((hs, ws), frame_format)   # (even sizes)
             self.luma_rows = hs if luma_rows is None else int(luma_rows)
             self.chroma_pitch = self.pitch if chroma_pitch is None else int(chroma_pitch)
             self.chroma_offset = self.luma_rows * self.pitch if chroma_offset is None else int(chroma_offset)
             self.sample_end = self.chroma_offset + (hs // 2 - 1) * self.chroma_pitch + self.row_bytes
+        else:
+            frame_shape((hs, ws), frame_format)   # (even sizes)
+            self.luma_rows = hs if luma_rows is None else int(luma_rows)
+            if chroma_pitch is None and self.pitch % 2:
+                raise ValueError(f"{frame_format} surface of {ws} x {hs}: the default chroma_pitch is pitch // 2 and the pitch "
+                                 f"{self.pitch} is odd: give chroma_pitch")
+            self.chroma_pitch = self.pitch // 2 if chroma_pitch is None else int(chroma_pitch)
+            first, plane = self.luma_rows * self.pitch, (hs // 2) * self.chroma_pitch
+            cb, cr = (first, first + plane) if frame_format == "yuv420p" else (first + plane, first)
+            self.chroma_offset = cb if chroma_offset is None else int(chroma_offset)
+            self.chroma2_offset = cr if chroma2_offset is None else int(chroma2_offset)
+            self.sample_end = max(self.chroma_offset, self.chroma2_offset) + (hs // 2 - 1) * self.chroma_pitch + self.chroma_row_bytes
         self.image_bytes = self.sample_end if image_bytes is None else int(image_bytes)
         self._check()
         self.key = None if self.tight else (self.pitch, self.luma_rows, self.chroma_pitch, self.chroma_offset, self.image_bytes)
+        if self.key is not None and frame_format in PLANAR:
+            self.key += (self.chroma2_offset,)
 
     def _check(self):
         hs, ws = self.src_hw
         what = self.describe()
         if self.pitch < self.row_bytes:
             raise ValueError(f"{what}: rows overlap (a row holds {self.row_bytes} sample bytes, the pitch is {self.pitch})")
-        if self.frame_format != "bgr":
+        if self.frame_format not in PIXEL_BYTES:
             if self.luma_rows < hs:
                 raise ValueError(f"{what}: luma_rows {self.luma_rows} is below the {hs} rows of the picture")
-            if self.chroma_pitch < self.row_bytes:
-                raise ValueError(f"{what}: chroma rows overlap (a row holds {self.row_bytes} sample bytes, the chroma pitch is "
+            if self.chroma_pitch < self.chroma_row_bytes:
+                raise ValueError(f"{what}: chroma rows overlap (a row holds {self.chroma_row_bytes} sample bytes, the chroma pitch is "
                                  f"{self.chroma_pitch})")
             luma_end = (hs - 1) * self.pitch + self.row_bytes
             if self.chroma_offset < luma_end:
                 raise ValueError(f"{what}: planes overlap (the luma samples end at byte {luma_end}, the chroma plane starts at "
                                  f"{self.chroma_offset})")
+            if self.frame_format in PLANAR:
+                if self.chroma2_offset < luma_end:
+                    raise ValueError(f"{what}: planes overlap (the luma samples end at byte {luma_end}, the Cr plane starts at "
+                                     f"{self.chroma2_offset})")
+                span = (hs // 2 - 1) * self.chroma_pitch + self.chroma_row_bytes
+                if self.chroma_offset < self.chroma2_offset + span and self.chroma2_offset < self.chroma_offset + span:
+                    raise ValueError(f"{what}: planes overlap (the Cb samples span bytes {self.chroma_offset} .. "
+                                     f"{self.chroma_offset + span}, the Cr samples {self.chroma2_offset} .. {self.chroma2_offset + span})")
             if self.frame_format == "p010" and (self.pitch % 2 or self.chroma_pitch % 2 or self.chroma_offset % 2):
                 raise ValueError(f"{what}: p010 samples are 16-bit words: pitch, chroma_pitch and chroma_offset must be even")
         if self.image_bytes < self.sample_end:
@@ -169,19 +224,27 @@ class SurfaceLayout:
         if max(self.pitch, self.chroma_pitch) > (1 << 30) or self.image_bytes > (1 << 40):
             raise ValueError(f"{what}: outside the kernel's limits (pitch 2^30, image 2^40 bytes)")
 
+    PIXELS = {"bgr": "interleaved BGR", "rgb": "interleaved RGB", "bgra": "4-byte BGRA pixels", "rgba": "4-byte RGBA pixels",
+              "yuyv": "packed 4:2:2, groups of (Y0, Cb, Y1, Cr)", "uyvy": "packed 4:2:2, groups of (Cb, Y0, Cr, Y1)"}
+
     def describe(self):
         """The layout in words (for error messages)."""
         hs, ws = self.src_hw
-        if self.frame_format == "bgr":
-            return f"bgr surface of {ws} x {hs} (interleaved BGR, row pitch {self.pitch})"
+        if self.frame_format in PIXEL_BYTES:
+            return f"{self.frame_format} surface of {ws} x {hs} ({self.PIXELS[self.frame_format]}, row pitch {self.pitch})"
+        if self.frame_format in PLANAR:
+            return (f"{self.frame_format} surface of {ws} x {hs} ({hs} luma rows at pitch {self.pitch} in a plane of {self.luma_rows}, "
+                    f"then two planes of {hs // 2} rows of {ws // 2} bytes at pitch {self.chroma_pitch}: Cb from byte {self.chroma_offset}, "
+                    f"Cr from byte {self.chroma2_offset})")
         pair = "(Cr, Cb)" if self.frame_format == "nv21" else "(Cb, Cr)"
         bits = ", u16 little-endian samples" if self.frame_format == "p010" else ""
         return (f"{self.frame_format} surface of {ws} x {hs} ({hs} luma rows at pitch {self.pitch} in a plane of {self.luma_rows}, then "
                 f"{hs // 2} rows of interleaved {pair} pairs at pitch {self.chroma_pitch} from byte {self.chroma_offset}{bits})")
 
     def __repr__(self):
+        second = f", chroma2_offset={self.chroma2_offset}" if self.frame_format in PLANAR else ""
         return (f"SurfaceLayout({self.src_hw}, {self.frame_format!r}, pitch={self.pitch}, luma_rows={self.luma_rows}, chroma_pitch="
-                f"{self.chroma_pitch}, chroma_offset={self.chroma_offset}, image_bytes={self.image_bytes})")
+                f"{self.chroma_pitch}, chroma_offset={self.chroma_offset}, image_bytes={self.image_bytes}{second})")
 
     @classmethod
     def make(cls, layout, src_hw, frame_format):
@@ -306,12 +369,13 @@ def check_surfaces(tensors, surface):
 
 def plan_key(src_hw, aug_config, frame_format="bgr", colour="jfif", layout=None):
     """What a ResamplePlan depends on: a frame whose key differs must not run on the plan's tables (nor a frame of another
-    format or colour standard on the plan's kernel; the standard says nothing about BGR frames and is left out of their key).
+    format or colour standard on the plan's kernel; the standard says nothing about BGR, RGB, BGRA or RGBA frames and is left
+    out of their key).
     `layout` (a SurfaceLayout or a dict of its keyword arguments) adds its own key unless it is tight: a frame never runs on a
     plan, or a captured graph, made for another layout."""
     _check_format(frame_format, colour)
     dims, crop, flip = resolve_aug(src_hw, aug_config)
-    key = (int(src_hw[0]), int(src_hw[1]), dims, crop, flip, frame_format, colour if frame_format != "bgr" else None)
+    key = (int(src_hw[0]), int(src_hw[1]), dims, crop, flip, frame_format, colour if frame_format not in RGB_ORDER else None)
     extra = None if layout is None else SurfaceLayout.make(layout, src_hw, frame_format).key
     return key if extra is None else key + (extra,)
 
@@ -339,7 +403,14 @@ class ResamplePlan:
     "p010": the same arrangement in u16 little-endian samples (sample = word >> 6; `p010_coefficients`), given as bytes: u8
     [Hs * 3 / 2, Ws * 2]. `layout` (a SurfaceLayout or a dict of its keyword arguments) describes a decoder's padded surface
     instead: one image is then u8 [image_bytes], `run` takes a contiguous batch of them and `run_surfaces` one tensor per
-    image. Without a layout (or with a tight one) the plan is the one described above."""
+    image. Without a layout (or with a tight one) the plan is the one described above.
+
+    "yuv420p" / "yvu420p" (I420 / YV12, a software decoder's planar 4:2:0): u8 [Hs * 3 / 2, Ws], Hs luma rows, then the Cb
+    plane and the Cr plane (yvu420p: Cr, then Cb) of Hs / 2 rows of Ws / 2 bytes each; chroma replicated as for nv12. "yuyv" /
+    "uyvy" (packed 4:2:2): u8 [Hs, Ws, 2], groups of (Y0, Cb, Y1, Cr) / (Cb, Y0, Cr, Y1), the pair belongs to columns 2j, 2j + 1
+    of its own row; Ws even, any Hs. "rgb": u8 [Hs, Ws, 3], R first. "bgra" / "rgba": u8 [Hs, Ws, 4], byte 3 ignored. The
+    YCbCr forms follow `colour` like nv12; the others are a byte permutation into the staged (B, G, R) row and `colour` is not
+    looked at. All take `layout` (SurfaceLayout has their fields) and `run_surfaces`."""
 
     def __init__(self, src_hw, aug_config=None, img_norm_cfg=None, frame_format="bgr", colour="jfif", layout=None):
         self.src_hw = (int(src_hw[0]), int(src_hw[1]))
@@ -347,7 +418,7 @@ class ResamplePlan:
         self.frame_format, self.colour = frame_format, colour
         self.surface = SurfaceLayout.make(layout, self.src_hw, frame_format)
         self.frame_shape = frame_shape(self.src_hw, frame_format) if self.surface.tight else (self.surface.image_bytes,)
-        self.yuv = None if frame_format == "bgr" else yuv_coefficients(colour)
+        self.yuv = None if frame_format in RGB_ORDER else yuv_coefficients(colour)
         self.resize_dims, self.crop, self.flip = resolve_aug(self.src_hw, aug_config)
         self.key = plan_key(self.src_hw, aug_config, frame_format, colour, self.surface)
         cfg = IMG_NORM_CFG if img_norm_cfg is None else img_norm_cfg
@@ -373,11 +444,13 @@ class ResamplePlan:
     def bytes_per_image(self, mid_pitch):
         h, w = self.out_hw
         mid = self.src_rows * mid_pitch
-        if self.yuv is None:
-            source = self.src_rows * self.src_hw[1] * 3
+        if self.frame_format in PIXEL_BYTES:   # one plane: a 4:2:2 row carries its own chroma, and the alpha bytes count as read
+            source = self.src_rows * self.surface.row_bytes
         else:   # the needed luma rows and the distinct chroma rows under them (needed bytes: both luma rows of a pair stage it)
             last = self.src_row0 + self.src_rows - 1
-            source = (self.src_rows + (last >> 1) - (self.src_row0 >> 1) + 1) * self.surface.row_bytes   # (sample bytes: no padding)
+            chroma_rows = (last >> 1) - (self.src_row0 >> 1) + 1
+            planes = 2 if self.frame_format in PLANAR else 1
+            source = self.src_rows * self.surface.row_bytes + chroma_rows * planes * self.surface.chroma_row_bytes   # (no padding)
         return dict(source=source, mid_write=mid, mid_read=mid, out=h * w * 8)
 
     # ------------------------------------------------------------------ device
@@ -409,8 +482,15 @@ class ResamplePlan:
         hs, ws = self.src_hw
         if not self.surface.tight:
             return f"u8 [..., {self.surface.image_bytes}] images, each a {self.surface.describe()}"
-        if self.yuv is None:
+        if self.frame_format == "bgr":
             return f"u8 [..., {hs}, {ws}, 3] frames (interleaved BGR)"
+        if self.frame_format in PIXEL_BYTES:
+            return (f"u8 [..., {hs}, {ws}, {PIXEL_BYTES[self.frame_format]}] {self.frame_format} frames "
+                    f"({SurfaceLayout.PIXELS[self.frame_format]}; a padded surface needs layout=)")
+        if self.frame_format in PLANAR:
+            order = "Cb plane, then the Cr plane" if self.frame_format == "yuv420p" else "Cr plane, then the Cb plane"
+            return (f"u8 [..., {hs * 3 // 2}, {ws}] {self.frame_format} frames ({hs} luma rows of {ws} bytes, then the {order}, each "
+                    f"{hs // 2} rows of {ws // 2} bytes; a padded surface needs layout=)")
         if self.frame_format == "p010":
             return (f"u8 [..., {hs * 3 // 2}, {ws * 2}] p010 frames (the bytes of u16 little-endian samples: {hs} luma rows, then {hs // 2} "
                     f"rows of interleaved (Cb, Cr) pairs, row pitch {ws * 2}; a padded surface needs layout=)")
@@ -433,7 +513,7 @@ class ResamplePlan:
         if not frames.is_cuda:
             raise RuntimeError("simpb_amd operators run on the GPU only (got a CPU tensor); there is no CPU fallback")
         if not frames.is_contiguous():
-            raise ValueError("ingest takes contiguous frames" + (" (interleaved pixels)" if self.yuv is None else ""))
+            raise ValueError("ingest takes contiguous frames" + (" (interleaved pixels)" if self.frame_format in RGB_ORDER else ""))
         n = int(frames.numel() // int(np.prod(self.frame_shape)))
         if n == 0:
             raise ValueError("ingest of an empty batch")
@@ -485,7 +565,7 @@ class ResamplePlan:
         ints = (n, hs, ws, h, w, self.taps_x, self.taps_y, self.src_row0, self.src_rows, int(self.flip), int(self.swap_rb))
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         sf = self.surface
-        if table is None and sf.tight and self.frame_format != "p010":   # today's forms, through today's entry points
+        if table is None and sf.tight and self.frame_format in ("bgr", "nv12", "nv21"):   # the first forms, through their entry points
             if self.yuv is None:
                 _lib.check(_lib.lib().simpb_preprocess_u8_nhwc4_f16(p(out), p(src), *tables, *ints, stream), "simpb_preprocess_u8_nhwc4_f16")
             else:
@@ -494,10 +574,15 @@ class ResamplePlan:
             return out
         null = ctypes.c_void_p(0)
         yuv = self.yuv if self.yuv is not None else (0, 1, 0, 0, 0, 0)
-        _lib.check(_lib.lib().simpb_preprocess_surface_nhwc4_f16(
-            p(out), p(src) if table is None else null, null if table is None else p(table), *tables, *ints,
-            SURFACE_FORMAT[self.frame_format], sf.pitch, sf.chroma_pitch, sf.chroma_offset, sf.image_bytes, *yuv, stream),
-            "simpb_preprocess_surface_nhwc4_f16")
+        images = (p(src) if table is None else null, null if table is None else p(table))
+        if SURFACE_FORMAT[self.frame_format] <= SURFACE_FORMAT["p010"]:
+            _lib.check(_lib.lib().simpb_preprocess_surface_nhwc4_f16(
+                p(out), *images, *tables, *ints, SURFACE_FORMAT[self.frame_format], sf.pitch, sf.chroma_pitch, sf.chroma_offset,
+                sf.image_bytes, *yuv, stream), "simpb_preprocess_surface_nhwc4_f16")
+        else:   # planar 4:2:0, packed 4:2:2 and the RGB-order family
+            _lib.check(_lib.lib().simpb_preprocess_planes_nhwc4_f16(
+                p(out), *images, *tables, *ints, SURFACE_FORMAT[self.frame_format], sf.pitch, sf.chroma_pitch, sf.chroma_offset,
+                sf.chroma2_offset, sf.image_bytes, *yuv, stream), "simpb_preprocess_planes_nhwc4_f16")
         return out
 
 
@@ -610,7 +695,7 @@ class RigPlan:
             sf = p.surface
             c.format, c.src_height, c.src_width = SURFACE_FORMAT[p.frame_format], p.src_hw[0], p.src_hw[1]
             c.src_row0, c.src_rows, c.taps_x, c.taps_y, c.flip = p.src_row0, p.src_rows, p.taps_x, p.taps_y, int(p.flip)
-            c.pitch, c.chroma_pitch, c.chroma_offset = sf.pitch, sf.chroma_pitch, sf.chroma_offset
+            c.pitch, c.chroma_pitch, c.chroma_offset, c.chroma2_offset = sf.pitch, sf.chroma_pitch, sf.chroma_offset, sf.chroma2_offset
             c.kx_offset, c.x_offset, c.ky_offset, c.y_offset = self.kx_offset[i], self.x_offset[i], self.ky_offset[i], self.y_offset[i]
             c.mid_row = self.mid_row[i]
             c.yoff, c.iy, c.irv, c.igu, c.igv, c.ibu = p.yuv if p.yuv is not None else (0, 1, 0, 0, 0, 0)

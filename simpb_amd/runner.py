@@ -388,7 +388,10 @@ class FrameRunner:
         raw_format="nv12" | "nv21", raw_colour="jfif" | "bt601" | "bt709" (with raw_input only): the frames are 4:2:0
         semi-planar YCbCr, u8 [bs, cams, Hs * 3 / 2, Ws] (preprocess.ResamplePlan has the layout), converted to BGR inside the
         ingest's first launch. The default "bgr" is the packed form above. "p010": the 10-bit form of NV12, u8 [bs, cams,
-        Hs * 3 / 2, Ws * 2] (raw_colour "bt601" or "bt709").
+        Hs * 3 / 2, Ws * 2] (raw_colour "bt601" or "bt709"). "yuv420p" / "yvu420p" (a software decoder's planar I420 / YV12): u8
+        [bs, cams, Hs * 3 / 2, Ws], three planes. "yuyv" / "uyvy" (packed 4:2:2, a camera without a codec): u8 [bs, cams, Hs, Ws, 2].
+        "rgb": u8 [bs, cams, Hs, Ws, 3], R first. "bgra" / "rgba": u8 [bs, cams, Hs, Ws, 4], byte 3 ignored; raw_colour says nothing
+        about the last three (preprocess.ResamplePlan has every layout).
         raw_layout=preprocess.SurfaceLayout or a dict of its keyword arguments (with raw_input only): every image is a decoder
         surface with a padded pitch / plane height / chroma offset; frames are then u8 [bs, cams, image_bytes].
         raw_surfaces=True (with raw_input only, with or without raw_layout): `img` is a nested list [bs][cams] of device u8

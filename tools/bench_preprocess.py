@@ -32,9 +32,17 @@
       leave at once (the grid is padded to the tallest camera) stands beside it. `runner`: SplitPipelinedRunner frames/s
       with the uniform rig (raw_rig) beside the raw_surfaces runner on the same surface pools, in alternating blocks.
 
+  (f) `planes` (--only-planes; not part of a plain run): the two ingest launches alone at R50 with 6 images for every frame
+      format of the other producers (planar yuv420p / yvu420p, packed yuyv / uyvy, rgb, bgra, rgba: tight frames through
+      simpb_preprocess_planes_nhwc4_f16) beside packed BGR and NV12 through their own entry points, --launches per block in
+      --blocks alternating blocks of one run. All forms hold the same pictures and must give the same operand. The vertical
+      launch is the same for every format, so a difference between two lines is a difference of their horizontal launches;
+      `source_bytes_per_image` (ResamplePlan.bytes_per_image) says which existing format a new one should sit with.
+
 A run that finds no GPU fails.
 
-    python tools/bench_preprocess.py [--launches 200] [--blocks 5] [--block-steps 40] [--only-surface | --skip-surface | --only-rig]
+    python tools/bench_preprocess.py [--launches 200] [--blocks 5] [--block-steps 40]
+                                     [--only-surface | --skip-surface | --only-rig | --only-planes]
 """
 import argparse
 import json
@@ -410,6 +418,61 @@ def rig_runner_leg(torch, args):
     return out
 
 
+def plane_frames(torch, nv12, bgr):
+    """The six pictures (NV12 u8 [6, 1350, 1600] and the BGR u8 [6, 900, 1600, 3] the ingest's rule makes of them) in every frame
+    format, tight: 4:2:2 repeats each chroma row, the 4-byte formats carry alpha 255."""
+    luma, pairs = nv12[:, :900], nv12[:, 900:].reshape(6, 450, 800, 2)
+    cb, cr = pairs[..., 0], pairs[..., 1]
+    planar = lambda a, b: torch.cat([luma.reshape(6, -1), a.reshape(6, -1), b.reshape(6, -1)], 1).reshape(6, 1350, 1600)   # noqa: E731
+    y2, cb2, cr2 = luma.reshape(6, 900, 800, 2), cb.repeat_interleave(2, 1), cr.repeat_interleave(2, 1)
+    yuyv = torch.stack([y2[..., 0], cb2, y2[..., 1], cr2], -1).reshape(6, 900, 1600, 2)
+    alpha = torch.full((6, 900, 1600, 1), 255, dtype=torch.uint8)
+    rgb = bgr.flip(-1)
+    frames = dict(bgr=bgr, nv12=nv12, yuv420p=planar(cb, cr), yvu420p=planar(cr, cb), yuyv=yuyv, uyvy=yuyv.flip(-1), rgb=rgb,
+                  bgra=torch.cat([bgr, alpha], -1), rgba=torch.cat([rgb, alpha], -1))
+    return {k: v.contiguous() for k, v in frames.items()}
+
+
+def planes_launch_leg(torch, args):
+    from simpb_amd import _lib
+    from simpb_amd.preprocess import ResamplePlan
+    aug = CONFIGS["r50_704x256"]
+    nv12, bgr = nv12_frames(torch, 0)
+    forms = {}
+    for fmt, host in plane_frames(torch, nv12[0], bgr[0]).items():
+        plan = ResamplePlan((900, 1600), aug, frame_format=fmt).reserve(6, "cuda")
+        forms[fmt] = (plan, host.cuda(), torch.empty(6, *plan.out_hw, 4, dtype=torch.float16, device="cuda"))
+    ref = None
+    for fmt, (plan, frames, dst) in forms.items():
+        for _ in range(20):
+            plan.run(frames, out=dst)
+        torch.cuda.synchronize()
+        ref = dst.clone() if ref is None else ref
+        assert torch.equal(dst, ref), fmt        # every format holds the same pictures: the same operand
+    blocks = {k: [] for k in forms}
+    for _ in range(args.blocks):
+        for fmt, (plan, frames, dst) in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.launches):
+                plan.run(frames, out=dst)
+            e1.record()
+            e1.synchronize()
+            blocks[fmt].append(e0.elapsed_time(e1) / args.launches)
+    out = {}
+    for fmt, v in blocks.items():
+        plan = forms[fmt][0]
+        per_image = plan.bytes_per_image(int(_lib.lib().simpb_preprocess_mid_pitch(plan.out_hw[1])))
+        ms = float(np.mean(v))
+        out[fmt] = dict(ms=round(ms, 5), block_ms=[round(x, 5) for x in v], spread_ms=round(max(v) - min(v), 5), images=6,
+                        launches=args.launches * args.blocks, source_bytes_per_image=per_image["source"],
+                        bytes_per_image=sum(per_image.values()), share_of_hbm_peak=round(6 * sum(per_image.values()) / HBM_PEAK * 1e3 / ms, 4))
+    for fmt, v in out.items():
+        v["ms_minus_bgr"] = round(v["ms"] - out["bgr"]["ms"], 5)
+        v["ms_minus_nv12"] = round(v["ms"] - out["nv12"]["ms"], 5)
+    return out
+
+
 def cpu_leg(frames=3):
     try:
         from PIL import Image
@@ -446,6 +509,7 @@ def main():
     ap.add_argument("--skip-surface", action="store_true", help="leave out the decoder-surface leg (d)")
     ap.add_argument("--only-surface", action="store_true", help="the decoder-surface leg (d) alone")
     ap.add_argument("--only-rig", action="store_true", help="the rig leg (e) alone")
+    ap.add_argument("--only-planes", action="store_true", help="the frame-format leg (f) alone")
     ap.add_argument("--profile-raw", action="store_true",
                     help="only the runner leg's raw form: the program to put behind `rocprofv3 --kernel-trace --stats --`")
     args = ap.parse_args()
@@ -458,6 +522,11 @@ def main():
         with torch.no_grad():
             rig = dict(launch=rig_launch_leg(torch, args), runner=None if args.skip_runner else rig_runner_leg(torch, args))
         print(json.dumps(dict(tool="bench_preprocess", device=torch.cuda.get_device_name(0), rig=rig)))
+        return
+    if args.only_planes:
+        with torch.no_grad():
+            planes = dict(launch=planes_launch_leg(torch, args))
+        print(json.dumps(dict(tool="bench_preprocess", device=torch.cuda.get_device_name(0), planes=planes)))
         return
     with torch.no_grad():
         surface = None
