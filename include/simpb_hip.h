@@ -85,6 +85,15 @@ int simpb_dfa_fused_forward_cams(
     const float* feat_logits, const float* cam_logits, float* loc_out, float* weights_out, int batch_size, int num_cams,
     int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups,
     const unsigned char* cam_valid, void* stream);
+/* The same for a rig of num_cams = 1..8 cameras (cam_valid may be NULL). The rest of the layout stays the shipped one
+ * (num_scale 4, num_fix 7, num_learn 6, num_groups 8, num_embeds 256): there is one compiled kernel per camera count, and
+ * anything else returns SIMPB_EINVAL before any HIP call. Six cameras launch the kernels the two entries above launch. */
+int simpb_dfa_fused_forward_rig(
+    float* output, const void* mc_ms_feat, int feat_is_f16, const int* spatial_shape, const int* scale_start_index,
+    const float* anchor, const float* learnable, const float* fix_scale, const float* projection_mat, const float* image_wh,
+    const float* feat_logits, const float* cam_logits, float* loc_out, float* weights_out, int batch_size, int num_cams,
+    int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups,
+    const unsigned char* cam_valid, void* stream);
 
 
 /* Replaces `deformable_aggregation_grad(...)` (ops/src/deformable_aggregation.cpp:64-84, launcher

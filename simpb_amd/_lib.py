@@ -36,6 +36,7 @@ SIGNATURES = {
     "simpb_deformable_aggregation_forward": ([_P] * 6 + [_I] * 8 + [_P], _I),
     "simpb_dfa_fused_forward": ([_P, _P, _I] + [_P] * 11 + [_I] * 9 + [_P], _I),
     "simpb_dfa_fused_forward_cams": ([_P, _P, _I] + [_P] * 11 + [_I] * 9 + [_P, _P], _I),
+    "simpb_dfa_fused_forward_rig": ([_P, _P, _I] + [_P] * 11 + [_I] * 9 + [_P, _P], _I),
     "simpb_deformable_aggregation_backward": ([_P] * 9 + [_I] * 8 + [_P], _I),
     "simpb_ms_deform_attn_grouped_forward": ([_P] * 7 + [_I] * 8 + [_P], _I),
     "simpb_msda_linear_forward": ([_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P] + [_I] * 8 + [_P], _I),

@@ -24,7 +24,10 @@ def _mha(dims, groups, drop):
 
 
 def simpb_plus(depth=50, input_shape=(704, 256), anchor="./data/nuscenes/nuscenes_kmeans900.npy", temporal=True,
-               pretrained="ckpts/resnet50-19c8e357.pth"):
+               pretrained="ckpts/resnet50-19c8e357.pth", num_cams=6):
+    """num_cams: cameras of one stream, 1..8 (the reference takes the rig from its config: SimPBHead(num_cams=),
+    DeformableFeatureAggregation(num_cams=), QueryGroupMultiScaleDeformableAttention(num_cams=), limit_corners_num). Six is
+    the shipped file, key for key; with use_camera_embed no weight depends on the count, so one checkpoint serves every rig."""
     e, g, lv, drop, ncls, ndn, ntdn = 256, 8, 4, 0.1, len(CLASS_NAMES), 5, 3
     cone = CLASS_NAMES.index("traffic_cone")
     head = dict(
@@ -41,7 +44,7 @@ def simpb_plus(depth=50, input_shape=(704, 256), anchor="./data/nuscenes/nuscene
         norm_layer=dict(type="LN", normalized_shape=e),
         ffn=dict(type="AsymmetricFFN", in_channels=e * 2, pre_norm=dict(type="LN"), embed_dims=e,
                  feedforward_channels=e * 4, num_fcs=2, ffn_drop=drop, act_cfg=dict(type="ReLU", inplace=True)),
-        dynamic_allocation=dict(type="DynamicQueryAllocation", limit_corners_num=[100] * 6),
+        dynamic_allocation=dict(type="DynamicQueryAllocation", limit_corners_num=[100] * num_cams),
         adaptive_aggregation=dict(type="AdaptiveQueryAggregation", self_attn=_mha(e * 2, g, drop), reweight=True,
                                   with_pos=True),
         qg_self_attn=dict(type="QueryGroupMultiheadAttention", batch_first=True, embed_dims=e * 2, num_heads=g,
@@ -52,7 +55,7 @@ def simpb_plus(depth=50, input_shape=(704, 256), anchor="./data/nuscenes/nuscene
         temp_graph_model=_mha(e * 2, g, drop) if temporal else None,
         graph_model=_mha(e * 2, g, drop),
         deformable_model=dict(
-            type="DeformableFeatureAggregation", embed_dims=e, num_groups=g, num_levels=lv, num_cams=6,
+            type="DeformableFeatureAggregation", embed_dims=e, num_groups=g, num_levels=lv, num_cams=num_cams,
             attn_drop=0.15, use_deformable_func=True, use_camera_embed=True, residual_mode="cat",
             kps_generator=dict(type="SparseBox3DKeyPointsGenerator", num_learnable_pts=6,
                                fix_scale=[[0, 0, 0], [0.45, 0, 0], [-0.45, 0, 0], [0, 0.45, 0], [0, -0.45, 0],
@@ -78,6 +81,9 @@ def simpb_plus(depth=50, input_shape=(704, 256), anchor="./data/nuscenes/nuscene
         decoder=dict(type="SparseBox3DDecoder"),
         reg_weights=[2.0] * 3 + [1.0] * 7,
     )
+    if num_cams != 6:   # (the shipped files leave these two at the classes' default of six)
+        head["num_cams"] = num_cams
+        head["qg_cross_attn"]["num_cams"] = num_cams
     model = dict(
         type="SimPB", use_grid_mask=True, use_deformable_func=True,
         img_backbone=dict(type="ResNet", depth=depth, num_stages=4, frozen_stages=-1, norm_eval=False, style="pytorch",

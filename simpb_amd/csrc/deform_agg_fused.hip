@@ -210,31 +210,41 @@ __global__ __launch_bounds__(kThreads) void daf_fused_rows(DfaArgs k) {
   meet_and_store(s_red, acc, wave, lane, k.out + row * C, 0, C);
 }
 
-// the shipped layout (config :221-238: 6 cameras, 4 levels, 7 fixed + 6 learnable key points, 8 groups of 32 channels)
-template <class FEAT>
+// the shipped layout (config :221-238: 4 levels, 7 fixed + 6 learnable key points, 8 groups of 32 channels) at CAMS cameras;
+// CAMS = 6 is the shipped rig, and both the shipped-layout entries and the rig entry launch these very instantiations for it
+template <class FEAT, int CAMS>
 void launch_fused(bool masked, dim3 grid, hipStream_t s, const DfaArgs& k) {
-  if (masked) hipLaunchKernelGGL((daf_fused_rows<FEAT, 6, 4, 7, 6, 8, 256, true>), grid, dim3(kThreads), 0, s, k);
-  else hipLaunchKernelGGL((daf_fused_rows<FEAT, 6, 4, 7, 6, 8, 256, false>), grid, dim3(kThreads), 0, s, k);
+  if (masked) hipLaunchKernelGGL((daf_fused_rows<FEAT, CAMS, 4, 7, 6, 8, 256, true>), grid, dim3(kThreads), 0, s, k);
+  else hipLaunchKernelGGL((daf_fused_rows<FEAT, CAMS, 4, 7, 6, 8, 256, false>), grid, dim3(kThreads), 0, s, k);
 }
 
-}  // namespace
+constexpr int kMaxRigCams = 8;   // 13 * CAMS <= 128 locations per row and CAMS * 416 <= kMaxW hold up to 9; the allocation kernels end at 8
 
-extern "C" int simpb_dfa_fused_forward_cams(
-    float* output, const void* mc_ms_feat, int feat_is_f16, const int* spatial_shape, const int* scale_start_index,
-    const float* anchor, const float* learnable, const float* fix_scale, const float* projection_mat, const float* image_wh,
-    const float* feat_logits, const float* cam_logits, float* loc_out, float* weights_out, int batch_size, int num_cams,
-    int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups,
-    const unsigned char* cam_valid, void* stream) {
+template <int CAMS>
+void launch_fused_cams(bool f16, bool masked, dim3 grid, hipStream_t s, const DfaArgs& k) {
+  if (f16) launch_fused<_Float16, CAMS>(masked, grid, s, k);
+  else launch_fused<float, CAMS>(masked, grid, s, k);
+}
+
+bool operands_given(const float* output, const void* mc_ms_feat, const int* spatial_shape, const int* scale_start_index,
+                    const float* anchor, const float* learnable, const float* fix_scale, const float* projection_mat,
+                    const float* image_wh, const float* feat_logits, const float* cam_logits, int batch_size, int num_cams,
+                    int num_feat, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups) {
   if (!output || !mc_ms_feat || !spatial_shape || !scale_start_index || !anchor || !fix_scale || !projection_mat ||
       !image_wh || !feat_logits || !cam_logits || (num_learn > 0 && !learnable))
-    return SIMPB_EINVAL;
-  if (batch_size <= 0 || batch_size > 65535 || num_cams <= 0 || num_feat <= 0 || num_scale <= 0 || num_anchors <= 0 ||
-      num_fix < 0 || num_learn < 0 || num_fix + num_learn <= 0 || num_groups <= 0)
-    return SIMPB_EINVAL;
-  // compiled for the shipped layout only; the three-launch route (simpb_dfa_points / simpb_dfa_weights /
-  // simpb_deformable_aggregation_forward) takes any other
-  if (num_cams != 6 || num_scale != 4 || num_fix != 7 || num_learn != 6 || num_groups != 8 || num_embeds != 256)
-    return SIMPB_EINVAL;
+    return false;
+  return !(batch_size <= 0 || batch_size > 65535 || num_cams <= 0 || num_feat <= 0 || num_scale <= 0 || num_anchors <= 0 ||
+           num_fix < 0 || num_learn < 0 || num_fix + num_learn <= 0 || num_groups <= 0);
+}
+
+// num_cams in 1..kMaxRigCams, the rest of the layout as shipped (validated by the callers; the count once more here, in front of
+// any HIP call: no count without a case of its own reaches a kernel compiled for another)
+int launch_rig(float* output, const void* mc_ms_feat, int feat_is_f16, const int* spatial_shape, const int* scale_start_index,
+               const float* anchor, const float* learnable, const float* fix_scale, const float* projection_mat,
+               const float* image_wh, const float* feat_logits, const float* cam_logits, float* loc_out, float* weights_out,
+               int batch_size, int num_cams, int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix,
+               int num_learn, int num_groups, const unsigned char* cam_valid, void* stream) {
+  if (num_cams < 1 || num_cams > kMaxRigCams) return SIMPB_EINVAL;
   (void)hipGetLastError();
   DfaArgs k;
   k.out = output; k.feat = mc_ms_feat; k.spatial_shape = spatial_shape; k.scale_start = scale_start_index;
@@ -244,11 +254,59 @@ extern "C" int simpb_dfa_fused_forward_cams(
   k.num_learn = num_learn; k.G = num_groups; k.cam_valid = cam_valid;
   hipStream_t s = static_cast<hipStream_t>(stream);
   dim3 grid(num_anchors, batch_size);
+  const bool f16 = feat_is_f16 != 0, masked = cam_valid != nullptr;
   const int tslot = simpb_timing_begin(SIMPB_KERNEL_DAF, stream);
-  if (feat_is_f16) launch_fused<_Float16>(cam_valid != nullptr, grid, s, k);
-  else launch_fused<float>(cam_valid != nullptr, grid, s, k);
+  switch (num_cams) {
+    case 1: launch_fused_cams<1>(f16, masked, grid, s, k); break;
+    case 2: launch_fused_cams<2>(f16, masked, grid, s, k); break;
+    case 3: launch_fused_cams<3>(f16, masked, grid, s, k); break;
+    case 4: launch_fused_cams<4>(f16, masked, grid, s, k); break;
+    case 5: launch_fused_cams<5>(f16, masked, grid, s, k); break;
+    case 6: launch_fused_cams<6>(f16, masked, grid, s, k); break;
+    case 7: launch_fused_cams<7>(f16, masked, grid, s, k); break;
+    case 8: launch_fused_cams<8>(f16, masked, grid, s, k); break;
+    default: break;   // (refused above)
+  }
+  static_assert(kMaxRigCams == 8, "one case per camera count");
   simpb_timing_end(tslot, stream);
   return simpb_check_launch();
+}
+
+}  // namespace
+
+extern "C" int simpb_dfa_fused_forward_rig(
+    float* output, const void* mc_ms_feat, int feat_is_f16, const int* spatial_shape, const int* scale_start_index,
+    const float* anchor, const float* learnable, const float* fix_scale, const float* projection_mat, const float* image_wh,
+    const float* feat_logits, const float* cam_logits, float* loc_out, float* weights_out, int batch_size, int num_cams,
+    int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups,
+    const unsigned char* cam_valid, void* stream) {
+  if (!operands_given(output, mc_ms_feat, spatial_shape, scale_start_index, anchor, learnable, fix_scale, projection_mat, image_wh,
+                      feat_logits, cam_logits, batch_size, num_cams, num_feat, num_scale, num_anchors, num_fix, num_learn, num_groups))
+    return SIMPB_EINVAL;
+  // the camera count is the one free dimension: a kernel per count, the rest compiled for the shipped layout
+  if (num_cams > kMaxRigCams || num_scale != 4 || num_fix != 7 || num_learn != 6 || num_groups != 8 || num_embeds != 256)
+    return SIMPB_EINVAL;
+  return launch_rig(output, mc_ms_feat, feat_is_f16, spatial_shape, scale_start_index, anchor, learnable, fix_scale, projection_mat,
+                    image_wh, feat_logits, cam_logits, loc_out, weights_out, batch_size, num_cams, num_feat, num_embeds, num_scale,
+                    num_anchors, num_fix, num_learn, num_groups, cam_valid, stream);
+}
+
+extern "C" int simpb_dfa_fused_forward_cams(
+    float* output, const void* mc_ms_feat, int feat_is_f16, const int* spatial_shape, const int* scale_start_index,
+    const float* anchor, const float* learnable, const float* fix_scale, const float* projection_mat, const float* image_wh,
+    const float* feat_logits, const float* cam_logits, float* loc_out, float* weights_out, int batch_size, int num_cams,
+    int num_feat, int num_embeds, int num_scale, int num_anchors, int num_fix, int num_learn, int num_groups,
+    const unsigned char* cam_valid, void* stream) {
+  if (!operands_given(output, mc_ms_feat, spatial_shape, scale_start_index, anchor, learnable, fix_scale, projection_mat, image_wh,
+                      feat_logits, cam_logits, batch_size, num_cams, num_feat, num_scale, num_anchors, num_fix, num_learn, num_groups))
+    return SIMPB_EINVAL;
+  // the shipped layout only (six cameras); simpb_dfa_fused_forward_rig takes 1..8 cameras, the three-launch route
+  // (simpb_dfa_points / simpb_dfa_weights / simpb_deformable_aggregation_forward) any other layout
+  if (num_cams != 6 || num_scale != 4 || num_fix != 7 || num_learn != 6 || num_groups != 8 || num_embeds != 256)
+    return SIMPB_EINVAL;
+  return launch_rig(output, mc_ms_feat, feat_is_f16, spatial_shape, scale_start_index, anchor, learnable, fix_scale, projection_mat,
+                    image_wh, feat_logits, cam_logits, loc_out, weights_out, batch_size, num_cams, num_feat, num_embeds, num_scale,
+                    num_anchors, num_fix, num_learn, num_groups, cam_valid, stream);
 }
 
 extern "C" int simpb_dfa_fused_forward(

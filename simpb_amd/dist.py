@@ -119,12 +119,16 @@ class DetectionGather:
     with rows2d > 0, the 2D record [streams, rows2d, 8] (decoder.py:230-251 returns boxes_2d / scores_2d / labels_2d /
     camidx_2d beside the 3D fields; apis/test.py:49-119 collects the whole dict) -- in ONE all_gather_into_tensor per
     frame, off the compute streams. rows2d is a fixed exchange capacity equal on every rank:
-    * compact2d=True (what bench.py uses): rows2d = num_output x num_cams and a runner's record is COMPACTED on the device
-      to the rows decode_with2d returns (slots of the kept 3D boxes, at most one per box and camera) -- 1 800 rows for 300
-      boxes x 6 cameras whatever the runners' slot capacities are, so a rank whose 2D set overflows and grows its capacity
+    * compact2d=True (what bench.py uses): rows2d = num_output x the head's num_cams and a runner's
+      record is COMPACTED on the device to the rows decode_with2d returns (slots of the kept 3D boxes, at most one per box
+      and camera) -- 1 800 rows for 300 boxes x 6 cameras, 2 400 for eight, whatever the runners' slot capacities are, so a rank whose 2D set overflows and grows its capacity
       mid-stream (runner.py) changes nothing about the exchange, and the ranks never have to agree on a size;
     * compact2d=False: the slot array itself, rows2d = num_anchor x num_cams (5 400: no set can exceed it); a runner's
       record is copied into the leading rows, the rest stay pad rows (camera = -1).
+
+    Every rank must bring the same record shape (streams, num_output, rows2d: a rank with another camera count has another
+    rows2d); the constructor compares them across the group and refuses a disagreement, which would otherwise corrupt or
+    hang the first all-gather.
 
     The send and receive buffers are persistent and owned by the side stream, so no allocator block crosses streams;
     the records handed to submit() are read on the side stream after it has waited for their producer streams and are
@@ -140,6 +144,15 @@ class DetectionGather:
         self.side = torch.cuda.Stream(device=self.device) if self.cuda else None
         self.n3, self.rows2d = num_output * RECORD_WIDTH, int(rows2d)
         self.compact2d = bool(compact2d) and self.rows2d > 0
+        if self.world > 1:
+            # one small all-gather of the shape, on the tensors' own side: the device with RCCL, the host with gloo
+            side = torch.device("cpu") if dist.get_backend(group) == "gloo" else self.device
+            mine = torch.tensor([int(streams), int(num_output), self.rows2d], dtype=torch.int64, device=side)
+            shapes = torch.empty(self.world, 3, dtype=torch.int64, device=side)
+            dist.all_gather_into_tensor(shapes.view(-1), mine, group=group)
+            if bool((shapes != mine).any()):
+                raise ValueError(f"DetectionGather: the ranks disagree on (streams, num_output, rows2d): {shapes.tolist()}; with "
+                                 "compact2d rows2d is num_output x the head's num_cams, so every rank must serve the same rig")
         width = self.n3 + self.rows2d * RECORD2D_WIDTH
         self.send_buf = torch.zeros(streams, width, device=self.device)
         self.recv_buf = torch.zeros(self.world, streams, width, device=self.device)

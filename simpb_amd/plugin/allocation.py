@@ -41,6 +41,17 @@ class Allocation2D:
         return trans, trans * self.is_center[..., None].float()
 
 
+MAX_STREAM_GROUPS = 96   # camera groups of one batch of independent streams (kMaxRaggedGroups of csrc/alloc.hip)
+
+
+def check_stream_groups(num_streams, num_cams):
+    """A batch of independent streams is one flat slot array over num_streams * num_cams camera groups, whose starts one
+    workgroup keeps in LDS: 96 groups at the most, i.e. 16 streams of six cameras or 12 of eight."""
+    if num_streams * num_cams > MAX_STREAM_GROUPS:
+        raise ValueError(f"{num_streams} independent streams of {num_cams} cameras are {num_streams * num_cams} camera groups; one "
+                         f"batch takes {MAX_STREAM_GROUPS}, i.e. at most {MAX_STREAM_GROUPS // num_cams} streams at {num_cams} cameras")
+
+
 @PLUGIN_LAYERS.register_module()
 class DynamicQueryAllocation(nn.Module):
     def __init__(self, with_attn_mask=False, with_project_wh=False, limit_anchor_size=[35, 35, 10],
@@ -98,6 +109,7 @@ class DynamicQueryAllocation(nn.Module):
         cams = proj.shape[1]
         if anchor3d.shape[-1] != 11 or tuple(proj.shape) != (bs, cams, 4, 4):
             raise ValueError("anchor3d must be [bs, N, 11] and projection_mat [bs, cams, 4, 4]")
+        check_stream_groups(bs, cams)
         wh = metas.get("image_wh_host")
         if wh is None:
             wh = tuple(int(v) for v in metas["image_wh"][0, 0].tolist())

@@ -118,8 +118,8 @@ class DeformableFeatureAggregation(BaseModule):
             learn = kps.learnable_fc(instance_feature).contiguous()
             feat_logits = linear_f32(instance_feature + anchor_embed, self.weights_fc.weight, self.weights_fc.bias)
             cam_logits = linear_f32(cam_embed, self.weights_fc.weight)
-        shipped_layout = (self.num_cams == 6 and self.num_levels == 4 and self.num_groups == 8 and self.embed_dims == 256
-                          and kps.fix_scale.shape[0] == 7 and kps.num_learnable_pts == 6)   # what the one-launch kernel is compiled for
+        shipped_layout = (1 <= self.num_cams <= 8 and self.num_levels == 4 and self.num_groups == 8 and self.embed_dims == 256
+                          and kps.fix_scale.shape[0] == 7 and kps.num_learnable_pts == 6)   # what the one-launch kernel is compiled for (one per camera count)
         if routes.R.fused_dfa and routes.R.dense and shipped_layout:
             # key points + projection + weight softmax inside the aggregation launch (csrc/deform_agg_fused.hip), reading the
             # f16 copy of the tokens where the FPN left one (the tokens are f16 numbers: same bits, half the gather bytes)

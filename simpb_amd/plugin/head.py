@@ -16,6 +16,8 @@ from .layers import BaseModule, fused_graph_attention
 
 __all__ = ["SimPBHead"]
 
+MAX_CAMS = 8   # cameras of one stream (kMaxStaticCams / kMaxAggCams of csrc/alloc.hip, kMaxRigCams of csrc/deform_agg_fused.hip)
+
 
 @HEADS.register_module()
 class SimPBHead(BaseModule):
@@ -95,6 +97,14 @@ class SimPBHead(BaseModule):
             "refine3d": [refine_layer3d, PLUGIN_LAYERS],
         }
         self.layers = nn.ModuleList([build(*self.op_config_map.get(op, [None, None])) for op in self.operation_order])
+        # the rig, checked once: the allocation / 2D->3D aggregation kernels keep a camera's slots in register arrays of eight
+        # (csrc/alloc.hip) and the one-launch 3D aggregation is compiled per camera count up to eight
+        if not 1 <= int(num_cams) <= MAX_CAMS:
+            raise ValueError(f"SimPBHead: num_cams={num_cams} is outside 1..{MAX_CAMS}")
+        for op, layer in zip(self.operation_order, self.layers):
+            if op in ("deformable", "qg_cross_attn") and layer is not None and layer.num_cams != num_cams:
+                setting = "deformable_model" if op == "deformable" else "qg_cross_attn"
+                raise ValueError(f"SimPBHead: {setting}.num_cams={layer.num_cams} disagrees with the head's num_cams={num_cams}")
         self.fc_before = nn.Linear(self.embed_dims, self.embed_dims * 2, bias=False)
         self.fc_after = nn.Linear(self.embed_dims * 2, self.embed_dims, bias=False)
         if self.decouple_attn2d and self.enable2d:

@@ -136,7 +136,7 @@ def dfa_fused(feat, spatial_shape, scale_start_index, anchor, learn, fix_scale, 
     out = torch.empty(bs, a, c, device=feat.device, dtype=torch.float32)
     loc = torch.empty(bs, a, p, cams, 2, device=feat.device) if want_operands else None
     w = torch.empty(bs, a, p, cams, lvls, num_groups, device=feat.device) if want_operands else None
-    status = _lib.lib().simpb_dfa_fused_forward_cams(
+    status = _lib.lib().simpb_dfa_fused_forward_rig(   # (1..8 cameras; six launch what simpb_dfa_fused_forward_cams launches)
         _ptr(out), _ptr(feat), 1 if feat.dtype == torch.float16 else 0, _ptr(spatial_shape), _ptr(scale_start_index),
         _ptr(anchor), _ptr(learn), _ptr(fix_scale), _ptr(proj), _ptr(image_wh), _ptr(feat_logits), _ptr(cam_logits),
         _ptr(loc) if loc is not None else None, _ptr(w) if w is not None else None, bs, cams, num_feat, c, lvls, a, num_fix,
@@ -192,7 +192,8 @@ def feature_maps_format(feature_maps, inverse=False):
     bs, num_cams = feature_maps[0].shape[:2]
     shapes = tuple(tuple(f.shape[-2:]) for f in feature_maps)
     col = torch.cat([f.reshape(bs, num_cams, f.shape[2], -1) for f in feature_maps], dim=-1)
-    col = col.permute(0, 1, 3, 2).flatten(1, 2)
+    # (one camera: flatten over a dimension of size 1 is a view of the permuted tensor, not the row-major buffer the kernels read)
+    col = col.permute(0, 1, 3, 2).flatten(1, 2).contiguous()
     spatial_shape, scale_start_index = _shape_tables(shapes, num_cams, col.device)
     return [col, spatial_shape, scale_start_index]
 

@@ -413,6 +413,9 @@ class FrameRunner:
         self.head = model.head
         self.bs = batch_size
         self.independent = bool(independent_streams) and batch_size > 1
+        if self.independent:   # (before anything is allocated: the allocation launch would refuse the first frame)
+            from .plugin.allocation import check_stream_groups
+            check_stream_groups(batch_size, self.head.num_cams)
         self.head.independent_streams = self.independent
         self.capacity = int(capacity)
         self.use_graph = use_graph

@@ -26,15 +26,28 @@ def randn(key, shape, seed=0):
     return _rng(key, seed).standard_normal(tuple(shape)).astype(np.float32)
 
 
-def camera_rig(image_wh=(704, 256), height=1.5, forward_offset=0.5):
-    """projection_mat f32[6,4,4] = K.E for the ring described in SURVEY.md §8(d).
+def ring(num_cams=6):
+    """(yaw in degrees, focal length in pixels of a 704-wide image) per camera. Six cameras: the nuScenes-like ring above.
+    Any other count: an even ring, yaw_i = -360 * i / N, every camera with a horizontal field of view of
+    min(120, 1.25 * 360 / N) degrees, so that neighbours overlap by a quarter and an object near a border is seen twice."""
+    if num_cams == 6:
+        return CAM_YAW_DEG, CAM_FOCAL
+    if num_cams < 1:
+        raise ValueError(f"a rig has at least one camera, got {num_cams}")
+    fov = min(120.0, 1.25 * 360.0 / num_cams)
+    focal = 352.0 / math.tan(math.radians(fov) / 2.0)
+    return tuple(-360.0 * i / num_cams for i in range(num_cams)), (focal,) * num_cams
+
+
+def camera_rig(image_wh=(704, 256), height=1.5, forward_offset=0.5, num_cams=6):
+    """projection_mat f32[num_cams,4,4] = K.E for the ring described in SURVEY.md §8(d) (`ring`).
 
     Ego frame: x forward, y left, z up. Camera frame: x right, y down, z forward.
     """
     w, h = image_wh
     sx = w / 704.0
     mats = []
-    for yaw_deg, focal in zip(CAM_YAW_DEG, CAM_FOCAL):
+    for yaw_deg, focal in zip(*ring(num_cams)):
         psi = math.radians(yaw_deg)
         fwd = np.array([math.cos(psi), math.sin(psi), 0.0])
         right = np.array([math.sin(psi), -math.cos(psi), 0.0])
@@ -79,15 +92,15 @@ def ego_pose(t, speed=5.0, yaw_rate=0.05):
     return pose
 
 
-def frame_metas(bs, frame_idx, image_wh=(704, 256), device="cpu", dt=0.5, stream_offset=100.0, jump=None):
+def frame_metas(bs, frame_idx, image_wh=(704, 256), device="cpu", dt=0.5, stream_offset=100.0, jump=None, num_cams=6):
     """metas dict of one frame (keys of the test pipeline, config :349-358): stream b is a
     different time origin so streams are not identical copies. jump=(b, frame, seconds) inserts
     a time gap in stream b from that frame on (exercises the bank's max_time_interval mask)."""
-    proj = torch.from_numpy(camera_rig(image_wh))[None].repeat(bs, 1, 1, 1)
+    proj = torch.from_numpy(camera_rig(image_wh, num_cams=num_cams))[None].repeat(bs, 1, 1, 1)
     if bs > 1:  # small per-stream perturbation of the intrinsics so batch items differ
         for b in range(bs):
             proj[b, :, 0, :] *= 1.0 + 0.01 * b
-    wh = torch.tensor([float(image_wh[0]), float(image_wh[1])]).view(1, 1, 2).repeat(bs, 6, 1)
+    wh = torch.tensor([float(image_wh[0]), float(image_wh[1])]).view(1, 1, 2).repeat(bs, num_cams, 1)
     ts, img_metas = [], []
     for b in range(bs):
         t = stream_offset * b + dt * frame_idx
@@ -125,9 +138,9 @@ def feature_maps_nchw(bs, frame_idx, image_wh=(704, 256), channels=256, num_cams
     return out
 
 
-def images(bs, frame_idx, image_wh=(704, 256), seed=0):
+def images(bs, frame_idx, image_wh=(704, 256), seed=0, num_cams=6):
     w, h = image_wh
-    return torch.from_numpy(randn(f"synth.img.f{frame_idx}", (bs, 6, 3, h, w), seed))
+    return torch.from_numpy(randn(f"synth.img.f{frame_idx}", (bs, num_cams, 3, h, w), seed))
 
 
 def raw_frames(bs, frame_idx, src_hw=(900, 1600), num_cams=6, seed=0):
