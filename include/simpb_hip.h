@@ -525,6 +525,42 @@ int simpb_conv3x3_group_tokens_forms_f16(int num_levels, float* tokens, void* to
                                          const void* const* bias, int num_images, const int* in_h, const int* in_w,
                                          int in_channels, int out_channels, int relu, const int* variant, void* stream);
 
+/* ---- The backbone convolutions over the LIVE images of a batch only --------------------------------------------------------
+ * A live-image table is a device array `live`, i32 [1 + num_images]: live[0] = L, the number of live images, and live[1 .. L]
+ * their indices in strictly ascending order; what lies behind entry L is not read. The host builds it (runner.live_images).
+ * Each entry point below is the one it is named after with one trailing argument, `const int* live`:
+ *   live == NULL  the launch of the entry point without the suffix, the same kernels, unchanged (those entry points ARE
+ *                 calls of these with NULL).
+ *   live != NULL  the convolution of the live images alone, by kernels of their own that walk L * out_h * out_w virtual
+ *                 pixels (csrc/conv_parts.h has the mapping): tiled and dealt over the XCDs as the full batch is, so the work
+ *                 that remains fills the whole chip. The grid is sized for the full batch and the tile counts are made from
+ *                 L in the kernel; a workgroup past the live total returns before its first load.
+ * The contract:
+ *   - The rows of a live image -- in y, tokens or tokens_f16 -- are BIT FOR BIT what the entry point without the suffix
+ *     writes for that image on the full batch under the same `variant`: every form adds an output pixel's products in a
+ *     fixed order that does not depend on which tile holds the pixel. variant 0 is still resolved from the FULL-batch shape
+ *     (num_images), on the host.
+ *   - No byte of a dead image's output rows is written, and none of its input, residual or source rows is read: they hold
+ *     afterwards what they held before, and may hold anything (NaN, stale frames) beforehand.
+ *   - L is clamped to 0 .. num_images and every index to 0 .. num_images - 1 inside the kernels: a wrong table gives wrong
+ *     pixels, never an access outside the arrays (the rule of the ingest tables above).
+ *   - L = 0 launches and writes nothing.
+ *   - SIMPB_EINVAL exactly where the entry point without the suffix returns it; `live` itself is not validated on the host
+ *     (it is a device pointer), 4-byte alignment is the caller's. */
+int simpb_stem_conv7x7_pool_f16_live(void* out, const void* img_nhwc4, const void* weight_packed, const void* bias,
+                                     int num_images, int height, int width, int out_channels, void* stream, const int* live);
+int simpb_conv1x1_nhwc_f16_live(void* y, const void* x, const void* weight, const void* bias, const void* residual,
+                                int num_images, int in_h, int in_w, int in_channels, int out_channels, int stride, int relu,
+                                int residual_upsample2x, const void* input_bias, int variant, void* stream, const int* live);
+int simpb_conv3x3_nhwc_f16_live(void* y, float* tokens, void* tokens_f16, int tokens_per_cam, int level_start, const void* x,
+                                const void* weight, const void* bias, int num_images, int in_h, int in_w, int in_channels,
+                                int out_channels, int stride, int relu, int variant, void* stream, const int* live);
+int simpb_conv3x3_group_tokens_forms_f16_live(int num_levels, float* tokens, void* tokens_f16, int tokens_per_cam,
+                                              const int* level_start, const void* const* x, const void* const* weight,
+                                              const void* const* bias, int num_images, const int* in_h, const int* in_w,
+                                              int in_channels, int out_channels, int relu, const int* variant, void* stream,
+                                              const int* live);
+
 /* Attention core of torch.nn.MultiheadAttention (between in_proj and out_proj), exact fp32, flash
  * style, head_dim = 64: out[b,q,h*64+d] = sum_k softmax_k(scale * Q[b,q,h,:].K[b,k,h,:]) V[b,k,h,d].
  * q/k/v/out are [batch, N, heads*64] with row strides ldq/ldk/ldv/ldo (floats; batches are N*ld apart),

@@ -55,6 +55,11 @@ SIGNATURES = {
     "simpb_conv3x3_group_choose_resident": ([_I, _I, _P, _P, _I, _I], _I),
     "simpb_conv3x3_group_tokens_forms_f16": ([_I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P], _I),
     "simpb_stem_conv7x7_pool_f16": ([_P] * 4 + [_I] * 4 + [_P], _I),
+    # the same four with a trailing live-image table (NULL: the entry point without the suffix)
+    "simpb_stem_conv7x7_pool_f16_live": ([_P] * 4 + [_I] * 4 + [_P, _P], _I),
+    "simpb_conv1x1_nhwc_f16_live": ([_P] * 5 + [_I] * 8 + [_P, _I, _P, _P], _I),
+    "simpb_conv3x3_nhwc_f16_live": ([_P, _P, _P, _I, _I, _P, _P, _P] + [_I] * 8 + [_P, _P], _I),
+    "simpb_conv3x3_group_tokens_forms_f16_live": ([_I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P], _I),
     "simpb_image_to_nhwc4_f16": ([_P, _P] + [ctypes.c_longlong] * 4 + [_I] * 4 + [_P], _I),
     "simpb_preprocess_u8_nhwc4_f16": ([_P] * 10 + [_I] * 11 + [_P], _I),
     "simpb_preprocess_yuv420sp_nhwc4_f16": ([_P] * 10 + [_I] * 18 + [_P], _I),

@@ -24,7 +24,8 @@
 // csrc/conv3x3.hip: the same convolution through its staged pipeline (TAPS = 1)
 extern "C" int simpb_conv_pointwise_staged(void* y, const void* x, const void* weight, const void* bias, const void* residual,
                                            int p_out, int in_h, int in_w, int ho, int wo, int in_channels, int out_channels,
-                                           int stride, int relu, int residual_upsample2x, int tiling, void* stream);
+                                           int stride, int relu, int residual_upsample2x, int tiling, void* stream,
+                                           const int* live);
 
 namespace {
 
@@ -32,11 +33,29 @@ using namespace simpb::conv;   // vector types, BN / BK / LDH / LDC / kThreads, 
 
 constexpr int BM = 128;
 
+// Lt: nothing (the launch as ever, the kernel as ever) or the LiveTable of a live launch (conv_parts.h): the grid is the full
+// batch's, the tile's rows are virtual pixels of the `walked` live ones, a workgroup whose 128 rows lie past them leaves before
+// its first load, and `real` turns a row into the pixel that is read and written (looked up once, in front of every store)
+template <class... Lt>
 __global__ __launch_bounds__(kThreads) void conv1x1_f16_kernel(_Float16* __restrict__ y, const _Float16* __restrict__ x,
                                                                const _Float16* __restrict__ w, const _Float16* __restrict__ bias,
                                                                const _Float16* __restrict__ residual, int P_out, int Cin,
                                                                int Cout, int relu, int stride, int Ho, int Wo, int H, int W,
-                                                               int res_up, const _Float16* __restrict__ in_bias) {
+                                                               int res_up, const _Float16* __restrict__ in_bias, const Lt... live) {
+  constexpr bool LIVE = sizeof...(Lt) != 0;
+  const LiveTable lt = table_of(live...);
+  const int walked = LIVE ? live_count(lt) * Ho * Wo : P_out;
+  const int* real_row = nullptr;
+  if constexpr (LIVE) {
+    if ((int)blockIdx.x * BM >= walked) return;
+    __shared__ int s_rows[BM];
+    live_tile_rows<BM>(s_rows, lt, blockIdx.x * BM, walked, Ho * Wo, P_out);
+    real_row = s_rows;
+  }
+  auto real = [&](int p) __attribute__((always_inline)) {   // (at the head of the kernel, where its own row is not in LDS yet)
+    if constexpr (LIVE) return live_pixel(lt, p, Ho * Wo);
+    else return p;
+  };
   // the epilogue tile reuses the staging memory (33 KB per workgroup instead of 61: four workgroups per CU)
   constexpr int kStageBytes = (BM + BN) * LDH * 2, kTileBytes = BM * LDC * 4;
   __shared__ __attribute__((aligned(16))) unsigned char smem[kStageBytes > kTileBytes ? kStageBytes : kTileBytes];
@@ -55,7 +74,7 @@ __global__ __launch_bounds__(kThreads) void conv1x1_f16_kernel(_Float16* __restr
   size_t arow[NA], brow[NB];
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
-    int p = min(p0 + sr + RS * i, P_out - 1);
+    int p = real(min(p0 + sr + RS * i, walked - 1));
     if (stride != 1) {  // output pixel (n, ho, wo) reads input pixel (n, ho * stride, wo * stride)
       const Pixel q = split_pixel(p, Ho, Wo);
       p = (q.n * H + q.ho * stride) * W + q.wo * stride;
@@ -117,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void conv1x1_f16_kernel(_Float16* __restr
   if (residual && cl < Cout) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      int p = min(pw + ((lane + 64 * i) >> 3), P_out - 1);
+      int p = real(min(pw + ((lane + 64 * i) >> 3), walked - 1));
       if (res_up) p = up2_row(p, Ho, Wo);
       rres[i] = *reinterpret_cast<const h16x8*>(residual + (size_t)p * Cout + cl);
     }
@@ -149,16 +168,18 @@ __global__ __launch_bounds__(kThreads) void conv1x1_f16_kernel(_Float16* __restr
   if (cl >= Cout) return;
   const h16x8 bv = *reinterpret_cast<const h16x8*>(bias + cl);
   tile_pieces<2, LDC>(mine, 0, lane, [&](int i, int r, int, const float (&v)[8]) __attribute__((always_inline)) {
-    const int p = pw + r;
+    const int p = LIVE ? real_row[wave * 32 + r] : pw + r;
     if (p < P_out) *reinterpret_cast<h16x8*>(y + (size_t)p * Cout + cl) = finish_piece(v, bv, rres[i], relu);
   });
 }
 
 }  // namespace
 
-extern "C" int simpb_conv1x1_nhwc_f16(void* y, const void* x, const void* weight, const void* bias, const void* residual,
-                                      int num_images, int in_h, int in_w, int in_channels, int out_channels, int stride,
-                                      int relu, int residual_upsample2x, const void* input_bias, int variant, void* stream) {
+// live: NULL (today's launch, the same kernels as ever) or the live-image table of conv_parts.h
+extern "C" int simpb_conv1x1_nhwc_f16_live(void* y, const void* x, const void* weight, const void* bias, const void* residual,
+                                           int num_images, int in_h, int in_w, int in_channels, int out_channels, int stride,
+                                           int relu, int residual_upsample2x, const void* input_bias, int variant, void* stream,
+                                           const int* live) {
   if (variant < 0 || variant > 4 || (input_bias && variant > 1)) return SIMPB_EINVAL;
   if (!y || !x || !weight || !bias || num_images <= 0 || in_h <= 0 || in_w <= 0 || in_channels <= 0 || out_channels <= 0 ||
       (stride != 1 && stride != 2) || in_channels % BK != 0 || out_channels % 8 != 0)  // BK = 64
@@ -187,14 +208,28 @@ extern "C" int simpb_conv1x1_nhwc_f16(void* y, const void* x, const void* weight
   if (variant > 1) {
     if ((long long)num_images * in_h * in_w * in_channels > (1ll << 31) - 1) return SIMPB_EINVAL;
     return simpb_conv_pointwise_staged(y, x, weight, bias, residual, (int)p_out, in_h, in_w, ho, wo, in_channels, out_channels,
-                                       stride, relu, residual_upsample2x, variant - 2, stream);
+                                       stride, relu, residual_upsample2x, variant - 2, stream, live);
   }
   dim3 grid((unsigned)((p_out + BM - 1) / BM), (out_channels + BN - 1) / BN);
   if (grid.y > 65535) return SIMPB_EINVAL;
-  hipLaunchKernelGGL(conv1x1_f16_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream),
-                     static_cast<_Float16*>(y), static_cast<const _Float16*>(x), static_cast<const _Float16*>(weight),
-                     static_cast<const _Float16*>(bias), static_cast<const _Float16*>(residual), (int)p_out, in_channels,
-                     out_channels, relu, stride, ho, wo, in_h, in_w, residual_upsample2x ? 1 : 0,
-                     static_cast<const _Float16*>(input_bias));
+  if (!live)
+    hipLaunchKernelGGL(conv1x1_f16_kernel<>, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       static_cast<_Float16*>(y), static_cast<const _Float16*>(x), static_cast<const _Float16*>(weight),
+                       static_cast<const _Float16*>(bias), static_cast<const _Float16*>(residual), (int)p_out, in_channels,
+                       out_channels, relu, stride, ho, wo, in_h, in_w, residual_upsample2x ? 1 : 0,
+                       static_cast<const _Float16*>(input_bias));
+  else
+    hipLaunchKernelGGL(conv1x1_f16_kernel<LiveTable>, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       static_cast<_Float16*>(y), static_cast<const _Float16*>(x), static_cast<const _Float16*>(weight),
+                       static_cast<const _Float16*>(bias), static_cast<const _Float16*>(residual), (int)p_out, in_channels, out_channels,
+                       relu, stride, ho, wo, in_h, in_w, residual_upsample2x ? 1 : 0, static_cast<const _Float16*>(input_bias),
+                       LiveTable{live, num_images});
   return simpb_check_launch();
+}
+
+extern "C" int simpb_conv1x1_nhwc_f16(void* y, const void* x, const void* weight, const void* bias, const void* residual,
+                                      int num_images, int in_h, int in_w, int in_channels, int out_channels, int stride,
+                                      int relu, int residual_upsample2x, const void* input_bias, int variant, void* stream) {
+  return simpb_conv1x1_nhwc_f16_live(y, x, weight, bias, residual, num_images, in_h, in_w, in_channels, out_channels, stride, relu,
+                                     residual_upsample2x, input_bias, variant, stream, nullptr);
 }

@@ -24,6 +24,9 @@
 // (the forms are stated once, as V1 .. V13 below; 1x1 convolutions run conv_staged_kernel with one tap: P0 .. P2.) Forms whose
 // bits agree add the same products in the same order with the same eight k-values in every matrix instruction, so variant 0's
 // choice between them changes no output.
+// Every form has a LIVE sibling for the *_live entry points (a launch over the live images of the batch only: conv_parts.h,
+// "the live-image table"): the same tile code with one more template argument, in kernels of their own, so that the code of
+// the forms above is what it was. A live form gives a live image's pixels the bits of its sibling on the full batch.
 //
 // The direct forms (1-4): the MFMA contraction does not care WHICH eight k-values a lane brings as long as both operands agree,
 // so lane (row r32, half kb) of a wave takes channels [32*kb, 32*kb + 32) of the chunk: its four 16-byte loads are 64 contiguous
@@ -119,13 +122,29 @@ __device__ __forceinline__ void emit_piece(const ConvArgs& a, int c0, int p, int
   }
 }
 
-template <int AF, bool KSPLIT, bool TOK16>
-__global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs a) {
+// The live forms' walk over flat tiles of BMt virtual pixels (conv_parts.h): the tile grid of `a` (gx, per_xcd) becomes that
+// of the live images, which the ordinary walk then deals out; everything else of `a`, P_out included, goes on describing
+// the real arrays. Uniform: one load of L and a few scalar operations.
+template <int BMt>
+__device__ __forceinline__ void live_flat_walk(ConvArgs& a, const LiveTable& lt) {
+  a.gx = (live_count(lt) * a.Ho * a.Wo + BMt - 1) / BMt;
+  a.per_xcd = (a.gx * a.gy + 7) >> 3;
+}
+
+// Lt: nothing (the launch as ever, the kernel as ever) or the LiveTable of a live launch. (The kernels whose tile is a
+// function of its own further below have a second kernel for the live form; here the body is the kernel's, and moving it
+// changes the registers of the ordinary form.)
+template <int AF, bool KSPLIT, bool TOK16, class... Lt>
+__global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(std::conditional_t<sizeof...(Lt) != 0, ConvArgs, const ConvArgs> a,
+                                                                  const Lt... live) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[kSmemBytes];
   _Float16* s_b = reinterpret_cast<_Float16*>(smem);
   float* s_c = reinterpret_cast<float*>(smem);
   constexpr int WROWS = 32 * AF;
   constexpr int BMt = KSPLIT ? WROWS : 4 * WROWS;
+  constexpr bool LIVE = sizeof...(Lt) != 0;
+  const LiveTable lt = table_of(live...);
+  if constexpr (LIVE) live_flat_walk<BMt>(a, lt);
 
   // channel blocks of one pixel block are next to each other in an XCD's range: neighbouring tiles share their activation rows
   const int tile = simpb::xcd_tile(a.per_xcd, a.gx * a.gy);
@@ -141,13 +160,23 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs
   const int per_tap = Cin / BK, nchunks = 9 * per_tap;
   const size_t K = (size_t)9 * Cin;
   const _Float16* __restrict__ wgt = a.w;
+  // LIVE: the tile's rows are virtual pixels of the `walked` live ones; what each is in memory is looked up once, in front of
+  // every store of the kernel, and kept for the epilogue (the barriers of the K loop lie between)
+  const int walked = LIVE ? live_count(lt) * a.Ho * a.Wo : a.P_out;
+  const int* real_row = nullptr;
+  if constexpr (LIVE) {
+    __shared__ int s_rows[BMt];
+    live_tile_rows<BMt>(s_rows, lt, p0, walked, a.Ho * a.Wo, a.P_out);
+    real_row = s_rows;
+  }
 
   // A: this lane's pixel per fragment: centre address (+ its half of the chunk) and the 9-bit in-image mask of its taps
   const _Float16* actr[AF];
   unsigned amask[AF];
 #pragma unroll
   for (int f = 0; f < AF; ++f) {
-    const Pixel q = split_pixel(min(p0 + row0 + 32 * f + r32, a.P_out - 1), a.Ho, a.Wo);
+    Pixel q = split_pixel(min(p0 + row0 + 32 * f + r32, walked - 1), a.Ho, a.Wo);
+    if constexpr (LIVE) q.n = live_image(lt, q.n);
     const int hc = q.ho * a.stride, wc = q.wo * a.stride;
     actr[f] = a.x + ((size_t)(q.n * H + hc) * W + wc) * Cin + 32 * kb;
     unsigned m = 0;
@@ -306,10 +335,10 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs
         for (int w4 = 0; w4 < 4; ++w4) s += s_c[(w4 * 32 + r) * LDC + c8 + e];
         v[e] = s;
       }
-      emit_piece<TOK16>(a, c0, p0 + 32 * f + r, c8, v);
+      emit_piece<TOK16>(a, c0, LIVE ? real_row[32 * f + r] : p0 + 32 * f + r, c8, v);
     } else {
       tile_pieces<2, LDC>(mine, 0, lane, [&](int, int r, int c8, const float (&v)[8]) __attribute__((always_inline)) {
-        emit_piece<TOK16>(a, c0, p0 + row0 + 32 * f + r, c8, v);
+        emit_piece<TOK16>(a, c0, LIVE ? real_row[row0 + 32 * f + r] : p0 + row0 + 32 * f + r, c8, v);
       });
     }
   }
@@ -333,8 +362,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const ConvArgs
 // do, where the pipeline's own map is [16 * j + 8 * kb, + 8). Which eight k-values share a matrix instruction decides how
 // their sum is rounded: with the direct map, KS = 1 adds exactly what conv3x3_f16_kernel<., false> adds and KS = 4 what
 // conv3x3_f16_kernel<., true> adds, in the same order -- the same bits, so replacing one by the other changes no output.
-template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16, int KS = 1, bool DIRECTK = false>
-__device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int tile) {
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16, int KS = 1, bool DIRECTK = false, bool LIVE = false>
+__device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int tile, const LiveTable& lt = {}) {
   constexpr int NT = 64 * WGM * WGN;   // threads of one K group
   constexpr int AF = BMt / WGM / 32, NF = BNt / WGN / 32;
   static_assert(AF * WGM * 32 == BMt && NF * WGN * 32 == BNt && NF <= 2, "tile = waves x 32-row / 32-column fragments");
@@ -358,6 +387,14 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
   const int nsteps = (nchunks + KS - 1) / KS;   // a group's chunk of a step past the last chunk is staged as zeros
   const size_t K = (size_t)TAPS * Cin;
   const _Float16* __restrict__ wgt = a.w;
+  // LIVE: as in conv3x3_f16_kernel, the rows' real pixels are looked up in front of every store and kept for the epilogue
+  const int walked = LIVE ? live_count(lt) * a.Ho * a.Wo : a.P_out;
+  const int* real_row = nullptr;
+  if constexpr (LIVE) {
+    __shared__ int s_rows[BMt];
+    live_tile_rows<BMt>(s_rows, lt, p0, walked, a.Ho * a.Wo, a.P_out);
+    real_row = s_rows;
+  }
 
   // piece i of this thread: index tid + NT * i -> (row, 8-half column) of the A or B part of the stage
   const int sc = (tid & 7) * 8;
@@ -366,7 +403,8 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
   static_assert(NA <= 5, "6 mask bits per staged row in one register");
 #pragma unroll
   for (int i = 0; i < NA; ++i) {
-    const Pixel q = split_pixel(min(p0 + ((tid + NT * i) >> 3), a.P_out - 1), a.Ho, a.Wo);
+    Pixel q = split_pixel(min(p0 + ((tid + NT * i) >> 3), walked - 1), a.Ho, a.Wo);
+    if constexpr (LIVE) q.n = live_image(lt, q.n);
     const int hc = q.ho * a.stride, wc = q.wo * a.stride;
     actr[i] = a.x + ((size_t)(q.n * H + hc) * W + wc) * Cin + sc;
     const unsigned rows = (hc > 0 ? 1u : 0u) | 2u | (hc + 1 < H ? 4u : 0u), cols = (wc > 0 ? 1u : 0u) | 2u | (wc + 1 < W ? 4u : 0u);
@@ -477,7 +515,7 @@ __device__ __forceinline__ void conv_staged_tile(const ConvArgs& a, const int ti
     __syncthreads();
     if (KS > 1 && grp) continue;          // K split: group 0 adds the partial tiles of its wave's place in every group
     tile_pieces<NF, LDW, KS>(mine, WGM * WGN * 32 * LDW, lane, [&](int, int r, int c8, const float (&v)[8]) __attribute__((always_inline)) {
-      emit_piece<TOK16>(a, cw, p0 + (wm * AF + f) * 32 + r, c8, v);
+      emit_piece<TOK16>(a, cw, LIVE ? real_row[(wm * AF + f) * 32 + r] : p0 + (wm * AF + f) * 32 + r, c8, v);
     });
   }
 }
@@ -489,6 +527,15 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 3 ? 3 : 2) void conv_s
   conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16>(a, tile);
 }
 
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
+__global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 3 ? 3 : 2) void conv_staged_live_kernel(const ConvArgs full, const LiveTable lt) {
+  ConvArgs a = full;
+  live_flat_walk<BMt>(a, lt);
+  const int tile = simpb::xcd_tile(a.per_xcd, a.gx * a.gy);
+  if (tile < 0) return;
+  conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16, 1, false, true>(a, tile, lt);
+}
+
 // the small maps with long K (3x3 variants 9-11): KS groups of waves, the direct kernels' k map (their sums, bit for bit)
 template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16, int KS>
 __global__ __launch_bounds__(64 * WGM * WGN * KS, 2) void conv_staged_ksplit_kernel(const ConvArgs a) {
@@ -497,12 +544,60 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS, 2) void conv_staged_ksplit_ker
   conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16, KS, true>(a, tile);
 }
 
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16, int KS>
+__global__ __launch_bounds__(64 * WGM * WGN * KS, 2) void conv_staged_ksplit_live_kernel(const ConvArgs full, const LiveTable lt) {
+  ConvArgs a = full;
+  live_flat_walk<BMt>(a, lt);
+  const int tile = simpb::xcd_tile(a.per_xcd, a.gx * a.gy);
+  if (tile < 0) return;
+  conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16, KS, true, true>(a, tile, lt);
+}
+
 template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
 __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 3 ? 3 : 2) void conv_staged_group_kernel(const ConvGroup g) {
   const int gt = simpb::xcd_tile(g.per_xcd, g.start[g.n]);
   if (gt < 0) return;
   const int j = group_problem(g, gt);
   conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16>(g.a[j], gt - g.start[j]);
+}
+
+// The live group walk: the problems' tile ranges start[j] follow from L, so they are made here; `a` becomes this workgroup's
+// problem over the live images; -> its tile there or -1. shrink(a): a problem's tile grid (gx) for the live count.
+template <class Shrink>
+__device__ __forceinline__ int live_group_tile(const ConvGroup& g, ConvArgs& a, Shrink&& shrink) {
+  int start[kMaxConvGroup + 1];
+  start[0] = 0;
+#pragma unroll
+  for (int t = 0; t < kMaxConvGroup; ++t) {
+    ConvArgs b = g.a[t];
+    shrink(b);
+    start[t + 1] = start[t] + (t < g.n ? b.gx * b.gy : 0);
+  }
+  const int total = start[kMaxConvGroup];
+  const int gt = simpb::xcd_tile((total + 7) >> 3, total);
+  if (gt < 0) return -1;
+  int j = 0;
+#pragma unroll
+  for (int t = 1; t < kMaxConvGroup; ++t)
+    if (t < g.n && gt >= start[t]) j = t;
+  int first = 0;
+#pragma unroll
+  for (int t = 0; t < kMaxConvGroup; ++t)
+    if (t == j) {
+      a = g.a[t];
+      first = start[t];
+    }
+  shrink(a);
+  return gt - first;
+}
+
+template <int BMt, int BNt, int WGM, int WGN, int TAPS, bool TOK16>
+__global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 3 ? 3 : 2) void conv_staged_group_live_kernel(const ConvGroup g, const LiveTable lt) {
+  const int L = live_count(lt);
+  ConvArgs a;
+  const int tile = live_group_tile(g, a, [&](ConvArgs& b) { b.gx = (L * b.Ho * b.Wo + BMt - 1) / BMt; });
+  if (tile < 0) return;
+  conv_staged_tile<BMt, BNt, WGM, WGN, TAPS, TOK16, 1, false, true>(a, tile, lt);
 }
 
 // ---- stride 1: the input tile stays in LDS (3x3 variants 12, 13) --------------------------------------------------------------
@@ -537,8 +632,8 @@ constexpr size_t resident_lds() {
   return run > tile ? run : tile;
 }
 
-template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
-__device__ __forceinline__ void conv_resident_tile(const ConvArgs& a, const int tile, unsigned char* smem) {
+template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16, bool LIVE = false>
+__device__ __forceinline__ void conv_resident_tile(const ConvArgs& a, const int tile, unsigned char* smem, const LiveTable& lt = {}) {
   constexpr int NT = 64 * WGM * WGN;
   constexpr int AF = TH * RTW / WGM / 32, NF = BNt / WGN / 32;
   static_assert(AF * WGM * 32 == TH * RTW && NF * WGN * 32 == BNt && NF <= 2, "tile = waves x 32-row / 32-column fragments");
@@ -559,7 +654,8 @@ __device__ __forceinline__ void conv_resident_tile(const ConvArgs& a, const int 
 
   const int tx = tile / a.gy, ty = tile - tx * a.gy;
   const int per_img = a.tiles_w * a.tiles_h;
-  const int img = tx / per_img, t2 = tx - img * per_img;
+  const int vimg = tx / per_img, t2 = tx - vimg * per_img;
+  const int img = LIVE ? live_image(lt, vimg) : vimg;   // a 2-D tile lies in ONE image: the real one, looked up once
   const int trow = t2 / a.tiles_w;
   const int y0 = trow * TH, x0 = (t2 - trow * a.tiles_w) * RTW;
   const int tid = threadIdx.x;
@@ -724,6 +820,12 @@ __device__ __forceinline__ void conv_resident_tile(const ConvArgs& a, const int 
   }
 }
 
+// the live forms' walk over the resident 2-D tiles: as live_flat_walk
+__device__ __forceinline__ void live_resident_walk(ConvArgs& a, int L) {
+  a.gx = L * a.tiles_w * a.tiles_h;
+  a.per_xcd = (a.gx * a.gy + 7) >> 3;
+}
+
 template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
 __global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char resident_smem[];
@@ -735,6 +837,16 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_kernel(const Con
 }
 
 template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
+__global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_live_kernel(const ConvArgs full, const LiveTable lt) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char resident_smem[];
+  ConvArgs a = full;
+  live_resident_walk(a, live_count(lt));
+  const int tile = simpb::xcd_tile(a.per_xcd, a.gx * a.gy);
+  if (tile < 0) return;
+  conv_resident_tile<CIN, TH, BNt, WGM, WGN, RING, TOK16, true>(a, tile, resident_smem, lt);
+}
+
+template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
 __global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_group_kernel(const ConvGroup g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char resident_smem[];
   const int gt = simpb::xcd_tile(g.per_xcd, g.start[g.n]);
@@ -743,9 +855,20 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_group_kernel(con
   conv_resident_tile<CIN, TH, BNt, WGM, WGN, RING, TOK16>(g.a[j], gt - g.start[j], resident_smem);
 }
 
+template <int CIN, int TH, int BNt, int WGM, int WGN, int RING, bool TOK16>
+__global__ __launch_bounds__(64 * WGM * WGN) void conv_resident_group_live_kernel(const ConvGroup g, const LiveTable lt) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char resident_smem[];
+  const int L = live_count(lt);
+  ConvArgs a;
+  const int tile = live_group_tile(g, a, [&](ConvArgs& b) { live_resident_walk(b, L); });
+  if (tile < 0) return;
+  conv_resident_tile<CIN, TH, BNt, WGM, WGN, RING, TOK16, true>(a, tile, resident_smem, lt);
+}
+
 // ---- host: the forms, each stated once ------------------------------------------------------------------------------------------
 // A form knows its tile count on a shape (what the choose_* rules ask), its grid (what the kernel walks), its threads and its
-// kernels; the entry points below take all of them from V1 .. V13 / P0 .. P2 and restate none.
+// kernels; the entry points below take all of them from V1 .. V13 / P0 .. P2 and restate none. A launch with a live-image
+// table (lt.live set) runs the form's live kernel on the SAME grid: the full batch's, of which the kernel uses what L needs.
 inline long long ceil_div(long long a, int b) { return (a + b - 1) / b; }
 
 // workgroups of the XCD walk over the gx x gy tiles of `a`
@@ -767,10 +890,11 @@ struct FlatTile {
 template <int AF, bool KSPLIT>
 struct Direct : FlatTile<(KSPLIT ? 32 : 128) * AF, BN> {
   template <int TAPS, bool TOK16>
-  static void launch(ConvArgs& a, hipStream_t stream) {
+  static void launch(ConvArgs& a, const LiveTable& lt, hipStream_t stream) {
     static_assert(TAPS == 9, "the direct forms are 3x3 only");
     Direct::grid(a);
-    hipLaunchKernelGGL((conv3x3_f16_kernel<AF, KSPLIT, TOK16>), dim3(xcd_blocks(a)), dim3(kThreads), 0, stream, a);
+    if (!lt.live) hipLaunchKernelGGL((conv3x3_f16_kernel<AF, KSPLIT, TOK16>), dim3(xcd_blocks(a)), dim3(kThreads), 0, stream, a);
+    else hipLaunchKernelGGL((conv3x3_f16_kernel<AF, KSPLIT, TOK16, LiveTable>), dim3(xcd_blocks(a)), dim3(kThreads), 0, stream, a, lt);
   }
 };
 
@@ -779,27 +903,34 @@ template <int BMt, int BNt, int WGM, int WGN, int KS = 0>
 struct Staged : FlatTile<BMt, BNt> {
   static constexpr int threads = 64 * WGM * WGN * (KS ? KS : 1);
   template <int TAPS, bool TOK16>
-  static void launch(ConvArgs& a, hipStream_t stream) {
+  static void launch(ConvArgs& a, const LiveTable& lt, hipStream_t stream) {
     Staged::grid(a);
     const dim3 blocks(xcd_blocks(a));
-    if constexpr (KS == 0) hipLaunchKernelGGL((conv_staged_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16>), blocks, dim3(threads), 0, stream, a);
-    else hipLaunchKernelGGL((conv_staged_ksplit_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16, KS>), blocks, dim3(threads), 0, stream, a);
+    if constexpr (KS == 0) {
+      if (!lt.live) hipLaunchKernelGGL((conv_staged_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16>), blocks, dim3(threads), 0, stream, a);
+      else hipLaunchKernelGGL((conv_staged_live_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16>), blocks, dim3(threads), 0, stream, a, lt);
+    } else {
+      if (!lt.live) hipLaunchKernelGGL((conv_staged_ksplit_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16, KS>), blocks, dim3(threads), 0, stream, a);
+      else hipLaunchKernelGGL((conv_staged_ksplit_live_kernel<BMt, BNt, WGM, WGN, TAPS, TOK16, KS>), blocks, dim3(threads), 0, stream, a, lt);
+    }
   }
   template <bool TOK16>
-  static void launch_group(const ConvGroup& g, hipStream_t stream) {
-    hipLaunchKernelGGL((conv_staged_group_kernel<BMt, BNt, WGM, WGN, 9, TOK16>), dim3((unsigned)(g.per_xcd * 8)), dim3(threads), 0, stream, g);
+  static void launch_group(const ConvGroup& g, const LiveTable& lt, hipStream_t stream) {
+    const dim3 blocks((unsigned)(g.per_xcd * 8));
+    if (!lt.live) hipLaunchKernelGGL((conv_staged_group_kernel<BMt, BNt, WGM, WGN, 9, TOK16>), blocks, dim3(threads), 0, stream, g);
+    else hipLaunchKernelGGL((conv_staged_group_live_kernel<BMt, BNt, WGM, WGN, 9, TOK16>), blocks, dim3(threads), 0, stream, g, lt);
   }
 };
 
 inline bool resident_shape(int cin, int stride) { return stride == 1 && (cin == 64 || cin == 128 || cin == 256); }
 
 // a kernel is allowed its dynamic LDS (more than 64 KB where Cin = 256) once
-template <auto kernel, class Arg>
-void launch_with_lds(size_t lds, unsigned blocks, int threads, const Arg& arg, hipStream_t stream) {
+template <auto kernel, class... Args>
+void launch_with_lds(size_t lds, unsigned blocks, int threads, hipStream_t stream, const Args&... args) {
   static const bool allowed =
       hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
   (void)allowed;
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, stream, arg);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, stream, args...);
 }
 
 // whole 2-D tiles of TH x RTW output pixels per image x BNt output channels, channel blocks of one tile next to each other
@@ -818,28 +949,31 @@ struct Resident {
   // Cin is a template argument of the kernels (64, 128 or 256: resident_shape): the one place that makes it one, for the
   // launch of one problem (Arg = ConvArgs) and of a group (Arg = ConvGroup)
   template <bool TOK16, class Arg>
-  static void launch_cin(int cin, unsigned blocks, const Arg& arg, hipStream_t stream) {
+  static void launch_cin(int cin, unsigned blocks, const Arg& arg, const LiveTable& lt, hipStream_t stream) {
     auto go = [&](auto cin_c) {
       constexpr int CIN = decltype(cin_c)::value;
       constexpr size_t lds = resident_lds<CIN, TH, BNt, WGM, WGN, RING>();
-      if constexpr (std::is_same_v<Arg, ConvGroup>)
-        launch_with_lds<conv_resident_group_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>>(lds, blocks, threads, arg, stream);
-      else
-        launch_with_lds<conv_resident_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>>(lds, blocks, threads, arg, stream);
+      if constexpr (std::is_same_v<Arg, ConvGroup>) {
+        if (!lt.live) launch_with_lds<conv_resident_group_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>>(lds, blocks, threads, stream, arg);
+        else launch_with_lds<conv_resident_group_live_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>>(lds, blocks, threads, stream, arg, lt);
+      } else {
+        if (!lt.live) launch_with_lds<conv_resident_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>>(lds, blocks, threads, stream, arg);
+        else launch_with_lds<conv_resident_live_kernel<CIN, TH, BNt, WGM, WGN, RING, TOK16>>(lds, blocks, threads, stream, arg, lt);
+      }
     };
     if (cin == 64) go(IC<64>{});
     else if (cin == 128) go(IC<128>{});
     else go(IC<256>{});
   }
   template <int TAPS, bool TOK16>
-  static void launch(ConvArgs& a, hipStream_t stream) {
+  static void launch(ConvArgs& a, const LiveTable& lt, hipStream_t stream) {
     static_assert(TAPS == 9, "the resident form is 3x3 only");
     grid(a);
-    launch_cin<TOK16>(a.Cin, xcd_blocks(a), a, stream);
+    launch_cin<TOK16>(a.Cin, xcd_blocks(a), a, lt, stream);
   }
   template <bool TOK16>
-  static void launch_group(const ConvGroup& g, hipStream_t stream) {
-    launch_cin<TOK16>(g.a[0].Cin, (unsigned)(g.per_xcd * 8), g, stream);
+  static void launch_group(const ConvGroup& g, const LiveTable& lt, hipStream_t stream) {
+    launch_cin<TOK16>(g.a[0].Cin, (unsigned)(g.per_xcd * 8), g, lt, stream);
   }
 };
 
@@ -863,7 +997,7 @@ using P1 = V6;                               // 128 x 128
 using P2 = Staged<64, 64, 2, 2>;             // 64 x 64 (four waves, 32 x 32 each): the sums of P0 bit for bit
 
 // 3x3 variant v is kVariant[v - 1] (TOK16: the kernels that write the f16 token rows alone)
-using Launch = void (*)(ConvArgs&, hipStream_t);
+using Launch = void (*)(ConvArgs&, const LiveTable&, hipStream_t);
 template <bool TOK16>
 constexpr Launch kVariant[13] = {V1::launch<9, TOK16>,  V2::launch<9, TOK16>,  V3::launch<9, TOK16>, V4::launch<9, TOK16>, V5::launch<9, TOK16>,
                                  V6::launch<9, TOK16>,  V7::launch<9, TOK16>,  V8::launch<9, TOK16>, V9::launch<9, TOK16>, V10::launch<9, TOK16>,
@@ -939,9 +1073,11 @@ extern "C" int simpb_conv3x3_group_choose_resident(int num_levels, int num_image
   return tiles >= 1024 ? 13 : 0;
 }
 
-extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, int tokens_per_cam, int level_start,
-                                      const void* x, const void* weight, const void* bias, int num_images, int in_h, int in_w,
-                                      int in_channels, int out_channels, int stride, int relu, int variant, void* stream) {
+// live: NULL (today's launch, the same kernels as ever) or the live-image table of conv_parts.h
+extern "C" int simpb_conv3x3_nhwc_f16_live(void* y, float* tokens, void* tokens_f16, int tokens_per_cam, int level_start,
+                                           const void* x, const void* weight, const void* bias, int num_images, int in_h, int in_w,
+                                           int in_channels, int out_channels, int stride, int relu, int variant, void* stream,
+                                           const int* live) {
   const bool to_tokens = tokens || tokens_f16;   // tokens == NULL with tokens_f16 set: the f16 rows alone
   if ((!y && !to_tokens) || (y && to_tokens) || (reinterpret_cast<size_t>(tokens_f16) & 15) || !x || !weight || !bias || num_images <= 0 || in_h <= 0 || in_w <= 0 ||
       in_channels <= 0 || out_channels <= 0 || (stride != 1 && stride != 2) || in_channels % BK != 0 || out_channels % 8 != 0 ||
@@ -971,18 +1107,27 @@ extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, 
     }
   }
   const bool tok16_alone = !tokens && tokens_f16;   // the f16 token rows alone: kernels without the fp32 stores
-  (tok16_alone ? kVariant<true> : kVariant<false>)[variant - 1](a, static_cast<hipStream_t>(stream));
+  (tok16_alone ? kVariant<true> : kVariant<false>)[variant - 1](a, LiveTable{live, num_images}, static_cast<hipStream_t>(stream));
   return simpb_check_launch();
+}
+
+extern "C" int simpb_conv3x3_nhwc_f16(void* y, float* tokens, void* tokens_f16, int tokens_per_cam, int level_start,
+                                      const void* x, const void* weight, const void* bias, int num_images, int in_h, int in_w,
+                                      int in_channels, int out_channels, int stride, int relu, int variant, void* stream) {
+  return simpb_conv3x3_nhwc_f16_live(y, tokens, tokens_f16, tokens_per_cam, level_start, x, weight, bias, num_images, in_h, in_w,
+                                     in_channels, out_channels, stride, relu, variant, stream, nullptr);
 }
 
 // The FPN's output convolutions (3x3, stride 1, Cin -> Cout, bias, no ReLU; mmdet FPN `fpn_convs[i].conv` after
 // tools/fuse_conv_bn.py:10-48) of up to four levels in ONE launch, each writing its level's token rows (f32 and, optionally,
 // f16; or, with tokens == NULL, f16 alone) as simpb_conv3x3_nhwc_f16 does with `tokens`: x[j] f16 NHWC [num_images, in_h[j], in_w[j], Cin], weight[j] f16
 // [Cout, 3, 3, Cin], bias[j] f16 [Cout], level_start[j] the level's first row inside a camera's tokens_per_cam rows.
-extern "C" int simpb_conv3x3_group_tokens_forms_f16(int num_levels, float* tokens, void* tokens_f16, int tokens_per_cam,
-                                                    const int* level_start, const void* const* x, const void* const* weight,
-                                                    const void* const* bias, int num_images, const int* in_h, const int* in_w,
-                                                    int in_channels, int out_channels, int relu, const int* variant, void* stream) {
+// live: NULL or the live-image table, as simpb_conv3x3_nhwc_f16_live; the forms are still chosen on the full batch.
+extern "C" int simpb_conv3x3_group_tokens_forms_f16_live(int num_levels, float* tokens, void* tokens_f16, int tokens_per_cam,
+                                                         const int* level_start, const void* const* x, const void* const* weight,
+                                                         const void* const* bias, int num_images, const int* in_h, const int* in_w,
+                                                         int in_channels, int out_channels, int relu, const int* variant,
+                                                         void* stream, const int* live) {
   if (num_levels < 1 || num_levels > kMaxConvGroup || (!tokens && !tokens_f16) || !level_start || !x || !weight || !bias || !in_h || !in_w ||
       num_images <= 0 || in_channels <= 0 || out_channels <= 0 || in_channels % BK != 0 || out_channels % 8 != 0 ||
       ((reinterpret_cast<size_t>(tokens) | reinterpret_cast<size_t>(tokens_f16)) & 15))
@@ -1023,9 +1168,18 @@ extern "C" int simpb_conv3x3_group_tokens_forms_f16(int num_levels, float* token
   (void)hipGetLastError();
   hipStream_t s = static_cast<hipStream_t>(stream);
   // the large levels first: the staged launch is the short one; tokens == NULL: the f16 token rows alone
-  if (form[1].n) (tokens ? V13::launch_group<false> : V13::launch_group<true>)(form[1], s);
-  if (form[0].n) (tokens ? V8::launch_group<false> : V8::launch_group<true>)(form[0], s);
+  const LiveTable lt{live, num_images};
+  if (form[1].n) (tokens ? V13::launch_group<false> : V13::launch_group<true>)(form[1], lt, s);
+  if (form[0].n) (tokens ? V8::launch_group<false> : V8::launch_group<true>)(form[0], lt, s);
   return simpb_check_launch();
+}
+
+extern "C" int simpb_conv3x3_group_tokens_forms_f16(int num_levels, float* tokens, void* tokens_f16, int tokens_per_cam,
+                                                    const int* level_start, const void* const* x, const void* const* weight,
+                                                    const void* const* bias, int num_images, const int* in_h, const int* in_w,
+                                                    int in_channels, int out_channels, int relu, const int* variant, void* stream) {
+  return simpb_conv3x3_group_tokens_forms_f16_live(num_levels, tokens, tokens_f16, tokens_per_cam, level_start, x, weight, bias,
+                                                   num_images, in_h, in_w, in_channels, out_channels, relu, variant, stream, nullptr);
 }
 
 // variant 0 for every level: what the detector runs
@@ -1041,14 +1195,16 @@ extern "C" int simpb_conv3x3_group_tokens_f16(int num_levels, float* tokens, voi
 // P0 .. P2 above.
 extern "C" int simpb_conv_pointwise_staged(void* y, const void* x, const void* weight, const void* bias, const void* residual,
                                            int p_out, int in_h, int in_w, int ho, int wo, int in_channels, int out_channels,
-                                           int stride, int relu, int residual_upsample2x, int tiling, void* stream) {
+                                           int stride, int relu, int residual_upsample2x, int tiling, void* stream,
+                                           const int* live) {
   ConvArgs a = conv_args(x, weight, bias, p_out, in_channels, out_channels, relu, stride, ho, wo, in_h, in_w);
   a.y = static_cast<_Float16*>(y);
   a.residual = static_cast<const _Float16*>(residual);
   a.res_up = residual_upsample2x ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (tiling == 0) P0::launch<1, false>(a, s);
-  else if (tiling == 1) P1::launch<1, false>(a, s);
-  else P2::launch<1, false>(a, s);
+  const LiveTable lt{live, p_out / (ho * wo)};
+  if (tiling == 0) P0::launch<1, false>(a, lt, s);
+  else if (tiling == 1) P1::launch<1, false>(a, lt, s);
+  else P2::launch<1, false>(a, lt, s);
   return simpb_check_launch();
 }

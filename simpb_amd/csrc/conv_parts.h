@@ -36,6 +36,41 @@ __device__ __forceinline__ int up2_row(int p, int Ho, int Wo) {
   return (q.n * (Ho >> 1) + (q.ho >> 1)) * (Wo >> 1) + (q.wo >> 1);
 }
 
+// ---- the live-image table (the *_live entry points of include/simpb_hip.h) ------------------------------------------------------
+// live: i32 [1 + images] on the device. live[0] = L, the number of live images; live[1 .. L] their indices, ascending; what
+// lies behind is not read. A live form walks VIRTUAL pixels: its launch covers L * Ho * Wo of them (the resident forms
+// L * tiles_h * tiles_w 2-D tiles, the stem L grid planes), tiled and dealt over the XCDs exactly as the full batch is, with
+// the tile count and per_xcd recomputed from L in the kernel -- the host sizes the grid for the full batch and the workgroups
+// past the live total, the high blockIdx.x >> 3 of every XCD, return before their first load. Virtual image v is real image
+// live[1 + v] wherever an address is formed -- x, residual (the nearest-2x read included), y, the token row -- and nowhere
+// else: which tile holds a pixel changes nothing of its sum, so a live image's rows are the full batch's bit for bit, and
+// nothing of a dead image is read or written. L and every index are clamped: a wrong table gives wrong pixels, never an
+// access outside the arrays.
+struct LiveTable {
+  const int* live;
+  int images;
+};
+__device__ __forceinline__ int live_count(const LiveTable& t) { return min(max(t.live[0], 0), t.images); }
+__device__ __forceinline__ int live_image(const LiveTable& t, int v) {
+  return min(max(t.live[1 + min(max(v, 0), t.images - 1)], 0), t.images - 1);
+}
+// what a kernel with an optional trailing LiveTable (a parameter pack of none or one) was given
+__device__ __forceinline__ LiveTable table_of() { return {nullptr, 0}; }
+__device__ __forceinline__ LiveTable table_of(const LiveTable& t) { return t; }
+// virtual output pixel p of a map of hw pixels per image -> the real one
+__device__ __forceinline__ int live_pixel(const LiveTable& t, int p, int hw) {
+  const int v = p / hw;
+  return live_image(t, v) * hw + (p - v * hw);
+}
+// A flat tile of BMt virtual pixels from p0 on (BMt <= the workgroup's threads): rows[i] = the real pixel of row i, or `none`
+// where the row lies past the `walked` live pixels. Filled at the head of a kernel, read in its epilogue behind a barrier:
+// the table is read from memory in front of the kernel's first store only, so no store is ever in flight beside these loads.
+template <int BMt>
+__device__ __forceinline__ void live_tile_rows(int* rows, const LiveTable& t, int p0, int walked, int hw, int none) {
+  const int i = threadIdx.x;
+  if (i < BMt) rows[i] = p0 + i < walked ? live_pixel(t, p0 + i, hw) : none;
+}
+
 // The epilogue element, eight channels of one output pixel: sum + bias + residual in fp32, ReLU, ONE rounding to fp16.
 // A launch without a residual passes zeros: a sum of accumulators that start at +0 is never -0, nor is that sum plus the
 // bias, so the added 0.f changes no bit.

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
 #include "store_fence.h"
+#include "conv_parts.h"
 
 #include "launch.h"
 
@@ -51,9 +52,12 @@ __global__ void image_to_nhwc4_kernel(h4* __restrict__ out, const float* __restr
   out[i] = v;
 }
 
+// Lt: nothing (the launch as ever, the kernel as ever) or the LiveTable of a live launch (conv_parts.h): blockIdx.z is then
+// the virtual image, and the planes past L leave at once
+template <class... Lt>
 __global__ __launch_bounds__(kThreads, 2) void stem_conv_pool_kernel(_Float16* __restrict__ out, const h4* __restrict__ img,
                                                                   const h4* __restrict__ wpack, const _Float16* __restrict__ bias,
-                                                                  int H, int W, int Ho, int Wo, int Hp, int Wp) {
+                                                                  int H, int W, int Ho, int Wo, int Hp, int Wp, const Lt... live) {
   // LDS: [input tile 41 x 74 x 8 B = 24 272 B | weights 28 x 2 x 64 x 8 B = 28 672 B], later reused for the conv tile, 32
   // channels at a time (612 x 40 halfs = 48 960 B): 53 KB per workgroup, three workgroups per CU
   constexpr int kInBytes = kIn_H * kIn_W * 8, kWBytes = kSteps * 2 * kCout * 8, kConvBytes = kConvPix * kConvLd * 2;
@@ -64,7 +68,12 @@ __global__ __launch_bounds__(kThreads, 2) void stem_conv_pool_kernel(_Float16* _
   _Float16* s_conv = reinterpret_cast<_Float16*>(smem);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = blockIdx.z;
+  int n = blockIdx.z;
+  if constexpr (sizeof...(Lt) != 0) {
+    const simpb::conv::LiveTable lt = simpb::conv::table_of(live...);
+    if (n >= simpb::conv::live_count(lt)) return;
+    n = simpb::conv::live_image(lt, n);
+  }
   const int py0 = blockIdx.y * kTP_H, px0 = blockIdx.x * kTP_W;
   const int cy0 = 2 * py0 - 1, cx0 = 2 * px0 - 1;      // conv pixel of tile position (0, 0)
   const int iy0 = 2 * cy0 - 3, ix0 = 2 * cx0 - 3;      // input pixel under it
@@ -186,8 +195,10 @@ extern "C" int simpb_image_to_nhwc4_f16(void* out, const float* img, long long s
   return simpb_check_launch();
 }
 
-extern "C" int simpb_stem_conv7x7_pool_f16(void* out, const void* img_nhwc4, const void* weight_packed, const void* bias,
-                                           int num_images, int height, int width, int out_channels, void* stream) {
+// live: NULL (today's launch, the same kernel as ever) or the live-image table of conv_parts.h
+extern "C" int simpb_stem_conv7x7_pool_f16_live(void* out, const void* img_nhwc4, const void* weight_packed, const void* bias,
+                                                int num_images, int height, int width, int out_channels, void* stream,
+                                                const int* live) {
   if (!out || !img_nhwc4 || !weight_packed || !bias || num_images <= 0 || num_images > 65535 || height < 1 || width < 1 ||
       out_channels != kCout)
     return SIMPB_EINVAL;
@@ -199,8 +210,18 @@ extern "C" int simpb_stem_conv7x7_pool_f16(void* out, const void* img_nhwc4, con
   if ((long long)num_images * height * width > (1ll << 31) - 1) return SIMPB_EINVAL;
   (void)hipGetLastError();
   dim3 grid((wp + kTP_W - 1) / kTP_W, (hp + kTP_H - 1) / kTP_H, num_images);
-  hipLaunchKernelGGL(stem_conv_pool_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream),
-                     static_cast<_Float16*>(out), static_cast<const h4*>(img_nhwc4), static_cast<const h4*>(weight_packed),
-                     static_cast<const _Float16*>(bias), height, width, ho, wo, hp, wp);
+  if (!live)
+    hipLaunchKernelGGL(stem_conv_pool_kernel<>, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       static_cast<_Float16*>(out), static_cast<const h4*>(img_nhwc4), static_cast<const h4*>(weight_packed),
+                       static_cast<const _Float16*>(bias), height, width, ho, wo, hp, wp);
+  else
+    hipLaunchKernelGGL(stem_conv_pool_kernel<simpb::conv::LiveTable>, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       static_cast<_Float16*>(out), static_cast<const h4*>(img_nhwc4), static_cast<const h4*>(weight_packed),
+                       static_cast<const _Float16*>(bias), height, width, ho, wo, hp, wp, simpb::conv::LiveTable{live, num_images});
   return simpb_check_launch();
+}
+
+extern "C" int simpb_stem_conv7x7_pool_f16(void* out, const void* img_nhwc4, const void* weight_packed, const void* bias,
+                                           int num_images, int height, int width, int out_channels, void* stream) {
+  return simpb_stem_conv7x7_pool_f16_live(out, img_nhwc4, weight_packed, bias, num_images, height, width, out_channels, stream, nullptr);
 }

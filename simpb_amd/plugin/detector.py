@@ -65,16 +65,18 @@ class Bottleneck(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
 
-    def forward(self, x):
+    def forward(self, x, live=None):
+        """live: None or a live-image table (ops._live_ptr) for the in-tree kernels: the images it leaves out are not
+        computed. A site that falls to a vendor or PyTorch route computes every image, as ever."""
         if getattr(self, "fused_epilogue", False) and x.is_cuda and x.dtype == torch.float16:
-            return self._forward_fused(x)
+            return self._forward_fused(x, live)
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
         return self.relu(out + identity)
 
-    def _forward_fused(self, x):
+    def _forward_fused(self, x, live=None):
         """BN already folded (SimPB.fuse_conv_bn): convolutions run without bias and each is followed
         by ONE epilogue kernel (bias [+ residual] [+ ReLU]) instead of add_, add and relu_."""
         from .ops import bias_act_, conv1x1_nhwc, conv3x3_nhwc
@@ -90,7 +92,7 @@ class Bottleneck(nn.Module):
             # the 1x1 convolutions with their whole epilogue in one launch (csrc/conv1x1.hip); anything the kernel
             # does not take (odd channel counts, an input that is not channels_last) goes the two-launch way
             if takes(m, t):
-                return conv1x1_nhwc(t, m.weight, m.bias, residual, relu, m.stride[0], input_bias=input_bias)
+                return conv1x1_nhwc(t, m.weight, m.bias, residual, relu, m.stride[0], input_bias=input_bias, live=live)
             assert input_bias is None
             _vendor_fallback("bottleneck 1x1 convolution", routes.R.conv1x1_kernel, f"{m.in_channels}->{m.out_channels}, stride {m.stride}")
             return bias_act_(conv(m, t), m.bias, residual, relu=relu)
@@ -101,7 +103,7 @@ class Bottleneck(nn.Module):
         if (routes.R.conv3x3_kernel and c2.in_channels % 64 == 0 and c2.out_channels % 8 == 0 and c2.stride[0] in (1, 2)
                 and c2.stride[0] == c2.stride[1] and c2.padding == (1, 1) and out.is_contiguous(memory_format=torch.channels_last)):
             # the 3x3 convolution as one implicit-GEMM launch with its bias + ReLU (csrc/conv3x3.hip)
-            out = conv3x3_nhwc(out, c2.weight, c2.bias, relu=True, stride=c2.stride[0])
+            out = conv3x3_nhwc(out, c2.weight, c2.bias, relu=True, stride=c2.stride[0], live=live)
             return pointwise(self.conv3, out, identity, relu=True)
         _vendor_fallback("bottleneck 3x3 convolution", routes.R.conv3x3_kernel, f"{c2.in_channels}->{c2.out_channels}, stride {c2.stride}")
         out = conv(c2, out)
@@ -155,19 +157,20 @@ class ResNet(BaseModule):
     def _stem_kernel_ok(self, x):
         return self._stem_kernel_usable() and x.is_cuda and x.dtype == torch.float32
 
-    def forward(self, x, nhwc4=False):
-        """nhwc4: x is the stem kernel's own operand, f16 [N, H, W, 4] (the camera frame ingest wrote it), not an NCHW image."""
+    def forward(self, x, nhwc4=False, live=None):
+        """nhwc4: x is the stem kernel's own operand, f16 [N, H, W, 4] (the camera frame ingest wrote it), not an NCHW image.
+        live: None or a live-image table (ops._live_ptr), handed to the stem kernel and to every bottleneck."""
         if nhwc4:
             if not (self._stem_kernel_usable() and x.is_cuda and x.dtype == torch.float16):
                 raise RuntimeError("an f16 NHWC4 image (raw camera frame ingest) needs the in-tree stem kernel: routes.stem_kernel on, "
                                    "a BN-folded fp16 backbone (fuse_conv_bn + half_backbone) with the 7x7 / stride 2 stem and the "
                                    "3x3 / stride 2 max-pool; there is no second route for it")
             from .ops import stem_conv_pool_nhwc4
-            x = stem_conv_pool_nhwc4(x, self.conv1.weight, self.conv1.bias)
+            x = stem_conv_pool_nhwc4(x, self.conv1.weight, self.conv1.bias, live)
         elif self._stem_kernel_ok(x):
             # the whole stem -- cast, 7x7 convolution, bias, ReLU, max-pool -- in two launches of our own (csrc/stem.hip)
             from .ops import stem_conv_pool
-            x = stem_conv_pool(x, self.conv1.weight, self.conv1.bias)
+            x = stem_conv_pool(x, self.conv1.weight, self.conv1.bias, live)
         elif getattr(self, "fused_epilogue", False) and x.is_cuda and x.dtype in (torch.float16, torch.float32):
             from .ops import bias_act_, bias_relu_maxpool
             _vendor_fallback("ResNet stem", routes.R.stem_kernel, f"7x7 convolution on {x.dtype} input of shape {tuple(x.shape)}")
@@ -184,7 +187,11 @@ class ResNet(BaseModule):
             x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         outs = []
         for i, name in enumerate(self.res_layers):
-            x = getattr(self, name)(x)
+            if live is None:
+                x = getattr(self, name)(x)
+            else:
+                for blk in getattr(self, name):
+                    x = blk(x, live)
             if i in self.out_indices:
                 outs.append(x)
         return tuple(outs)
@@ -222,7 +229,8 @@ class FPN(BaseModule):
             self.lateral_convs.append(ConvModule(in_channels[i], out_channels, 1))
             self.fpn_convs.append(ConvModule(out_channels, out_channels, 3, padding=1))
 
-    def forward(self, inputs):
+    def forward(self, inputs, live=None):
+        """live: None or a live-image table (ops._live_ptr) for the in-tree lateral and output convolutions."""
         x0 = inputs[self.start_level]
         if (routes.R.conv1x1_kernel and x0.is_cuda and x0.dtype == torch.float16 and self.upsample_cfg.get("mode") == "nearest"
                 and all(t.is_contiguous(memory_format=torch.channels_last) for t in inputs)
@@ -243,7 +251,7 @@ class FPN(BaseModule):
                         up, up2x = laterals[i + 1], True  # nearest 2x read inside the launch: no upsampled map
                     else:
                         up = F.interpolate(laterals[i + 1], size=xin.shape[2:], **self.upsample_cfg)
-                laterals[i] = conv1x1_nhwc(xin, conv.weight, conv.bias, up, relu=False, residual_upsample2x=up2x)
+                laterals[i] = conv1x1_nhwc(xin, conv.weight, conv.bias, up, relu=False, residual_upsample2x=up2x, live=live)
             tokens_for = getattr(self, "tokens_for", None)   # (bs, num_cams) set by SimPB.extract_feat for this call
             self.wrote_tokens = None
             if (routes.R.conv3x3_kernel and tokens_for is not None
@@ -268,11 +276,12 @@ class FPN(BaseModule):
                     # one launch for the four levels: the small levels' tiles fill the last round of the large one
                     from .ops import conv3x3_group_tokens
                     conv3x3_group_tokens(laterals, [m.conv.weight for m in self.fpn_convs], [m.conv.bias for m in self.fpn_convs],
-                                         col, per_cam, starts, col16)
+                                         col, per_cam, starts, col16, live=live)
                 else:
                     for i in range(n):
                         conv = self.fpn_convs[i].conv
-                        conv3x3_nhwc(laterals[i], conv.weight, conv.bias, relu=False, tokens=(col, per_cam, starts[i], col16))
+                        conv3x3_nhwc(laterals[i], conv.weight, conv.bias, relu=False, tokens=(col, per_cam, starts[i], col16),
+                                     live=live)
                 if col is not None:
                     col.simpb_f16 = col16
                 self.deferred_output_bias = False
@@ -357,13 +366,15 @@ class SimPB(BaseModule):
                     blk.fused_epilogue = True
         return self
 
-    def extract_feat(self, img, return_depth=False, metas=None, raw_plan=None):
+    def extract_feat(self, img, return_depth=False, metas=None, raw_plan=None, live=None):
         """simpb.py:64-91. A uint8 `img` is the raw form: camera frames as decoded, in the layout of `raw_plan`
         (simpb_amd.preprocess.ResamplePlan): [bs, cams, Hs, Ws, 3] or [N, Hs, Ws, 3] for a "bgr" plan, [bs, cams, Hs * 3 / 2, Ws] or
         [N, Hs * 3 / 2, Ws] for an "nv12" / "nv21" one, [bs, cams, image_bytes] or [N, image_bytes] for a plan with a padded
         surface layout. They are converted / resized / cropped / flipped / normalised on the device
         straight into the stem's operand; a frame whose shape is not the plan's is refused. An int64 `img` [bs, cams] or [N] on
-        the device is the pointer form of the same: the address of one surface per image (ResamplePlan.run_table)."""
+        the device is the pointer form of the same: the address of one surface per image (ResamplePlan.run_table).
+        live: None or a live-image table (include/simpb_hip.h; contiguous i32 [1 + bs * cams] on the device): the backbone and
+        the neck compute the images it lists and no other; the token rows of the rest hold whatever the memory held."""
         bs = img.shape[0]
         table = img.dtype == torch.int64
         raw = table or img.dtype == torch.uint8
@@ -388,7 +399,8 @@ class SimPB(BaseModule):
             num_cams = 1
         if not raw and self.fp16_enabled and not (img.dtype == torch.float32 and getattr(self.img_backbone, "_stem_kernel_ok", lambda t: False)(img)):
             img = img.half().contiguous(memory_format=torch.channels_last)   # (the stem kernel route casts inside its own launch)
-        feature_maps = self.img_backbone(img, nhwc4=True) if raw else self.img_backbone(img)
+        extra = {} if live is None else dict(live=live)
+        feature_maps = self.img_backbone(img, nhwc4=True, **extra) if raw else self.img_backbone(img, **extra)
         biases = None
         if self.img_neck is not None:
             # fp16 fused path: the four output convolutions of the FPN run without their bias and the bias is added
@@ -398,7 +410,7 @@ class SimPB(BaseModule):
                              and m.conv.out_channels % 8 == 0 for m in self.img_neck.fpn_convs))
             self.img_neck.defer_output_bias = defer
             self.img_neck.tokens_for = (bs, num_cams) if defer and feature_maps[0].shape[0] == bs * num_cams else None
-            feature_maps = list(self.img_neck(feature_maps))
+            feature_maps = list(self.img_neck(feature_maps, **extra))
             if getattr(self.img_neck, "wrote_tokens", None) is not None:
                 tokens, self.img_neck.wrote_tokens = self.img_neck.wrote_tokens, None
                 return tokens

@@ -498,11 +498,23 @@ def bias_relu_maxpool(x, bias):
     return y
 
 
-def conv1x1_nhwc(x, weight, bias, residual=None, relu=True, stride=1, residual_upsample2x=False, input_bias=None, variant=0):
+def _live_ptr(live, n, device):
+    """The `live` argument of the convolutions: None, or a live-image table (include/simpb_hip.h), contiguous i32 [1 + N] on
+    the device. The images it leaves out are neither read nor written: their rows of the result hold what the memory held."""
+    if live is None:
+        return None
+    if live.dtype != torch.int32 or tuple(live.shape) != (1 + n,) or not live.is_contiguous() or live.device != device:
+        raise ValueError(f"live: a contiguous i32 [{1 + n}] tensor on the images' device (runner.live_images)")
+    return _ptr(live)
+
+
+def conv1x1_nhwc(x, weight, bias, residual=None, relu=True, stride=1, residual_upsample2x=False, input_bias=None, variant=0,
+                 live=None):
     """relu?(conv1x1(x, weight, stride) + bias + residual?) for a channels_last f16 tensor, one launch
     (csrc/conv1x1.hip). x [N, Cin, H, W]; weight [Cout, Cin, 1, 1] f16; bias f16 [Cout]. With residual_upsample2x the
     residual is [N, Cout, H/2, W/2] and is read with nearest-neighbour 2x upsampling (the FPN top-down sum). With
-    input_bias (f16 [Cin]) x is first replaced by relu(x + input_bias): the epilogue of the convolution that produced it."""
+    input_bias (f16 [Cin]) x is first replaced by relu(x + input_bias): the epilogue of the convolution that produced it.
+    live: None or a live-image table (_live_ptr): only those images are computed."""
     _require_gpu(x, weight, bias)
     n, cin, h, w = x.shape
     cout = weight.shape[0]
@@ -522,20 +534,22 @@ def conv1x1_nhwc(x, weight, bias, residual=None, relu=True, stride=1, residual_u
     w2 = weight.reshape(cout, cin)
     if not w2.is_contiguous():
         w2 = w2.contiguous()
-    status = _lib.lib().simpb_conv1x1_nhwc_f16(_ptr(y), _ptr(x), _ptr(w2), _ptr(bias), _ptr(residual) if residual is not None else None,
-                                               n, h, w, cin, cout, stride, 1 if relu else 0,
-                                               1 if residual_upsample2x else 0,
-                                               _ptr(input_bias) if input_bias is not None else None, variant, _stream())
+    status = _lib.lib().simpb_conv1x1_nhwc_f16_live(_ptr(y), _ptr(x), _ptr(w2), _ptr(bias), _ptr(residual) if residual is not None else None,
+                                                    n, h, w, cin, cout, stride, 1 if relu else 0,
+                                                    1 if residual_upsample2x else 0,
+                                                    _ptr(input_bias) if input_bias is not None else None, variant, _stream(),
+                                                    _live_ptr(live, n, x.device))
     _lib.check(status, "simpb_conv1x1_nhwc_f16")
     return y
 
 
-def conv3x3_nhwc(x, weight, bias, relu=True, stride=1, tokens=None, variant=0):
+def conv3x3_nhwc(x, weight, bias, relu=True, stride=1, tokens=None, variant=0, live=None):
     """relu?(conv3x3(x, weight, stride, padding=1) + bias) for a channels_last f16 tensor, one launch (csrc/conv3x3.hip).
     x [N, Cin, H, W]; weight f16 [Cout, Cin, 3, 3] (channels_last, i.e. [Cout][3][3][Cin] in memory); bias f16 [Cout].
     tokens = (col_feats f32 [bs, cams * tokens_per_cam, Cout], tokens_per_cam, level_start[, col_f16]): the result is written
     as fp32 token rows of this level (feature_maps_format layout) instead of a map (and, with col_f16, as the same rows in
-    f16), and None is returned. col_feats None with col_f16 given: the f16 rows alone."""
+    f16), and None is returned. col_feats None with col_f16 given: the f16 rows alone.
+    live: None or a live-image table (_live_ptr): only those images are computed."""
     _require_gpu(x, weight, bias)
     n, cin, h, w = x.shape
     cout = weight.shape[0]
@@ -563,9 +577,9 @@ def conv3x3_nhwc(x, weight, bias, relu=True, stride=1, tokens=None, variant=0):
         if ((col is not None and col.dtype != torch.float32) or not rows.is_contiguous() or rows.shape[-1] != cout
                 or rows.numel() != n * per_cam * cout or start < 0 or start + ho * wo > per_cam):
             raise ValueError("tokens: (contiguous f32 [bs, cams * tokens_per_cam, Cout] with bs * cams == N, tokens_per_cam, level_start)")
-    status = _lib.lib().simpb_conv3x3_nhwc_f16(_ptr(y) if y is not None else None, _ptr(col) if col is not None else None,
-                                               _ptr(col16) if col16 is not None else None, per_cam, start, _ptr(x), _ptr(weight), _ptr(bias), n, h, w, cin, cout, stride,
-                                               1 if relu else 0, variant, _stream())
+    status = _lib.lib().simpb_conv3x3_nhwc_f16_live(_ptr(y) if y is not None else None, _ptr(col) if col is not None else None,
+                                                    _ptr(col16) if col16 is not None else None, per_cam, start, _ptr(x), _ptr(weight), _ptr(bias), n, h, w, cin, cout, stride,
+                                                    1 if relu else 0, variant, _stream(), _live_ptr(live, n, x.device))
     _lib.check(status, "simpb_conv3x3_nhwc_f16")
     return y
 
@@ -590,12 +604,13 @@ def conv3x3_group_resident_for(num_images, hws, in_channels, out_channels):
                                                               int(in_channels), int(out_channels)))
 
 
-def conv3x3_group_tokens(xs, weights, biases, col, per_cam, starts, col16=None, relu=False, variants=None):
+def conv3x3_group_tokens(xs, weights, biases, col, per_cam, starts, col16=None, relu=False, variants=None, live=None):
     """conv3x3_nhwc(..., tokens=...) of up to four levels in ONE launch (csrc/conv3x3.hip: conv_staged_group_kernel): the
     FPN's output convolutions. xs: channels_last f16 [N, Cin, H_j, W_j]; weights f16 [Cout, Cin, 3, 3]; biases f16 [Cout];
     col f32 [bs, cams * per_cam, Cout] (and col16, the same rows in f16; col None: the f16 rows alone); starts[j] = level j's
     first row inside a camera. variants: per level 8 (staged tiles) or 13 (resident tiles), None = the library's rule for the
-    whole launch; the levels of one form share a launch."""
+    whole launch; the levels of one form share a launch. live: None or a live-image table (_live_ptr): only those images'
+    token rows are computed."""
     import ctypes
     if col is None and col16 is None:
         raise ValueError("conv3x3_group_tokens: an f32 or an f16 token buffer")
@@ -620,11 +635,11 @@ def conv3x3_group_tokens(xs, weights, biases, col, per_cam, starts, col16=None, 
     arr_p, arr_i = ctypes.c_void_p * k, ctypes.c_int * k
     if variants is not None and len(variants) != k:
         raise ValueError("conv3x3_group_tokens: one variant per level")
-    status = _lib.lib().simpb_conv3x3_group_tokens_forms_f16(
+    status = _lib.lib().simpb_conv3x3_group_tokens_forms_f16_live(
         k, _ptr(col) if col is not None else None, _ptr(col16) if col16 is not None else None, int(per_cam), arr_i(*[int(v) for v in starts]),
         arr_p(*[x.data_ptr() for x in xs]), arr_p(*[w.data_ptr() for w in ws]), arr_p(*[b.data_ptr() for b in biases]), n,
         arr_i(*[x.shape[2] for x in xs]), arr_i(*[x.shape[3] for x in xs]), cin, cout, 1 if relu else 0,
-        arr_i(*[int(v) for v in variants]) if variants is not None else None, _stream())
+        arr_i(*[int(v) for v in variants]) if variants is not None else None, _stream(), _live_ptr(live, n, xs[0].device))
     _lib.check(status, "simpb_conv3x3_group_tokens_forms_f16")
 
 
@@ -644,9 +659,10 @@ def _stem_weight_packed(weight):
     return hit[1]
 
 
-def stem_conv_pool(img, weight, bias):
+def stem_conv_pool(img, weight, bias, live=None):
     """maxpool3x3s2p1(relu(conv7x7s2p3(half(img)) + bias)) in one launch (csrc/stem.hip) behind a cast pass of our own. img f32
-    [N, 3, H, W] (any strides); weight f16/f32 [64, 3, 7, 7]; bias [64] -> f16 [N, 64, Hp, Wp] channels_last."""
+    [N, 3, H, W] (any strides); weight f16/f32 [64, 3, 7, 7]; bias [64] -> f16 [N, 64, Hp, Wp] channels_last. live: None or a
+    live-image table (_live_ptr) for the stem launch; the cast pass runs on every image."""
     _require_gpu(img, weight, bias)
     n, c, h, w = img.shape
     if img.dtype != torch.float32 or c != 3 or tuple(weight.shape) != (64, 3, 7, 7) or bias.numel() != 64 or h < 1 or w < 1:
@@ -655,12 +671,13 @@ def stem_conv_pool(img, weight, bias):
     x4 = torch.empty(n, h, w, 4, device=img.device, dtype=torch.float16)
     _lib.check(lib.simpb_image_to_nhwc4_f16(_ptr(x4), _ptr(img), img.stride(0), img.stride(1), img.stride(2), img.stride(3), n, c, h, w,
                                             _stream()), "simpb_image_to_nhwc4_f16")
-    return stem_conv_pool_nhwc4(x4, weight, bias)
+    return stem_conv_pool_nhwc4(x4, weight, bias, live)
 
 
-def stem_conv_pool_nhwc4(x4, weight, bias):
+def stem_conv_pool_nhwc4(x4, weight, bias, live=None):
     """The stem launch alone, on an operand that is f16 [N, H, W, 4] (RGB + 0) already: what stem_conv_pool's cast pass or
-    the camera frame ingest (preprocess_frames) wrote. -> f16 [N, 64, Hp, Wp] channels_last."""
+    the camera frame ingest (preprocess_frames) wrote. -> f16 [N, 64, Hp, Wp] channels_last. live: None or a live-image table
+    (_live_ptr): only those images are computed."""
     _require_gpu(x4, weight, bias)
     if (x4.dtype != torch.float16 or x4.dim() != 4 or x4.shape[3] != 4 or not x4.is_contiguous() or tuple(weight.shape) != (64, 3, 7, 7)
             or bias.numel() != 64 or x4.shape[1] < 1 or x4.shape[2] < 1):
@@ -671,8 +688,8 @@ def stem_conv_pool_nhwc4(x4, weight, bias):
     hp, wp = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
     out = torch.empty((n, 64, hp, wp), device=x4.device, dtype=torch.float16, memory_format=torch.channels_last)
     b16 = bias if bias.dtype == torch.float16 and bias.is_contiguous() else bias.half().contiguous()
-    _lib.check(lib.simpb_stem_conv7x7_pool_f16(_ptr(out), _ptr(x4), _ptr(_stem_weight_packed(weight)), _ptr(b16), n, h, w, 64,
-                                               _stream()), "simpb_stem_conv7x7_pool_f16")
+    _lib.check(lib.simpb_stem_conv7x7_pool_f16_live(_ptr(out), _ptr(x4), _ptr(_stem_weight_packed(weight)), _ptr(b16), n, h, w, 64,
+                                                    _stream(), _live_ptr(live, n, x4.device)), "simpb_stem_conv7x7_pool_f16")
     return out
 
 

@@ -272,6 +272,26 @@ def normalise_cameras(cameras, num_streams, num_cams, active=None):
     return None if all(all(row) for row in out) else tuple(out)
 
 
+IDLE_IMAGES = ("compute", "skip")
+
+
+def live_images(active, cameras, bs, cams):
+    """The live-image table of a frame (include/simpb_hip.h): np.int32 [1 + bs * cams] with the number L of live images in
+    front, their indices ascending behind it and zeros behind those. Image s * cams + c is live iff stream s is active and its
+    camera c is valid. active / cameras: what normalise_active / normalise_cameras return -- None (all true), one bool per
+    stream, one row of `cams` bools per stream; a paused stream's camera row is not looked at. Pure host function."""
+    if active is not None and len(active) != bs:
+        raise ValueError(f"active has {len(active)} entries for {bs} streams")
+    if cameras is not None and (len(cameras) != bs or any(len(row) != cams for row in cameras)):
+        raise ValueError(f"cameras is not {bs} rows of {cams} entries")
+    live = [s * cams + c for s in range(bs) if active is None or active[s]
+            for c in range(cams) if cameras is None or cameras[s][c]]
+    table = np.zeros(1 + bs * cams, np.int32)
+    table[0] = len(live)
+    table[1:1 + len(live)] = live
+    return table
+
+
 class FrameInputs:
     """The per-frame decoder inputs of ONE frame in flight: a host buffer (pinned where the device is a GPU) and a device
     buffer for each, by name in `host` / `dev`:
@@ -377,7 +397,7 @@ class FrameRunner:
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
                  raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
-                 raw_layout=None, raw_surfaces=False, raw_rig=None):
+                 raw_layout=None, raw_surfaces=False, raw_rig=None, idle_images="compute"):
         """independent_streams: the batch is a set of independent camera streams, each decoded exactly as a batch of one
         would be (`capacity` 2D slots per stream; SimPBHead.independent_streams) -- the throughput form of BASELINE config
         #3. False: the reference's batch semantics (camera groups padded to the max over the batch).
@@ -408,7 +428,21 @@ class FrameRunner:
         world_output=dict(classes=..., tracking=bool, threshold=float | None): a second output per frame, the WORLD RECORD
         (csrc/world.hip, results.py): boxes in the global frame, threshold and class ranges applied, kept rows packed, a
         row count per stream -- one more launch at the end of the decoder, inside its graph. Each stream's img_metas entry
-        must then carry results.POSE_KEYS. None (default): nothing of this exists."""
+        must then carry results.POSE_KEYS. None (default): nothing of this exists.
+
+        idle_images="compute" | "skip": what the backbone does with the image of a paused stream (step's `active`) or of a
+        camera that delivered nothing (`cameras`). "compute" (default): it runs on every image slot, as ever. "skip": from the
+        first frame with such an image on, every frame stages its live-image table (live_images) with the images, and the
+        backbone's convolutions walk the live images only (the *_live entry points of include/simpb_hip.h): the rest is
+        neither read nor written. Results are the same bits for every stream that takes part. Until that first frame
+        nothing is staged and the graphs are the ordinary ones; that frame drops every graph once (stats["image_skip"]
+        counts the frames staged with a table, an all-live frame with the full one)."""
+        if idle_images not in IDLE_IMAGES:
+            raise ValueError(f"idle_images={idle_images!r}: one of {IDLE_IMAGES}")
+        self.idle_images = idle_images
+        self.skipping = False               # True from the first frame with a dead image on (idle_images="skip"): the backbone reads live_dev
+        self.live_pin = self.live_dev = None    # per feature slot: the live-image table, pinned host side and fixed device side
+        self.live_staged = None             # per feature slot: event behind the slot's last copy out of its pinned table
         self.model = model
         self.head = model.head
         self.bs = batch_size
@@ -667,8 +701,40 @@ class FrameRunner:
         pin.copy_(torch.tensor(frames[0], dtype=torch.int64))
         dst.copy_(pin, non_blocking=True)
 
-    def _extract(self, img, raw):
-        return self.model.extract_feat(raw, raw_plan=self.plan) if raw is not None else self.model.extract_feat(img)
+    def _extract(self, img, raw, slot=0):
+        extra = dict(live=self.live_dev[slot]) if self.skipping else {}
+        return self.model.extract_feat(raw, raw_plan=self.plan, **extra) if raw is not None else self.model.extract_feat(img, **extra)
+
+    FEATURE_SLOTS = 1
+
+    def _idle(self, mask, cams):
+        """idle_images="skip": the frame's live-image table (host), or None while no frame has had a dead image. The first
+        frame that has one switches the runner over, before anything of it is enqueued: every graph is dropped once (the
+        backbone's, and the decoder's bound to them) and the tables get their pinned host side and their device address."""
+        if self.idle_images != "skip" or (not self.skipping and mask is None and cams is None):
+            return None
+        if not self.skipping:
+            torch.cuda.synchronize(self.device)   # nothing in flight replays a backbone graph that does not read the table
+            self._drop_all_graphs()
+            n = 1 + self.bs * self.head.num_cams
+            self.live_pin = [torch.zeros(n, dtype=torch.int32).pin_memory() for _ in range(self.FEATURE_SLOTS)]
+            self.live_dev = [torch.zeros(n, dtype=torch.int32, device=self.device) for _ in range(self.FEATURE_SLOTS)]
+            self.live_staged = [None] * self.FEATURE_SLOTS
+            self.skipping = True
+        self.stats["image_skip"] = self.stats.get("image_skip", 0) + 1
+        return live_images(mask, cams, self.bs, self.head.num_cams)
+
+    def _stage_live(self, slot, table):
+        """The frame's live-image table into the slot's device buffer, on the current stream -- the one the slot's images are
+        staged on and its backbone runs on, in front of both."""
+        if table is None:
+            return
+        if self.live_staged[slot] is not None:
+            self.live_staged[slot].synchronize()   # the slot's last copy out of its pinned table (long done)
+        self.live_pin[slot].numpy()[:] = table
+        self.live_dev[slot].copy_(self.live_pin[slot], non_blocking=True)
+        self.live_staged[slot] = torch.cuda.Event()
+        self.live_staged[slot].record(torch.cuda.current_stream())
 
     # A frame that is captured and replayed exposes nothing but its records, so it computes nothing else (routes.lean_tokens,
     # routes.lean_refine2d; profiles/lean_frames.md). Both act for the length of a capture only: eager frames (use_graph=False,
@@ -835,15 +901,17 @@ class FrameRunner:
         inputs.fill(metas, prev, mask, cams, self.masked, self.cam_masked, restart)
         return inputs.metas(metas["img_metas"], self.wh, self.wh_host)
 
-    def _stage(self, img, metas, mask=None, cams=None, restart=None, prev="last"):
+    def _stage(self, img, metas, mask=None, cams=None, restart=None, prev="last", live=None):
         """Copy this frame's inputs into the static device buffers (a few small async copies); returns the head's metas.
-        prev: what the frame is staged against (None: a cold frame); by default the metas of the frame last returned."""
+        prev: what the frame is staged against (None: a cold frame); by default the metas of the frame last returned.
+        live: the frame's live-image table (_idle) or None."""
         if prev == "last":
             prev = self.prev_metas
         if self.raw is None:
             self.img.copy_(img, non_blocking=True)
         else:
             self._stage_frames(self.raw, img, self.pin_table)
+        self._stage_live(0, live)
         dmetas = self._fill_inputs(self.inputs, metas, prev, mask, cams, restart)
         self.inputs.upload(torch.cuda.current_stream())
         return dmetas
@@ -928,7 +996,7 @@ class FrameRunner:
 
         cameras: None, or one sequence of num_cams bools per stream; a camera with False delivered no frame. The stream is
         then decoded exactly as the reference decodes it when given the remaining cameras only: the camera's image slot (u8:
-        anything; f32: anything finite -- the backbone still runs on it) and its projection_mat row are ignored, its 2D
+        anything; f32: anything finite -- the backbone still runs on it unless idle_images="skip") and its projection_mat row are ignored, its 2D
         list is empty, and bank, track ids, ego-motion and time step go on as ever: a camera that comes back simply takes
         part again. A cold frame may have missing cameras. A stream that takes part needs at least one camera (ValueError:
         pause it instead); a paused stream's row is not looked at. An overflowed frame is re-run with its own mask.
@@ -953,7 +1021,7 @@ class FrameRunner:
         anew because of an adoption (stats["adopt"] counts the frames that had one)."""
         mask, cams, metas, img, flags, adopt, prev = self._admit(self.prev_metas, img, metas, active, cameras, restart, adopt)
         aug = self._aug(metas)
-        dmetas = self._stage(img, metas, mask, cams, flags, prev)
+        dmetas = self._stage(img, metas, mask, cams, flags, prev, self._idle(mask, cams))
         warm = prev is not None
         if adopt is not None:   # eager launches between replays, in front of the frame: no graph knows of them
             self._import(adopt, None)
@@ -1036,6 +1104,7 @@ class PipelinedRunner(FrameRunner):
     # the decoder of frame t is the critical path (a chain of ~170 dependent small launches); the
     # backbone of frame t+1 only has to be done by the time that chain ends: decoder stream first
     STREAM_PRIORITIES = (0, -1)             # (backbone, decoder)
+    FEATURE_SLOTS = 2                       # backbone(t+1) runs beside decoder(t): a live-image table per slot, as the images
 
     def __init__(self, *args, **kwargs):
         """Arguments: FrameRunner's."""
@@ -1095,7 +1164,7 @@ class PipelinedRunner(FrameRunner):
     def _features(self, slot):
         """Backbone + FPN + token format, plus everything of the decoder that depends on the features
         alone: the value projections of the three 2D cross-attention layers."""
-        fm = list(self._extract(self.imgs[slot], self.raws[slot]))
+        fm = list(self._extract(self.imgs[slot], self.raws[slot], slot))
         if hasattr(self.head, "precompute_values") and len(fm) == 3:
             fm.append(self.head.precompute_values(fm))
         return fm
@@ -1192,11 +1261,13 @@ class PipelinedRunner(FrameRunner):
         adoptions). A launch with an adoption waits for the decoder still in flight, behind enqueuing its own backbone: the
         slot's previous occupant must have committed its last frame before the adopted rows replace its own."""
         mask, cams, metas, img, flags, adopt, prev = self._admit(self.last_metas, img, metas, active, cameras, restart, adopt)
+        live = self._idle(mask, cams)
         slot = self.count % 2
         cur = torch.cuda.current_stream()
         self.s_bb.wait_stream(cur)
         self.s_head.wait_stream(cur)
         with torch.cuda.stream(self.s_bb):
+            self._stage_live(slot, live)   # (with the slot's images, not with the decoder's inputs: the decoder of the frame before still runs)
             if self.raw is None:
                 self.imgs[slot].copy_(img, non_blocking=True)
             elif not self.surfaces:

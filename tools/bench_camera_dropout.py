@@ -1,7 +1,7 @@
 """What a missing camera saves (and what the full rig pays for the mask existing): steady-state frames/s with cameras masked
 (`step(..., cameras=)`), synthetic inputs as bench.py's.
 
-    python tools/bench_camera_dropout.py [--rounds 5] [--steps 100] [--out FILE.json]
+    python tools/bench_camera_dropout.py [--rounds 5] [--steps 100] [--idle-images skip] [--out FILE.json]
 
 Three tables:
   1. the bs = 1 split runner (SplitPipelinedRunner, what `bench.py --gpus 1` times) with 6 / 5 / 3 / 1 of the 6 cameras valid;
@@ -18,8 +18,9 @@ two device synchronisations, host clock. Reported per mask: the median over the 
 its blocks. "6 valid" runs through the masked graphs with an all-ones mask: what the full rig costs once a camera has been
 lost; the cost with `cameras=None` is bench.py's own number. There is no pass mark.
 
-A masked camera still costs the ingest and the backbone on its image slot (fixed shapes, one graph); it costs no 2D slots, no
-share of the 3D aggregation's gathers."""
+A masked camera still costs the ingest and, with --idle-images compute (the default), the backbone on its image slot; it
+costs no 2D slots, no share of the 3D aggregation's gathers. --idle-images skip builds the runners of tables 1 and 2 with
+idle_images="skip" and adds the per-launch table of tools/_image_skip.py (profiles/image_skip.md)."""
 import argparse
 import ctypes
 import json
@@ -169,6 +170,8 @@ def main():
     ap.add_argument("--prime", type=int, default=10)
     ap.add_argument("--capacity", type=int, default=1536)
     ap.add_argument("--image-wh", type=int, nargs=2, default=(704, 256))
+    ap.add_argument("--idle-images", choices=["compute", "skip"], default="compute", help="the runners' idle_images")
+    ap.add_argument("--tables", type=int, nargs="+", default=[1, 2, 3], help="which of the three tables to measure")
     ap.add_argument("--out", default=None, help="also write the result as JSON to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -181,28 +184,37 @@ def main():
     wh = tuple(args.image_wh)
     build = lambda bs: bench.build_model(SimpleNamespace(depth=50, image_wh=wh, bs=bs, residual_damp=1.0, token_std=None), device)  # noqa: E731
     result = dict(tool="bench_camera_dropout", device=torch.cuda.get_device_name(0), image_wh=list(wh), capacity=args.capacity,
-                  rounds=args.rounds, steps_per_block=args.steps, warmup_after_switch=args.warmup)
+                  rounds=args.rounds, steps_per_block=args.steps, warmup_after_switch=args.warmup, idle_images=args.idle_images)
 
     model = build(1)
-    result["launches"] = time_launches(model, wh, args)
-    runner = SplitPipelinedRunner(model, 1, (wh[1], wh[0]), capacity=args.capacity, device=device, use_graph=True)
-    masks = {f"{k} of {CAMS} valid": [first_valid(k)] for k in args.valid}
-    result["split_bs1"] = rows_of(time_runner(runner, 1, wh, masks, args), 1)
-    result["split_bs1_stats"] = dict(runner.stats)
-    table("bs = 1, SplitPipelinedRunner", result["split_bs1"])
-    del runner, model
+    result["launches"] = time_launches(model, wh, args) if 3 in args.tables else []
+    if 1 in args.tables:
+        runner = SplitPipelinedRunner(model, 1, (wh[1], wh[0]), capacity=args.capacity, device=device, use_graph=True,
+                                      idle_images=args.idle_images)
+        masks = {f"{k} of {CAMS} valid": [first_valid(k)] for k in args.valid}
+        result["split_bs1"] = rows_of(time_runner(runner, 1, wh, masks, args), 1)
+        result["split_bs1_stats"] = dict(runner.stats)
+        table(f"bs = 1, SplitPipelinedRunner, idle_images={args.idle_images}", result["split_bs1"])
+        del runner
+    del model
     torch.cuda.empty_cache()
 
-    if args.bs > 0:
+    if args.bs > 0 and 2 in args.tables:
         bs = args.bs
         model = build(bs)
         runner = PipelinedRunner(model, bs, (wh[1], wh[0]), capacity=args.capacity, device=device, use_graph=True,
-                                 independent_streams=True)
+                                 independent_streams=True, idle_images=args.idle_images)
         masks = {f"camera 1 down in {d} of {bs} streams": [[not (c == 1 and s < d) for c in range(CAMS)] for s in range(bs)]
                  for d in args.down_in if d <= bs}
         result["batch"] = rows_of(time_runner(runner, bs, wh, masks, args), bs)
         result["batch_stats"] = dict(runner.stats)
-        table(f"bs = {bs}, PipelinedRunner, independent streams", result["batch"])
+        table(f"bs = {bs}, PipelinedRunner, independent streams, idle_images={args.idle_images}", result["batch"])
+        del runner, model
+        torch.cuda.empty_cache()
+    if args.idle_images == "skip":
+        import _image_skip
+        result["image_skip_launches"] = _image_skip.launch_table()
+        _image_skip.print_launch_table(result["image_skip_launches"])
 
     print("\nthe launches alone (bs = 1 frame)")
     print("| valid cameras | fused aggregation, us (median / min) | static allocation, us per call (3 launches) | 2D slots |")
