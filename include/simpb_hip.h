@@ -1058,6 +1058,64 @@ int simpb_aggregate_2d_to_3d_alpha(float* out_q, float* out_pos, const float* q3
                                    int batch_size, int num_anchors, int num_cams, int num_query, int channels,
                                    void* stream);
 
+/* ---- Camera health: which cameras of a frame delivered a usable image, decided on the device behind the ingest ----
+ * Two launches. The first reads every image once and leaves integer statistics; the second turns them, the host's masks and
+ * a small persistent state into the u8 [batch_size, num_cams] camera mask the *_cams entry points above read, in the same
+ * frame, without a host round trip. Every statistic is an integer that does not depend on the order of summation, and the
+ * verdict's float64 arithmetic rounds once per operation (no contraction): a host model reproduces both bit for bit.
+ *
+ * Statistics of image n, X = f16 [height, width, 4] as the ingest writes it (channels 0..2 used, channel 3 never looked at):
+ *   q(x) = x * 2^24 as int64 (exact for every finite f16); a non-finite x counts in nonfinite[n] and contributes 0;
+ *   S[n][i][j][k] = sum of q over cell (i, j) of the fixed SIMPB_HEALTH_GRID x SIMPB_HEALTH_GRID grid, per channel k: rows
+ *     [i * height / 8, (i + 1) * height / 8), columns [j * width / 8, (j + 1) * width / 8) (integer division);
+ *   hash[n] = sum over (y, x, k < 3) of mix(bits16(X[y, x, k]) | (((y * width + x) * 3 + k) << 16)) mod 2^64, mix = the
+ *     splitmix64 finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31).
+ * They are left as PARTIAL ROWS, int64 [num_images, SIMPB_HEALTH_BANDS, SIMPB_HEALTH_PARTIAL_WORDS]: band i * 8 + b is the
+ * b-th eighth of the rows of cell row i (rows r0 + b * n / 8 .. r0 + (b + 1) * n / 8 of its n rows; possibly none), and a
+ * row holds S of that band's pixels as [j * 3 + k] (24 words), the band's part of the hash (word 24) and its non-finite
+ * count (word 25). Every word of every row is written by plain stores on every call: nothing has to be zeroed in between.
+ * images: 8-byte aligned (any image may start off a 16-byte boundary). 8 <= height, width <= 16384; num_images <= 65535. */
+#define SIMPB_HEALTH_GRID 8
+#define SIMPB_HEALTH_BANDS 64
+#define SIMPB_HEALTH_PARTIAL_WORDS 26
+int simpb_image_health_stats(long long* partials, const void* images, int num_images, int height, int width, void* stream);
+/* Bytes of the partial rows of num_images images (a multiple of 8, below 2^31); SIMPB_EINVAL (1: no size is that small)
+ * for sizes the launch refuses. */
+int simpb_image_health_partials_bytes(int num_images, int height, int width);
+
+#define SIMPB_HEALTH_DARK 1
+#define SIMPB_HEALTH_BRIGHT 2
+#define SIMPB_HEALTH_FLAT 4
+#define SIMPB_HEALTH_FROZEN 8
+#define SIMPB_HEALTH_FAIL_OPEN 16
+#define SIMPB_HEALTH_NONFINITE 32
+typedef struct simpb_health_params {
+  double dark_below, bright_above, flat_below; /* levels 0..255 of the preprocessed image; read where the check is on */
+  double mean[3], std[3];                      /* of the normalisation, in the channel order of the normalised tensor */
+  int check_dark, check_bright, check_flat, check_frozen; /* 0: the check is off */
+  int frozen_after;                            /* >= 1 where check_frozen */
+  int act;                                     /* 0: flags are reported, cam_out = cam_in */
+} simpb_health_params;
+/* Persistent state per (stream, camera), 16 bytes: what the frozen check remembers. */
+typedef struct simpb_health_state {
+  unsigned long long prev_hash;
+  unsigned int repeats, frames;
+} simpb_health_state;
+/* The verdict for image s * num_cams + c of `partials` (the rows are added in band order). A camera is CONSIDERED iff
+ * active[s] && cam_in[s][c] (u8, device; NULL = all ones); one that is not keeps its state, gets flags 0, and its rows are
+ * not read. For a considered one, per channel level_k = double(sum_ij S[k]) / (double(height * width) * 2^24) * std_k +
+ * mean_k, L = (level_0 + level_1 + level_2) / 3, and Lc[i][j] the same from one cell and its pixel count;
+ *   DARK: L < dark_below   BRIGHT: L > bright_above   FLAT: max Lc - min Lc < flat_below   NONFINITE: nonfinite > 0
+ *   FROZEN: repeats >= frozen_after after { repeats = frames > 0 && hash == prev_hash ? repeats + 1 : 0; prev_hash = hash;
+ *   frames += 1 } (all comparisons strict as written).
+ * If every considered camera of a stream has one of these, none is dropped and each gets FAIL_OPEN as well.
+ * flags u8 [batch_size, num_cams]; cam_out u8 [batch_size, num_cams] = cam_in && !(fault && act && !fail_open);
+ * state: simpb_health_state [batch_size, num_cams], read and written. num_cams <= 64, batch_size <= 65535. */
+int simpb_camera_health_verdict(unsigned char* cam_out, unsigned char* flags, simpb_health_state* state,
+                                const long long* partials, const unsigned char* cam_in, const unsigned char* active,
+                                simpb_health_params params, int batch_size, int num_cams, int height, int width,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,13 @@ class RigCamera(ctypes.Structure):
                 [("chroma2_offset", _LL)])
 
 
+class HealthParams(ctypes.Structure):
+    """simpb_health_params of include/simpb_hip.h, passed by value."""
+    _fields_ = [("dark_below", ctypes.c_double), ("bright_above", ctypes.c_double), ("flat_below", ctypes.c_double),
+                ("mean", ctypes.c_double * 3), ("std", ctypes.c_double * 3),
+                ("check_dark", _I), ("check_bright", _I), ("check_flat", _I), ("check_frozen", _I), ("frozen_after", _I), ("act", _I)]
+
+
 SIGNATURES = {
     "simpb_abi_version": ([], _I),
     "simpb_last_error": ([], ctypes.c_char_p),
@@ -93,6 +100,9 @@ SIGNATURES = {
     "simpb_decode2d_record_cams": ([_P] * 6 + [_I] * 4 + [_P, _I, _P], _I),
     "simpb_decode2d_record_ragged_cams": ([_P] * 7 + [_I] * 5 + [_P, _P], _I),
     "simpb_world_record": ([_P] * 5 + [WorldTables, _I, _P], _I),
+    "simpb_image_health_stats": ([_P, _P, _I, _I, _I, _P], _I),
+    "simpb_image_health_partials_bytes": ([_I, _I, _I], _I),
+    "simpb_camera_health_verdict": ([_P] * 6 + [HealthParams] + [_I] * 4 + [_P], _I),
     "simpb_topk_rows": ([_P, _P, _P, _I, _I, _I, _P], _I),
     "simpb_rowdot_sigmoid": ([_P, _P, _I, _P, _P, _I, _I, _P, _P], _I),
     "simpb_anchor_projection": ([_P] * 4 + [_I] * 2 + [_P], _I),

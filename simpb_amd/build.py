@@ -23,7 +23,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 NO_PACKED_FP32 = ["-fno-slp-vectorize", "-fno-vectorize"]
 ROW_KERNEL_FILES = ("deform_agg", "deform_agg_fused", "msda", "msda_lin", "alloc", "bank", "rowops", "dfa_prep", "decode", "format",
                     "preprocess",   # (integer resampling + a table: nothing to pack, and it runs beside the decoder)
-                    "world")        # (double arithmetic on record rows, the last launch of the decoder stream)
+                    "world",        # (double arithmetic on record rows, the last launch of the decoder stream)
+                    "health")       # (integer sums and a little double arithmetic behind the ingest, beside the decoder)
 
 
 def flags_for(src):

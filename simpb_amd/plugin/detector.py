@@ -366,7 +366,7 @@ class SimPB(BaseModule):
                     blk.fused_epilogue = True
         return self
 
-    def extract_feat(self, img, return_depth=False, metas=None, raw_plan=None, live=None):
+    def extract_feat(self, img, return_depth=False, metas=None, raw_plan=None, live=None, on_ingest=None):
         """simpb.py:64-91. A uint8 `img` is the raw form: camera frames as decoded, in the layout of `raw_plan`
         (simpb_amd.preprocess.ResamplePlan): [bs, cams, Hs, Ws, 3] or [N, Hs, Ws, 3] for a "bgr" plan, [bs, cams, Hs * 3 / 2, Ws] or
         [N, Hs * 3 / 2, Ws] for an "nv12" / "nv21" one, [bs, cams, image_bytes] or [N, image_bytes] for a plan with a padded
@@ -374,7 +374,9 @@ class SimPB(BaseModule):
         straight into the stem's operand; a frame whose shape is not the plan's is refused. An int64 `img` [bs, cams] or [N] on
         the device is the pointer form of the same: the address of one surface per image (ResamplePlan.run_table).
         live: None or a live-image table (include/simpb_hip.h; contiguous i32 [1 + bs * cams] on the device): the backbone and
-        the neck compute the images it lists and no other; the token rows of the rest hold whatever the memory held."""
+        the neck compute the images it lists and no other; the token rows of the rest hold whatever the memory held.
+        on_ingest: None or a callable taking the ingest's output (f16 [N, h, w, 4], the stem's operand), called right behind
+        the ingest on its stream (raw frames only: the runners' camera health)."""
         bs = img.shape[0]
         table = img.dtype == torch.int64
         raw = table or img.dtype == torch.uint8
@@ -392,6 +394,8 @@ class SimPB(BaseModule):
             raw_plan.check_frames(img)
             num_cams = img.shape[1] if lead == 2 else 1
             img = raw_plan.run(img)
+        elif on_ingest is not None:
+            raise ValueError("on_ingest follows the device ingest: it needs raw frames")
         elif img.dim() == 5:
             num_cams = img.shape[1]
             img = img.flatten(end_dim=1)
@@ -399,6 +403,8 @@ class SimPB(BaseModule):
             num_cams = 1
         if not raw and self.fp16_enabled and not (img.dtype == torch.float32 and getattr(self.img_backbone, "_stem_kernel_ok", lambda t: False)(img)):
             img = img.half().contiguous(memory_format=torch.channels_last)   # (the stem kernel route casts inside its own launch)
+        if on_ingest is not None:
+            on_ingest(img)
         extra = {} if live is None else dict(live=live)
         feature_maps = self.img_backbone(img, nhwc4=True, **extra) if raw else self.img_backbone(img, **extra)
         biases = None

@@ -397,7 +397,7 @@ class FrameRunner:
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
                  raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
-                 raw_layout=None, raw_surfaces=False, raw_rig=None, idle_images="compute"):
+                 raw_layout=None, raw_surfaces=False, raw_rig=None, idle_images="compute", camera_health=None):
         """independent_streams: the batch is a set of independent camera streams, each decoded exactly as a batch of one
         would be (`capacity` 2D slots per stream; SimPBHead.independent_streams) -- the throughput form of BASELINE config
         #3. False: the reference's batch semantics (camera groups padded to the max over the batch).
@@ -436,13 +436,36 @@ class FrameRunner:
         backbone's convolutions walk the live images only (the *_live entry points of include/simpb_hip.h): the rest is
         neither read nor written. Results are the same bits for every stream that takes part. Until that first frame
         nothing is staged and the graphs are the ordinary ones; that frame drops every graph once (stats["image_skip"]
-        counts the frames staged with a table, an all-live frame with the full one)."""
+        counts the frames staged with a table, an all-live frame with the full one).
+
+        camera_health=health.CameraHealth (or a dict of its keywords; raw frames only: raw_input or raw_rig): every frame gets
+        two more launches right behind the ingest, on its stream and inside its graph (csrc/health.hip): integer statistics of
+        every image, then a verdict per camera -- dark, bright, flat (a covered lens), frozen (the same pixels again),
+        non-finite -- that writes the camera mask the decoder of this very frame reads, ANDed with the host's `cameras` /
+        `active`. A faulty camera is decoded as a missing one (step's `cameras`); if every camera of a stream is faulty none is
+        dropped (fail open). The runner is camera-masked from construction, one captured graph serves every verdict, and the
+        frozen check's state advances once per ingested frame (a re-run after a 2D overflow re-reads the verdict). The flags
+        (health.DARK ...) come back with the records: res[s]["img_bbox"]["camera_health"] (u8 [cams]), `last_health`,
+        stats["health_dropped"], and `health_state()`. With act=False they are reported and nothing is dropped. With
+        idle_images="skip" a camera the device drops is still computed by the backbone: the host cannot know of it before it
+        enqueues the frame. None (default): nothing of this is allocated, staged or launched."""
         if idle_images not in IDLE_IMAGES:
             raise ValueError(f"idle_images={idle_images!r}: one of {IDLE_IMAGES}")
         self.idle_images = idle_images
         self.skipping = False               # True from the first frame with a dead image on (idle_images="skip"): the backbone reads live_dev
         self.live_pin = self.live_dev = None    # per feature slot: the live-image table, pinned host side and fixed device side
         self.live_staged = None             # per feature slot: event behind the slot's last copy out of its pinned table
+        self.health = None                  # health.CameraHealth (camera_health=); None: nothing of it exists
+        self.health_slots = None            # per feature slot: partial rows, cam_eff, flags and the staged host masks
+        self.health_dev_state = None        # the frozen check's state, one per runner: int64 [bs, cams, 2]
+        self.last_health = None             # flags u8 [bs, cams] (numpy) of the frame last returned
+        self.health_hold = False            # True while a frame is re-run: its verdict stands, the state does not advance again
+        if camera_health is not None:
+            from .health import CameraHealth
+            if raw_input is None and raw_rig is None:
+                raise ValueError("camera_health looks at the images the device ingest writes: it needs raw frames (raw_input= or "
+                                 "raw_rig=), not tensor input")
+            self.health = CameraHealth.make(camera_health)
         self.model = model
         self.head = model.head
         self.bs = batch_size
@@ -498,6 +521,8 @@ class FrameRunner:
         self.masked = False                 # True from the first frame with a paused stream on: the graphs read `active`
         self.last_active = (True,) * batch_size   # mask of the frame last returned
         self.cam_masked = False             # True from the first frame with a missing camera on: the graphs read `cam`
+        if self.health is not None:
+            self._health_setup()
         bank = self.head.instance_bank
         time_step = (bank.max_time_interval, bank.default_time_interval) if self.SLOT_INPUTS else None
         self.slot_inputs = [FrameInputs(batch_size, cams, dev, time_step, pose=world_output is not None)
@@ -515,6 +540,8 @@ class FrameRunner:
         self.warm_frames = 0
         self.host3d = self.host2d = self.host_flag = None
         self.stats = dict(eager=0, replay=0, overflow=0)   # (+ "restart": frames that restarted a stream, from the first one on)
+        if self.health is not None:
+            self.stats["health_dropped"] = 0   # cameras the verdict took out of a frame, summed over the frames returned
         self.decoded = [False] * batch_size   # per slot: it has taken part in a frame here (export_stream needs that)
         self.last_rec3d = None      # device record f32 [bs, num_output, 15] of the frame last returned (dist.DetectionGather)
         self.last_rec2d = None      # ... and its 2D record f32 [bs, capacity, 8]
@@ -703,6 +730,9 @@ class FrameRunner:
 
     def _extract(self, img, raw, slot=0):
         extra = dict(live=self.live_dev[slot]) if self.skipping else {}
+        launches = self._health_launches(slot)
+        if launches is not None:
+            extra["on_ingest"] = launches
         return self.model.extract_feat(raw, raw_plan=self.plan, **extra) if raw is not None else self.model.extract_feat(img, **extra)
 
     FEATURE_SLOTS = 1
@@ -735,6 +765,77 @@ class FrameRunner:
         self.live_dev[slot].copy_(self.live_pin[slot], non_blocking=True)
         self.live_staged[slot] = torch.cuda.Event()
         self.live_staged[slot].record(torch.cuda.current_stream())
+
+    # ------------------------------------------------------------------ camera health
+    def _health_setup(self):
+        """camera_health: the buffers of every feature slot and the one state. The graphs read the slot's cam_eff in place
+        of the host's mask from the first frame on (all ones until a camera is dropped)."""
+        from . import health as H
+        dev, bs, cams = self.device, self.bs, self.head.num_cams
+        h, w = self.image_hw
+        self.health_params = self.health.params(self.img_norm_cfg)
+        words = H.partials_bytes(bs * cams, h, w) // 8
+        pin = lambda t: t.pin_memory() if torch.device(dev).type == "cuda" else t   # noqa: E731
+        self.health_slots = [dict(partials=torch.zeros(words, dtype=torch.int64, device=dev),
+                                  cam_eff=torch.ones(bs, cams, dtype=torch.uint8, device=dev),
+                                  flags=torch.zeros(bs, cams, dtype=torch.uint8, device=dev),
+                                  masks_pin=pin(torch.ones(bs + bs * cams, dtype=torch.uint8)),   # active | cam, the host's
+                                  masks=torch.ones(bs + bs * cams, dtype=torch.uint8, device=dev),
+                                  staged=None, host=pin(torch.zeros(bs, cams, dtype=torch.uint8)))
+                             for _ in range(self.FEATURE_SLOTS)]
+        self.health_dev_state = H.new_state(bs, cams, dev)
+        self.cam_masked = True
+
+    def _stage_health(self, slot, mask, cams):
+        """The host's `active` and `cameras` rows for the slot's verdict, on the current stream -- the one the slot's images
+        are staged on and its ingest runs on (as _stage_live; not with the decoder's FrameInputs, which travel on another)."""
+        if self.health is None:
+            return
+        hs = self.health_slots[slot]
+        if hs["staged"] is not None:
+            hs["staged"].synchronize()   # the slot's last copy out of its pinned rows (long done)
+        rows = hs["masks_pin"].numpy()
+        rows[:self.bs] = 1 if mask is None else mask
+        rows[self.bs:] = 1 if cams is None else np.asarray(cams, np.uint8).reshape(-1)
+        hs["masks"].copy_(hs["masks_pin"], non_blocking=True)
+        hs["staged"] = torch.cuda.Event()
+        hs["staged"].record(torch.cuda.current_stream())
+
+    def _health_launches(self, slot):
+        """The callable extract_feat runs right behind the ingest (None: no camera health, or a re-run of the frame)."""
+        if self.health is None or self.health_hold:
+            return None
+        from . import health as H
+        hs, bs, cams = self.health_slots[slot], self.bs, self.head.num_cams
+
+        def launches(images):
+            H.image_health_stats(images, out=hs["partials"])
+            H.camera_health_verdict(hs["partials"], self.health_dev_state, self.health_params, self.image_hw,
+                                    cam_in=hs["masks"][bs:].view(bs, cams), active=hs["masks"][:bs],
+                                    cam_out=hs["cam_eff"], flags=hs["flags"])
+        return launches
+
+    def health_state(self):
+        """camera_health: a host copy of the frozen check's state behind everything enqueued so far: dict(prev_hash u64,
+        repeats u32, frames u32), each [bs, cams] -- `frames` counts the frames a camera took part in."""
+        if self.health is None:
+            raise ValueError("health_state: this runner was built without camera_health")
+        from .health import state_to_host
+        torch.cuda.synchronize(self.device)
+        return state_to_host(self.health_dev_state)
+
+    def _health_results(self, results, flags):
+        """The frame's flags (host u8 [bs, cams]) into its results, last_health and stats["health_dropped"]."""
+        from .health import FAIL_OPEN, FAULTS
+        flags = flags.numpy().copy()
+        self.last_health = flags
+        if self.health.act:
+            dropped = ((flags & FAULTS) != 0) & ((flags & FAIL_OPEN) == 0)
+            self.stats["health_dropped"] = self.stats.get("health_dropped", 0) + int(dropped.sum())
+        for i, res in enumerate(results):
+            if res is not None:
+                res["img_bbox"]["camera_health"] = flags[i]
+        return results
 
     # A frame that is captured and replayed exposes nothing but its records, so it computes nothing else (routes.lean_tokens,
     # routes.lean_refine2d; profiles/lean_frames.md). Both act for the length of a capture only: eager frames (use_graph=False,
@@ -895,11 +996,15 @@ class FrameRunner:
         s = self._check_export(s)
         return self._export(s, self.prev_metas["img_metas"])
 
-    def _fill_inputs(self, inputs, metas, prev, mask, cams, restart=None):
-        """The frame's decoder inputs into `inputs` (host side) -> the metas dict the head reads them through."""
+    def _fill_inputs(self, inputs, metas, prev, mask, cams, restart=None, slot=0):
+        """The frame's decoder inputs into `inputs` (host side) -> the metas dict the head reads them through. With
+        camera_health the camera mask it names is the verdict of feature slot `slot`, not the host's."""
         self.inputs = inputs
         inputs.fill(metas, prev, mask, cams, self.masked, self.cam_masked, restart)
-        return inputs.metas(metas["img_metas"], self.wh, self.wh_host)
+        dmetas = inputs.metas(metas["img_metas"], self.wh, self.wh_host)
+        if self.health is not None:
+            dmetas["camera_valid"] = self.health_slots[slot]["cam_eff"]
+        return dmetas
 
     def _stage(self, img, metas, mask=None, cams=None, restart=None, prev="last", live=None):
         """Copy this frame's inputs into the static device buffers (a few small async copies); returns the head's metas.
@@ -912,11 +1017,16 @@ class FrameRunner:
         else:
             self._stage_frames(self.raw, img, self.pin_table)
         self._stage_live(0, live)
+        self._stage_health(0, mask, cams)
         dmetas = self._fill_inputs(self.inputs, metas, prev, mask, cams, restart)
         self.inputs.upload(torch.cuda.current_stream())
         return dmetas
 
-    def _results(self, rec3d, rec2d, mask, world=None, count=None):
+    def _results(self, rec3d, rec2d, mask, world=None, count=None, health=None):
+        results = self._results_of(rec3d, rec2d, mask, world, count)
+        return results if health is None else self._health_results(results, health)
+
+    def _results_of(self, rec3d, rec2d, mask, world=None, count=None):
         self.last_active = mask if mask is not None else (True,) * self.bs
         rec3d, rec2d = rec3d.numpy(), rec2d.numpy()
         if mask is None:
@@ -978,6 +1088,8 @@ class FrameRunner:
         self.host3d.copy_(rec3d, non_blocking=True)
         self.host2d.copy_(rec2d, non_blocking=True)
         self.host_flag.copy_(flags, non_blocking=True)
+        if self.health is not None:
+            self.health_slots[0]["host"].copy_(self.health_slots[0]["flags"], non_blocking=True)
         torch.cuda.current_stream().synchronize()
         return self.host3d, self.host2d, bool(self.host_flag.any())
 
@@ -1053,16 +1165,21 @@ class FrameRunner:
             self._grow()
             if not warm:
                 self.head.instance_bank.reset()  # a cold frame starts from an empty bank again
-            rec = self._frame(dmetas, aug)
+            self.health_hold = True   # (camera_health: the frame's verdict stands and its state has advanced)
+            try:
+                rec = self._frame(dmetas, aug)
+            finally:
+                self.health_hold = False
             self.stats["eager"] += 1
             rec3d, rec2d, overflow = self._read_back(*rec)
         self.last_rec3d, self.last_rec2d = rec[0], rec[1]
         self.prev_metas = dict(img_metas=metas["img_metas"])
         self.head.instance_bank.metas = self.prev_metas
+        health = self.health_slots[0]["host"] if self.health is not None else None
         if self.world_output is None:
-            return self._results(rec3d, rec2d, mask)
+            return self._results(rec3d, rec2d, mask, health=health)
         self.last_world, self.last_world_count = rec[3], rec[4]
-        return self._results(rec3d, rec2d, mask, self.host_world, self.host_count)
+        return self._results(rec3d, rec2d, mask, self.host_world, self.host_count, health=health)
 
 
 @dataclass
@@ -1225,6 +1342,8 @@ class PipelinedRunner(FrameRunner):
                 self.host[slot] = h
             for dst, src in zip(h, rec):
                 dst.copy_(src, non_blocking=True)
+            if self.health is not None:   # (written on the backbone stream in front of bb_done, which this stream waited for)
+                self.health_slots[slot]["host"].copy_(self.health_slots[slot]["flags"], non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.s_head)
         return done
@@ -1234,7 +1353,7 @@ class PipelinedRunner(FrameRunner):
         frame's adoptions are imported on the decoder stream right in front of it."""
         self.prev_metas = prev   # (what the base class's helpers look at)
         inputs = self.slot_inputs[slot]
-        dmetas = self._fill_inputs(inputs, metas, prev, mask, cams, restart)
+        dmetas = self._fill_inputs(inputs, metas, prev, mask, cams, restart, slot)
         records = self._import(adopt, self.s_head) if adopt is not None else None
         rec = self._run_head(slot, inputs, dmetas, self._aug(metas), prev is not None, force_eager)
         return Job(slot, metas, prev, rec, self._enqueue_readback(slot, rec), mask, cams, surfaces, restart, adopt, records)
@@ -1268,6 +1387,7 @@ class PipelinedRunner(FrameRunner):
         self.s_head.wait_stream(cur)
         with torch.cuda.stream(self.s_bb):
             self._stage_live(slot, live)   # (with the slot's images, not with the decoder's inputs: the decoder of the frame before still runs)
+            self._stage_health(slot, mask, cams)
             if self.raw is None:
                 self.imgs[slot].copy_(img, non_blocking=True)
             elif not self.surfaces:
@@ -1303,10 +1423,11 @@ class PipelinedRunner(FrameRunner):
             state._sealed = True
         self.last_rec3d, self.last_rec2d = job.rec[0], job.rec[1]
         self.prev_metas = dict(img_metas=job.metas["img_metas"])
+        health = self.health_slots[job.slot]["host"] if self.health is not None else None
         if self.world_output is None:
-            return self._results(h[0], h[1], job.active)
+            return self._results(h[0], h[1], job.active, health=health)
         self.last_world, self.last_world_count = job.rec[3], job.rec[4]
-        return self._results(h[0], h[1], job.active, h[3], h[4])
+        return self._results(h[0], h[1], job.active, h[3], h[4], health=health)
 
     def _settle(self, job):
         """Wait for a decoder in flight and, if its 2D set overflowed, re-run it and whatever was enqueued behind it -> the
