@@ -79,10 +79,13 @@ __global__ __launch_bounds__(kThreads) void msda_grouped_bwd(
       for (int m = lanes_per_head / 2; m >= 1; m >>= 1) {
         ga_p += __shfl_xor(ga_p, m); gx_p += __shfl_xor(gx_p, m); gy_p += __shfl_xor(gy_p, m);
       }
+      // A sample with no tap inside the map (far away, infinite or NaN) gives zeros, as mmcv's does: its fractions may be
+      // NaN, and NaN * 0 is not 0. Chosen at the store, so the arithmetic of every other sample is what it always was.
+      const bool any = t1 | t2 | t3 | t4;
       if (head_lead) {
-        ga[lvl * P + pt] = ga_p;
-        gl[(lvl * P + pt) * 2] = gx_p;
-        gl[(lvl * P + pt) * 2 + 1] = gy_p;
+        ga[lvl * P + pt] = any ? ga_p : 0.f;
+        gl[(lvl * P + pt) * 2] = any ? gx_p : 0.f;
+        gl[(lvl * P + pt) * 2 + 1] = any ? gy_p : 0.f;
       }
     }
   }

@@ -252,6 +252,8 @@ class MSDeformAttnGroupedFunction(Function):
         value, spatial_shapes, level_start_index, sampling_locations, attention_weights, query_cam = ctx.saved_tensors
         bs, num_cams, num_value, heads, ch = value.shape
         _, nq, _, lvls, pts, _ = sampling_locations.shape
+        if nq == 0:   # forward launched nothing: no query reads a value, and the two other gradients are empty
+            return torch.zeros_like(value), None, None, torch.empty_like(sampling_locations), torch.empty_like(attention_weights), None
         g_value = torch.empty_like(value)
         g_loc = torch.empty_like(sampling_locations)
         g_attn = torch.empty_like(attention_weights)

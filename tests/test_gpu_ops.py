@@ -494,8 +494,8 @@ def test_daf_backward_vs_autograd_of_oracle(shape):
 
 
 def test_msda_grouped_backward_vs_autograd_of_oracle():
-    """[parity unpinned: the sampler is mmcv's] gradients of the grouped HIP sampler against torch
-    autograd through the oracle's grid_sample formulation, per camera group."""
+    """Gradients of the grouped HIP sampler against torch autograd through the oracle's grid_sample
+    formulation, per camera group (against float64, edge by edge: tests/test_samplers_backward_float64.py)."""
     R = _oracle()
     cfg = dict(bs=2, nq=41, heads=8, ch=32, shapes=[(8, 22), (4, 11), (2, 6), (1, 3)], pts=4, ncam=6)
     value, ss, lsi, loc, aw, groups = _msda_inputs(seed=13, **cfg)
