@@ -356,6 +356,24 @@ def linear_f32(x, weight, bias=None, relu=False):
     return y.reshape(x.shape[:-1] + (n,))
 
 
+def _attention_rows(t):
+    """(t, row stride) of a [bs, N, E] operand in the form csrc/attention.hip reads: fp32, unit inner stride, batches N rows
+    apart, rows a multiple of four floats apart from a 16-byte aligned start. A view that already is (a slice of a fused
+    projection) is passed as it stands; anything else is copied."""
+    bs, n = t.shape[:2]
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.stride(2) != 1 or (bs > 1 and t.stride(0) != n * t.stride(1)) or t.stride(1) % 4 or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t, t.stride(1)
+
+
+def _attention_mode(split):
+    """The `split` argument of the attention operators as the kernel family 0 / 1 / 2; None: 1 if the route is on."""
+    from . import routes
+    return (1 if routes.R.attention_split_fp16 else 0) if split is None else int(split)
+
+
 def attention_f32(q, k, v, num_heads, query_cam=None, group_start=None, split=None):
     """softmax(q k^T / sqrt(hd)) v per head, fp32 in and out, flash style (csrc/attention.hip). q [bs, Nq, E],
     k/v [bs, Nk, E] with unit inner stride (row-strided views of a fused projection are fine), E =
@@ -370,16 +388,7 @@ def attention_f32(q, k, v, num_heads, query_cam=None, group_start=None, split=No
     if hd != 64 or e != num_heads * 64 or k.shape[2] != e or v.shape[2] != e or v.shape[1] != nk:
         raise ValueError("attention_f32 needs head_dim 64 and matching q/k/v widths")
 
-    def rows(t, n):
-        if t.dtype != torch.float32:
-            t = t.float()
-        if t.stride(2) != 1 or (bs > 1 and t.stride(0) != n * t.stride(1)) or t.stride(1) % 4 or t.data_ptr() % 16:
-            t = t.contiguous()
-        return t, t.stride(1)
-
-    q, ldq = rows(q, nq)
-    k, ldk = rows(k, nk)
-    v, ldv = rows(v, nk)
+    (q, ldq), (k, ldk), (v, ldv) = (_attention_rows(t) for t in (q, k, v))
     out = torch.empty(bs, nq, e, device=q.device, dtype=torch.float32)
     if (query_cam is None) != (group_start is None):
         raise ValueError("query_cam and group_start go together")
@@ -388,8 +397,7 @@ def attention_f32(q, k, v, num_heads, query_cam=None, group_start=None, split=No
             raise ValueError("grouped attention needs i32 query_cam [N] / group_start [cams+1] over one slot set")
     if nq == 0:
         return out
-    from . import routes
-    mode = (1 if routes.R.attention_split_fp16 else 0) if split is None else int(split)
+    mode = _attention_mode(split)
     tables = (_ptr(query_cam) if query_cam is not None else None, _ptr(group_start) if group_start is not None else None)
     if mode == 2:
         status = _lib.lib().simpb_attention_split_halfs(_ptr(out), _ptr(q), _ptr(k), _ptr(v), *tables, bs, num_heads, hd, nq, nk,
@@ -415,20 +423,11 @@ def attention_select(q, k, v, k2, v2, select, num_heads, split=None):
     if select.dtype != torch.uint8 or select.numel() != bs or not select.is_contiguous():
         raise ValueError("attention_select: select must be a contiguous u8 [bs] tensor")
 
-    def rows(t):
-        n = t.shape[1]
-        if t.dtype != torch.float32:
-            t = t.float()
-        if t.stride(2) != 1 or (bs > 1 and t.stride(0) != n * t.stride(1)) or t.stride(1) % 4 or t.data_ptr() % 16:
-            t = t.contiguous()
-        return t, t.stride(1)
-
-    (q, ldq), (k, ldk), (v, ldv), (k2, ldk2), (v2, ldv2) = rows(q), rows(k), rows(v), rows(k2), rows(v2)
+    (q, ldq), (k, ldk), (v, ldv), (k2, ldk2), (v2, ldv2) = (_attention_rows(t) for t in (q, k, v, k2, v2))
     out = torch.empty(bs, nq, e, device=q.device, dtype=torch.float32)
     if nq == 0:
         return out
-    from . import routes
-    mode = (1 if routes.R.attention_split_fp16 else 0) if split is None else int(split)
+    mode = _attention_mode(split)
     _lib.check(_lib.lib().simpb_attention_select(mode, _ptr(out), _ptr(q), _ptr(k), _ptr(v), _ptr(k2), _ptr(v2), _ptr(select), bs,
                                                  num_heads, hd, nq, k.shape[1], k2.shape[1], ldq, ldk, ldv, ldk2, ldv2, e,
                                                  1.0 / (hd ** 0.5), _stream()), "simpb_attention_select")

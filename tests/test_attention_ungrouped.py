@@ -216,8 +216,8 @@ def test_decay_and_grow_move_the_running_maximum_as_described(kind, waves, nk):
 
 
 def _is_refused(a, entry):
-    """The validation of csrc/attention.hip (attention_launch, and the selector branch of simpb_attention_select) restated on
-    the host: is call `a` turned away before any HIP call? The refusal test asserts this of every call BEFORE it makes it, so a
+    """The validation of csrc/attention.hip (check_args, with the second set's rules for the selector of
+    simpb_attention_select) restated on the host: is call `a` turned away before any HIP call? The refusal test asserts this of every call BEFORE it makes it, so a
     case that is in fact a valid call fails the test on the host instead of launching on a placeholder address where a device
     is present. entry: "tables" (the three single-set entry points), "select_null" (no selector, takes no tables) or "select"."""
     e = a["heads"] * 64
