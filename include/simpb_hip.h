@@ -358,6 +358,45 @@ int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table, void* mid
                                    int num_cams, int num_images, int out_height, int out_width, int kx_len, int x_len, int ky_len,
                                    int y_len, int mid_rows, int swap_rb, void* stream);
 
+/* The same ingest for cameras with a MOUNT ROLL: the fourth step of the reference's ResizeCropFlipImage._img_transform,
+ * PIL.Image.rotate(r) with its defaults (augment.py:92,105), behind resize, crop and flip: a nearest-neighbour inverse affine
+ * map in 16.16 fixed point about the image centre. The caller reduces a camera's roll to six integers a0 .. a5
+ * (simpb_amd/preprocess.py:roll_integers restates Pillow's rule, its transposes for 180 and square 90 / 270 degrees included);
+ * the kernels know the six integers and nothing else. With L the h x w image the entry points above compute BEFORE the table
+ * (L[y][x][c], a byte), output pixel (x, y) is
+ *   xin = (a2 + y * a1 + x * a0) >> 16,  yin = (a5 + y * a4 + x * a3) >> 16          (64-bit, arithmetic shift)
+ *   out[y][x][c] = lut[c][L[yin][xin][swap_rb ? 2 - c : c]]  where 0 <= xin < out_width and 0 <= yin < out_height,
+ *   out[y][x][c] = lut[c][0] (black, normalised) elsewhere;  out[y][x][3] = 0.
+ * The row (65536, 0, 32768, 0, 65536, 32768) is the identity and gives the level entry point's bits.
+ * The roll is a gather inside the vertical pass: the horizontal pass, `mid` and the row range src_row0 / src_rows are the
+ * level path's own (a roll maps rows of the cropped image onto rows of the cropped image); still two launches and one
+ * intermediate. The range test on (xin, yin) comes first and every index behind it is clamped as in the level pass: a wrong
+ * table gives wrong pixels, never an access outside mid, ky, ylo or yn.
+ *
+ * simpb_preprocess_roll_nhwc4_f16: the arguments of simpb_preprocess_planes_nhwc4_f16 (every format, tight or padded, a
+ * contiguous batch or an address table), then
+ *   roll       HOST int32 [roll_cams][6], read before the call returns and handed to the kernel by value
+ *   roll_cams  1 .. SIMPB_RIG_MAX_CAMS: image n takes row n % roll_cams (1: one roll for all images)
+ * simpb_preprocess_rig_roll_nhwc4_f16: the arguments of simpb_preprocess_rig_nhwc4_f16, then roll HOST int32 [num_cams][6]:
+ * camera c takes row c; a level camera of a mixed rig takes the identity row; a skipped image (address 0) stays f16 zeros.
+ * SIMPB_EINVAL, and nothing launched or written: whatever the level form refuses; a null roll; roll_cams outside 1..16; an
+ * out_height or out_width above SIMPB_PREPROCESS_MAX_ROLL_SIZE (Pillow leaves its fixed-point path where a corner coordinate
+ * reaches 32768; below this size that cannot happen). Two launches on `stream`; no allocation, no synchronisation (graph
+ * capture safe). The 2D records (simpb_decode2d_record*) do not change: the reference's decode_box2d does not look at rotate. */
+#define SIMPB_PREPROCESS_MAX_ROLL_SIZE 8192
+int simpb_preprocess_roll_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
+                                    const int* xlo, const int* xn, const int* ky, const int* ylo, const int* yn, const void* lut,
+                                    int num_images, int src_height, int src_width, int out_height, int out_width, int taps_x,
+                                    int taps_y, int src_row0, int src_rows, int flip, int swap_rb, int format, long long pitch,
+                                    long long chroma_pitch, long long chroma_offset, long long chroma2_offset,
+                                    long long image_stride, int yoff, int iy, int irv, int igu, int igv, int ibu, const int* roll,
+                                    int roll_cams, void* stream);
+int simpb_preprocess_rig_roll_nhwc4_f16(void* out, const void* image_table, void* mid, const int* kx, const int* xlo,
+                                        const int* xn, const int* ky, const int* ylo, const int* yn, const void* lut,
+                                        const simpb_rig_camera* cams, int num_cams, int num_images, int out_height, int out_width,
+                                        int kx_len, int x_len, int ky_len, int y_len, int mid_rows, int swap_rb, const int* roll,
+                                        void* stream);
+
 /* Grouped small GEMM of the decoder: up to 4 independent problems per launch, each
  *   y[M, 0:N] (row stride ldy) = relu?( [x0 | x1 | ...][M, K] . w[N, K]^T (row stride ldw) + bias[N] )
  * where x is given as up to 4 column segments (pointer, row stride, width; widths sum to K). This is

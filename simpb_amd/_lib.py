@@ -74,6 +74,9 @@ SIGNATURES = {
     "simpb_preprocess_planes_nhwc4_f16": ([_P] * 11 + [_I] * 12 + [_LL] * 5 + [_I] * 6 + [_P], _I),
     "simpb_preprocess_mid_pitch": ([_I], _I),
     "simpb_preprocess_rig_nhwc4_f16": ([_P] * 10 + [ctypes.POINTER(RigCamera)] + [_I] * 10 + [_P], _I),
+    # the two above with a camera roll: + host int32 [cams][6] (and, uniform, the number of rows)
+    "simpb_preprocess_roll_nhwc4_f16": ([_P] * 11 + [_I] * 12 + [_LL] * 5 + [_I] * 6 + [ctypes.POINTER(_I), _I, _P], _I),
+    "simpb_preprocess_rig_roll_nhwc4_f16": ([_P] * 10 + [ctypes.POINTER(RigCamera)] + [_I] * 10 + [ctypes.POINTER(_I), _P], _I),
     "simpb_linear_f16in_split": ([_P] * 5 + [_I] * 3 + [_P], _I),
     "simpb_format_tokens": ([_P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
     "simpb_attention_f32": ([_P] * 6 + [_I] * 9 + [_F, _P], _I),

@@ -30,6 +30,9 @@
 // What other producers deliver (simpb_preprocess_planes_nhwc4_f16, and per camera of a rig) are further branches of
 // stage_bgr_row and nothing else: planar 4:2:0 (three planes: a software decoder), packed 4:2:2 (YUYV / UYVY: a camera without
 // a codec) by the same integer rule with replicated chroma, and RGB / BGRA / RGBA as a byte permutation into the (B, G, R) row.
+// A camera's mount ROLL (the reference's img.rotate: simpb_preprocess_roll_nhwc4_f16, simpb_preprocess_rig_roll_nhwc4_f16) is a
+// second form of the vertical pass, a gather by six integers per camera (resample_cols_lut_roll_row); the level forms above
+// are launched as ever where no camera is rolled.
 // Every load of a thread is retired before its stores are issued (store_fence.h).
 #include <hip/hip_runtime.h>
 #include "../../include/simpb_hip.h"
@@ -463,6 +466,124 @@ __global__ __launch_bounds__(kThreads) void resample_cols_lut_rig_kernel(_Float1
                         ylo + c.y_offset, yn + c.y_offset, lut, c.src_row0, c.src_rows, w, c.taps_y, swap_rb, pitch, table[n] == 0ull);
 }
 
+// A camera's MOUNT ROLL (simpb_preprocess_roll_nhwc4_f16, simpb_preprocess_rig_roll_nhwc4_f16): the reference's fourth step,
+// PIL.Image.rotate(r) with its defaults, is a nearest-neighbour inverse affine map in 16.16 fixed point over the image that
+// resize, crop and flip give. Output pixel (x, y) is the level pass's pixel (xin, yin),
+//   xin = (a2 + y * a1 + x * a0) >> 16,  yin = (a5 + y * a4 + x * a3) >> 16     (64-bit, arithmetic shift)
+// where 0 <= xin < w and 0 <= yin < h, and black -- lut[c][0] -- elsewhere. The roll maps rows of the cropped image onto rows
+// of the cropped image, so the horizontal pass and `mid` are the level path's own, and the roll is a GATHER in the vertical
+// pass: the thread still owns 4 neighbouring output pixels and writes two 16-byte stores, but each pixel brings its own row
+// of ky and its own column of mid. The six integers per camera are the host's (simpb_amd/preprocess.py:roll_integers) and
+// travel by value; the kernel knows nothing else of the angle. (65536, 0, 32768, 0, 65536, 32768) is the identity.
+struct RollTable { int a[SIMPB_RIG_MAX_CAMS][6]; };
+
+constexpr int kMaxRollSize = SIMPB_PREPROCESS_MAX_ROLL_SIZE;
+
+// One output row of one image, the rolled vertical pass + table (arguments as resample_cols_lut_row; `a`: the image's six
+// integers, uniform over the workgroup):
+//   out[y][x][c] = lut[c][clip8(2^21 + sum_t mid[ylo[yin] - row0 + t][xin][swap ? 2 - c : c] * ky[yin][t])], out[..][3] = 0
+// The range test on (xin, yin) comes first; behind it the tap count, `first`, the row and the dword index are clamped as the
+// level pass clamps them, and a pixel out of range (or a tap past its pixel's count) loads from row / column 0 with a
+// coefficient of 0: a wrong table gives wrong pixels, never an access outside mid, ky, ylo or yn. The three bytes of a pixel
+// start at byte 3 * xin of a row, at any alignment: they are cut out of the aligned dword that holds the first and the one
+// behind it (the row's last dword again where there is none; 3 * xin + 2 < 3 * w <= pitch, so the bytes wanted lie in the two).
+__device__ __forceinline__ void resample_cols_lut_roll_row(_Float16* __restrict__ out_image, const unsigned char* __restrict__ mid_image,
+                                                           const int* __restrict__ ky, const int* __restrict__ ylo,
+                                                           const int* __restrict__ yn, const _Float16* __restrict__ lut, int row0,
+                                                           int rows, int h, int w, int taps, int swap_rb, int pitch, bool zero,
+                                                           const int* a) {
+  __shared__ _Float16 s_lut[3 * 256];
+  const int tid = threadIdx.x, y = blockIdx.y;
+  for (int i = tid; i < 3 * 256; i += kThreads) s_lut[i] = lut[i];
+  __syncthreads();
+  const int g = blockIdx.x * kThreads + tid;   // group of 4 output pixels
+  if (4 * g >= w) return;
+  const int pitch4 = pitch >> 2;
+  const long long a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4], a5 = a[5];
+  int cnt[4], first[4], dword[4], shift[4], krow[4];
+  bool inside[4];
+  int most = 0;
+#pragma unroll
+  for (int px = 0; px < 4; ++px) {
+    const int x = 4 * g + px;
+    const long long xs = (a2 + y * a1 + x * a0) >> 16, ys = (a5 + y * a4 + x * a3) >> 16;
+    inside[px] = !zero && xs >= 0 && xs < w && ys >= 0 && ys < h;
+    const int xin = inside[px] ? (int)xs : 0, yin = inside[px] ? (int)ys : 0;
+    cnt[px] = inside[px] ? max(min(min(yn[yin], taps), rows), 0) : 0;
+    first[px] = min(max(ylo[yin] - row0, 0), rows - cnt[px]);
+    dword[px] = (3 * xin) >> 2;
+    shift[px] = 8 * ((3 * xin) & 3);
+    krow[px] = yin * taps;   // (h <= 8192, taps <= 64)
+    most = max(most, cnt[px]);
+  }
+  int acc[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) acc[i] = 1 << (kPrecision - 1);
+  for (int t = 0; t < most; ++t) {   // (most <= taps: ky[krow + t] lies in the pixel's own row of ky)
+#pragma unroll
+    for (int px = 0; px < 4; ++px) {
+      const unsigned int* p = reinterpret_cast<const unsigned int*>(mid_image + (size_t)min(first[px] + t, rows - 1) * pitch);
+      const unsigned int d0 = p[dword[px]], d1 = p[min(dword[px] + 1, pitch4 - 1)];
+      const int c = t < cnt[px] ? ky[krow[px] + t] : 0;
+      const unsigned int v = (unsigned int)((((unsigned long long)d1 << 32) | d0) >> shift[px]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) acc[px * 3 + i] += (int)((v >> (8 * i)) & 255u) * c;
+    }
+  }
+  h8 v[2];
+#pragma unroll
+  for (int px = 0; px < 4; ++px) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int ci = swap_rb ? 2 - c : c;
+      v[px >> 1][(px & 1) * 4 + c] = zero ? (_Float16)0.f : s_lut[c * 256 + (inside[px] ? clip8(acc[px * 3 + ci]) : 0)];
+    }
+    v[px >> 1][(px & 1) * 4 + 3] = (_Float16)0.f;
+  }
+  simpb::pin(v[0]);
+  simpb::pin(v[1]);
+  simpb::loads_retired();
+  _Float16* o = out_image + ((size_t)y * w + 4 * g) * 4;
+  if (4 * g + 4 <= w) {
+    *reinterpret_cast<h8*>(o) = v[0];
+    *reinterpret_cast<h8*>(o + 8) = v[1];
+  } else {   // the last, partial group of a width that is no multiple of 4
+#pragma unroll
+    for (int px = 0; px < 3; ++px)
+      if (4 * g + px < w) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[px * 4 + c] = v[px >> 1][(px & 1) * 4 + c];
+      }
+  }
+}
+
+// The rolled vertical pass of a uniform batch: image n takes row n % roll_cams of the table.
+__global__ __launch_bounds__(kThreads) void resample_cols_lut_roll_kernel(_Float16* __restrict__ out, const unsigned char* __restrict__ mid,
+                                                                          const int* __restrict__ ky, const int* __restrict__ ylo,
+                                                                          const int* __restrict__ yn, const _Float16* __restrict__ lut,
+                                                                          int row0, int rows, int h, int w, int taps, int swap_rb,
+                                                                          int pitch, RollTable roll, int roll_cams) {
+  const int n = blockIdx.z;
+  resample_cols_lut_roll_row(out + (size_t)n * h * w * 4, mid + (size_t)n * rows * pitch, ky, ylo, yn, lut, row0, rows, h, w, taps,
+                             swap_rb, pitch, false, roll.a[n % roll_cams]);
+}
+
+// The rolled vertical pass of a rig: resample_cols_lut_rig_kernel with camera c's six integers.
+__global__ __launch_bounds__(kThreads) void resample_cols_lut_rig_roll_kernel(_Float16* __restrict__ out,
+                                                                              const unsigned char* __restrict__ mid,
+                                                                              const unsigned long long* __restrict__ table, Rig rig,
+                                                                              int num_cams, const int* __restrict__ ky,
+                                                                              const int* __restrict__ ylo, const int* __restrict__ yn,
+                                                                              const _Float16* __restrict__ lut, int h, int w,
+                                                                              int swap_rb, int pitch, int mid_rows, RollTable roll) {
+  const int n = blockIdx.z;
+  const int stream = n / num_cams, cam = n - stream * num_cams;
+  const simpb_rig_camera& c = rig.cam[cam];
+  resample_cols_lut_roll_row(out + (size_t)n * h * w * 4, mid + ((size_t)stream * mid_rows + c.mid_row) * pitch, ky + c.ky_offset,
+                             ylo + c.y_offset, yn + c.y_offset, lut, c.src_row0, c.src_rows, h, w, c.taps_y, swap_rb, pitch,
+                             table[n] == 0ull, roll.a[cam]);
+}
+
 }  // namespace
 
 // bytes of one intermediate row: whole groups of 4 pixels, rounded up to 16 bytes
@@ -489,20 +610,28 @@ static bool bad_arguments(const void* out, const void* src, const void* mid, con
   return (reinterpret_cast<size_t>(lut) & 1) != 0;
 }
 
-// the vertical pass + table, and the status of both launches
+// the vertical pass + table (rolled where `roll` is given: image n takes row n % roll_cams), and the status of both launches
 static int finish_vertical(void* out, const void* mid, const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
-                           int out_height, int out_width, int taps_y, int src_row0, int src_rows, int swap_rb, int pitch, hipStream_t s) {
+                           int out_height, int out_width, int taps_y, int src_row0, int src_rows, int swap_rb, int pitch, hipStream_t s,
+                           const RollTable* roll = nullptr, int roll_cams = 0) {
   const int groups = (out_width + 3) / 4;
-  hipLaunchKernelGGL(resample_cols_lut_kernel, dim3((groups + kThreads - 1) / kThreads, out_height, num_images), dim3(kThreads), 0, s,
-                     static_cast<_Float16*>(out), static_cast<const unsigned char*>(mid), ky, ylo, yn,
-                     static_cast<const _Float16*>(lut), src_row0, src_rows, out_height, out_width, taps_y, swap_rb ? 1 : 0, pitch);
+  const dim3 grid((groups + kThreads - 1) / kThreads, out_height, num_images);
+  if (roll)
+    hipLaunchKernelGGL(resample_cols_lut_roll_kernel, grid, dim3(kThreads), 0, s, static_cast<_Float16*>(out),
+                       static_cast<const unsigned char*>(mid), ky, ylo, yn, static_cast<const _Float16*>(lut), src_row0, src_rows,
+                       out_height, out_width, taps_y, swap_rb ? 1 : 0, pitch, *roll, roll_cams);
+  else
+    hipLaunchKernelGGL(resample_cols_lut_kernel, grid, dim3(kThreads), 0, s, static_cast<_Float16*>(out),
+                       static_cast<const unsigned char*>(mid), ky, ylo, yn, static_cast<const _Float16*>(lut), src_row0, src_rows,
+                       out_height, out_width, taps_y, swap_rb ? 1 : 0, pitch);
   return simpb_check_launch();
 }
 
 // the horizontal pass of one source format on a checked surface, then the vertical pass
 static int launch_surface(int format, void* out, const Surface& sf, void* mid, const int* kx, const int* xlo, const int* xn, const int* ky,
                           const int* ylo, const int* yn, const void* lut, int num_images, int src_width, int out_height, int out_width,
-                          int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb, const YuvCoeffs& q, void* stream) {
+                          int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb, const YuvCoeffs& q, void* stream,
+                          const RollTable* roll, int roll_cams) {
   const int pitch = mid_pitch(out_width);
   hipStream_t s = static_cast<hipStream_t>(stream);
   (void)hipGetLastError();
@@ -524,7 +653,8 @@ static int launch_surface(int format, void* out, const Surface& sf, void* mid, c
     default: SIMPB_ROWS(kP010); break;
   }
 #undef SIMPB_ROWS
-  return finish_vertical(out, mid, ky, ylo, yn, lut, num_images, out_height, out_width, taps_y, src_row0, src_rows, swap_rb, pitch, s);
+  return finish_vertical(out, mid, ky, ylo, yn, lut, num_images, out_height, out_width, taps_y, src_row0, src_rows, swap_rb, pitch, s,
+                         roll, roll_cams);
 }
 
 extern "C" int simpb_preprocess_u8_nhwc4_f16(void* out, const void* src, void* mid, const int* kx, const int* xlo, const int* xn,
@@ -600,13 +730,13 @@ static long long surface_extent(int format, int src_height, int src_width, long 
   return (chroma_offset > chroma2_offset ? chroma_offset : chroma2_offset) + span;
 }
 
-// what both surface entry points do behind their own check of `format`
+// what the surface entry points do behind their own check of `format` (roll: the rolled one's table, or null)
 static int preprocess_surface(void* out, const void* src, const void* image_table, void* mid, const int* kx, const int* xlo,
                               const int* xn, const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
                               int src_height, int src_width, int out_height, int out_width, int taps_x, int taps_y, int src_row0,
                               int src_rows, int flip, int swap_rb, int format, long long pitch, long long chroma_pitch,
                               long long chroma_offset, long long chroma2_offset, long long image_stride, const YuvCoeffs& q,
-                              void* stream) {
+                              void* stream, const RollTable* roll = nullptr, int roll_cams = 0) {
   if ((src != nullptr) == (image_table != nullptr)) return SIMPB_EINVAL;   // exactly one form of the images
   if (bad_arguments(out, src ? src : image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height,
                     out_width, taps_x, taps_y, src_row0, src_rows))
@@ -623,7 +753,7 @@ static int preprocess_surface(void* out, const void* src, const void* image_tabl
   const Surface sf = {static_cast<const unsigned char*>(src), static_cast<const unsigned long long*>(image_table), image_stride,
                       chroma_offset, pitch, chroma_pitch, chroma2_offset};
   return launch_surface(format, out, sf, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_width, out_height, out_width, taps_x, taps_y,
-                        src_row0, src_rows, flip, swap_rb, q, stream);
+                        src_row0, src_rows, flip, swap_rb, q, stream, roll, roll_cams);
 }
 
 extern "C" int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
@@ -652,11 +782,33 @@ extern "C" int simpb_preprocess_planes_nhwc4_f16(void* out, const void* src, con
                             chroma2_offset, image_stride, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream);
 }
 
-extern "C" int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table, void* mid, const int* kx, const int* xlo,
-                                              const int* xn, const int* ky, const int* ylo, const int* yn, const void* lut,
-                                              const simpb_rig_camera* cams, int num_cams, int num_images, int out_height,
-                                              int out_width, int kx_len, int x_len, int ky_len, int y_len, int mid_rows, int swap_rb,
-                                              void* stream) {
+// what both rolled entry points refuse on top of their level forms (before any HIP call); `table` takes the rows otherwise
+static bool bad_roll(RollTable& table, const int* roll, int roll_cams, int out_height, int out_width) {
+  if (!roll || roll_cams < 1 || roll_cams > SIMPB_RIG_MAX_CAMS || out_height > kMaxRollSize || out_width > kMaxRollSize) return true;
+  table = RollTable{};
+  for (int i = 0; i < roll_cams * 6; ++i) table.a[i / 6][i % 6] = roll[i];
+  return false;
+}
+
+extern "C" int simpb_preprocess_roll_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
+                                               const int* xlo, const int* xn, const int* ky, const int* ylo, const int* yn,
+                                               const void* lut, int num_images, int src_height, int src_width, int out_height,
+                                               int out_width, int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb,
+                                               int format, long long pitch, long long chroma_pitch, long long chroma_offset,
+                                               long long chroma2_offset, long long image_stride, int yoff, int iy, int irv, int igu,
+                                               int igv, int ibu, const int* roll, int roll_cams, void* stream) {
+  RollTable table;
+  if (bad_roll(table, roll, roll_cams, out_height, out_width) || !known_format(format)) return SIMPB_EINVAL;
+  return preprocess_surface(out, src, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height,
+                            out_width, taps_x, taps_y, src_row0, src_rows, flip, swap_rb, format, pitch, chroma_pitch, chroma_offset,
+                            chroma2_offset, image_stride, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream, &table, roll_cams);
+}
+
+// what both rig entry points do (roll: the rolled one's table, one row per camera, or null)
+static int preprocess_rig(void* out, const void* image_table, void* mid, const int* kx, const int* xlo, const int* xn, const int* ky,
+                          const int* ylo, const int* yn, const void* lut, const simpb_rig_camera* cams, int num_cams, int num_images,
+                          int out_height, int out_width, int kx_len, int x_len, int ky_len, int y_len, int mid_rows, int swap_rb,
+                          void* stream, const RollTable* roll) {
   if (!cams || num_cams <= 0 || num_cams > SIMPB_RIG_MAX_CAMS || num_images <= 0 || num_images % num_cams) return SIMPB_EINVAL;
   if (kx_len <= 0 || x_len <= 0 || ky_len <= 0 || y_len <= 0 || mid_rows <= 0) return SIMPB_EINVAL;
   if (reinterpret_cast<size_t>(image_table) & 7) return SIMPB_EINVAL;
@@ -710,8 +862,34 @@ extern "C" int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table
                      (size_t)(lds.src_bytes + lds.out_bytes + 2 * lds.plane_bytes), s, static_cast<unsigned char*>(mid), table, rig,
                      num_cams, kx, xlo, xn, out_width, pitch, mid_rows, lds);
   const int groups = (out_width + 3) / 4;
-  hipLaunchKernelGGL(resample_cols_lut_rig_kernel, dim3((groups + kThreads - 1) / kThreads, out_height, num_images), dim3(kThreads), 0, s,
-                     static_cast<_Float16*>(out), static_cast<const unsigned char*>(mid), table, rig, num_cams, ky, ylo, yn,
-                     static_cast<const _Float16*>(lut), out_height, out_width, swap_rb ? 1 : 0, pitch, mid_rows);
+  const dim3 grid((groups + kThreads - 1) / kThreads, out_height, num_images);
+  if (roll)
+    hipLaunchKernelGGL(resample_cols_lut_rig_roll_kernel, grid, dim3(kThreads), 0, s, static_cast<_Float16*>(out),
+                       static_cast<const unsigned char*>(mid), table, rig, num_cams, ky, ylo, yn, static_cast<const _Float16*>(lut),
+                       out_height, out_width, swap_rb ? 1 : 0, pitch, mid_rows, *roll);
+  else
+    hipLaunchKernelGGL(resample_cols_lut_rig_kernel, grid, dim3(kThreads), 0, s, static_cast<_Float16*>(out),
+                       static_cast<const unsigned char*>(mid), table, rig, num_cams, ky, ylo, yn, static_cast<const _Float16*>(lut),
+                       out_height, out_width, swap_rb ? 1 : 0, pitch, mid_rows);
   return simpb_check_launch();
+}
+
+extern "C" int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table, void* mid, const int* kx, const int* xlo,
+                                              const int* xn, const int* ky, const int* ylo, const int* yn, const void* lut,
+                                              const simpb_rig_camera* cams, int num_cams, int num_images, int out_height,
+                                              int out_width, int kx_len, int x_len, int ky_len, int y_len, int mid_rows, int swap_rb,
+                                              void* stream) {
+  return preprocess_rig(out, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, cams, num_cams, num_images, out_height, out_width, kx_len,
+                        x_len, ky_len, y_len, mid_rows, swap_rb, stream, nullptr);
+}
+
+extern "C" int simpb_preprocess_rig_roll_nhwc4_f16(void* out, const void* image_table, void* mid, const int* kx, const int* xlo,
+                                                   const int* xn, const int* ky, const int* ylo, const int* yn, const void* lut,
+                                                   const simpb_rig_camera* cams, int num_cams, int num_images, int out_height,
+                                                   int out_width, int kx_len, int x_len, int ky_len, int y_len, int mid_rows,
+                                                   int swap_rb, const int* roll, void* stream) {
+  RollTable table;
+  if (bad_roll(table, roll, num_cams, out_height, out_width)) return SIMPB_EINVAL;
+  return preprocess_rig(out, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, cams, num_cams, num_images, out_height, out_width, kx_len,
+                        x_len, ky_len, y_len, mid_rows, swap_rb, stream, &table);
 }

@@ -23,7 +23,11 @@ Frames of the other producers in a vehicle are taken as they lie as well: a soft
 "yvu420p" = YV12), the packed 4:2:2 of a camera that reaches the host without a codec ("yuyv", "uyvy"), and the RGB-order and
 4-byte pixels of loaders, ISPs and compositors ("rgb", "bgra", "rgba"). The YCbCr ones follow `yuv_coefficients` with
 replicated chroma, the others are a byte permutation: no new arithmetic, and the output equals the BGR plan's on the
-host-converted frames bit for bit."""
+host-converted frames bit for bit.
+
+A camera's mount roll -- the reference function's fourth step, `img.rotate(rotate)` (augment.py:92,105) -- is `roll=` of a
+ResamplePlan or CameraSource: `roll_integers` reduces it to the six 16.16 fixed-point integers of Pillow's nearest-neighbour affine
+map, which the vertical pass applies as a gather; the aug_config's own `rotate` stays refused (0 in the reference's test mode)."""
 import ctypes
 import math
 
@@ -338,6 +342,82 @@ def resolve_aug(src_hw, aug_config):
     return dims, crop, bool(aug.get("flip", False))
 
 
+# ---------------------------------------------------------------------- a camera's mount roll (the reference's img.rotate)
+ROLL_MAX_SIZE = 8192                                  # SIMPB_PREPROCESS_MAX_ROLL_SIZE of include/simpb_hip.h
+ROLL_IDENTITY = (65536, 0, 32768, 0, 65536, 32768)    # the six integers of a level camera
+
+
+def check_roll(roll):
+    """A camera's roll in degrees as a float; ValueError for anything but a finite real number (a bool is not one)."""
+    if isinstance(roll, (bool, np.bool_)) or not isinstance(roll, (int, float, np.integer, np.floating)) or not math.isfinite(roll):
+        raise ValueError(f"a camera's roll is a finite real number of degrees, got {roll!r}")
+    return float(roll)
+
+
+def is_rolled(roll):
+    """False where `Image.rotate(roll)` is a copy (roll % 360 == 0): that camera takes the level path."""
+    return check_roll(roll) % 360.0 != 0.0
+
+
+def roll_integers(roll, out_hw):
+    """The six int32 (a0 .. a5) that `PIL.Image.rotate(roll)` with its defaults (nearest neighbour, no expand, about the image
+    centre) comes to on an image of out_hw = (h, w): output pixel (x, y) is input pixel
+
+        xin = (a2 + y * a1 + x * a0) >> 16,  yin = (a5 + y * a4 + x * a3) >> 16     (arithmetic shift)
+
+    where 0 <= xin < w and 0 <= yin < h, and black elsewhere. `roll` is in degrees, positive counter-clockwise on screen.
+    Restated from Pillow: Image.rotate (the matrix, rounded to 15 decimals, and the transposes it takes for 180 degrees always
+    and for 90 / 270 degrees on a square image) and affine_fixed of src/libImaging/Geometry.c (FIX(v) = floor(v * 65536 + 0.5),
+    the half-pixel offset folded into a2 / a5). roll % 360 == 0 gives ROLL_IDENTITY. Pillow leaves fixed point where a corner's
+    source coordinate reaches 32768: a rolled image is limited to ROLL_MAX_SIZE a side, where that cannot happen (|coordinate|
+    <= 3 * 8192 / 2 + 8192 * sqrt(2) < 32768)."""
+    angle = check_roll(roll) % 360.0
+    h, w = int(out_hw[0]), int(out_hw[1])
+    if angle == 0.0:
+        return ROLL_IDENTITY
+    if h <= 0 or w <= 0 or h > ROLL_MAX_SIZE or w > ROLL_MAX_SIZE:
+        raise ValueError(f"a rolled image is 1 .. {ROLL_MAX_SIZE} pixels a side (Pillow's fixed-point range), got {w} x {h}")
+    one, half = 1 << 16, 1 << 15
+    if angle == 180.0:                       # Transpose.ROTATE_180: (x, y) <- (w - 1 - x, h - 1 - y)
+        return (-one, 0, (w << 16) - half, 0, -one, (h << 16) - half)
+    if angle == 90.0 and w == h:             # Transpose.ROTATE_90: (x, y) <- (w - 1 - y, x)
+        return (0, -one, (w << 16) - half, one, 0, half)
+    if angle == 270.0 and w == h:            # Transpose.ROTATE_270: (x, y) <- (y, h - 1 - x)
+        return (0, one, half, -one, 0, (h << 16) - half)
+    t = -math.radians(angle)
+    m = [round(math.cos(t), 15), round(math.sin(t), 15), 0.0, round(-math.sin(t), 15), round(math.cos(t), 15), 0.0]
+    cx, cy = w / 2, h / 2
+    m[2] = m[0] * -cx + m[1] * -cy + m[2]
+    m[5] = m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    fix = lambda v: int(math.floor(v * 65536.0 + 0.5))   # noqa: E731
+    ints = (fix(m[0]), fix(m[1]), fix(m[2] + m[0] * 0.5 + m[1] * 0.5), fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5))
+    assert all(-(1 << 31) <= v < (1 << 31) for v in ints)
+    return ints
+
+
+def roll_matrix(roll, out_hw):
+    """float64 [3, 3]: the rotation block of `_img_transform`'s matrix (augment.py:119-128) for `roll` degrees about
+    (crop_w / 2, crop_h / 2), with the reference's signs; it multiplies resize, crop and flip from the left."""
+    rad = check_roll(roll) / 180 * np.pi
+    m = np.array([[np.cos(rad), np.sin(rad), 0], [-np.sin(rad), np.cos(rad), 0], [0, 0, 1]])
+    centre = np.array([out_hw[1], out_hw[0]]) / 2
+    m[:2, 2] = -m[:2, :2] @ centre + centre
+    return m
+
+
+def aug_matrix(aug_config, crop, flip, roll, out_hw):
+    """float64 [3, 3]: what `ResizeCropFlipImage._img_transform` returns (augment.py:111-129) for a resolved crop / flip and a
+    roll: resize on the diagonal, minus the crop origin, the flip, then the rotation block."""
+    m = np.eye(3)
+    m[:2, :2] *= (aug_config or {}).get("resize", 1)
+    m[:2, 2] -= np.array(crop[:2])
+    if flip:
+        m = np.array([[-1, 0, crop[2] - crop[0]], [0, 1, 0], [0, 0, 1]]) @ m
+    return roll_matrix(roll, out_hw) @ m if roll != 0 else m
+
+
 def check_surfaces(tensors, surface):
     """A flat list of tensors, one surface (SurfaceLayout `surface`) each: u8, contiguous, all on one GPU, and each tensor's
     storage holds the image's bytes up to its last sample from data_ptr() on. Any base alignment is taken (an even one for
@@ -367,17 +447,32 @@ def check_surfaces(tensors, surface):
     return device
 
 
-def plan_key(src_hw, aug_config, frame_format="bgr", colour="jfif", layout=None):
+def _rolls(roll):
+    """`roll` of a ResamplePlan as a tuple of floats: a number (one roll for every image), or a sequence of 1 .. 16 of them
+    (image n takes entry n % len: one per camera of a runner's [bs, cams] batch)."""
+    if isinstance(roll, (list, tuple, np.ndarray)):
+        rolls = tuple(check_roll(r) for r in roll)
+        if not 1 <= len(rolls) <= RIG_MAX_CAMS:
+            raise ValueError(f"a list of rolls has 1 .. {RIG_MAX_CAMS} entries (one per camera), got {len(rolls)}")
+        return rolls
+    return (check_roll(roll),)
+
+
+def plan_key(src_hw, aug_config, frame_format="bgr", colour="jfif", layout=None, roll=0.0):
     """What a ResamplePlan depends on: a frame whose key differs must not run on the plan's tables (nor a frame of another
     format or colour standard on the plan's kernel; the standard says nothing about BGR, RGB, BGRA or RGBA frames and is left
     out of their key).
     `layout` (a SurfaceLayout or a dict of its keyword arguments) adds its own key unless it is tight: a frame never runs on a
-    plan, or a captured graph, made for another layout."""
+    plan, or a captured graph, made for another layout.
+    `roll` (degrees; a number or one per camera) adds its own entry where a camera is rolled (roll % 360 != 0), and nothing
+    otherwise: every key of a level plan is what it was, and a frame never runs on the integers of another roll."""
     _check_format(frame_format, colour)
     dims, crop, flip = resolve_aug(src_hw, aug_config)
     key = (int(src_hw[0]), int(src_hw[1]), dims, crop, flip, frame_format, colour if frame_format not in RGB_ORDER else None)
     extra = None if layout is None else SurfaceLayout.make(layout, src_hw, frame_format).key
-    return key if extra is None else key + (extra,)
+    key = key if extra is None else key + (extra,)
+    rolls = _rolls(roll)
+    return key + (("roll",) + tuple(r % 360.0 for r in rolls),) if any(is_rolled(r) for r in rolls) else key
 
 
 def _device(device):
@@ -410,9 +505,16 @@ class ResamplePlan:
     "uyvy" (packed 4:2:2): u8 [Hs, Ws, 2], groups of (Y0, Cb, Y1, Cr) / (Cb, Y0, Cr, Y1), the pair belongs to columns 2j, 2j + 1
     of its own row; Ws even, any Hs. "rgb": u8 [Hs, Ws, 3], R first. "bgra" / "rgba": u8 [Hs, Ws, 4], byte 3 ignored. The
     YCbCr forms follow `colour` like nv12; the others are a byte permutation into the staged (B, G, R) row and `colour` is not
-    looked at. All take `layout` (SurfaceLayout has their fields) and `run_surfaces`."""
+    looked at. All take `layout` (SurfaceLayout has their fields) and `run_surfaces`.
 
-    def __init__(self, src_hw, aug_config=None, img_norm_cfg=None, frame_format="bgr", colour="jfif", layout=None):
+    `roll`: the camera's mount roll in degrees, positive counter-clockwise on screen -- the reference's fourth step,
+    `img.rotate(rotate)` (augment.py:92,105), behind resize, crop and flip, with Pillow's bytes (`roll_integers`); black
+    corners are normalised like any pixel. A number, or one per camera (image n takes roll[n % len]). It is a property of the
+    mount and is given beside the aug_config, whose own `rotate` stays refused (0 in the reference's test mode). A plan
+    without a rolled camera launches exactly what it launched before. The 2D records do not change: the reference's
+    decode_box2d (detection3d/decoder.py:36-51) does not look at rotate."""
+
+    def __init__(self, src_hw, aug_config=None, img_norm_cfg=None, frame_format="bgr", colour="jfif", layout=None, roll=0.0):
         self.src_hw = (int(src_hw[0]), int(src_hw[1]))
         _check_format(frame_format, colour)
         self.frame_format, self.colour = frame_format, colour
@@ -420,12 +522,17 @@ class ResamplePlan:
         self.frame_shape = frame_shape(self.src_hw, frame_format) if self.surface.tight else (self.surface.image_bytes,)
         self.yuv = None if frame_format in RGB_ORDER else yuv_coefficients(colour)
         self.resize_dims, self.crop, self.flip = resolve_aug(self.src_hw, aug_config)
-        self.key = plan_key(self.src_hw, aug_config, frame_format, colour, self.surface)
+        self.rolls = _rolls(roll)
+        self.rolled = any(is_rolled(r) for r in self.rolls)
+        self.aug_config = dict(aug_config or {})
+        self.key = plan_key(self.src_hw, aug_config, frame_format, colour, self.surface, roll)
         cfg = IMG_NORM_CFG if img_norm_cfg is None else img_norm_cfg
         self.img_norm_cfg = dict(mean=list(cfg["mean"]), std=list(cfg["std"]), to_rgb=bool(cfg.get("to_rgb", True)))
         self.swap_rb = self.img_norm_cfg["to_rgb"]
         x0, y0, x1, y1 = self.crop
         self.out_hw = (y1 - y0, x1 - x0)
+        # int32 [cams][6], identity rows for the level cameras (None: no camera is rolled)
+        self.roll_ints = np.asarray([roll_integers(r, self.out_hw) for r in self.rolls], np.int32) if self.rolled else None
         xlo, xn, kx = coefficients(self.src_hw[1], self.resize_dims[0])
         ylo, yn, ky = coefficients(self.src_hw[0], self.resize_dims[1])
         # the kept columns' / rows' slice only; taps: the width of Pillow's coefficient rows (11 at 1600 -> 704, 7 at -> 1408)
@@ -439,6 +546,12 @@ class ResamplePlan:
         self.src_rows = int((self.ylo + self.yn).max()) - self.src_row0
         self.lut = normalise_lut(self.img_norm_cfg)
         self._dev = None
+
+    def image_transform(self, camera=0):
+        """float64 [3, 3]: the matrix `ResizeCropFlipImage._img_transform` returns (augment.py:111-129) for this plan and the
+        roll of `camera` (its entry of a list of rolls): resize, minus the crop origin, the flip, then the rotation block about
+        (crop_w / 2, crop_h / 2). A caller multiplies it into the camera's intrinsics, as the reference's pipeline does."""
+        return aug_matrix(self.aug_config, self.crop, self.flip, self.rolls[camera % len(self.rolls)], self.out_hw)
 
     # ------------------------------------------------------------------ traffic the algorithm needs (tools/bench_preprocess.py)
     def bytes_per_image(self, mid_pitch):
@@ -565,6 +678,15 @@ class ResamplePlan:
         ints = (n, hs, ws, h, w, self.taps_x, self.taps_y, self.src_row0, self.src_rows, int(self.flip), int(self.swap_rb))
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         sf = self.surface
+        if self.rolled:   # one entry point for every format and layout (the planes entry point's arguments, then the roll)
+            null = ctypes.c_void_p(0)
+            yuv = self.yuv if self.yuv is not None else (0, 1, 0, 0, 0, 0)
+            rows = self.roll_ints.ctypes.data_as(ctypes.POINTER(ctypes.c_int))   # (read before the call returns)
+            _lib.check(_lib.lib().simpb_preprocess_roll_nhwc4_f16(
+                p(out), p(src) if table is None else null, null if table is None else p(table), *tables, *ints,
+                SURFACE_FORMAT[self.frame_format], sf.pitch, sf.chroma_pitch, sf.chroma_offset, sf.chroma2_offset, sf.image_bytes, *yuv,
+                rows, len(self.rolls), stream), "simpb_preprocess_roll_nhwc4_f16")
+            return out
         if table is None and sf.tight and self.frame_format in ("bgr", "nv12", "nv21"):   # the first forms, through their entry points
             if self.yuv is None:
                 _lib.check(_lib.lib().simpb_preprocess_u8_nhwc4_f16(p(out), p(src), *tables, *ints, stream), "simpb_preprocess_u8_nhwc4_f16")
@@ -593,10 +715,12 @@ RIG_MAX_CAMS = 16     # SIMPB_RIG_MAX_CAMS of include/simpb_hip.h
 class CameraSource:
     """One camera of a rig (RigPlan): what a ResamplePlan takes for that camera alone, with the same checks. A camera of a
     rig gives its scale as the reference's scalar `resize` (with `crop` and `flip`): the 2D boxes are mapped back to source
-    pixels by that scalar (decoder.py:36-51), so an explicit, possibly anisotropic `resize_dims` is refused."""
+    pixels by that scalar (decoder.py:36-51), so an explicit, possibly anisotropic `resize_dims` is refused. `roll`: this
+    camera's mount roll in degrees (ResamplePlan has the rule)."""
 
-    def __init__(self, src_hw, aug_config=None, frame_format="bgr", colour="jfif", layout=None):
+    def __init__(self, src_hw, aug_config=None, frame_format="bgr", colour="jfif", layout=None, roll=0.0):
         self.src_hw = (int(src_hw[0]), int(src_hw[1]))
+        self.roll = check_roll(roll)
         self.aug_config = dict(aug_config or {})
         if self.aug_config.get("resize_dims") is not None:
             raise ValueError("a camera of a rig gives its scale as `resize` (with crop / flip): resize_dims is not taken, the 2D "
@@ -607,11 +731,11 @@ class CameraSource:
         self.resize = float(self.aug_config.get("resize", 1))
         self.resize_dims, self.crop, self.flip = resolve_aug(self.src_hw, self.aug_config)
         self.out_hw = (self.crop[3] - self.crop[1], self.crop[2] - self.crop[0])
-        self.key = plan_key(self.src_hw, self.aug_config, frame_format, colour, self.surface) + (self.resize,)
+        self.key = plan_key(self.src_hw, self.aug_config, frame_format, colour, self.surface, self.roll) + (self.resize,)
 
     def plan(self, img_norm_cfg=None):
         """The ResamplePlan of this camera alone."""
-        return ResamplePlan(self.src_hw, self.aug_config, img_norm_cfg, self.frame_format, self.colour, self.surface)
+        return ResamplePlan(self.src_hw, self.aug_config, img_norm_cfg, self.frame_format, self.colour, self.surface, self.roll)
 
     def describe(self):
         return f"{self.frame_format} {self.src_hw[1]} x {self.src_hw[0]} -> {self.out_hw[1]} x {self.out_hw[0]}"
@@ -649,6 +773,9 @@ class RigPlan:
             setattr(self, name, tuple(getattr(p, name) for p in self.plans))
         self.yuv = tuple(p.yuv for p in self.plans)
         self.surfaces = tuple(p.surface for p in self.plans)
+        # a rig with a rolled camera: int32 [cams][6], identity rows for its level cameras (None: today's entry point)
+        self.rolled = any(p.rolled for p in self.plans)
+        self.roll_ints = np.asarray([roll_integers(s.roll, self.out_hw) for s in sources], np.int32) if self.rolled else None
         # where each camera's tables start in the concatenation, and its rows in one stream's intermediate block
         ends = lambda sizes: [int(v) for v in np.concatenate([[0], np.cumsum(sizes)])]   # noqa: E731
         self.kx_offset, self.x_offset = ends([k.size for k in self.kx]), ends([v.size for v in self.xlo])
@@ -659,22 +786,19 @@ class RigPlan:
 
     # ------------------------------------------------------------------ what a caller multiplies / hands on
     def image_transforms(self):
-        """float64 [cams, 3, 3]: per camera the matrix `ResizeCropFlipImage._img_transform` returns (augment.py:111-118 with
-        rotate = 0): resize on the diagonal, minus the crop origin, then the flip. A caller multiplies it into the camera's
-        intrinsics, as the reference's pipeline does."""
+        """float64 [cams, 3, 3]: per camera the matrix `ResizeCropFlipImage._img_transform` returns (augment.py:111-129):
+        resize on the diagonal, minus the crop origin, the flip, then the rotation block of the camera's roll about
+        (crop_w / 2, crop_h / 2) (nothing for a level camera). A caller multiplies it into the camera's intrinsics, as the
+        reference's pipeline does."""
         out = np.zeros((self.num_cams, 3, 3), np.float64)
         for i, s in enumerate(self.sources):
-            m = np.eye(3)
-            m[:2, :2] *= s.aug_config.get("resize", 1)
-            m[:2, 2] -= np.array(s.crop[:2])
-            if s.flip:
-                m = np.array([[-1, 0, s.crop[2] - s.crop[0]], [0, 1, 0], [0, 0, 1]]) @ m
-            out[i] = m
+            out[i] = aug_matrix(s.aug_config, s.crop, s.flip, s.roll, s.out_hw)
         return out
 
     def box2d_table(self):
         """float32 [cams, 4] = (crop_w, crop_h, crop_y0, 1 / resize) per camera: what the 2D record kernels take as four
-        scalars for a uniform rig (1 / resize in fp32, as simpb_decode2d_record computes it)."""
+        scalars for a uniform rig (1 / resize in fp32, as simpb_decode2d_record computes it). A camera's roll does not enter:
+        the reference's decode_box2d (detection3d/decoder.py:36-51) does not look at rotate."""
         out = np.zeros((self.num_cams, 4), np.float32)
         for i, s in enumerate(self.sources):
             x0, y0, x1, y1 = s.crop
@@ -779,8 +903,12 @@ class RigPlan:
         elif out.dtype != torch.float16 or tuple(out.shape) != (n, h, w, 4) or not out.is_contiguous():
             raise ValueError(f"ingest writes f16 [{n}, {h}, {w}, 4]")
         p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
-        _lib.check(_lib.lib().simpb_preprocess_rig_nhwc4_f16(
-            p(out), p(table), p(d["mid"]), *(p(d[name]) for name in self.TABLES), p(d["lut"]), d["cams"], self.num_cams, n, h, w,
-            d["kx"].numel(), d["xlo"].numel(), d["ky"].numel(), d["ylo"].numel(), self.mid_rows, int(self.swap_rb),
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "simpb_preprocess_rig_nhwc4_f16")
+        args = (p(out), p(table), p(d["mid"]), *(p(d[name]) for name in self.TABLES), p(d["lut"]), d["cams"], self.num_cams, n, h, w,
+                d["kx"].numel(), d["xlo"].numel(), d["ky"].numel(), d["ylo"].numel(), self.mid_rows, int(self.swap_rb))
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self.rolled:
+            rows = self.roll_ints.ctypes.data_as(ctypes.POINTER(ctypes.c_int))   # (read before the call returns)
+            _lib.check(_lib.lib().simpb_preprocess_rig_roll_nhwc4_f16(*args, rows, stream), "simpb_preprocess_rig_roll_nhwc4_f16")
+        else:
+            _lib.check(_lib.lib().simpb_preprocess_rig_nhwc4_f16(*args, stream), "simpb_preprocess_rig_nhwc4_f16")
         return out

@@ -397,7 +397,7 @@ class FrameRunner:
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
                  raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
-                 raw_layout=None, raw_surfaces=False, raw_rig=None, idle_images="compute", camera_health=None):
+                 raw_layout=None, raw_surfaces=False, raw_rig=None, idle_images="compute", camera_health=None, raw_roll=None):
         """independent_streams: the batch is a set of independent camera streams, each decoded exactly as a batch of one
         would be (`capacity` 2D slots per stream; SimPBHead.independent_streams) -- the throughput form of BASELINE config
         #3. False: the reference's batch semantics (camera groups padded to the max over the batch).
@@ -424,6 +424,12 @@ class FrameRunner:
         image size. `img` is the nested list [bs][cams] of raw_surfaces, with the same lifetime rule; a None (paused stream,
         masked camera) is an image the ingest skips. metas["img_metas"][0]["aug_config"] is not read: the ingest and the 2D
         record both follow the rig (preprocess.RigPlan); `set_raw_rig` changes it between frames.
+        raw_roll=degrees | [degrees per camera] (with raw_input only; every raw_format, raw_layout and raw_surfaces): the cameras'
+        mount roll, positive counter-clockwise on screen -- the reference's `img.rotate` behind resize, crop and flip, done inside
+        the ingest's second launch with Pillow's bytes (preprocess.ResamplePlan has the rule). It is a property of the mount, not
+        of the frame: the aug_config's own `rotate` stays refused. With raw_rig each CameraSource brings its own `roll`. The 2D
+        records are unchanged: the reference's decode_box2d does not look at rotate. camera_health sees the rolled image, black
+        corners included. None, or rolls that are all multiples of 360: nothing of this is launched.
 
         world_output=dict(classes=..., tracking=bool, threshold=float | None): a second output per frame, the WORLD RECORD
         (csrc/world.hip, results.py): boxes in the global frame, threshold and class ranges applied, kept rows packed, a
@@ -452,6 +458,20 @@ class FrameRunner:
         if idle_images not in IDLE_IMAGES:
             raise ValueError(f"idle_images={idle_images!r}: one of {IDLE_IMAGES}")
         self.idle_images = idle_images
+        self.raw_roll = 0.0                 # raw_roll=: one roll for every camera, or a tuple of one per camera (degrees)
+        if raw_roll is not None:
+            from .preprocess import check_roll
+            if raw_rig is not None:
+                raise ValueError("raw_rig describes every camera by itself: each CameraSource brings its own roll=, raw_roll must not "
+                                 "be given with it")
+            if raw_input is None:
+                raise ValueError("raw_roll describes raw frames: it needs raw_input=(Hs, Ws)")
+            if isinstance(raw_roll, (list, tuple)):
+                if len(raw_roll) != model.head.num_cams:
+                    raise ValueError(f"raw_roll lists {len(raw_roll)} rolls, the model has {model.head.num_cams} cameras")
+                self.raw_roll = tuple(check_roll(r) for r in raw_roll)
+            else:
+                self.raw_roll = check_roll(raw_roll)
         self.skipping = False               # True from the first frame with a dead image on (idle_images="skip"): the backbone reads live_dev
         self.live_pin = self.live_dev = None    # per feature slot: the live-image table, pinned host side and fixed device side
         self.live_staged = None             # per feature slot: event behind the slot's last copy out of its pinned table
@@ -506,7 +526,7 @@ class FrameRunner:
             self.img, self.raw = torch.zeros(batch_size, cams, 3, h, w, device=dev), None
         else:   # (no fp32 staging buffer in this mode)
             from .preprocess import SurfaceLayout, frame_shape, plan_key
-            plan_key(self.raw_input, None, raw_format, raw_colour)   # (an unknown format or standard is refused here)
+            plan_key(self.raw_input, None, raw_format, raw_colour, None, self.raw_roll)   # (an unknown format or standard is refused here)
             self.img = None
             if raw_layout is not None:
                 self.raw_layout = SurfaceLayout.make(raw_layout, self.raw_input, raw_format)
@@ -660,9 +680,10 @@ class FrameRunner:
             self.plan.reserve(self.bs * self.head.num_cams, self.device)
             return
         aug = metas["img_metas"][0]["aug_config"]
-        if self.plan is not None and self.plan.key == plan_key(self.raw_input, aug, self.raw_format, self.raw_colour, self.raw_layout):
+        if self.plan is not None and self.plan.key == plan_key(self.raw_input, aug, self.raw_format, self.raw_colour, self.raw_layout,
+                                                               self.raw_roll):
             return
-        plan = ResamplePlan(self.raw_input, aug, self.img_norm_cfg, self.raw_format, self.raw_colour, self.raw_layout)
+        plan = ResamplePlan(self.raw_input, aug, self.img_norm_cfg, self.raw_format, self.raw_colour, self.raw_layout, self.raw_roll)
         if plan.out_hw != self.image_hw:
             raise ValueError(f"aug_config {aug} turns {self.raw_input} frames into {plan.out_hw} images; this runner was built for "
                              f"{self.image_hw}")
