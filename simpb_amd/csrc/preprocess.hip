@@ -1,6 +1,6 @@
-// Camera frame ingest (gfx950): raw u8 [N, Hs, Ws, 3] frames as an image decoder delivers them -> the stem's operand, f16
+// Camera frame ingest (gfx950): raw u8 frames as a decoder, a camera or a loader delivers them -> the stem's operand, f16
 // [N, h, w, 4] with channel 3 = 0 (what simpb_stem_conv7x7_pool_f16 reads). It replaces the reference's test pipeline on
-// the host, ResizeCropFlipImage (datasets/pipelines/augment.py:86-106: PIL resize + crop + left-right flip) and
+// the host, ResizeCropFlipImage (datasets/pipelines/augment.py:86-106: PIL resize + crop + left-right flip + rotate) and
 // NormalizeMultiviewImage (transform_3d.py:438-466), and the fp32 cast pass of csrc/stem.hip behind it.
 //
 // The resize is Pillow's 8-bit resampler restated: integer coefficients with 22 fractional bits (computed by the host in
@@ -10,31 +10,32 @@
 // order, mean / std and the f16 rounding sit in a [3][256] table made by the host, so that no floating-point
 // instruction (and no contraction rule of the compiler) enters the result.
 //
-// Two launches with a u8 intermediate [N, rows, pitch] in HBM (1.2 MB per camera at 1600 x 900 -> 704 x 256):
-//   1. horizontal: one workgroup per (needed source row, image). The row is staged in LDS (16-byte chunks where the row
-//      starts on a 16-byte boundary; neighbouring output columns share almost all of their taps), a thread makes whole
-//      output pixels, the resampled row goes through LDS again and leaves as 16-byte chunks.
-//   2. vertical + table: a thread owns 4 neighbouring output pixels = 12 intermediate bytes per tap row (three aligned
-//      dwords), and writes them as two 16-byte stores.
-// 4:2:0 semi-planar YCbCr frames (NV12 / NV21, u8 [N, Hs * 3 / 2, Ws]: what hardware video and JPEG decoders deliver) enter
-// through a second horizontal kernel: it stages the luma row and its chroma row (Ws bytes each) and converts them once, in
-// int32 with 16 fractional bits, into the same (B, G, R) LDS row; filter, store and the vertical pass are the BGR route's own.
-// A decoder's SURFACE (simpb_preprocess_surface_nhwc4_f16) enters through a third horizontal kernel, a template over the
-// source format (BGR, NV12, NV21, and P010 in u16): row pitch, chroma pitch and offset and the image stride are arguments,
-// and the images are either one contiguous batch or a device table of one address per image. It reads no byte outside a
-// needed row's samples and shares filter, store and the vertical pass with the other two, which keep the tight forms.
-// A RIG of cameras that differ (simpb_preprocess_rig_nhwc4_f16) is two launches as well: image n belongs to camera n % cams,
-// each camera has its own descriptor (format, size, layout, row range, taps, tables), passed by value, and both rig kernels
-// are the surface path's device functions (stage_bgr_row, filter_row_and_store, resample_cols_lut_row) behind a
-// per-workgroup choice of the descriptor; address 0 in the table skips an image, whose output block is written as zeros.
-// What other producers deliver (simpb_preprocess_planes_nhwc4_f16, and per camera of a rig) are further branches of
-// stage_bgr_row and nothing else: planar 4:2:0 (three planes: a software decoder), packed 4:2:2 (YUYV / UYVY: a camera without
-// a codec) by the same integer rule with replicated chroma, and RGB / BGRA / RGBA as a byte permutation into the (B, G, R) row.
-// A camera's mount ROLL (the reference's img.rotate: simpb_preprocess_roll_nhwc4_f16, simpb_preprocess_rig_roll_nhwc4_f16) is a
-// second form of the vertical pass, a gather by six integers per camera (resample_cols_lut_roll_row); the level forms above
-// are launched as ever where no camera is rolled.
+// THE TWO PASSES. Every ingest is two launches with a u8 intermediate `mid` [N, rows, pitch] in HBM (1.2 MB per camera at
+// 1600 x 900 -> 704 x 256):
+//   1. horizontal: one workgroup per (needed source row, image). The row is staged in LDS as (B, G, R) bytes (stage_row,
+//      stage_bgr_row; neighbouring output columns share almost all of their taps), a thread makes whole output pixels, the
+//      resampled row goes through LDS again and leaves as 16-byte chunks (filter_row_and_store).
+//   2. vertical + table: a thread owns 4 neighbouring output pixels, sums their taps into 12 accumulators and writes them
+//      through the table as two 16-byte stores (stage_lut, store_lut_group).
+// THE SOURCE FORMATS differ in how a row becomes the (B, G, R) row and in nothing else: stage_bgr_row<F> takes interleaved
+// BGR as it lies, RGB / BGRA / RGBA as a byte permutation, and 4:2:0 semi-planar (NV12 / NV21, P010 in u16), planar 4:2:0
+// and packed 4:2:2 (YUYV / UYVY) through one integer YCbCr rule with replicated chroma (yuv_pair_to_bgr). with_format maps
+// the runtime code to the instantiation, for the host's launch and inside the rig kernel alike.
+// THREE WAYS TO ADDRESS THE IMAGES. A tight contiguous batch of BGR or NV12 / NV21 frames (simpb_preprocess_u8_nhwc4_f16,
+// simpb_preprocess_yuv420sp_nhwc4_f16) has a horizontal kernel of its own each, where the host decides once whether rows go
+// as 16-byte chunks. A SURFACE (simpb_preprocess_surface_nhwc4_f16, simpb_preprocess_planes_nhwc4_f16) has row pitch, chroma
+// pitch and offsets and the image stride as arguments, and its images are one contiguous batch or a device table of one
+// address per image; it reads no byte outside a needed row's samples. A RIG of cameras that differ
+// (simpb_preprocess_rig_nhwc4_f16) gives image n the descriptor of camera n % cams (format, size, layout, row range, taps,
+// tables), passed by value, behind a per-workgroup choice; address 0 in its table skips an image, whose output block is
+// written as zeros. The vertical pass has a kernel for the uniform batch and one for the rig, which fill a ColsImage each.
+// LEVEL AND ROLLED. A camera's mount roll (the reference's img.rotate: simpb_preprocess_roll_nhwc4_f16,
+// simpb_preprocess_rig_roll_nhwc4_f16) is a second accumulation loop of the vertical pass, a gather by six integers per
+// camera (resample_cols_lut_roll_row) in front of the same epilogue; the level loop is launched as ever where no camera is
+// rolled.
 // Every load of a thread is retired before its stores are issued (store_fence.h).
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "../../include/simpb_hip.h"
 #include "store_fence.h"
 
@@ -50,11 +51,13 @@ constexpr int kMaxOutW = 2048;    // staged resampled row: 6 KB
 constexpr int kMaxTaps = SIMPB_PREPROCESS_MAX_TAPS;
 constexpr int kPrecision = 22;
 
-__device__ __forceinline__ int clip8(int acc) { return min(max(acc >> kPrecision, 0), 255); }
+// the one clamp to a byte: of a filter sum (>> kPrecision) and of a converted colour (>> its fractional bits)
+__device__ __forceinline__ int clamp8(int v) { return min(max(v, 0), 255); }
 
-// The part of the horizontal pass both source formats share: the staged [Ws][3] row `s_src` (complete: the caller has
+// ---------------------------------------------------------------------------------------------- the horizontal pass
+// The part of the horizontal pass every source shares: the staged [Ws][3] row `s_src` (complete: the caller has
 // synchronised) -> row `mid_row` of the intermediate.
-//   mid_row[j][c] = clip8(2^21 + sum_t s_src[xlo[jj] + t][c] * kx[jj][t]),  jj = flip ? w - 1 - j : j
+//   mid_row[j][c] = clamp8((2^21 + sum_t s_src[xlo[jj] + t][c] * kx[jj][t]) >> 22),  jj = flip ? w - 1 - j : j
 __device__ __forceinline__ void filter_row_and_store(unsigned char* __restrict__ mid_row, const unsigned char* s_src, unsigned char* s_out,
                                                      const int* __restrict__ kx, const int* __restrict__ xlo,
                                                      const int* __restrict__ xn, int Ws, int w, int taps, int flip, int pitch) {
@@ -76,7 +79,7 @@ __device__ __forceinline__ void filter_row_and_store(unsigned char* __restrict__
         a1 += (int)s[1] * c;
         a2 += (int)s[2] * c;
       }
-      v0 = clip8(a0); v1 = clip8(a1); v2 = clip8(a2);
+      v0 = clamp8(a0 >> kPrecision); v1 = clamp8(a1 >> kPrecision); v2 = clamp8(a2 >> kPrecision);
     }
     s_out[j * 3] = (unsigned char)v0;
     s_out[j * 3 + 1] = (unsigned char)v1;
@@ -90,19 +93,55 @@ __device__ __forceinline__ void filter_row_and_store(unsigned char* __restrict__
   for (int i = tid; i < (pitch >> 4); i += kThreads) o16[i] = s16[i];
 }
 
-// `bytes` of one source row into LDS: 16-byte chunks where the caller found pointer and width to allow them
-__device__ __forceinline__ void stage_row(unsigned char* s_dst, const unsigned char* __restrict__ p, int bytes, int vec16) {
+// Exactly `bytes` of one source row into LDS, as 16-byte chunks where the row allows them and bytewise where not.
+// kGiven (the tight batches): the host found every row to start on a 16-byte boundary and to be whole chunks, and says so
+// in `vec16`; there is no tail to copy, and none is paid for.
+// kByAddress (surfaces and rigs): never a byte past `bytes` (a surface may end at its last sample, and what lies between
+// two rows is not the caller's to read). A row that starts on a 16-byte boundary goes as floor(bytes / 16) chunks and a
+// bytewise tail; any other row bytewise. The choice is made here, from the row's own address (uniform over the workgroup):
+// with a pitch that is no multiple of 16 it alternates from row to row, and under a captured graph the address table
+// changes between replays while the kernel arguments do not.
+enum Chunks { kGiven, kByAddress };
+
+template <Chunks kChunks>
+__device__ __forceinline__ void stage_row(unsigned char* s_dst, const unsigned char* __restrict__ p, int bytes, int vec16 = 0) {
   const int tid = threadIdx.x;
+  if constexpr (kChunks == kByAddress) vec16 = (reinterpret_cast<size_t>(p) & 15) == 0;
   if (vec16) {
+    const int chunks = bytes >> 4;
     const uint4* p16 = reinterpret_cast<const uint4*>(p);
     uint4* s16 = reinterpret_cast<uint4*>(s_dst);
-    for (int i = tid; i < (bytes >> 4); i += kThreads) s16[i] = p16[i];
+    for (int i = tid; i < chunks; i += kThreads) s16[i] = p16[i];
+    if constexpr (kChunks == kByAddress)
+      for (int i = (chunks << 4) + tid; i < bytes; i += kThreads) s_dst[i] = p[i];
   } else {
     for (int i = tid; i < bytes; i += kThreads) s_dst[i] = p[i];
   }
 }
 
-// mid[n][r][j][c] = clip8(2^21 + sum_t src[n][row0 + r][xlo[jj] + t][c] * kx[jj][t]),  jj = flip ? w - 1 - j : j
+// One chroma pair and its two luma samples -> two (B, G, R) pixels at d[0 .. 5]: the integer YCbCr rule of every YCbCr
+// format, with S = kShift fractional bits and chroma centre C = kCentre: 16 / 128 for 8-bit samples, 18 / 512 for 10-bit ones
+// (P010), whose luma offset is 4 * yoff as well:
+//   c = iy * (Y - yoff) + 2^(S-1),  R = clamp8((c + irv * (Cr - C)) >> S),  G = clamp8((c + igu * (Cb - C) + igv * (Cr - C)) >> S),
+//   B = clamp8((c + ibu * (Cb - C)) >> S)     (int32, arithmetic shift, clamp to 0..255)
+struct YuvCoeffs { int yoff, iy, irv, igu, igv, ibu; };
+
+template <int kShift = 16, int kCentre = 128>
+__device__ __forceinline__ void yuv_pair_to_bgr(unsigned char* d, int y0, int y1, int cb, int cr, const YuvCoeffs& q) {
+  cb -= kCentre; cr -= kCentre;
+  const int yoff = q.yoff << (kShift - 16);
+  const int dr = q.irv * cr, dg = q.igu * cb + q.igv * cr, db = q.ibu * cb;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = q.iy * ((i ? y1 : y0) - yoff) + (1 << (kShift - 1));
+    d[3 * i] = (unsigned char)clamp8((c + db) >> kShift);
+    d[3 * i + 1] = (unsigned char)clamp8((c + dg) >> kShift);
+    d[3 * i + 2] = (unsigned char)clamp8((c + dr) >> kShift);
+  }
+}
+
+// A tight batch of BGR frames, u8 [N][Hs][Ws][3]:
+// mid[n][r][j][c] = clamp8((2^21 + sum_t src[n][row0 + r][xlo[jj] + t][c] * kx[jj][t]) >> 22),  jj = flip ? w - 1 - j : j
 __global__ __launch_bounds__(kThreads) void resample_rows_kernel(unsigned char* __restrict__ mid, const unsigned char* __restrict__ src,
                                                                  const int* __restrict__ kx, const int* __restrict__ xlo,
                                                                  const int* __restrict__ xn, int Hs, int Ws, int row0, int rows,
@@ -111,21 +150,15 @@ __global__ __launch_bounds__(kThreads) void resample_rows_kernel(unsigned char* 
   __shared__ __attribute__((aligned(16))) unsigned char s_out[kMaxOutW * 3 + 16];
   const int r = blockIdx.x, n = blockIdx.y;
   const size_t row_bytes = (size_t)Ws * 3;
-  stage_row(s_src, src + ((size_t)n * Hs + row0 + r) * row_bytes, (int)row_bytes, vec16);
+  stage_row<kGiven>(s_src, src + ((size_t)n * Hs + row0 + r) * row_bytes, (int)row_bytes, vec16);
   __syncthreads();
   filter_row_and_store(mid + ((size_t)n * rows + r) * pitch, s_src, s_out, kx, xlo, xn, Ws, w, taps, flip, pitch);
 }
 
-// 4:2:0 semi-planar source (NV12 / NV21): one image is u8 [Hs * 3 / 2][Ws], Hs luma rows, then Hs / 2 rows of interleaved
-// chroma pairs, (Cb, Cr) or with `vu` (Cr, Cb); chroma sample (i, j) covers luma rows 2i, 2i + 1 and columns 2j, 2j + 1
-// (replicated). The luma row and its chroma row are staged, converted once into the (B, G, R) row the BGR kernel stages,
-//   c = iy * (Y - yoff) + 2^15,  R = clamp((c + irv * (Cr - 128)) >> 16),  G = clamp((c + igu * (Cb - 128) + igv * (Cr - 128)) >> 16),
-//   B = clamp((c + ibu * (Cb - 128)) >> 16)     (int32, arithmetic shift, clamp to 0..255),
-// and filtered by the same code.
-struct YuvCoeffs { int yoff, iy, irv, igu, igv, ibu; };
-
-__device__ __forceinline__ int clamp8(int v) { return min(max(v, 0), 255); }
-
+// A tight batch of 4:2:0 semi-planar frames (NV12 / NV21): one image is u8 [Hs * 3 / 2][Ws], Hs luma rows, then Hs / 2 rows
+// of interleaved chroma pairs, (Cb, Cr) or with `vu` (Cr, Cb); chroma sample (i, j) covers luma rows 2i, 2i + 1 and columns
+// 2j, 2j + 1 (replicated). The luma row and its chroma row are staged, converted once into the (B, G, R) row the BGR kernel
+// stages (yuv_pair_to_bgr) and filtered by the same code.
 __global__ __launch_bounds__(kThreads) void resample_rows_yuv420sp_kernel(unsigned char* __restrict__ mid, const unsigned char* __restrict__ src,
                                                                           const int* __restrict__ kx, const int* __restrict__ xlo,
                                                                           const int* __restrict__ xn, int Hs, int Ws, int row0, int rows,
@@ -137,21 +170,11 @@ __global__ __launch_bounds__(kThreads) void resample_rows_yuv420sp_kernel(unsign
   const int tid = threadIdx.x, r = blockIdx.x, n = blockIdx.y;
   const int row = row0 + r;
   const unsigned char* image = src + (size_t)n * (Hs + (Hs >> 1)) * Ws;
-  stage_row(s_luma, image + (size_t)row * Ws, Ws, vec16);
-  stage_row(s_chroma, image + (size_t)(Hs + (row >> 1)) * Ws, Ws, vec16);
+  stage_row<kGiven>(s_luma, image + (size_t)row * Ws, Ws, vec16);
+  stage_row<kGiven>(s_chroma, image + (size_t)(Hs + (row >> 1)) * Ws, Ws, vec16);
   __syncthreads();
-  for (int x = 2 * tid; x < Ws; x += 2 * kThreads) {   // a chroma pair and its two luma samples (Ws is even)
-    const int cb = (int)s_chroma[x + vu] - 128, cr = (int)s_chroma[x + 1 - vu] - 128;
-    const int dr = q.irv * cr, dg = q.igu * cb + q.igv * cr, db = q.ibu * cb;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int c = q.iy * ((int)s_luma[x + i] - q.yoff) + (1 << 15);
-      unsigned char* d = s_src + (x + i) * 3;
-      d[0] = (unsigned char)clamp8((c + db) >> 16);
-      d[1] = (unsigned char)clamp8((c + dg) >> 16);
-      d[2] = (unsigned char)clamp8((c + dr) >> 16);
-    }
-  }
+  for (int x = 2 * tid; x < Ws; x += 2 * kThreads)   // a chroma pair and its two luma samples (Ws is even)
+    yuv_pair_to_bgr(s_src + x * 3, (int)s_luma[x], (int)s_luma[x + 1], (int)s_chroma[x + vu], (int)s_chroma[x + 1 - vu], q);
   __syncthreads();
   filter_row_and_store(mid + ((size_t)n * rows + r) * pitch, s_src, s_out, kx, xlo, xn, Ws, w, taps, flip, pitch);
 }
@@ -170,6 +193,31 @@ constexpr int kBgr = SIMPB_SURFACE_BGR, kNv12 = SIMPB_SURFACE_NV12, kNv21 = SIMP
 constexpr int kYuv420p = SIMPB_SURFACE_YUV420P, kYuyv = SIMPB_SURFACE_YUYV, kUyvy = SIMPB_SURFACE_UYVY, kRgb = SIMPB_SURFACE_RGB;
 constexpr int kBgra = SIMPB_SURFACE_BGRA, kRgba = SIMPB_SURFACE_RGBA;
 
+// The one place where a runtime format code becomes a compile-time constant: fn(std::integral_constant<int, F>) for the
+// code's F, and true; false, and nothing called, for a code that is no format (the entry points refuse it before any launch).
+// kLastIsElse is for the rig kernel alone: there the last format stands for every other code as well, so that the choice
+// has no path that stages nothing (the loads of the camera's layout stay in front of it) and ends in no wrong access.
+template <bool kLastIsElse = false, class Fn>
+__host__ __device__ __forceinline__ bool with_format(int format, Fn&& fn) {
+  switch (format) {
+#define SIMPB_FORMAT(F) case F: fn(std::integral_constant<int, F>{}); return true
+    SIMPB_FORMAT(kBgr);
+    SIMPB_FORMAT(kNv12);
+    SIMPB_FORMAT(kNv21);
+    SIMPB_FORMAT(kYuv420p);
+    SIMPB_FORMAT(kYuyv);
+    SIMPB_FORMAT(kUyvy);
+    SIMPB_FORMAT(kRgb);
+    SIMPB_FORMAT(kBgra);
+    SIMPB_FORMAT(kRgba);
+#undef SIMPB_FORMAT
+    default:
+      if (!kLastIsElse && format != kP010) return false;
+      fn(std::integral_constant<int, kP010>{});
+      return true;
+  }
+}
+
 // LDS bytes of the two staging planes of a source `width` wide, s_luma and s_chroma (one plane each; a multiple of 16). A
 // packed row that is converted or compacted on its way into the (B, G, R) row (4:2:2: 2 bytes per pixel, BGRA / RGBA: 4) is
 // staged from s_luma on and runs through into s_chroma, which lies right behind it; the two chroma rows of planar 4:2:0 share
@@ -181,62 +229,28 @@ __host__ __device__ constexpr int plane_bytes(int format, int width) {
                               : (width + 15) / 16 * 16;   // (NV12 / NV21: a luma and a chroma row; 4:2:2: the halves of its row)
 }
 
-// Exactly `bytes` of one source row into LDS, never a byte past them (a surface may end at its last sample, and what lies
-// between two rows is not the caller's to read). A row that starts on a 16-byte boundary goes as floor(bytes / 16) chunks and
-// a bytewise tail; any other row bytewise. The choice is made here, from the row's own address (uniform over the workgroup):
-// with a pitch that is no multiple of 16 it alternates from row to row, and under a captured graph the address table
-// changes between replays while the kernel arguments do not.
-__device__ __forceinline__ void stage_row(unsigned char* s_dst, const unsigned char* __restrict__ p, int bytes) {
-  const int tid = threadIdx.x;
-  if ((reinterpret_cast<size_t>(p) & 15) == 0) {
-    const int chunks = bytes >> 4;
-    const uint4* p16 = reinterpret_cast<const uint4*>(p);
-    uint4* s16 = reinterpret_cast<uint4*>(s_dst);
-    for (int i = tid; i < chunks; i += kThreads) s16[i] = p16[i];
-    for (int i = (chunks << 4) + tid; i < bytes; i += kThreads) s_dst[i] = p[i];
-  } else {
-    for (int i = tid; i < bytes; i += kThreads) s_dst[i] = p[i];
-  }
-}
-
 // One source row of a surface as the (B, G, R) row the filter reads, for every source format. `image` is the image's first
-// byte, luma (or BGR) row r at + r * pitch, chroma row i at + chroma_offset + i * chroma_pitch.
-// kBgr: the surface's own interleaved row, staged where the filter reads it (s_luma / s_chroma are not looked at). 4:2:0
-// semi-planar (kNv12: (Cb, Cr) pairs, kNv21: (Cr, Cb), u8; kP010: (Cb, Cr), u16 little-endian with the 10-bit sample in the high
-// bits): chroma sample (i, j) covers luma rows 2i, 2i + 1 and columns 2j, 2j + 1 (replicated). The luma row and the chroma row
-// under it are staged (Ws samples each in s_luma / s_chroma) and converted once into the (B, G, R) row, with S = 16 fractional
-// bits, chroma centre C = 128 for u8 and S = 18, C = 512, yoff * 4 for 10-bit samples:
-//   c = iy * (Y - yoff) + 2^(S-1),  R = clamp((c + irv * (Cr - C)) >> S),  G = clamp((c + igu * (Cb - C) + igv * (Cr - C)) >> S),
-//   B = clamp((c + ibu * (Cb - C)) >> S)     (int32, arithmetic shift, clamp to 0..255)
-// Chroma rows that lie under no needed luma row are never read. Returns with s_src complete (synchronised).
-// What follows is the 8-bit rule (S = 16, C = 128) on other arrangements of the same samples, and byte permutations:
-// kYuv420p (I420 / YV12): three planes, the Cb row i of Ws / 2 bytes at + chroma_offset + i * chroma_pitch and the Cr row at
-// + chroma2_offset + i * chroma_pitch; which plane comes first in memory is the caller's to say through the two offsets.
-// kYuyv / kUyvy (packed 4:2:2): one plane, a row is Ws / 2 groups (Y0, Cb, Y1, Cr) / (Cb, Y0, Cr, Y1); the pair belongs to
-// columns 2j, 2j + 1 of its own row. kRgb: the BGR row with bytes 0 and 2 of every pixel exchanged. kBgra / kRgba: 4 bytes per
-// pixel, byte 3 is dropped whatever it holds.
-__device__ __forceinline__ void yuv_pair_to_bgr(unsigned char* d, int y0, int y1, int cb, int cr, const YuvCoeffs& q) {
-  cb -= 128; cr -= 128;
-  const int dr = q.irv * cr, dg = q.igu * cb + q.igv * cr, db = q.ibu * cb;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = q.iy * ((i ? y1 : y0) - q.yoff) + (1 << 15);
-    d[3 * i] = (unsigned char)clamp8((c + db) >> 16);
-    d[3 * i + 1] = (unsigned char)clamp8((c + dg) >> 16);
-    d[3 * i + 2] = (unsigned char)clamp8((c + dr) >> 16);
-  }
-}
-
+// byte, luma (or BGR) row r at + r * pitch, chroma row i at + chroma_offset + i * chroma_pitch. Returns with s_src complete
+// (synchronised). Chroma rows that lie under no needed luma row are never read.
+// kBgr: the surface's own interleaved row, staged where the filter reads it (s_luma / s_chroma are not looked at). kRgb: the
+// BGR row with bytes 0 and 2 of every pixel exchanged. kBgra / kRgba: 4 bytes per pixel, byte 3 is dropped whatever it holds.
+// The YCbCr formats are arrangements of the samples that yuv_pair_to_bgr takes. 4:2:0 semi-planar (kNv12: (Cb, Cr) pairs,
+// kNv21: (Cr, Cb), u8; kP010: (Cb, Cr), u16 little-endian with the 10-bit sample in the high bits): chroma sample (i, j) covers
+// luma rows 2i, 2i + 1 and columns 2j, 2j + 1 (replicated); the luma row and the chroma row under it are staged, Ws samples
+// each in s_luma / s_chroma. kYuv420p (I420 / YV12): three planes, the Cb row i of Ws / 2 bytes at + chroma_offset +
+// i * chroma_pitch and the Cr row at + chroma2_offset + i * chroma_pitch; which plane comes first in memory is the caller's to
+// say through the two offsets. kYuyv / kUyvy (packed 4:2:2): one plane, a row is Ws / 2 groups (Y0, Cb, Y1, Cr) /
+// (Cb, Y0, Cr, Y1); the pair belongs to columns 2j, 2j + 1 of its own row.
 template <int F>
 __device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned char* s_luma, unsigned char* s_chroma,
                                               const unsigned char* __restrict__ image, long long pitch, long long chroma_offset,
                                               long long chroma_pitch, long long chroma2_offset, int row, int Ws, const YuvCoeffs& q) {
   const int tid = threadIdx.x;
   if constexpr (F == kBgr) {
-    stage_row(s_src, image + (size_t)row * pitch, Ws * 3);
+    stage_row<kByAddress>(s_src, image + (size_t)row * pitch, Ws * 3);
     __syncthreads();
   } else if constexpr (F == kRgb) {   // permuted where it lies: a thread exchanges the ends of its own pixels
-    stage_row(s_src, image + (size_t)row * pitch, Ws * 3);
+    stage_row<kByAddress>(s_src, image + (size_t)row * pitch, Ws * 3);
     __syncthreads();
     for (int x = tid; x < Ws; x += kThreads) {
       unsigned char* d = s_src + x * 3;
@@ -246,7 +260,7 @@ __device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned cha
     }
     __syncthreads();
   } else if constexpr (F == kBgra || F == kRgba) {   // the row of dwords (LDS is 16-byte aligned), compacted
-    stage_row(s_luma, image + (size_t)row * pitch, Ws * 4);
+    stage_row<kByAddress>(s_luma, image + (size_t)row * pitch, Ws * 4);
     __syncthreads();
     const unsigned int* px = reinterpret_cast<const unsigned int*>(s_luma);
     for (int x = tid; x < Ws; x += kThreads) {
@@ -258,7 +272,7 @@ __device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned cha
     }
     __syncthreads();
   } else if constexpr (F == kYuyv || F == kUyvy) {   // one dword = one chroma pair and its two luma samples (Ws is even)
-    stage_row(s_luma, image + (size_t)row * pitch, Ws * 2);
+    stage_row<kByAddress>(s_luma, image + (size_t)row * pitch, Ws * 2);
     __syncthreads();
     const unsigned int* group = reinterpret_cast<const unsigned int*>(s_luma);
     constexpr int kY = F == kYuyv ? 0 : 8, kC = 8 - kY;   // bit of Y0 and of Cb inside the group
@@ -270,38 +284,27 @@ __device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned cha
     __syncthreads();
   } else if constexpr (F == kYuv420p) {
     unsigned char* s_cr = s_chroma + (((Ws >> 1) + 15) & ~15);   // (plane_bytes: the second half of s_chroma)
-    stage_row(s_luma, image + (size_t)row * pitch, Ws);
-    stage_row(s_chroma, image + chroma_offset + (size_t)(row >> 1) * chroma_pitch, Ws >> 1);
-    stage_row(s_cr, image + chroma2_offset + (size_t)(row >> 1) * chroma_pitch, Ws >> 1);
+    stage_row<kByAddress>(s_luma, image + (size_t)row * pitch, Ws);
+    stage_row<kByAddress>(s_chroma, image + chroma_offset + (size_t)(row >> 1) * chroma_pitch, Ws >> 1);
+    stage_row<kByAddress>(s_cr, image + chroma2_offset + (size_t)(row >> 1) * chroma_pitch, Ws >> 1);
     __syncthreads();
     for (int j = tid; 2 * j < Ws; j += kThreads)
       yuv_pair_to_bgr(s_src + j * 6, (int)s_luma[2 * j], (int)s_luma[2 * j + 1], (int)s_chroma[j], (int)s_cr[j], q);
     __syncthreads();
   } else {
+    static_assert(F == kNv12 || F == kNv21 || F == kP010, "a format without a branch of its own");
     constexpr int kSample = F == kP010 ? 2 : 1;   // bytes per sample
-    constexpr int kShift = F == kP010 ? 18 : 16, kCentre = F == kP010 ? 512 : 128, kVu = F == kNv21 ? 1 : 0;
-    stage_row(s_luma, image + (size_t)row * pitch, Ws * kSample);
-    stage_row(s_chroma, image + chroma_offset + (size_t)(row >> 1) * chroma_pitch, Ws * kSample);
+    constexpr int kVu = F == kNv21 ? 1 : 0;
+    stage_row<kByAddress>(s_luma, image + (size_t)row * pitch, Ws * kSample);
+    stage_row<kByAddress>(s_chroma, image + chroma_offset + (size_t)(row >> 1) * chroma_pitch, Ws * kSample);
     __syncthreads();
-    const int yoff = F == kP010 ? 4 * q.yoff : q.yoff;
     for (int x = 2 * tid; x < Ws; x += 2 * kThreads) {   // a chroma pair and its two luma samples (Ws is even)
-      int cb, cr, y0, y1;
       if constexpr (F == kP010) {   // sample = word >> 6: the low six bits are ignored whatever they hold
         const unsigned short* l = reinterpret_cast<const unsigned short*>(s_luma);
         const unsigned short* c = reinterpret_cast<const unsigned short*>(s_chroma);
-        cb = (int)(c[x] >> 6); cr = (int)(c[x + 1] >> 6); y0 = (int)(l[x] >> 6); y1 = (int)(l[x + 1] >> 6);
+        yuv_pair_to_bgr<18, 512>(s_src + x * 3, (int)(l[x] >> 6), (int)(l[x + 1] >> 6), (int)(c[x] >> 6), (int)(c[x + 1] >> 6), q);
       } else {
-        cb = (int)s_chroma[x + kVu]; cr = (int)s_chroma[x + 1 - kVu]; y0 = (int)s_luma[x]; y1 = (int)s_luma[x + 1];
-      }
-      cb -= kCentre; cr -= kCentre;
-      const int dr = q.irv * cr, dg = q.igu * cb + q.igv * cr, db = q.ibu * cb;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int c = q.iy * ((i ? y1 : y0) - yoff) + (1 << (kShift - 1));
-        unsigned char* d = s_src + (x + i) * 3;
-        d[0] = (unsigned char)clamp8((c + db) >> kShift);
-        d[1] = (unsigned char)clamp8((c + dg) >> kShift);
-        d[2] = (unsigned char)clamp8((c + dr) >> kShift);
+        yuv_pair_to_bgr(s_src + x * 3, (int)s_luma[x], (int)s_luma[x + 1], (int)s_chroma[x + kVu], (int)s_chroma[x + 1 - kVu], q);
       }
     }
     __syncthreads();
@@ -309,7 +312,7 @@ __device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned cha
 }
 
 // The horizontal pass over a surface, one workgroup per (needed source row, image), for every source format (stage_bgr_row):
-//   mid[n][r][j][c] = clip8(2^21 + sum_t bgr[n][row0 + r][xlo[jj] + t][c] * kx[jj][t]),  jj = flip ? w - 1 - j : j
+//   mid[n][r][j][c] = clamp8((2^21 + sum_t bgr[n][row0 + r][xlo[jj] + t][c] * kx[jj][t]) >> 22),  jj = flip ? w - 1 - j : j
 template <int F>
 __global__ __launch_bounds__(kThreads) void resample_rows_surface_kernel(unsigned char* __restrict__ mid, Surface sf,
                                                                          const int* __restrict__ kx, const int* __restrict__ xlo,
@@ -335,8 +338,9 @@ __global__ __launch_bounds__(kThreads) void resample_rows_surface_kernel(unsigne
 struct Rig { simpb_rig_camera cam[SIMPB_RIG_MAX_CAMS]; };
 
 // The horizontal pass of a rig: the grid spans the tallest camera's rows, and a workgroup past its own camera's rows -- or
-// whose image has address 0 (the image is skipped: the vertical pass writes zeros) -- leaves before any barrier. Stream
-// n / num_cams keeps its cameras' rows one behind the other in a block of `mid_rows` rows, camera c from row mid_row on.
+// whose image has address 0 (the image is skipped: the vertical pass writes zeros) -- leaves before any barrier; a camera whose
+// format is none (the entry point has refused such a rig) is staged as the last format (with_format<true>). Stream n / num_cams keeps its cameras' rows one
+// behind the other in a block of `mid_rows` rows, camera c from row mid_row on.
 // LDS is dynamic, sized by the entry point for the rig at hand (RigLds: the widest camera's (B, G, R) row, the resampled row,
 // and the widest staging planes of any camera, plane_bytes), not for the widest source the file takes: a rig of 1600-wide NV12
 // cameras holds 10 KB per workgroup where the static arrays of the surface kernel hold 26 KB, and a BGR rig has no planes.
@@ -360,45 +364,78 @@ __global__ __launch_bounds__(kThreads) void resample_rows_rig_kernel(unsigned ch
   if (image == nullptr) return;
   const YuvCoeffs q = {c.yoff, c.iy, c.irv, c.igu, c.igv, c.ibu};
   const int row = c.src_row0 + r, Ws = c.src_width;
-#define SIMPB_STAGE(F) \
-  case F: stage_bgr_row<F>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, c.chroma2_offset, row, Ws, q); break
-  switch (c.format) {
-    SIMPB_STAGE(kBgr);
-    SIMPB_STAGE(kNv12);
-    SIMPB_STAGE(kNv21);
-    SIMPB_STAGE(kYuv420p);
-    SIMPB_STAGE(kYuyv);
-    SIMPB_STAGE(kUyvy);
-    SIMPB_STAGE(kRgb);
-    SIMPB_STAGE(kBgra);
-    SIMPB_STAGE(kRgba);
-    default: stage_bgr_row<kP010>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, c.chroma2_offset, row, Ws, q); break;
-  }
-#undef SIMPB_STAGE
+  with_format<true>(c.format, [&](auto f) {
+    stage_bgr_row<decltype(f)::value>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, c.chroma2_offset, row, Ws, q);
+  });
   filter_row_and_store(mid + ((size_t)stream * mid_rows + c.mid_row + r) * pitch, s_src, s_out, kx + c.kx_offset, xlo + c.x_offset,
                        xn + c.x_offset, Ws, w, c.taps_x, c.flip, pitch);
 }
 
-// One output row of one image, the vertical pass + table: `out_image` f16 [h][w][4], `mid_image` the image's `rows`
-// intermediate rows (source rows row0 ..), ky / ylo / yn the image's own tables; y = blockIdx.y, the groups of 4 pixels along
-// blockIdx.x.
-//   out[y][x][c] = lut[c][clip8(2^21 + sum_t mid[ylo[y] - row0 + t][x][swap ? 2 - c : c] * ky[y][t])], out[..][3] = 0
-// zero (uniform over the workgroup): nothing of mid_image is read and the row is written as f16 zeros.
-__device__ __forceinline__ void resample_cols_lut_row(_Float16* __restrict__ out_image, const unsigned char* __restrict__ mid_image,
-                                                      const int* __restrict__ ky, const int* __restrict__ ylo,
-                                                      const int* __restrict__ yn, const _Float16* __restrict__ lut, int row0, int rows,
-                                                      int w, int taps, int swap_rb, int pitch, bool zero) {
+// ------------------------------------------------------------------------------------------------ the vertical pass
+// Image n as the vertical pass sees it: `mid` its `rows` intermediate rows (source rows row0 ..), ky / ylo / yn its own
+// tables; zero (uniform over the workgroup): nothing of mid is read and the image is written as f16 zeros. The two kernels
+// below fill it, each for its way of addressing the images, and that is all they do.
+struct ColsImage {
+  const unsigned char* mid;
+  const int *ky, *ylo, *yn;
+  int row0, rows, taps;
+  bool zero;
+};
+
+// The epilogue of both forms of the vertical pass, in two halves around the accumulation loop. First the [3][256] table
+// goes into LDS (the caller's barrier completes it) ...
+__device__ __forceinline__ void stage_lut(_Float16* s_lut, const _Float16* __restrict__ lut) {
+  for (int i = threadIdx.x; i < 3 * 256; i += kThreads) s_lut[i] = lut[i];
+}
+
+// ... then the 12 sums of group g of row y (4 pixels x 3 channels) go through it and out as two 16-byte stores:
+//   out[y][4 g + px][c] = lut[c][inside[px] ? clamp8(acc[3 px + (swap ? 2 - c : c)] >> 22) : 0],  out[..][3] = 0
+// (all of it f16 zeros where `zero`). The values are pinned and every load of the thread retired before the first store.
+__device__ __forceinline__ void store_lut_group(_Float16* __restrict__ out_image, const _Float16* s_lut, const int (&acc)[12],
+                                                const bool (&inside)[4], bool zero, int y, int g, int w, int swap_rb) {
+  h8 v[2];
+#pragma unroll
+  for (int px = 0; px < 4; ++px) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int ci = swap_rb ? 2 - c : c;
+      v[px >> 1][(px & 1) * 4 + c] = zero ? (_Float16)0.f : s_lut[c * 256 + (inside[px] ? clamp8(acc[px * 3 + ci] >> kPrecision) : 0)];
+    }
+    v[px >> 1][(px & 1) * 4 + 3] = (_Float16)0.f;
+  }
+  simpb::pin(v[0]);
+  simpb::pin(v[1]);
+  simpb::loads_retired();
+  _Float16* o = out_image + ((size_t)y * w + 4 * g) * 4;
+  if (4 * g + 4 <= w) {
+    *reinterpret_cast<h8*>(o) = v[0];
+    *reinterpret_cast<h8*>(o + 8) = v[1];
+  } else {   // the last, partial group of a width that is no multiple of 4
+#pragma unroll
+    for (int px = 0; px < 3; ++px)
+      if (4 * g + px < w) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[px * 4 + c] = v[px >> 1][(px & 1) * 4 + c];
+      }
+  }
+}
+
+// One output row of one image, the level vertical pass + table: `out_image` f16 [h][w][4]; y = blockIdx.y, the groups of 4
+// pixels along blockIdx.x. A thread reads 12 intermediate bytes per tap row (three aligned dwords).
+//   out[y][x][c] = lut[c][clamp8((2^21 + sum_t mid[ylo[y] - row0 + t][x][swap ? 2 - c : c] * ky[y][t]) >> 22)], out[..][3] = 0
+__device__ __forceinline__ void resample_cols_lut_row(_Float16* __restrict__ out_image, const ColsImage& im,
+                                                      const _Float16* __restrict__ lut, int w, int swap_rb, int pitch) {
   __shared__ _Float16 s_lut[3 * 256];
   __shared__ int s_k[kMaxTaps];
   const int tid = threadIdx.x, y = blockIdx.y;
-  for (int i = tid; i < 3 * 256; i += kThreads) s_lut[i] = lut[i];
-  const int cnt = zero ? 0 : min(min(yn[y], taps), rows);
-  if (tid < cnt) s_k[tid] = ky[(size_t)y * taps + tid];
+  stage_lut(s_lut, lut);
+  const int cnt = im.zero ? 0 : min(min(im.yn[y], im.taps), im.rows);
+  if (tid < cnt) s_k[tid] = im.ky[(size_t)y * im.taps + tid];
   __syncthreads();
   const int g = blockIdx.x * kThreads + tid;   // group of 4 output pixels
   if (4 * g >= w) return;
-  const int first = zero ? 0 : min(max(ylo[y] - row0, 0), rows - cnt);   // (clamped like the horizontal pass: never outside `mid`)
-  const unsigned int* p = reinterpret_cast<const unsigned int*>(mid_image + (size_t)first * pitch) + 3 * g;
+  const int first = im.zero ? 0 : min(max(im.ylo[y] - im.row0, 0), im.rows - cnt);   // (clamped like the horizontal pass: never outside `mid`)
+  const unsigned int* p = reinterpret_cast<const unsigned int*>(im.mid + (size_t)first * pitch) + 3 * g;
   const int pitch4 = pitch >> 2;
   int acc[12];
 #pragma unroll
@@ -414,56 +451,8 @@ __device__ __forceinline__ void resample_cols_lut_row(_Float16* __restrict__ out
       acc[8 + i] += (int)((d2 >> (8 * i)) & 255u) * c;
     }
   }
-  h8 v[2];
-#pragma unroll
-  for (int px = 0; px < 4; ++px) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int ci = swap_rb ? 2 - c : c;
-      v[px >> 1][(px & 1) * 4 + c] = zero ? (_Float16)0.f : s_lut[c * 256 + clip8(acc[px * 3 + ci])];
-    }
-    v[px >> 1][(px & 1) * 4 + 3] = (_Float16)0.f;
-  }
-  simpb::pin(v[0]);
-  simpb::pin(v[1]);
-  simpb::loads_retired();
-  _Float16* o = out_image + ((size_t)y * w + 4 * g) * 4;
-  if (4 * g + 4 <= w) {
-    *reinterpret_cast<h8*>(o) = v[0];
-    *reinterpret_cast<h8*>(o + 8) = v[1];
-  } else {   // the last, partial group of a width that is no multiple of 4
-#pragma unroll
-    for (int px = 0; px < 3; ++px)
-      if (4 * g + px < w) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) o[px * 4 + c] = v[px >> 1][(px & 1) * 4 + c];
-      }
-  }
-}
-
-// out[n][y][x][c] = lut[c][clip8(2^21 + sum_t mid[n][ylo[y] - row0 + t][x][swap ? 2 - c : c] * ky[y][t])], out[..][3] = 0
-__global__ __launch_bounds__(kThreads) void resample_cols_lut_kernel(_Float16* __restrict__ out, const unsigned char* __restrict__ mid,
-                                                                     const int* __restrict__ ky, const int* __restrict__ ylo,
-                                                                     const int* __restrict__ yn, const _Float16* __restrict__ lut,
-                                                                     int row0, int rows, int h, int w, int taps, int swap_rb, int pitch) {
-  const int n = blockIdx.z;
-  resample_cols_lut_row(out + (size_t)n * h * w * 4, mid + (size_t)n * rows * pitch, ky, ylo, yn, lut, row0, rows, w, taps, swap_rb,
-                        pitch, false);
-}
-
-// The vertical pass of a rig: image n reads its camera's ky / ylo / yn, row range and taps, and its own rows of its stream's
-// intermediate block; an image whose address is 0 is written as zeros.
-__global__ __launch_bounds__(kThreads) void resample_cols_lut_rig_kernel(_Float16* __restrict__ out, const unsigned char* __restrict__ mid,
-                                                                         const unsigned long long* __restrict__ table, Rig rig,
-                                                                         int num_cams, const int* __restrict__ ky,
-                                                                         const int* __restrict__ ylo, const int* __restrict__ yn,
-                                                                         const _Float16* __restrict__ lut, int h, int w, int swap_rb,
-                                                                         int pitch, int mid_rows) {
-  const int n = blockIdx.z;
-  const int stream = n / num_cams;
-  const simpb_rig_camera& c = rig.cam[n - stream * num_cams];
-  resample_cols_lut_row(out + (size_t)n * h * w * 4, mid + ((size_t)stream * mid_rows + c.mid_row) * pitch, ky + c.ky_offset,
-                        ylo + c.y_offset, yn + c.y_offset, lut, c.src_row0, c.src_rows, w, c.taps_y, swap_rb, pitch, table[n] == 0ull);
+  const bool inside[4] = {true, true, true, true};
+  store_lut_group(out_image, s_lut, acc, inside, im.zero, y, g, w, swap_rb);
 }
 
 // A camera's MOUNT ROLL (simpb_preprocess_roll_nhwc4_f16, simpb_preprocess_rig_roll_nhwc4_f16): the reference's fourth step,
@@ -475,26 +464,35 @@ __global__ __launch_bounds__(kThreads) void resample_cols_lut_rig_kernel(_Float1
 // pass: the thread still owns 4 neighbouring output pixels and writes two 16-byte stores, but each pixel brings its own row
 // of ky and its own column of mid. The six integers per camera are the host's (simpb_amd/preprocess.py:roll_integers) and
 // travel by value; the kernel knows nothing else of the angle. (65536, 0, 32768, 0, 65536, 32768) is the identity.
-struct RollTable { int a[SIMPB_RIG_MAX_CAMS][6]; };
+// Image n of a uniform batch takes row n % cams of the table, an image of a rig its camera's.
+struct RollTable {
+  static constexpr bool kRolled = true;
+  int a[SIMPB_RIG_MAX_CAMS][6];
+  int cams;
+  __device__ __forceinline__ const int* row(int camera) const { return a[camera]; }
+};
+struct Level {   // in the table's place where no camera is rolled
+  static constexpr bool kRolled = false;
+  static constexpr int cams = 1;
+  __device__ __forceinline__ const int* row(int) const { return nullptr; }
+};
 
 constexpr int kMaxRollSize = SIMPB_PREPROCESS_MAX_ROLL_SIZE;
 
 // One output row of one image, the rolled vertical pass + table (arguments as resample_cols_lut_row; `a`: the image's six
 // integers, uniform over the workgroup):
-//   out[y][x][c] = lut[c][clip8(2^21 + sum_t mid[ylo[yin] - row0 + t][xin][swap ? 2 - c : c] * ky[yin][t])], out[..][3] = 0
+//   out[y][x][c] = lut[c][clamp8((2^21 + sum_t mid[ylo[yin] - row0 + t][xin][swap ? 2 - c : c] * ky[yin][t]) >> 22)], out[..][3] = 0
 // The range test on (xin, yin) comes first; behind it the tap count, `first`, the row and the dword index are clamped as the
 // level pass clamps them, and a pixel out of range (or a tap past its pixel's count) loads from row / column 0 with a
 // coefficient of 0: a wrong table gives wrong pixels, never an access outside mid, ky, ylo or yn. The three bytes of a pixel
 // start at byte 3 * xin of a row, at any alignment: they are cut out of the aligned dword that holds the first and the one
 // behind it (the row's last dword again where there is none; 3 * xin + 2 < 3 * w <= pitch, so the bytes wanted lie in the two).
-__device__ __forceinline__ void resample_cols_lut_roll_row(_Float16* __restrict__ out_image, const unsigned char* __restrict__ mid_image,
-                                                           const int* __restrict__ ky, const int* __restrict__ ylo,
-                                                           const int* __restrict__ yn, const _Float16* __restrict__ lut, int row0,
-                                                           int rows, int h, int w, int taps, int swap_rb, int pitch, bool zero,
+__device__ __forceinline__ void resample_cols_lut_roll_row(_Float16* __restrict__ out_image, const ColsImage& im,
+                                                           const _Float16* __restrict__ lut, int h, int w, int swap_rb, int pitch,
                                                            const int* a) {
   __shared__ _Float16 s_lut[3 * 256];
   const int tid = threadIdx.x, y = blockIdx.y;
-  for (int i = tid; i < 3 * 256; i += kThreads) s_lut[i] = lut[i];
+  stage_lut(s_lut, lut);
   __syncthreads();
   const int g = blockIdx.x * kThreads + tid;   // group of 4 output pixels
   if (4 * g >= w) return;
@@ -507,13 +505,13 @@ __device__ __forceinline__ void resample_cols_lut_roll_row(_Float16* __restrict_
   for (int px = 0; px < 4; ++px) {
     const int x = 4 * g + px;
     const long long xs = (a2 + y * a1 + x * a0) >> 16, ys = (a5 + y * a4 + x * a3) >> 16;
-    inside[px] = !zero && xs >= 0 && xs < w && ys >= 0 && ys < h;
+    inside[px] = !im.zero && xs >= 0 && xs < w && ys >= 0 && ys < h;
     const int xin = inside[px] ? (int)xs : 0, yin = inside[px] ? (int)ys : 0;
-    cnt[px] = inside[px] ? max(min(min(yn[yin], taps), rows), 0) : 0;
-    first[px] = min(max(ylo[yin] - row0, 0), rows - cnt[px]);
+    cnt[px] = inside[px] ? max(min(min(im.yn[yin], im.taps), im.rows), 0) : 0;
+    first[px] = min(max(im.ylo[yin] - im.row0, 0), im.rows - cnt[px]);
     dword[px] = (3 * xin) >> 2;
     shift[px] = 8 * ((3 * xin) & 3);
-    krow[px] = yin * taps;   // (h <= 8192, taps <= 64)
+    krow[px] = yin * im.taps;   // (h <= 8192, taps <= 64)
     most = max(most, cnt[px]);
   }
   int acc[12];
@@ -522,67 +520,66 @@ __device__ __forceinline__ void resample_cols_lut_roll_row(_Float16* __restrict_
   for (int t = 0; t < most; ++t) {   // (most <= taps: ky[krow + t] lies in the pixel's own row of ky)
 #pragma unroll
     for (int px = 0; px < 4; ++px) {
-      const unsigned int* p = reinterpret_cast<const unsigned int*>(mid_image + (size_t)min(first[px] + t, rows - 1) * pitch);
+      const unsigned int* p = reinterpret_cast<const unsigned int*>(im.mid + (size_t)min(first[px] + t, im.rows - 1) * pitch);
       const unsigned int d0 = p[dword[px]], d1 = p[min(dword[px] + 1, pitch4 - 1)];
-      const int c = t < cnt[px] ? ky[krow[px] + t] : 0;
+      const int c = t < cnt[px] ? im.ky[krow[px] + t] : 0;
       const unsigned int v = (unsigned int)((((unsigned long long)d1 << 32) | d0) >> shift[px]);
 #pragma unroll
       for (int i = 0; i < 3; ++i) acc[px * 3 + i] += (int)((v >> (8 * i)) & 255u) * c;
     }
   }
-  h8 v[2];
-#pragma unroll
-  for (int px = 0; px < 4; ++px) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int ci = swap_rb ? 2 - c : c;
-      v[px >> 1][(px & 1) * 4 + c] = zero ? (_Float16)0.f : s_lut[c * 256 + (inside[px] ? clip8(acc[px * 3 + ci]) : 0)];
-    }
-    v[px >> 1][(px & 1) * 4 + 3] = (_Float16)0.f;
-  }
-  simpb::pin(v[0]);
-  simpb::pin(v[1]);
-  simpb::loads_retired();
-  _Float16* o = out_image + ((size_t)y * w + 4 * g) * 4;
-  if (4 * g + 4 <= w) {
-    *reinterpret_cast<h8*>(o) = v[0];
-    *reinterpret_cast<h8*>(o + 8) = v[1];
-  } else {   // the last, partial group of a width that is no multiple of 4
-#pragma unroll
-    for (int px = 0; px < 3; ++px)
-      if (4 * g + px < w) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) o[px * 4 + c] = v[px >> 1][(px & 1) * 4 + c];
-      }
-  }
+  store_lut_group(out_image, s_lut, acc, inside, im.zero, y, g, w, swap_rb);
 }
 
-// The rolled vertical pass of a uniform batch: image n takes row n % roll_cams of the table.
-__global__ __launch_bounds__(kThreads) void resample_cols_lut_roll_kernel(_Float16* __restrict__ out, const unsigned char* __restrict__ mid,
-                                                                          const int* __restrict__ ky, const int* __restrict__ ylo,
-                                                                          const int* __restrict__ yn, const _Float16* __restrict__ lut,
-                                                                          int row0, int rows, int h, int w, int taps, int swap_rb,
-                                                                          int pitch, RollTable roll, int roll_cams) {
+// One output row of one image, level or rolled (`a`: the image's six integers, looked at by the rolled form alone)
+template <bool kRolled>
+__device__ __forceinline__ void resample_cols_lut_either_row(_Float16* __restrict__ out_image, const ColsImage& im,
+                                                             const _Float16* __restrict__ lut, int h, int w, int swap_rb, int pitch,
+                                                             const int* a) {
+  if constexpr (kRolled) resample_cols_lut_roll_row(out_image, im, lut, h, w, swap_rb, pitch, a);
+  else resample_cols_lut_row(out_image, im, lut, w, swap_rb, pitch);
+}
+
+// The vertical pass of a uniform batch, level (Roll = Level) or rolled (RollTable): every image has the plan's one set of
+// tables and its own block of `rows` intermediate rows.
+template <class Roll>
+__global__ __launch_bounds__(kThreads) void resample_cols_lut_kernel(_Float16* __restrict__ out, const unsigned char* __restrict__ mid,
+                                                                     const int* __restrict__ ky, const int* __restrict__ ylo,
+                                                                     const int* __restrict__ yn, const _Float16* __restrict__ lut,
+                                                                     int row0, int rows, int h, int w, int taps, int swap_rb, int pitch,
+                                                                     Roll roll) {
   const int n = blockIdx.z;
-  resample_cols_lut_roll_row(out + (size_t)n * h * w * 4, mid + (size_t)n * rows * pitch, ky, ylo, yn, lut, row0, rows, h, w, taps,
-                             swap_rb, pitch, false, roll.a[n % roll_cams]);
+  const ColsImage im = {mid + (size_t)n * rows * pitch, ky, ylo, yn, row0, rows, taps, false};
+  resample_cols_lut_either_row<Roll::kRolled>(out + (size_t)n * h * w * 4, im, lut, h, w, swap_rb, pitch, roll.row(n % roll.cams));
 }
 
-// The rolled vertical pass of a rig: resample_cols_lut_rig_kernel with camera c's six integers.
-__global__ __launch_bounds__(kThreads) void resample_cols_lut_rig_roll_kernel(_Float16* __restrict__ out,
-                                                                              const unsigned char* __restrict__ mid,
-                                                                              const unsigned long long* __restrict__ table, Rig rig,
-                                                                              int num_cams, const int* __restrict__ ky,
-                                                                              const int* __restrict__ ylo, const int* __restrict__ yn,
-                                                                              const _Float16* __restrict__ lut, int h, int w,
-                                                                              int swap_rb, int pitch, int mid_rows, RollTable roll) {
+// The vertical pass of a rig, level or rolled: image n reads its camera's ky / ylo / yn, row range and taps, and its own rows
+// of its stream's intermediate block; an image whose address is 0 is written as zeros.
+template <class Roll>
+__global__ __launch_bounds__(kThreads) void resample_cols_lut_rig_kernel(_Float16* __restrict__ out, const unsigned char* __restrict__ mid,
+                                                                         const unsigned long long* __restrict__ table, Rig rig,
+                                                                         int num_cams, const int* __restrict__ ky,
+                                                                         const int* __restrict__ ylo, const int* __restrict__ yn,
+                                                                         const _Float16* __restrict__ lut, int h, int w, int swap_rb,
+                                                                         int pitch, int mid_rows, Roll roll) {
   const int n = blockIdx.z;
   const int stream = n / num_cams, cam = n - stream * num_cams;
   const simpb_rig_camera& c = rig.cam[cam];
-  resample_cols_lut_roll_row(out + (size_t)n * h * w * 4, mid + ((size_t)stream * mid_rows + c.mid_row) * pitch, ky + c.ky_offset,
-                             ylo + c.y_offset, yn + c.y_offset, lut, c.src_row0, c.src_rows, h, w, c.taps_y, swap_rb, pitch,
-                             table[n] == 0ull, roll.a[cam]);
+  const ColsImage im = {mid + ((size_t)stream * mid_rows + c.mid_row) * pitch, ky + c.ky_offset, ylo + c.y_offset, yn + c.y_offset,
+                        c.src_row0, c.src_rows, c.taps_y, table[n] == 0ull};
+  resample_cols_lut_either_row<Roll::kRolled>(out + (size_t)n * h * w * 4, im, lut, h, w, swap_rb, pitch, roll.row(cam));
 }
+
+// ---------------------------------------------------------------------------------------------------- the host side
+// What every entry point is given beside its images, filled once from its argument list: the device arrays ...
+struct Tables {
+  void* mid;
+  const int *kx, *xlo, *xn, *ky, *ylo, *yn;
+  const void* lut;
+};
+
+// ... and the numbers (flip and swap_rb as 0 / 1). A rig has one per camera, for the checks.
+struct Shape { int num_images, src_height, src_width, out_height, out_width, taps_x, taps_y, src_row0, src_rows, flip, swap_rb; };
 
 }  // namespace
 
@@ -593,85 +590,70 @@ extern "C" int simpb_preprocess_mid_pitch(int out_width) {
   return (out_width <= 0 || out_width > kMaxOutW) ? 0 : mid_pitch(out_width);
 }
 
-// what every entry point refuses (before any HIP call)
-static bool bad_arguments(const void* out, const void* src, const void* mid, const int* kx, const int* xlo, const int* xn, const int* ky,
-                          const int* ylo, const int* yn, const void* lut, int num_images, int src_height, int src_width, int out_height,
-                          int out_width, int taps_x, int taps_y, int src_row0, int src_rows) {
-  if (!out || !src || !mid || !kx || !xlo || !xn || !ky || !ylo || !yn || !lut) return true;
-  if (num_images <= 0 || num_images > 65535 || src_height <= 0 || src_width <= 0 || out_height <= 0 || out_width <= 0 ||
-      out_height > 65535 || src_width > kMaxSrcW || out_width > kMaxOutW)
+// what every entry point refuses (before any HIP call); `images` is the batch or the address table
+static bool bad_arguments(const void* out, const void* images, const Tables& t, const Shape& sh) {
+  if (!out || !images || !t.mid || !t.kx || !t.xlo || !t.xn || !t.ky || !t.ylo || !t.yn || !t.lut) return true;
+  if (sh.num_images <= 0 || sh.num_images > 65535 || sh.src_height <= 0 || sh.src_width <= 0 || sh.out_height <= 0 ||
+      sh.out_width <= 0 || sh.out_height > 65535 || sh.src_width > kMaxSrcW || sh.out_width > kMaxOutW)
     return true;
-  if (taps_x <= 0 || taps_y <= 0 || taps_x > kMaxTaps || taps_y > kMaxTaps) return true;
-  if (src_row0 < 0 || src_rows <= 0 || (long long)src_row0 + src_rows > src_height) return true;
-  if ((reinterpret_cast<size_t>(out) | reinterpret_cast<size_t>(mid)) & 15) return true;
-  if ((reinterpret_cast<size_t>(kx) | reinterpret_cast<size_t>(xlo) | reinterpret_cast<size_t>(xn) | reinterpret_cast<size_t>(ky) |
-       reinterpret_cast<size_t>(ylo) | reinterpret_cast<size_t>(yn)) & 3)
+  if (sh.taps_x <= 0 || sh.taps_y <= 0 || sh.taps_x > kMaxTaps || sh.taps_y > kMaxTaps) return true;
+  if (sh.src_row0 < 0 || sh.src_rows <= 0 || (long long)sh.src_row0 + sh.src_rows > sh.src_height) return true;
+  if ((reinterpret_cast<size_t>(out) | reinterpret_cast<size_t>(t.mid)) & 15) return true;
+  if ((reinterpret_cast<size_t>(t.kx) | reinterpret_cast<size_t>(t.xlo) | reinterpret_cast<size_t>(t.xn) |
+       reinterpret_cast<size_t>(t.ky) | reinterpret_cast<size_t>(t.ylo) | reinterpret_cast<size_t>(t.yn)) & 3)
     return true;
-  return (reinterpret_cast<size_t>(lut) & 1) != 0;
+  return (reinterpret_cast<size_t>(t.lut) & 1) != 0;
 }
 
-// the vertical pass + table (rolled where `roll` is given: image n takes row n % roll_cams), and the status of both launches
-static int finish_vertical(void* out, const void* mid, const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
-                           int out_height, int out_width, int taps_y, int src_row0, int src_rows, int swap_rb, int pitch, hipStream_t s,
-                           const RollTable* roll = nullptr, int roll_cams = 0) {
+// The vertical launch of every entry point, and the status of both launches: launch(grid, block, Level or RollTable) starts
+// the caller's kernel, rolled where `roll` is given.
+template <class Launch>
+static int launch_vertical(int num_images, int out_height, int out_width, const RollTable* roll, Launch&& launch) {
   const int groups = (out_width + 3) / 4;
-  const dim3 grid((groups + kThreads - 1) / kThreads, out_height, num_images);
-  if (roll)
-    hipLaunchKernelGGL(resample_cols_lut_roll_kernel, grid, dim3(kThreads), 0, s, static_cast<_Float16*>(out),
-                       static_cast<const unsigned char*>(mid), ky, ylo, yn, static_cast<const _Float16*>(lut), src_row0, src_rows,
-                       out_height, out_width, taps_y, swap_rb ? 1 : 0, pitch, *roll, roll_cams);
-  else
-    hipLaunchKernelGGL(resample_cols_lut_kernel, grid, dim3(kThreads), 0, s, static_cast<_Float16*>(out),
-                       static_cast<const unsigned char*>(mid), ky, ylo, yn, static_cast<const _Float16*>(lut), src_row0, src_rows,
-                       out_height, out_width, taps_y, swap_rb ? 1 : 0, pitch);
+  const dim3 grid((groups + kThreads - 1) / kThreads, out_height, num_images), block(kThreads);
+  if (roll) launch(grid, block, *roll);
+  else launch(grid, block, Level{});
   return simpb_check_launch();
 }
 
+// the vertical pass + table of a uniform batch
+static int uniform_vertical(void* out, const Tables& t, const Shape& sh, const RollTable* roll, hipStream_t s) {
+  return launch_vertical(sh.num_images, sh.out_height, sh.out_width, roll, [&](dim3 grid, dim3 block, auto r) {
+    hipLaunchKernelGGL(resample_cols_lut_kernel<decltype(r)>, grid, block, 0, s, static_cast<_Float16*>(out),
+                       static_cast<const unsigned char*>(t.mid), t.ky, t.ylo, t.yn, static_cast<const _Float16*>(t.lut), sh.src_row0,
+                       sh.src_rows, sh.out_height, sh.out_width, sh.taps_y, sh.swap_rb, mid_pitch(sh.out_width), r);
+  });
+}
+
 // the horizontal pass of one source format on a checked surface, then the vertical pass
-static int launch_surface(int format, void* out, const Surface& sf, void* mid, const int* kx, const int* xlo, const int* xn, const int* ky,
-                          const int* ylo, const int* yn, const void* lut, int num_images, int src_width, int out_height, int out_width,
-                          int taps_x, int taps_y, int src_row0, int src_rows, int flip, int swap_rb, const YuvCoeffs& q, void* stream,
-                          const RollTable* roll, int roll_cams) {
-  const int pitch = mid_pitch(out_width);
+static int launch_surface(int format, void* out, const Surface& sf, const Tables& t, const Shape& sh, const YuvCoeffs& q, void* stream,
+                          const RollTable* roll) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   (void)hipGetLastError();
-  const dim3 grid(src_rows, num_images), block(kThreads);
-  unsigned char* m = static_cast<unsigned char*>(mid);
-  const int f = flip ? 1 : 0;
-#define SIMPB_ROWS(F) \
-  hipLaunchKernelGGL(resample_rows_surface_kernel<F>, grid, block, 0, s, m, sf, kx, xlo, xn, src_width, src_row0, src_rows, out_width, taps_x, f, pitch, q)
-  switch (format) {
-    case kBgr: SIMPB_ROWS(kBgr); break;
-    case kNv12: SIMPB_ROWS(kNv12); break;
-    case kNv21: SIMPB_ROWS(kNv21); break;
-    case kYuv420p: SIMPB_ROWS(kYuv420p); break;
-    case kYuyv: SIMPB_ROWS(kYuyv); break;
-    case kUyvy: SIMPB_ROWS(kUyvy); break;
-    case kRgb: SIMPB_ROWS(kRgb); break;
-    case kBgra: SIMPB_ROWS(kBgra); break;
-    case kRgba: SIMPB_ROWS(kRgba); break;
-    default: SIMPB_ROWS(kP010); break;
-  }
-#undef SIMPB_ROWS
-  return finish_vertical(out, mid, ky, ylo, yn, lut, num_images, out_height, out_width, taps_y, src_row0, src_rows, swap_rb, pitch, s,
-                         roll, roll_cams);
+  const bool known = with_format(format, [&](auto f) {
+    hipLaunchKernelGGL(resample_rows_surface_kernel<decltype(f)::value>, dim3(sh.src_rows, sh.num_images), dim3(kThreads), 0, s,
+                       static_cast<unsigned char*>(t.mid), sf, t.kx, t.xlo, t.xn, sh.src_width, sh.src_row0, sh.src_rows, sh.out_width,
+                       sh.taps_x, sh.flip, mid_pitch(sh.out_width), q);
+  });
+  if (!known) return SIMPB_EINVAL;   // (not reached: every entry point has checked `format`)
+  return uniform_vertical(out, t, sh, roll, s);
 }
 
 extern "C" int simpb_preprocess_u8_nhwc4_f16(void* out, const void* src, void* mid, const int* kx, const int* xlo, const int* xn,
                                              const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
                                              int src_height, int src_width, int out_height, int out_width, int taps_x, int taps_y,
                                              int src_row0, int src_rows, int flip, int swap_rb, void* stream) {
-  if (bad_arguments(out, src, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height, out_width, taps_x,
-                    taps_y, src_row0, src_rows))
-    return SIMPB_EINVAL;
-  const int pitch = mid_pitch(out_width);
+  const Tables t = {mid, kx, xlo, xn, ky, ylo, yn, lut};
+  const Shape sh = {num_images, src_height, src_width, out_height, out_width, taps_x, taps_y, src_row0, src_rows, flip ? 1 : 0,
+                    swap_rb ? 1 : 0};
+  if (bad_arguments(out, src, t, sh)) return SIMPB_EINVAL;
   const int vec16 = ((size_t)src_width * 3 % 16 == 0 && (reinterpret_cast<size_t>(src) & 15) == 0) ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   (void)hipGetLastError();
   hipLaunchKernelGGL(resample_rows_kernel, dim3(src_rows, num_images), dim3(kThreads), 0, s, static_cast<unsigned char*>(mid),
                      static_cast<const unsigned char*>(src), kx, xlo, xn, src_height, src_width, src_row0, src_rows, out_width,
-                     taps_x, flip ? 1 : 0, pitch, vec16);
-  return finish_vertical(out, mid, ky, ylo, yn, lut, num_images, out_height, out_width, taps_y, src_row0, src_rows, swap_rb, pitch, s);
+                     taps_x, sh.flip, mid_pitch(out_width), vec16);
+  return uniform_vertical(out, t, sh, nullptr, s);
 }
 
 extern "C" int simpb_preprocess_yuv420sp_nhwc4_f16(void* out, const void* src, void* mid, const int* kx, const int* xlo, const int* xn,
@@ -679,11 +661,11 @@ extern "C" int simpb_preprocess_yuv420sp_nhwc4_f16(void* out, const void* src, v
                                                    int src_height, int src_width, int out_height, int out_width, int taps_x,
                                                    int taps_y, int src_row0, int src_rows, int flip, int swap_rb, int vu_order, int yoff,
                                                    int iy, int irv, int igu, int igv, int ibu, void* stream) {
-  if (bad_arguments(out, src, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height, out_width, taps_x,
-                    taps_y, src_row0, src_rows))
-    return SIMPB_EINVAL;
+  const Tables t = {mid, kx, xlo, xn, ky, ylo, yn, lut};
+  const Shape sh = {num_images, src_height, src_width, out_height, out_width, taps_x, taps_y, src_row0, src_rows, flip ? 1 : 0,
+                    swap_rb ? 1 : 0};
+  if (bad_arguments(out, src, t, sh)) return SIMPB_EINVAL;
   if ((src_height & 1) || (src_width & 1) || (vu_order != 0 && vu_order != 1) || iy <= 0) return SIMPB_EINVAL;
-  const int pitch = mid_pitch(out_width);
   // every luma and chroma row starts on a 16-byte boundary when the width is a multiple of 16 and the first image does
   const int vec16 = (src_width % 16 == 0 && (reinterpret_cast<size_t>(src) & 15) == 0) ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -691,8 +673,8 @@ extern "C" int simpb_preprocess_yuv420sp_nhwc4_f16(void* out, const void* src, v
   const YuvCoeffs q = {yoff, iy, irv, igu, igv, ibu};
   hipLaunchKernelGGL(resample_rows_yuv420sp_kernel, dim3(src_rows, num_images), dim3(kThreads), 0, s, static_cast<unsigned char*>(mid),
                      static_cast<const unsigned char*>(src), kx, xlo, xn, src_height, src_width, src_row0, src_rows, out_width,
-                     taps_x, flip ? 1 : 0, pitch, vec16, vu_order, q);
-  return finish_vertical(out, mid, ky, ylo, yn, lut, num_images, out_height, out_width, taps_y, src_row0, src_rows, swap_rb, pitch, s);
+                     taps_x, sh.flip, mid_pitch(out_width), vec16, vu_order, q);
+  return uniform_vertical(out, t, sh, nullptr, s);
 }
 
 // [lo, lo + len) of two ranges overlap
@@ -730,30 +712,23 @@ static long long surface_extent(int format, int src_height, int src_width, long 
   return (chroma_offset > chroma2_offset ? chroma_offset : chroma2_offset) + span;
 }
 
-// what the surface entry points do behind their own check of `format` (roll: the rolled one's table, or null)
-static int preprocess_surface(void* out, const void* src, const void* image_table, void* mid, const int* kx, const int* xlo,
-                              const int* xn, const int* ky, const int* ylo, const int* yn, const void* lut, int num_images,
-                              int src_height, int src_width, int out_height, int out_width, int taps_x, int taps_y, int src_row0,
-                              int src_rows, int flip, int swap_rb, int format, long long pitch, long long chroma_pitch,
-                              long long chroma_offset, long long chroma2_offset, long long image_stride, const YuvCoeffs& q,
-                              void* stream, const RollTable* roll = nullptr, int roll_cams = 0) {
-  if ((src != nullptr) == (image_table != nullptr)) return SIMPB_EINVAL;   // exactly one form of the images
-  if (bad_arguments(out, src ? src : image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height,
-                    out_width, taps_x, taps_y, src_row0, src_rows))
-    return SIMPB_EINVAL;
-  if (reinterpret_cast<size_t>(image_table) & 7) return SIMPB_EINVAL;
-  const long long end = surface_extent(format, src_height, src_width, pitch, chroma_pitch, chroma_offset, chroma2_offset, q.iy);
+// what the surface entry points do behind their own check of `format`: `sf` as the caller gave it (both forms of the images,
+// one of them null), checked and set right here (roll: the rolled one's table, or null)
+static int preprocess_surface(void* out, Surface sf, int format, const Tables& t, const Shape& sh, const YuvCoeffs& q, void* stream,
+                              const RollTable* roll = nullptr) {
+  if ((sf.src != nullptr) == (sf.table != nullptr)) return SIMPB_EINVAL;   // exactly one form of the images
+  if (bad_arguments(out, sf.src ? static_cast<const void*>(sf.src) : sf.table, t, sh)) return SIMPB_EINVAL;
+  if (reinterpret_cast<size_t>(sf.table) & 7) return SIMPB_EINVAL;
+  const long long end = surface_extent(format, sh.src_height, sh.src_width, sf.pitch, sf.chroma_pitch, sf.chroma_offset,
+                                       sf.chroma2_offset, q.iy);
   if (end < 0) return SIMPB_EINVAL;
-  if (src) {
-    if (image_stride < end || image_stride > (1LL << 40)) return SIMPB_EINVAL;
-    if (format == kP010 && ((image_stride | (long long)reinterpret_cast<size_t>(src)) & 1)) return SIMPB_EINVAL;
+  if (sf.src) {
+    if (sf.image_stride < end || sf.image_stride > (1LL << 40)) return SIMPB_EINVAL;
+    if (format == kP010 && ((sf.image_stride | (long long)reinterpret_cast<size_t>(sf.src)) & 1)) return SIMPB_EINVAL;
   } else {
-    image_stride = 0;   // (not looked at)
+    sf.image_stride = 0;   // (not looked at)
   }
-  const Surface sf = {static_cast<const unsigned char*>(src), static_cast<const unsigned long long*>(image_table), image_stride,
-                      chroma_offset, pitch, chroma_pitch, chroma2_offset};
-  return launch_surface(format, out, sf, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_width, out_height, out_width, taps_x, taps_y,
-                        src_row0, src_rows, flip, swap_rb, q, stream, roll, roll_cams);
+  return launch_surface(format, out, sf, t, sh, q, stream, roll);
 }
 
 extern "C" int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
@@ -764,9 +739,12 @@ extern "C" int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, co
                                                   long long image_stride, int yoff, int iy, int irv, int igu, int igv, int ibu,
                                                   void* stream) {
   if (format != kBgr && format != kNv12 && format != kNv21 && format != kP010) return SIMPB_EINVAL;
-  return preprocess_surface(out, src, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height,
-                            out_width, taps_x, taps_y, src_row0, src_rows, flip, swap_rb, format, pitch, chroma_pitch, chroma_offset, 0,
-                            image_stride, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream);
+  const Surface sf = {static_cast<const unsigned char*>(src), static_cast<const unsigned long long*>(image_table), image_stride,
+                      chroma_offset, pitch, chroma_pitch, 0};
+  const Tables t = {mid, kx, xlo, xn, ky, ylo, yn, lut};
+  const Shape sh = {num_images, src_height, src_width, out_height, out_width, taps_x, taps_y, src_row0, src_rows, flip ? 1 : 0,
+                    swap_rb ? 1 : 0};
+  return preprocess_surface(out, sf, format, t, sh, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream);
 }
 
 extern "C" int simpb_preprocess_planes_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
@@ -777,15 +755,19 @@ extern "C" int simpb_preprocess_planes_nhwc4_f16(void* out, const void* src, con
                                                  long long chroma2_offset, long long image_stride, int yoff, int iy, int irv, int igu,
                                                  int igv, int ibu, void* stream) {
   if (!known_format(format)) return SIMPB_EINVAL;
-  return preprocess_surface(out, src, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height,
-                            out_width, taps_x, taps_y, src_row0, src_rows, flip, swap_rb, format, pitch, chroma_pitch, chroma_offset,
-                            chroma2_offset, image_stride, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream);
+  const Surface sf = {static_cast<const unsigned char*>(src), static_cast<const unsigned long long*>(image_table), image_stride,
+                      chroma_offset, pitch, chroma_pitch, chroma2_offset};
+  const Tables t = {mid, kx, xlo, xn, ky, ylo, yn, lut};
+  const Shape sh = {num_images, src_height, src_width, out_height, out_width, taps_x, taps_y, src_row0, src_rows, flip ? 1 : 0,
+                    swap_rb ? 1 : 0};
+  return preprocess_surface(out, sf, format, t, sh, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream);
 }
 
 // what both rolled entry points refuse on top of their level forms (before any HIP call); `table` takes the rows otherwise
 static bool bad_roll(RollTable& table, const int* roll, int roll_cams, int out_height, int out_width) {
   if (!roll || roll_cams < 1 || roll_cams > SIMPB_RIG_MAX_CAMS || out_height > kMaxRollSize || out_width > kMaxRollSize) return true;
   table = RollTable{};
+  table.cams = roll_cams;
   for (int i = 0; i < roll_cams * 6; ++i) table.a[i / 6][i % 6] = roll[i];
   return false;
 }
@@ -799,16 +781,18 @@ extern "C" int simpb_preprocess_roll_nhwc4_f16(void* out, const void* src, const
                                                int igv, int ibu, const int* roll, int roll_cams, void* stream) {
   RollTable table;
   if (bad_roll(table, roll, roll_cams, out_height, out_width) || !known_format(format)) return SIMPB_EINVAL;
-  return preprocess_surface(out, src, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, src_height, src_width, out_height,
-                            out_width, taps_x, taps_y, src_row0, src_rows, flip, swap_rb, format, pitch, chroma_pitch, chroma_offset,
-                            chroma2_offset, image_stride, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream, &table, roll_cams);
+  const Surface sf = {static_cast<const unsigned char*>(src), static_cast<const unsigned long long*>(image_table), image_stride,
+                      chroma_offset, pitch, chroma_pitch, chroma2_offset};
+  const Tables t = {mid, kx, xlo, xn, ky, ylo, yn, lut};
+  const Shape sh = {num_images, src_height, src_width, out_height, out_width, taps_x, taps_y, src_row0, src_rows, flip ? 1 : 0,
+                    swap_rb ? 1 : 0};
+  return preprocess_surface(out, sf, format, t, sh, YuvCoeffs{yoff, iy, irv, igu, igv, ibu}, stream, &table);
 }
 
 // what both rig entry points do (roll: the rolled one's table, one row per camera, or null)
-static int preprocess_rig(void* out, const void* image_table, void* mid, const int* kx, const int* xlo, const int* xn, const int* ky,
-                          const int* ylo, const int* yn, const void* lut, const simpb_rig_camera* cams, int num_cams, int num_images,
-                          int out_height, int out_width, int kx_len, int x_len, int ky_len, int y_len, int mid_rows, int swap_rb,
-                          void* stream, const RollTable* roll) {
+static int preprocess_rig(void* out, const void* image_table, const Tables& t, const simpb_rig_camera* cams, int num_cams,
+                          int num_images, int out_height, int out_width, int kx_len, int x_len, int ky_len, int y_len, int mid_rows,
+                          int swap_rb, void* stream, const RollTable* roll) {
   if (!cams || num_cams <= 0 || num_cams > SIMPB_RIG_MAX_CAMS || num_images <= 0 || num_images % num_cams) return SIMPB_EINVAL;
   if (kx_len <= 0 || x_len <= 0 || ky_len <= 0 || y_len <= 0 || mid_rows <= 0) return SIMPB_EINVAL;
   if (reinterpret_cast<size_t>(image_table) & 7) return SIMPB_EINVAL;
@@ -816,9 +800,9 @@ static int preprocess_rig(void* out, const void* image_table, void* mid, const i
   for (int i = 0; i < num_cams; ++i) {
     const simpb_rig_camera& c = cams[i];
     // (the rules of simpb_preprocess_surface_nhwc4_f16 in its address-table form, camera by camera)
-    if (bad_arguments(out, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, num_images, c.src_height, c.src_width, out_height, out_width,
-                      c.taps_x, c.taps_y, c.src_row0, c.src_rows))
-      return SIMPB_EINVAL;
+    const Shape cs = {num_images, c.src_height, c.src_width, out_height, out_width, c.taps_x, c.taps_y, c.src_row0, c.src_rows,
+                      c.flip ? 1 : 0, swap_rb ? 1 : 0};
+    if (bad_arguments(out, image_table, t, cs)) return SIMPB_EINVAL;
     if (!known_format(c.format)) return SIMPB_EINVAL;
     long long chroma_pitch = c.chroma_pitch, chroma_offset = c.chroma_offset, chroma2_offset = c.chroma2_offset;
     if (surface_extent(c.format, c.src_height, c.src_width, c.pitch, chroma_pitch, chroma_offset, chroma2_offset, c.iy) < 0)
@@ -840,6 +824,7 @@ static int preprocess_rig(void* out, const void* image_table, void* mid, const i
     }
     max_rows = c.src_rows > max_rows ? c.src_rows : max_rows;
   }
+  const unsigned long long* table = static_cast<const unsigned long long*>(image_table);
   Rig rig = {};
   for (int i = 0; i < num_cams; ++i) {
     rig.cam[i] = cams[i];
@@ -857,21 +842,14 @@ static int preprocess_rig(void* out, const void* image_table, void* mid, const i
   const RigLds lds = {(src_bytes + 15) / 16 * 16, pitch + 16, planes};
   hipStream_t s = static_cast<hipStream_t>(stream);
   (void)hipGetLastError();
-  const unsigned long long* table = static_cast<const unsigned long long*>(image_table);
   hipLaunchKernelGGL(resample_rows_rig_kernel, dim3(max_rows, num_images), dim3(kThreads),
-                     (size_t)(lds.src_bytes + lds.out_bytes + 2 * lds.plane_bytes), s, static_cast<unsigned char*>(mid), table, rig,
-                     num_cams, kx, xlo, xn, out_width, pitch, mid_rows, lds);
-  const int groups = (out_width + 3) / 4;
-  const dim3 grid((groups + kThreads - 1) / kThreads, out_height, num_images);
-  if (roll)
-    hipLaunchKernelGGL(resample_cols_lut_rig_roll_kernel, grid, dim3(kThreads), 0, s, static_cast<_Float16*>(out),
-                       static_cast<const unsigned char*>(mid), table, rig, num_cams, ky, ylo, yn, static_cast<const _Float16*>(lut),
-                       out_height, out_width, swap_rb ? 1 : 0, pitch, mid_rows, *roll);
-  else
-    hipLaunchKernelGGL(resample_cols_lut_rig_kernel, grid, dim3(kThreads), 0, s, static_cast<_Float16*>(out),
-                       static_cast<const unsigned char*>(mid), table, rig, num_cams, ky, ylo, yn, static_cast<const _Float16*>(lut),
-                       out_height, out_width, swap_rb ? 1 : 0, pitch, mid_rows);
-  return simpb_check_launch();
+                     (size_t)(lds.src_bytes + lds.out_bytes + 2 * lds.plane_bytes), s, static_cast<unsigned char*>(t.mid), table, rig,
+                     num_cams, t.kx, t.xlo, t.xn, out_width, pitch, mid_rows, lds);
+  return launch_vertical(num_images, out_height, out_width, roll, [&](dim3 grid, dim3 block, auto r) {
+    hipLaunchKernelGGL(resample_cols_lut_rig_kernel<decltype(r)>, grid, block, 0, s, static_cast<_Float16*>(out),
+                       static_cast<const unsigned char*>(t.mid), table, rig, num_cams, t.ky, t.ylo, t.yn,
+                       static_cast<const _Float16*>(t.lut), out_height, out_width, swap_rb ? 1 : 0, pitch, mid_rows, r);
+  });
 }
 
 extern "C" int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table, void* mid, const int* kx, const int* xlo,
@@ -879,8 +857,9 @@ extern "C" int simpb_preprocess_rig_nhwc4_f16(void* out, const void* image_table
                                               const simpb_rig_camera* cams, int num_cams, int num_images, int out_height,
                                               int out_width, int kx_len, int x_len, int ky_len, int y_len, int mid_rows, int swap_rb,
                                               void* stream) {
-  return preprocess_rig(out, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, cams, num_cams, num_images, out_height, out_width, kx_len,
-                        x_len, ky_len, y_len, mid_rows, swap_rb, stream, nullptr);
+  const Tables t = {mid, kx, xlo, xn, ky, ylo, yn, lut};
+  return preprocess_rig(out, image_table, t, cams, num_cams, num_images, out_height, out_width, kx_len, x_len, ky_len, y_len, mid_rows,
+                        swap_rb, stream, nullptr);
 }
 
 extern "C" int simpb_preprocess_rig_roll_nhwc4_f16(void* out, const void* image_table, void* mid, const int* kx, const int* xlo,
@@ -890,6 +869,7 @@ extern "C" int simpb_preprocess_rig_roll_nhwc4_f16(void* out, const void* image_
                                                    int swap_rb, const int* roll, void* stream) {
   RollTable table;
   if (bad_roll(table, roll, num_cams, out_height, out_width)) return SIMPB_EINVAL;
-  return preprocess_rig(out, image_table, mid, kx, xlo, xn, ky, ylo, yn, lut, cams, num_cams, num_images, out_height, out_width, kx_len,
-                        x_len, ky_len, y_len, mid_rows, swap_rb, stream, &table);
+  const Tables t = {mid, kx, xlo, xn, ky, ylo, yn, lut};
+  return preprocess_rig(out, image_table, t, cams, num_cams, num_images, out_height, out_width, kx_len, x_len, ky_len, y_len, mid_rows,
+                        swap_rb, stream, &table);
 }

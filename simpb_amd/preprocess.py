@@ -484,7 +484,79 @@ def _device(device):
     return device
 
 
-class ResamplePlan:
+class _Resident:
+    """The device side that a ResamplePlan and a RigPlan have alike: `_dev`, a dict of what is resident on one device (the tables
+    the plan's `upload` names, `pitch`, the intermediate buffer `mid` and the address table `table`, both made on first use and
+    kept), the output's rule, and the address table behind `run_surfaces` / `run_table`."""
+
+    _dev = None
+
+    def _upload(self, device, plans, **arrays):
+        """`arrays` (numpy) onto `device` as the new `_dev`; ValueError where a plan of `plans` is outside the kernel's limits."""
+        import torch
+        from . import _lib
+        for p in plans:
+            if p.taps_x > 64 or p.taps_y > 64 or p.src_hw[1] > 4096 or p.out_hw[1] > 2048:
+                raise ValueError(f"ingest of {p.src_hw} -> {p.resize_dims} is outside the kernel's limits "
+                                 "(source width 4096, output width 2048, 64 taps)")
+        device = _device(device)
+        self._dev = dict(device=device, pitch=int(_lib.lib().simpb_preprocess_mid_pitch(self.out_hw[1])), mid=None, table=None,
+                         **{name: torch.from_numpy(np.ascontiguousarray(a)).to(device) for name, a in arrays.items()})
+        return self
+
+    def _resident(self, device):
+        """`_dev` on `device` (uploaded now unless it is there already)."""
+        if self._dev is None or self._dev["device"] != _device(device):
+            self.upload(device)
+        return self._dev
+
+    def _reserve_mid(self, device, rows):
+        """The intermediate buffer of at least `rows` rows (of all images together) on `device`."""
+        d = self._resident(device)
+        if d["mid"] is None or d["mid"].numel() < rows * d["pitch"]:
+            import torch
+            d["mid"] = torch.empty(rows * d["pitch"], dtype=torch.uint8, device=d["device"])
+        return self
+
+    def intermediate(self):
+        """The u8 intermediate buffer of the last launch (None before the first `reserve`): what tools/ingest_bits.py compares."""
+        return None if self._dev is None else self._dev["mid"]
+
+    def _out(self, out, n, device):
+        """The output of `n` images: `out` checked, or a new tensor."""
+        import torch
+        h, w = self.out_hw
+        if out is None:
+            return torch.empty(n, h, w, 4, dtype=torch.float16, device=device)
+        if out.dtype != torch.float16 or tuple(out.shape) != (n, h, w, 4) or not out.is_contiguous():
+            raise ValueError(f"ingest writes f16 [{n}, {h}, {w}, 4]")
+        return out
+
+    def run_surfaces(self, tensors, out=None):
+        """One device u8 tensor per image (a flat list; each its own allocation, or a view into one) -> f16 [N, h, w, 4] as
+        `run`. The addresses go into a resident int64 table that the launch reads; the tensors must stay alive and unchanged
+        until the launch has run. (A rig: streams * cams of them, None where an image is skipped.)"""
+        import torch
+        ptrs, device = self.surface_table(tensors)
+        n = len(ptrs)
+        self.reserve(n, device)
+        d = self._dev
+        if d["table"] is None or d["table"].numel() < n:
+            d["table"] = torch.zeros(n, dtype=torch.int64, device=d["device"])
+        # (a copy out of pageable memory: the host buffer is free again when the call returns)
+        d["table"][:n].copy_(torch.tensor(ptrs, dtype=torch.int64))
+        return self.run_table(d["table"][:n], out)
+
+    @staticmethod
+    def _check_table(table):
+        """The number of addresses of a `run_table` argument; ValueError unless it is a contiguous device int64 tensor."""
+        import torch
+        if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.numel() == 0:
+            raise ValueError("the surface table is a contiguous device int64 tensor with one address per image")
+        return int(table.numel())
+
+
+class ResamplePlan(_Resident):
     """Tables of one ingest configuration; `upload(device)` makes them resident, `run(frames)` launches.
 
     frame_format "bgr": u8 [..., Hs, Ws, 3] interleaved pixels. "nv12" / "nv21": one image is a contiguous u8 [Hs * 3 / 2, Ws]:
@@ -545,7 +617,6 @@ class ResamplePlan:
         self.src_row0 = int(self.ylo.min())
         self.src_rows = int((self.ylo + self.yn).max()) - self.src_row0
         self.lut = normalise_lut(self.img_norm_cfg)
-        self._dev = None
 
     def image_transform(self, camera=0):
         """float64 [3, 3]: the matrix `ResizeCropFlipImage._img_transform` returns (augment.py:111-129) for this plan and the
@@ -568,27 +639,11 @@ class ResamplePlan:
 
     # ------------------------------------------------------------------ device
     def upload(self, device):
-        import torch
-        from . import _lib
-        lib = _lib.lib()
-        if self.taps_x > 64 or self.taps_y > 64 or self.src_hw[1] > 4096 or self.out_hw[1] > 2048:
-            raise ValueError(f"ingest of {self.src_hw} -> {self.resize_dims} is outside the kernel's limits "
-                             "(source width 4096, output width 2048, 64 taps)")
-        device = _device(device)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)   # noqa: E731
-        self._dev = dict(device=device, kx=t(self.kx), xlo=t(self.xlo), xn=t(self.xn), ky=t(self.ky), ylo=t(self.ylo),
-                         yn=t(self.yn), lut=t(self.lut), pitch=int(lib.simpb_preprocess_mid_pitch(self.out_hw[1])), mid=None, table=None)
-        return self
+        return self._upload(device, (self,), kx=self.kx, xlo=self.xlo, xn=self.xn, ky=self.ky, ylo=self.ylo, yn=self.yn, lut=self.lut)
 
     def reserve(self, num_images, device):
         """Allocate the intermediate buffer for `num_images` now (a runner does this before any graph capture)."""
-        import torch
-        if self._dev is None or self._dev["device"] != _device(device):
-            self.upload(device)
-        d = self._dev
-        if d["mid"] is None or d["mid"].numel() < num_images * self.src_rows * d["pitch"]:
-            d["mid"] = torch.empty(num_images * self.src_rows * d["pitch"], dtype=torch.uint8, device=d["device"])
-        return self
+        return self._reserve_mid(device, num_images * self.src_rows)
 
     def layout(self):
         """The frames `run` takes, in words (for error messages)."""
@@ -639,72 +694,44 @@ class ResamplePlan:
         tensors = list(tensors)
         return [t.data_ptr() for t in tensors], check_surfaces(tensors, self.surface)
 
-    def run_surfaces(self, tensors, out=None):
-        """One device u8 tensor per image (a flat list; each its own allocation, or a view into one) -> f16 [N, h, w, 4] as
-        `run`. The addresses go into a resident int64 table that the launch reads; the tensors must stay alive and unchanged
-        until the launch has run."""
-        import torch
-        ptrs, device = self.surface_table(tensors)
-        n = len(ptrs)
-        self.reserve(n, device)
-        d = self._dev
-        if d["table"] is None or d["table"].numel() < n:
-            d["table"] = torch.zeros(n, dtype=torch.int64, device=d["device"])
-        # (a copy out of pageable memory: the host buffer is free again when the call returns)
-        d["table"][:n].copy_(torch.tensor(ptrs, dtype=torch.int64))
-        return self.run_table(d["table"][:n], out)
-
     def run_table(self, table, out=None):
         """table: device int64 [...], contiguous: the address of one surface per image (as `surface_table` checks them). The
         launch reads the table when it runs, so a captured launch follows the addresses written into it before each replay."""
-        import torch
-        if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.numel() == 0:
-            raise ValueError("the surface table is a contiguous device int64 tensor with one address per image")
-        return self._launch(int(table.numel()), table.device, out, table=table)
+        return self._launch(self._check_table(table), table.device, out, table=table)
 
     def _launch(self, n, device, out, src=None, table=None):
         import torch
         from . import _lib
-        hs, ws = self.src_hw
-        h, w = self.out_hw
         self.reserve(n, device)
-        d = self._dev
-        if out is None:
-            out = torch.empty(n, h, w, 4, dtype=torch.float16, device=device)
-        elif out.dtype != torch.float16 or tuple(out.shape) != (n, h, w, 4) or not out.is_contiguous():
-            raise ValueError(f"ingest writes f16 [{n}, {h}, {w}, 4]")
+        d, sf, code = self._dev, self.surface, SURFACE_FORMAT[self.frame_format]
+        out = self._out(out, n, device)
         p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
         tables = (p(d["mid"]), p(d["kx"]), p(d["xlo"]), p(d["xn"]), p(d["ky"]), p(d["ylo"]), p(d["yn"]), p(d["lut"]))
-        ints = (n, hs, ws, h, w, self.taps_x, self.taps_y, self.src_row0, self.src_rows, int(self.flip), int(self.swap_rb))
+        ints = (n, *self.src_hw, *self.out_hw, self.taps_x, self.taps_y, self.src_row0, self.src_rows, int(self.flip), int(self.swap_rb))
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        sf = self.surface
-        if self.rolled:   # one entry point for every format and layout (the planes entry point's arguments, then the roll)
+
+        def images():   # both forms of the images, exactly one of them given
             null = ctypes.c_void_p(0)
+            return (p(src), null) if table is None else (null, p(table))
+
+        def layout(*second):   # what a surface entry point takes behind the ints (`second`: chroma2_offset, where it has one)
             yuv = self.yuv if self.yuv is not None else (0, 1, 0, 0, 0, 0)
+            return (code, sf.pitch, sf.chroma_pitch, sf.chroma_offset, *second, sf.image_bytes, *yuv)
+
+        # the one decision: which entry point, and what it takes in front of the tables and between the ints and the stream
+        tight = table is None and sf.tight
+        if self.rolled:   # one entry point for every format and layout (the planes entry point's arguments, then the roll)
             rows = self.roll_ints.ctypes.data_as(ctypes.POINTER(ctypes.c_int))   # (read before the call returns)
-            _lib.check(_lib.lib().simpb_preprocess_roll_nhwc4_f16(
-                p(out), p(src) if table is None else null, null if table is None else p(table), *tables, *ints,
-                SURFACE_FORMAT[self.frame_format], sf.pitch, sf.chroma_pitch, sf.chroma_offset, sf.chroma2_offset, sf.image_bytes, *yuv,
-                rows, len(self.rolls), stream), "simpb_preprocess_roll_nhwc4_f16")
-            return out
-        if table is None and sf.tight and self.frame_format in ("bgr", "nv12", "nv21"):   # the first forms, through their entry points
-            if self.yuv is None:
-                _lib.check(_lib.lib().simpb_preprocess_u8_nhwc4_f16(p(out), p(src), *tables, *ints, stream), "simpb_preprocess_u8_nhwc4_f16")
-            else:
-                _lib.check(_lib.lib().simpb_preprocess_yuv420sp_nhwc4_f16(p(out), p(src), *tables, *ints, int(self.frame_format == "nv21"),
-                                                                          *self.yuv, stream), "simpb_preprocess_yuv420sp_nhwc4_f16")
-            return out
-        null = ctypes.c_void_p(0)
-        yuv = self.yuv if self.yuv is not None else (0, 1, 0, 0, 0, 0)
-        images = (p(src) if table is None else null, null if table is None else p(table))
-        if SURFACE_FORMAT[self.frame_format] <= SURFACE_FORMAT["p010"]:
-            _lib.check(_lib.lib().simpb_preprocess_surface_nhwc4_f16(
-                p(out), *images, *tables, *ints, SURFACE_FORMAT[self.frame_format], sf.pitch, sf.chroma_pitch, sf.chroma_offset,
-                sf.image_bytes, *yuv, stream), "simpb_preprocess_surface_nhwc4_f16")
+            name, head, tail = "simpb_preprocess_roll_nhwc4_f16", images(), (*layout(sf.chroma2_offset), rows, len(self.rolls))
+        elif tight and self.frame_format == "bgr":   # the first forms, through their entry points
+            name, head, tail = "simpb_preprocess_u8_nhwc4_f16", (p(src),), ()
+        elif tight and self.frame_format in ("nv12", "nv21"):
+            name, head, tail = "simpb_preprocess_yuv420sp_nhwc4_f16", (p(src),), (int(self.frame_format == "nv21"), *self.yuv)
+        elif code <= SURFACE_FORMAT["p010"]:
+            name, head, tail = "simpb_preprocess_surface_nhwc4_f16", images(), layout()
         else:   # planar 4:2:0, packed 4:2:2 and the RGB-order family
-            _lib.check(_lib.lib().simpb_preprocess_planes_nhwc4_f16(
-                p(out), *images, *tables, *ints, SURFACE_FORMAT[self.frame_format], sf.pitch, sf.chroma_pitch, sf.chroma_offset,
-                sf.chroma2_offset, sf.image_bytes, *yuv, stream), "simpb_preprocess_planes_nhwc4_f16")
+            name, head, tail = "simpb_preprocess_planes_nhwc4_f16", images(), layout(sf.chroma2_offset)
+        _lib.check(getattr(_lib.lib(), name)(p(out), *head, *tables, *ints, *tail, stream), name)
         return out
 
 
@@ -741,7 +768,7 @@ class CameraSource:
         return f"{self.frame_format} {self.src_hw[1]} x {self.src_hw[0]} -> {self.out_hw[1]} x {self.out_hw[0]}"
 
 
-class RigPlan:
+class RigPlan(_Resident):
     """Tables of a rig of 1 .. 16 cameras that may differ in source size, format, colour standard, surface layout, resize, crop
     and flip, and give one output size: per camera exactly what its own ResamplePlan holds (`plans`), concatenated camera
     by camera for the device, and one normalisation table. A rig takes surfaces only -- one device u8 tensor per image, in
@@ -782,7 +809,6 @@ class RigPlan:
         self.ky_offset, self.y_offset = ends([k.size for k in self.ky]), ends([v.size for v in self.ylo])
         self.mid_row = ends(self.src_rows)
         self.mid_rows = self.mid_row[-1]
-        self._dev = None
 
     # ------------------------------------------------------------------ what a caller multiplies / hands on
     def image_transforms(self):
@@ -807,9 +833,7 @@ class RigPlan:
 
     def box2d_device(self, device):
         """`box2d_table` on the device (resident: a captured 2D record reads it)."""
-        if self._dev is None or self._dev["device"] != _device(device):
-            self.upload(device)
-        return self._dev["box2d"]
+        return self._resident(device)["box2d"]
 
     def descriptors(self):
         """The rig as the host array of simpb_rig_camera that simpb_preprocess_rig_nhwc4_f16 takes."""
@@ -827,31 +851,16 @@ class RigPlan:
 
     # ------------------------------------------------------------------ device
     def upload(self, device):
-        import torch
-        from . import _lib
-        for p in self.plans:
-            if p.taps_x > 64 or p.taps_y > 64 or p.src_hw[1] > 4096 or p.out_hw[1] > 2048:
-                raise ValueError(f"ingest of {p.src_hw} -> {p.resize_dims} is outside the kernel's limits "
-                                 "(source width 4096, output width 2048, 64 taps)")
-        device = _device(device)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)   # noqa: E731
-        cat = lambda name: t(np.concatenate([a.reshape(-1) for a in getattr(self, name)]))   # noqa: E731
-        self._dev = dict(device=device, lut=t(self.lut), box2d=t(self.box2d_table()), mid=None, table=None, cams=self.descriptors(),
-                         pitch=int(_lib.lib().simpb_preprocess_mid_pitch(self.out_hw[1])), **{n: cat(n) for n in self.TABLES})
+        cat = lambda name: np.concatenate([a.reshape(-1) for a in getattr(self, name)])   # noqa: E731
+        self._upload(device, self.plans, lut=self.lut, box2d=self.box2d_table(), **{n: cat(n) for n in self.TABLES})
+        self._dev["cams"] = self.descriptors()
         return self
 
     def reserve(self, num_images, device):
         """Allocate the intermediate buffer for `num_images` (whole streams) now (a runner does this before any capture)."""
-        import torch
         if num_images <= 0 or num_images % self.num_cams:
             raise ValueError(f"a rig of {self.num_cams} cameras takes whole streams: {num_images} images")
-        if self._dev is None or self._dev["device"] != _device(device):
-            self.upload(device)
-        d = self._dev
-        need = num_images // self.num_cams * self.mid_rows * d["pitch"]
-        if d["mid"] is None or d["mid"].numel() < need:
-            d["mid"] = torch.empty(need, dtype=torch.uint8, device=d["device"])
-        return self
+        return self._reserve_mid(device, num_images // self.num_cams * self.mid_rows)
 
     def surface_table(self, tensors):
         """(addresses, device) of a flat list of streams * cams device u8 tensors in (stream, camera) order, each checked by
@@ -875,33 +884,15 @@ class RigPlan:
             raise ValueError("ingest of a rig without a single surface")
         return [0 if t is None else t.data_ptr() for t in tensors], device
 
-    def run_surfaces(self, tensors, out=None):
-        """One device u8 tensor (or None) per image, streams * cams of them -> f16 [N, h, w, 4]. The addresses go into a
-        resident int64 table that the launch reads; the tensors must stay alive and unchanged until the launch has run."""
-        import torch
-        ptrs, device = self.surface_table(tensors)
-        n = len(ptrs)
-        self.reserve(n, device)
-        d = self._dev
-        if d["table"] is None or d["table"].numel() < n:
-            d["table"] = torch.zeros(n, dtype=torch.int64, device=d["device"])
-        d["table"][:n].copy_(torch.tensor(ptrs, dtype=torch.int64))
-        return self.run_table(d["table"][:n], out)
-
     def run_table(self, table, out=None):
         """table: device int64 [...], contiguous, streams * cams addresses (as `surface_table` checks them; 0 skips the image).
         The launch reads the table when it runs, so a captured launch follows the addresses written before each replay."""
         import torch
         from . import _lib
-        if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.numel() == 0:
-            raise ValueError("the surface table is a contiguous device int64 tensor with one address per image")
-        n, (h, w) = int(table.numel()), self.out_hw
+        n, (h, w) = self._check_table(table), self.out_hw
         self.reserve(n, table.device)
         d = self._dev
-        if out is None:
-            out = torch.empty(n, h, w, 4, dtype=torch.float16, device=table.device)
-        elif out.dtype != torch.float16 or tuple(out.shape) != (n, h, w, 4) or not out.is_contiguous():
-            raise ValueError(f"ingest writes f16 [{n}, {h}, {w}, 4]")
+        out = self._out(out, n, table.device)
         p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
         args = (p(out), p(table), p(d["mid"]), *(p(d[name]) for name in self.TABLES), p(d["lut"]), d["cams"], self.num_cams, n, h, w,
                 d["kx"].numel(), d["xlo"].numel(), d["ky"].numel(), d["ylo"].numel(), self.mid_rows, int(self.swap_rb))

@@ -73,7 +73,7 @@ def test_square_crop_takes_the_transpose_integers(roll):
     assert_same_bits(got, torch.rot90(level, 1 if roll == 90 else 3, (1, 2)), roll)     # a pure permutation of the level pixels
 
 
-def _run_rows(plan, frames, rows):
+def run_rows(plan, frames, rows):
     """The rolled entry point with a table of the test's own making (a plan only ever hands over its cameras' integers)."""
     plan.roll_ints, plan.rolls = np.ascontiguousarray(rows, np.int32), (0.0,) * len(rows)
     return plan.run(frames)
@@ -87,7 +87,7 @@ def test_identity_rows_give_the_level_bits(flip):
     level = P.ResamplePlan(SRC, aug).run(dev)
     assert_same_bits(level, expected(bgr, aug, [0]))
     for cams in (1, 3, 16):
-        got = _run_rows(P.ResamplePlan(SRC, aug, roll=5), dev, [P.ROLL_IDENTITY] * cams)
+        got = run_rows(P.ResamplePlan(SRC, aug, roll=5), dev, [P.ROLL_IDENTITY] * cams)
         assert_same_bits(got, level, (flip, cams))
 
 
@@ -129,7 +129,7 @@ def test_p010():
 RIG_ROLLS = (0, 180, -4.5)
 
 
-def _rig(rolls=RIG_ROLLS):
+def rolled_rig(rolls=RIG_ROLLS):
     """Three cameras of different source size and format to 24 x 40, with their BGR pictures and surfaces (two streams)."""
     specs = [((64, 96), dict(resize=0.5, crop=(4, 4, 44, 28)), "bgr", "jfif", None),
              ((100, 168), dict(resize=0.25, crop=(1, 1, 41, 25)), "nv12", "bt601", dict(pitch=176)),
@@ -154,14 +154,14 @@ def _rig(rolls=RIG_ROLLS):
 
 
 def test_rig_kernel():
-    sources, surfaces, bgrs = _rig()
+    sources, surfaces, bgrs = rolled_rig()
     rig = P.RigPlan(sources)
     assert rig.rolled and tuple(rig.roll_ints[0]) == P.ROLL_IDENTITY
     got = rig.run_surfaces(surfaces)
     want = torch.cat([expected(b[None], s.aug_config, [s.roll]) for b, s in zip(bgrs, sources * 2)])
     assert_same_bits(got, want)
     # the level camera's block equals the unrolled rig's (the level entry point)
-    level_sources, _, _ = _rig((0, 0, 0))
+    level_sources, _, _ = rolled_rig((0, 0, 0))
     level = P.RigPlan(level_sources)
     assert not level.rolled
     assert_same_bits(got[0::3], level.run_surfaces(surfaces)[0::3], "level camera")
@@ -199,7 +199,7 @@ def test_refused_call_leaves_the_output_untouched():
     assert fn(*([null] + ptrs[1:]), *good, rows, 1, stream) == 1
     assert fn(*(ptrs[:2] + [p(src)] + ptrs[3:]), *good, rows, 1, stream) == 1          # both forms of the images
     # the rig's rolled entry point: no table, and a camera the level form refuses
-    sources, surfaces, _ = _rig()
+    sources, surfaces, _ = rolled_rig()
     rig = P.RigPlan(sources)
     rig_out = torch.full((3, 24, 40, 4), 7.0, dtype=torch.float16, device="cuda")
     rig.run_surfaces(surfaces[:3], torch.empty_like(rig_out))                         # (uploads the tables, makes `mid` and the address table)

@@ -1,4 +1,4 @@
-"""Measures the per-camera mount roll of the camera frame ingest (csrc/preprocess.hip: resample_cols_lut_roll_kernel) on the
+"""Measures the per-camera mount roll of the camera frame ingest (csrc/preprocess.hip: resample_cols_lut_kernel<RollTable>) on the
 GPU, beside the level pass it stands in for; one JSON line out. The workload is tools/bench_preprocess.py's: six 1600 x 900
 NV12 cameras -> 704 x 256 (the R50 configuration).
 
