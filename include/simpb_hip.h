@@ -301,13 +301,40 @@ int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, const void* i
  * odd src_width for a YCbCr format, an odd src_height for _YUV420P; iy <= 0 for a YCbCr format; a pitch below the row's
  * sample bytes (src_width * 1, 2, 2, 3, 4, 4 in the order above), a chroma_pitch below src_width / 2; a chroma plane that
  * starts before the luma samples end; Cb and Cr planes that overlap; with src, an image_stride below the image's last
- * sample. Two launches on `stream`; no allocation, no synchronisation (graph capture safe). */
+ * sample. Two launches on `stream`; no allocation, no synchronisation (graph capture safe).
+ *
+ * JPEG-DECODER PLANES. A JPEG's images reach the reference through libjpeg at its defaults, whose "fancy" upsampling
+ * interpolates the subsampled chroma planes before the colour conversion. Two additions give that decoder's bytes to a caller
+ * who hands over the file's own planes (or those of any decoder whose chroma is centre-sited):
+ *   _YUV444P      three planes, u8, of src_height rows of src_width bytes: luma at `pitch`, Cb at chroma_offset + r *
+ *                 chroma_pitch, Cr at chroma2_offset + r * chroma_pitch; every pixel has its own chroma sample. Any size. What a
+ *                 4:4:4 JPEG decodes to. Refused like _YUV420P: a chroma_pitch below src_width, planes that overlap.
+ *   format | SIMPB_SURFACE_CHROMA_JPEG, for _NV12, _NV21, _YUV420P, _YUYV and _UYVY: the same samples, the same layout rules
+ *                 and the same colour rule, but every pixel gets its own interpolated Cb / Cr. C a chroma plane [Hc][Wc],
+ *                 int32, j = x >> 1, l = max(j - 1, 0), r = min(j + 1, Wc - 1):
+ *                 4:2:0 (libjpeg h2v2_fancy_upsample), luma row y, i = y >> 1:
+ *                   near = C[i],  far = C[clamp(i + (y odd ? 1 : -1), 0, Hc - 1)],  s[k] = 3 * near[k] + far[k]
+ *                   x even: (3 * s[j] + s[l] + 8) >> 4        x odd: (3 * s[j] + s[r] + 7) >> 4
+ *                 4:2:2 (libjpeg h2v1_fancy_upsample), c the row's own chroma:
+ *                   x even: (3 * c[j] + c[l] + 1) >> 2        x odd: (3 * c[j] + c[r] + 2) >> 2
+ *                 The far row of 4:2:0 is read even where no needed luma row lies over it (exactly its sample bytes, like
+ *                 every row). With libjpeg's own constants (yoff, iy, irv, igu, igv, ibu) = (0, 65536, 91881, -22554, -46802,
+ *                 116130) -- its FIX(1.40200), FIX(0.34414), FIX(0.71414), FIX(1.77200), colour "jpeg" of
+ *                 simpb_amd/preprocess.py -- the (B, G, R) row is the one libjpeg decodes from the same planes, byte for byte
+ *                 (pinned to libjpeg-turbo through Pillow for 4:2:0, 4:4:4 and the constants; the 4:2:2 rule is stated from
+ *                 libjpeg's published algorithm, which hands out no native 4:2:2 planes to pin it to).
+ *   The flag is taken in `format` here, by simpb_preprocess_roll_nhwc4_f16 and in simpb_rig_camera.format (a rig may mix
+ *   cameras with and without it). SIMPB_EINVAL, and nothing launched or written: the flag on a format without subsampled 8-bit
+ *   chroma (_BGR, _RGB, _BGRA, _RGBA, _P010, _YUV444P), any other bit above the codes, codes 4..7, 14, 15 and negative ones.
+ *   simpb_preprocess_surface_nhwc4_f16 takes codes 0..3 and no flag. */
 #define SIMPB_SURFACE_YUV420P 8
 #define SIMPB_SURFACE_YUYV 9
 #define SIMPB_SURFACE_UYVY 10
 #define SIMPB_SURFACE_RGB 11
 #define SIMPB_SURFACE_BGRA 12
 #define SIMPB_SURFACE_RGBA 13
+#define SIMPB_SURFACE_YUV444P 16
+#define SIMPB_SURFACE_CHROMA_JPEG 0x100
 int simpb_preprocess_planes_nhwc4_f16(void* out, const void* src, const void* image_table, void* mid, const int* kx,
                                       const int* xlo, const int* xn, const int* ky, const int* ylo, const int* yn,
                                       const void* lut, int num_images, int src_height, int src_width, int out_height,
@@ -340,7 +367,8 @@ int simpb_preprocess_mid_pitch(int out_width);
  * The horizontal grid spans the largest src_rows of the rig; a workgroup past its camera's rows leaves at once. Its LDS is
  * sized for the rig's widest cameras, not for the widest source this file takes: at most 34832 bytes, reached by a 4096-wide
  * _P010 camera (two planes of 8192 bytes) and equally by a 4096-wide _BGRA / _RGBA one (its row of 16384 bytes is staged
- * before it is compacted), each beside the 12288-byte (B, G, R) row and the 6160-byte resampled row.
+ * before it is compacted), each beside the 12288-byte (B, G, R) row and the 6160-byte resampled row; a camera of interpolated
+ * 4:2:0 chroma (SIMPB_SURFACE_CHROMA_JPEG) adds the far chroma row of the widest such camera, at most 4096 bytes more.
  * SIMPB_EINVAL, and nothing launched or written: num_cams outside 1..16; num_images no multiple of num_cams; for any camera,
  * whatever simpb_preprocess_planes_nhwc4_f16 refuses in its address-table form; a table range or an intermediate range
  * that leaves its array or overlaps another camera's. Two launches on `stream`; no allocation, no synchronisation. */

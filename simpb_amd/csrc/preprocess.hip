@@ -19,8 +19,15 @@
 //      through the table as two 16-byte stores (stage_lut, store_lut_group).
 // THE SOURCE FORMATS differ in how a row becomes the (B, G, R) row and in nothing else: stage_bgr_row<F> takes interleaved
 // BGR as it lies, RGB / BGRA / RGBA as a byte permutation, and 4:2:0 semi-planar (NV12 / NV21, P010 in u16), planar 4:2:0
-// and packed 4:2:2 (YUYV / UYVY) through one integer YCbCr rule with replicated chroma (yuv_pair_to_bgr). with_format maps
-// the runtime code to the instantiation, for the host's launch and inside the rig kernel alike.
+// and packed 4:2:2 (YUYV / UYVY) through one integer YCbCr rule per pixel (yuv_to_bgr) with replicated chroma, and planar
+// 4:4:4 with the chroma it has. with_format maps the runtime code to the instantiation, for the host's launch and inside the
+// rig kernel alike.
+// JPEG-DECODER PLANES. A format code | SIMPB_SURFACE_CHROMA_JPEG (the five 8-bit formats with subsampled chroma) is a format of
+// its own whose chroma is interpolated as libjpeg's decoder does it at its defaults ("fancy" upsampling: fancy_pair states
+// h2v2 for 4:2:0 and h2v1 for 4:2:2 in int32); a 4:2:0 workgroup stages one more chroma row for it, the far one. With
+// libjpeg's colour constants (the caller's: colour "jpeg" of simpb_amd/preprocess.py) and the native planes of a JPEG the
+// (B, G, R) row is the one libjpeg decodes from that file. Pinned to libjpeg-turbo through Pillow: 4:2:0, 4:4:4 and the
+// constants (tests/test_chroma_host.py); stated from libjpeg's published algorithm only: 4:2:2.
 // THREE WAYS TO ADDRESS THE IMAGES. A tight contiguous batch of BGR or NV12 / NV21 frames (simpb_preprocess_u8_nhwc4_f16,
 // simpb_preprocess_yuv420sp_nhwc4_f16) has a horizontal kernel of its own each, where the host decides once whether rows go
 // as 16-byte chunks. A SURFACE (simpb_preprocess_surface_nhwc4_f16, simpb_preprocess_planes_nhwc4_f16) has row pitch, chroma
@@ -119,25 +126,41 @@ __device__ __forceinline__ void stage_row(unsigned char* s_dst, const unsigned c
   }
 }
 
-// One chroma pair and its two luma samples -> two (B, G, R) pixels at d[0 .. 5]: the integer YCbCr rule of every YCbCr
-// format, with S = kShift fractional bits and chroma centre C = kCentre: 16 / 128 for 8-bit samples, 18 / 512 for 10-bit ones
-// (P010), whose luma offset is 4 * yoff as well:
+// One pixel -> its (B, G, R) bytes at d[0 .. 2]: the integer YCbCr rule of every YCbCr format, with S = kShift fractional bits
+// and chroma centre C = kCentre: 16 / 128 for 8-bit samples, 18 / 512 for 10-bit ones (P010), whose luma offset is 4 * yoff as well:
 //   c = iy * (Y - yoff) + 2^(S-1),  R = clamp8((c + irv * (Cr - C)) >> S),  G = clamp8((c + igu * (Cb - C) + igv * (Cr - C)) >> S),
 //   B = clamp8((c + ibu * (Cb - C)) >> S)     (int32, arithmetic shift, clamp to 0..255)
+// Every pixel brings its own Cb / Cr: the same pair for both pixels where chroma is replicated (the products are then computed
+// once), an interpolated one each where it is not (fancy_pair).
 struct YuvCoeffs { int yoff, iy, irv, igu, igv, ibu; };
 
 template <int kShift = 16, int kCentre = 128>
-__device__ __forceinline__ void yuv_pair_to_bgr(unsigned char* d, int y0, int y1, int cb, int cr, const YuvCoeffs& q) {
+__device__ __forceinline__ void yuv_to_bgr(unsigned char* d, int y, int cb, int cr, const YuvCoeffs& q) {
   cb -= kCentre; cr -= kCentre;
-  const int yoff = q.yoff << (kShift - 16);
-  const int dr = q.irv * cr, dg = q.igu * cb + q.igv * cr, db = q.ibu * cb;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = q.iy * ((i ? y1 : y0) - yoff) + (1 << (kShift - 1));
-    d[3 * i] = (unsigned char)clamp8((c + db) >> kShift);
-    d[3 * i + 1] = (unsigned char)clamp8((c + dg) >> kShift);
-    d[3 * i + 2] = (unsigned char)clamp8((c + dr) >> kShift);
-  }
+  const int c = q.iy * (y - (q.yoff << (kShift - 16))) + (1 << (kShift - 1));
+  d[0] = (unsigned char)clamp8((c + q.ibu * cb) >> kShift);
+  d[1] = (unsigned char)clamp8((c + q.igu * cb + q.igv * cr) >> kShift);
+  d[2] = (unsigned char)clamp8((c + q.irv * cr) >> kShift);
+}
+
+// INTERPOLATED CHROMA (SIMPB_SURFACE_CHROMA_JPEG): libjpeg's "fancy" upsampling, the triangle filter its decoder applies to
+// the subsampled planes of a JPEG at its defaults, in int32. For chroma pair j of a row of Wc pairs, with t(k) the pair's two
+// samples after the vertical step and l = max(j - 1, 0), r = min(j + 1, Wc - 1):
+//   column 2j:      (3 t(j) + t(l) + kEven) >> kBits         column 2j + 1:  (3 t(j) + t(r) + kOdd) >> kBits
+// 4:2:0 (h2v2_fancy_upsample): t(k) = 3 near[k] + far[k], near = chroma row r >> 1, far = the row above it for an even luma
+// row r and the row below for an odd one, clamped to the plane; kEven / kOdd / kBits = 8 / 7 / 4.
+// 4:2:2 (h2v1_fancy_upsample): t(k) = the row's own sample; 1 / 2 / 2.
+// tap(k, cb, cr) gives t(k) of both components; cb / cr take the two columns' samples.
+template <int kEven, int kOdd, int kBits, class Tap>
+__device__ __forceinline__ void fancy_pair(int j, int Wc, Tap&& tap, int (&cb)[2], int (&cr)[2]) {
+  int b, r, bl, rl, br, rr;
+  tap(j, b, r);
+  tap(max(j - 1, 0), bl, rl);
+  tap(min(j + 1, Wc - 1), br, rr);
+  cb[0] = (3 * b + bl + kEven) >> kBits;
+  cb[1] = (3 * b + br + kOdd) >> kBits;
+  cr[0] = (3 * r + rl + kEven) >> kBits;
+  cr[1] = (3 * r + rr + kOdd) >> kBits;
 }
 
 // A tight batch of BGR frames, u8 [N][Hs][Ws][3]:
@@ -158,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void resample_rows_kernel(unsigned char* 
 // A tight batch of 4:2:0 semi-planar frames (NV12 / NV21): one image is u8 [Hs * 3 / 2][Ws], Hs luma rows, then Hs / 2 rows
 // of interleaved chroma pairs, (Cb, Cr) or with `vu` (Cr, Cb); chroma sample (i, j) covers luma rows 2i, 2i + 1 and columns
 // 2j, 2j + 1 (replicated). The luma row and its chroma row are staged, converted once into the (B, G, R) row the BGR kernel
-// stages (yuv_pair_to_bgr) and filtered by the same code.
+// stages (yuv_to_bgr) and filtered by the same code.
 __global__ __launch_bounds__(kThreads) void resample_rows_yuv420sp_kernel(unsigned char* __restrict__ mid, const unsigned char* __restrict__ src,
                                                                           const int* __restrict__ kx, const int* __restrict__ xlo,
                                                                           const int* __restrict__ xn, int Hs, int Ws, int row0, int rows,
@@ -173,8 +196,11 @@ __global__ __launch_bounds__(kThreads) void resample_rows_yuv420sp_kernel(unsign
   stage_row<kGiven>(s_luma, image + (size_t)row * Ws, Ws, vec16);
   stage_row<kGiven>(s_chroma, image + (size_t)(Hs + (row >> 1)) * Ws, Ws, vec16);
   __syncthreads();
-  for (int x = 2 * tid; x < Ws; x += 2 * kThreads)   // a chroma pair and its two luma samples (Ws is even)
-    yuv_pair_to_bgr(s_src + x * 3, (int)s_luma[x], (int)s_luma[x + 1], (int)s_chroma[x + vu], (int)s_chroma[x + 1 - vu], q);
+  for (int x = 2 * tid; x < Ws; x += 2 * kThreads) {   // a chroma pair and its two luma samples (Ws is even)
+    const int cb = s_chroma[x + vu], cr = s_chroma[x + 1 - vu];
+    yuv_to_bgr(s_src + x * 3, (int)s_luma[x], cb, cr, q);
+    yuv_to_bgr(s_src + x * 3 + 3, (int)s_luma[x + 1], cb, cr, q);
+  }
   __syncthreads();
   filter_row_and_store(mid + ((size_t)n * rows + r) * pitch, s_src, s_out, kx, xlo, xn, Ws, w, taps, flip, pitch);
 }
@@ -187,16 +213,28 @@ struct Surface {
   const unsigned char* src;
   const unsigned long long* table;
   long long image_stride, chroma_offset, pitch, chroma_pitch, chroma2_offset;
+  int chroma_rows;   // rows of a 4:2:0 chroma plane (src_height / 2): where the far row of interpolated chroma is clamped
 };
 
 constexpr int kBgr = SIMPB_SURFACE_BGR, kNv12 = SIMPB_SURFACE_NV12, kNv21 = SIMPB_SURFACE_NV21, kP010 = SIMPB_SURFACE_P010;
 constexpr int kYuv420p = SIMPB_SURFACE_YUV420P, kYuyv = SIMPB_SURFACE_YUYV, kUyvy = SIMPB_SURFACE_UYVY, kRgb = SIMPB_SURFACE_RGB;
-constexpr int kBgra = SIMPB_SURFACE_BGRA, kRgba = SIMPB_SURFACE_RGBA;
+constexpr int kBgra = SIMPB_SURFACE_BGRA, kRgba = SIMPB_SURFACE_RGBA, kYuv444p = SIMPB_SURFACE_YUV444P;
+// A format code with this flag is a format of its own: the same samples, chroma interpolated (fancy_pair). The five formats
+// with subsampled 8-bit chroma take it, and nothing else does.
+constexpr int kJpeg = SIMPB_SURFACE_CHROMA_JPEG;
+__host__ __device__ constexpr int base_format(int format) { return format & ~kJpeg; }
+__host__ __device__ constexpr bool takes_jpeg_chroma(int base) {
+  return base == kNv12 || base == kNv21 || base == kYuv420p || base == kYuyv || base == kUyvy;
+}
 
 // The one place where a runtime format code becomes a compile-time constant: fn(std::integral_constant<int, F>) for the
 // code's F, and true; false, and nothing called, for a code that is no format (the entry points refuse it before any launch).
 // kLastIsElse is for the rig kernel alone: there the last format stands for every other code as well, so that the choice
 // has no path that stages nothing (the loads of the camera's layout stay in front of it) and ends in no wrong access.
+// Interpolated chroma is a template parameter like the format, not a branch inside the replicated code: the instantiations
+// of replicated chroma are the code they were (the same instruction counts and registers in every horizontal kernel but the
+// rig's, which gains the new arms), and a rig pays for the interpolated form only in the workgroups of a camera that asks
+// for it (profiles/jpeg_chroma.md has the figures).
 template <bool kLastIsElse = false, class Fn>
 __host__ __device__ __forceinline__ bool with_format(int format, Fn&& fn) {
   switch (format) {
@@ -210,6 +248,12 @@ __host__ __device__ __forceinline__ bool with_format(int format, Fn&& fn) {
     SIMPB_FORMAT(kRgb);
     SIMPB_FORMAT(kBgra);
     SIMPB_FORMAT(kRgba);
+    SIMPB_FORMAT(kYuv444p);
+    SIMPB_FORMAT(kNv12 | kJpeg);
+    SIMPB_FORMAT(kNv21 | kJpeg);
+    SIMPB_FORMAT(kYuv420p | kJpeg);
+    SIMPB_FORMAT(kYuyv | kJpeg);
+    SIMPB_FORMAT(kUyvy | kJpeg);
 #undef SIMPB_FORMAT
     default:
       if (!kLastIsElse && format != kP010) return false;
@@ -221,12 +265,19 @@ __host__ __device__ __forceinline__ bool with_format(int format, Fn&& fn) {
 // LDS bytes of the two staging planes of a source `width` wide, s_luma and s_chroma (one plane each; a multiple of 16). A
 // packed row that is converted or compacted on its way into the (B, G, R) row (4:2:2: 2 bytes per pixel, BGRA / RGBA: 4) is
 // staged from s_luma on and runs through into s_chroma, which lies right behind it; the two chroma rows of planar 4:2:0 share
-// s_chroma, the Cr row in its second half. BGR and RGB rows are staged where the filter reads them.
+// s_chroma, the Cr row in its second half, and so do the two full-width chroma rows of planar 4:4:4. BGR and RGB rows are
+// staged where the filter reads them. Interpolated chroma changes nothing here: a 4:2:0 format stages its far chroma row in a
+// third plane of the same size, s_far, behind s_chroma (far_plane), and 4:2:2 reads its neighbours in the row it has.
 __host__ __device__ constexpr int plane_bytes(int format, int width) {
-  return format == kBgr || format == kRgb ? 0
-         : format == kP010 || format == kBgra || format == kRgba ? (2 * width + 15) / 16 * 16
-         : format == kYuv420p ? 2 * ((width / 2 + 15) / 16 * 16)
-                              : (width + 15) / 16 * 16;   // (NV12 / NV21: a luma and a chroma row; 4:2:2: the halves of its row)
+  const int base = base_format(format);
+  return base == kBgr || base == kRgb ? 0
+         : base == kP010 || base == kBgra || base == kRgba ? (2 * width + 15) / 16 * 16
+         : base == kYuv420p ? 2 * ((width / 2 + 15) / 16 * 16)
+         : base == kYuv444p ? 2 * ((width + 15) / 16 * 16)
+                            : (width + 15) / 16 * 16;   // (NV12 / NV21: a luma and a chroma row; 4:2:2: the halves of its row)
+}
+__host__ __device__ constexpr bool far_plane(int format) {
+  return (format & kJpeg) && (base_format(format) == kNv12 || base_format(format) == kNv21 || base_format(format) == kYuv420p);
 }
 
 // One source row of a surface as the (B, G, R) row the filter reads, for every source format. `image` is the image's first
@@ -234,19 +285,92 @@ __host__ __device__ constexpr int plane_bytes(int format, int width) {
 // (synchronised). Chroma rows that lie under no needed luma row are never read.
 // kBgr: the surface's own interleaved row, staged where the filter reads it (s_luma / s_chroma are not looked at). kRgb: the
 // BGR row with bytes 0 and 2 of every pixel exchanged. kBgra / kRgba: 4 bytes per pixel, byte 3 is dropped whatever it holds.
-// The YCbCr formats are arrangements of the samples that yuv_pair_to_bgr takes. 4:2:0 semi-planar (kNv12: (Cb, Cr) pairs,
+// The YCbCr formats are arrangements of the samples that yuv_to_bgr takes. 4:2:0 semi-planar (kNv12: (Cb, Cr) pairs,
 // kNv21: (Cr, Cb), u8; kP010: (Cb, Cr), u16 little-endian with the 10-bit sample in the high bits): chroma sample (i, j) covers
 // luma rows 2i, 2i + 1 and columns 2j, 2j + 1 (replicated); the luma row and the chroma row under it are staged, Ws samples
 // each in s_luma / s_chroma. kYuv420p (I420 / YV12): three planes, the Cb row i of Ws / 2 bytes at + chroma_offset +
 // i * chroma_pitch and the Cr row at + chroma2_offset + i * chroma_pitch; which plane comes first in memory is the caller's to
 // say through the two offsets. kYuyv / kUyvy (packed 4:2:2): one plane, a row is Ws / 2 groups (Y0, Cb, Y1, Cr) /
-// (Cb, Y0, Cr, Y1); the pair belongs to columns 2j, 2j + 1 of its own row.
+// (Cb, Y0, Cr, Y1); the pair belongs to columns 2j, 2j + 1 of its own row. kYuv444p: three planes of Ws bytes a row, addressed
+// like kYuv420p, a Cb and a Cr sample per pixel: nothing to replicate or interpolate (what a 4:4:4 JPEG decodes to).
+// F | kJpeg (the five 8-bit formats with subsampled chroma): the same samples, centre-sited, interpolated by fancy_pair. A
+// 4:2:0 row stages a second chroma row, the far one, in s_far (arranged like s_chroma): row (row >> 1) - 1 for an even luma
+// row and + 1 for an odd one, clamped to 0 .. chroma_rows - 1. It is read whether or not a needed luma row lies over it, and
+// like every row exactly its sample bytes; 4:2:2 reads the neighbouring pairs of the row it has staged.
 template <int F>
-__device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned char* s_luma, unsigned char* s_chroma,
+__device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned char* s_luma, unsigned char* s_chroma, unsigned char* s_far,
                                               const unsigned char* __restrict__ image, long long pitch, long long chroma_offset,
-                                              long long chroma_pitch, long long chroma2_offset, int row, int Ws, const YuvCoeffs& q) {
+                                              long long chroma_pitch, long long chroma2_offset, int chroma_rows, int row, int Ws,
+                                              const YuvCoeffs& q) {
   const int tid = threadIdx.x;
-  if constexpr (F == kBgr) {
+  [[maybe_unused]] const int far = min(max((row >> 1) + ((row & 1) ? 1 : -1), 0), chroma_rows - 1);
+  if constexpr (F == (kYuyv | kJpeg) || F == (kUyvy | kJpeg)) {   // (Ws is even)
+    stage_row<kByAddress>(s_luma, image + (size_t)row * pitch, Ws * 2);
+    __syncthreads();
+    const unsigned int* group = reinterpret_cast<const unsigned int*>(s_luma);
+    constexpr int kY = base_format(F) == kYuyv ? 0 : 8, kC = 8 - kY;   // bit of Y0 and of Cb inside the group
+    const int Wc = Ws >> 1;
+    for (int j = tid; j < Wc; j += kThreads) {
+      int cb[2], cr[2];
+      fancy_pair<1, 2, 2>(j, Wc, [&](int k, int& b, int& r) {
+        const unsigned int v = group[k];
+        b = (int)((v >> kC) & 255u);
+        r = (int)((v >> (kC + 16)) & 255u);
+      }, cb, cr);
+      const unsigned int v = group[j];
+      yuv_to_bgr(s_src + j * 6, (int)((v >> kY) & 255u), cb[0], cr[0], q);
+      yuv_to_bgr(s_src + j * 6 + 3, (int)((v >> (kY + 16)) & 255u), cb[1], cr[1], q);
+    }
+    __syncthreads();
+  } else if constexpr (F == (kYuv420p | kJpeg)) {
+    const int Wc = Ws >> 1, half = (Wc + 15) & ~15;   // (plane_bytes: the Cr row in the second half of s_chroma / s_far)
+    stage_row<kByAddress>(s_luma, image + (size_t)row * pitch, Ws);
+    stage_row<kByAddress>(s_chroma, image + chroma_offset + (size_t)(row >> 1) * chroma_pitch, Wc);
+    stage_row<kByAddress>(s_chroma + half, image + chroma2_offset + (size_t)(row >> 1) * chroma_pitch, Wc);
+    stage_row<kByAddress>(s_far, image + chroma_offset + (size_t)far * chroma_pitch, Wc);
+    stage_row<kByAddress>(s_far + half, image + chroma2_offset + (size_t)far * chroma_pitch, Wc);
+    __syncthreads();
+    for (int j = tid; j < Wc; j += kThreads) {
+      int cb[2], cr[2];
+      fancy_pair<8, 7, 4>(j, Wc, [&](int k, int& b, int& r) {
+        b = 3 * (int)s_chroma[k] + (int)s_far[k];
+        r = 3 * (int)s_chroma[half + k] + (int)s_far[half + k];
+      }, cb, cr);
+      yuv_to_bgr(s_src + j * 6, (int)s_luma[2 * j], cb[0], cr[0], q);
+      yuv_to_bgr(s_src + j * 6 + 3, (int)s_luma[2 * j + 1], cb[1], cr[1], q);
+    }
+    __syncthreads();
+  } else if constexpr (F == (kNv12 | kJpeg) || F == (kNv21 | kJpeg)) {
+    constexpr int kB = base_format(F) == kNv21 ? 8 : 0, kR = 8 - kB;   // bit of Cb and of Cr inside a pair
+    const int Wc = Ws >> 1;
+    stage_row<kByAddress>(s_luma, image + (size_t)row * pitch, Ws);
+    stage_row<kByAddress>(s_chroma, image + chroma_offset + (size_t)(row >> 1) * chroma_pitch, Ws);
+    stage_row<kByAddress>(s_far, image + chroma_offset + (size_t)far * chroma_pitch, Ws);
+    __syncthreads();
+    const unsigned short* near2 = reinterpret_cast<const unsigned short*>(s_chroma);   // one chroma pair (LDS is 16-byte aligned)
+    const unsigned short* far2 = reinterpret_cast<const unsigned short*>(s_far);
+    const unsigned short* luma2 = reinterpret_cast<const unsigned short*>(s_luma);
+    for (int j = tid; j < Wc; j += kThreads) {
+      int cb[2], cr[2];
+      fancy_pair<8, 7, 4>(j, Wc, [&](int k, int& b, int& r) {
+        const unsigned int n = near2[k], f = far2[k];
+        b = 3 * (int)((n >> kB) & 255u) + (int)((f >> kB) & 255u);
+        r = 3 * (int)((n >> kR) & 255u) + (int)((f >> kR) & 255u);
+      }, cb, cr);
+      const unsigned int y = luma2[j];
+      yuv_to_bgr(s_src + j * 6, (int)(y & 255u), cb[0], cr[0], q);
+      yuv_to_bgr(s_src + j * 6 + 3, (int)(y >> 8), cb[1], cr[1], q);
+    }
+    __syncthreads();
+  } else if constexpr (F == kYuv444p) {
+    unsigned char* s_cr = s_chroma + ((Ws + 15) & ~15);   // (plane_bytes: the second half of s_chroma)
+    stage_row<kByAddress>(s_luma, image + (size_t)row * pitch, Ws);
+    stage_row<kByAddress>(s_chroma, image + chroma_offset + (size_t)row * chroma_pitch, Ws);
+    stage_row<kByAddress>(s_cr, image + chroma2_offset + (size_t)row * chroma_pitch, Ws);
+    __syncthreads();
+    for (int x = tid; x < Ws; x += kThreads) yuv_to_bgr(s_src + x * 3, (int)s_luma[x], (int)s_chroma[x], (int)s_cr[x], q);
+    __syncthreads();
+  } else if constexpr (F == kBgr) {
     stage_row<kByAddress>(s_src, image + (size_t)row * pitch, Ws * 3);
     __syncthreads();
   } else if constexpr (F == kRgb) {   // permuted where it lies: a thread exchanges the ends of its own pixels
@@ -278,8 +402,9 @@ __device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned cha
     constexpr int kY = F == kYuyv ? 0 : 8, kC = 8 - kY;   // bit of Y0 and of Cb inside the group
     for (int j = tid; 2 * j < Ws; j += kThreads) {
       const unsigned int v = group[j];
-      yuv_pair_to_bgr(s_src + j * 6, (int)((v >> kY) & 255u), (int)((v >> (kY + 16)) & 255u), (int)((v >> kC) & 255u),
-                      (int)((v >> (kC + 16)) & 255u), q);
+      const int cb = (int)((v >> kC) & 255u), cr = (int)((v >> (kC + 16)) & 255u);
+      yuv_to_bgr(s_src + j * 6, (int)((v >> kY) & 255u), cb, cr, q);
+      yuv_to_bgr(s_src + j * 6 + 3, (int)((v >> (kY + 16)) & 255u), cb, cr, q);
     }
     __syncthreads();
   } else if constexpr (F == kYuv420p) {
@@ -288,8 +413,11 @@ __device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned cha
     stage_row<kByAddress>(s_chroma, image + chroma_offset + (size_t)(row >> 1) * chroma_pitch, Ws >> 1);
     stage_row<kByAddress>(s_cr, image + chroma2_offset + (size_t)(row >> 1) * chroma_pitch, Ws >> 1);
     __syncthreads();
-    for (int j = tid; 2 * j < Ws; j += kThreads)
-      yuv_pair_to_bgr(s_src + j * 6, (int)s_luma[2 * j], (int)s_luma[2 * j + 1], (int)s_chroma[j], (int)s_cr[j], q);
+    for (int j = tid; 2 * j < Ws; j += kThreads) {
+      const int cb = s_chroma[j], cr = s_cr[j];
+      yuv_to_bgr(s_src + j * 6, (int)s_luma[2 * j], cb, cr, q);
+      yuv_to_bgr(s_src + j * 6 + 3, (int)s_luma[2 * j + 1], cb, cr, q);
+    }
     __syncthreads();
   } else {
     static_assert(F == kNv12 || F == kNv21 || F == kP010, "a format without a branch of its own");
@@ -302,9 +430,13 @@ __device__ __forceinline__ void stage_bgr_row(unsigned char* s_src, unsigned cha
       if constexpr (F == kP010) {   // sample = word >> 6: the low six bits are ignored whatever they hold
         const unsigned short* l = reinterpret_cast<const unsigned short*>(s_luma);
         const unsigned short* c = reinterpret_cast<const unsigned short*>(s_chroma);
-        yuv_pair_to_bgr<18, 512>(s_src + x * 3, (int)(l[x] >> 6), (int)(l[x + 1] >> 6), (int)(c[x] >> 6), (int)(c[x + 1] >> 6), q);
+        const int cb = c[x] >> 6, cr = c[x + 1] >> 6;
+        yuv_to_bgr<18, 512>(s_src + x * 3, (int)(l[x] >> 6), cb, cr, q);
+        yuv_to_bgr<18, 512>(s_src + x * 3 + 3, (int)(l[x + 1] >> 6), cb, cr, q);
       } else {
-        yuv_pair_to_bgr(s_src + x * 3, (int)s_luma[x], (int)s_luma[x + 1], (int)s_chroma[x + kVu], (int)s_chroma[x + 1 - kVu], q);
+        const int cb = s_chroma[x + kVu], cr = s_chroma[x + 1 - kVu];
+        yuv_to_bgr(s_src + x * 3, (int)s_luma[x], cb, cr, q);
+        yuv_to_bgr(s_src + x * 3 + 3, (int)s_luma[x + 1], cb, cr, q);
       }
     }
     __syncthreads();
@@ -321,13 +453,15 @@ __global__ __launch_bounds__(kThreads) void resample_rows_surface_kernel(unsigne
   __shared__ __attribute__((aligned(16))) unsigned char s_src[kMaxSrcW * 3];
   __shared__ __attribute__((aligned(16))) unsigned char s_out[kMaxOutW * 3 + 16];
   // (a BGR / RGB row is staged where the filter reads it; a packed 4:2:2 or 4-byte row lies in s_luma as a whole)
-  constexpr bool kPacked = F == kYuyv || F == kUyvy || F == kBgra || F == kRgba;
+  constexpr bool kPacked = base_format(F) == kYuyv || base_format(F) == kUyvy || F == kBgra || F == kRgba;
   constexpr int kPlane = plane_bytes(F, kMaxSrcW) == 0 ? 16 : plane_bytes(F, kMaxSrcW);
   __shared__ __attribute__((aligned(16))) unsigned char s_luma[kPacked ? 2 * kPlane : kPlane];
   __shared__ __attribute__((aligned(16))) unsigned char s_chroma[kPacked ? 16 : kPlane];
+  __shared__ __attribute__((aligned(16))) unsigned char s_far[far_plane(F) ? kPlane : 16];   // (interpolated 4:2:0 alone)
   const int r = blockIdx.x, n = blockIdx.y;
   const unsigned char* image = sf.table ? reinterpret_cast<const unsigned char*>(sf.table[n]) : sf.src + (size_t)n * sf.image_stride;
-  stage_bgr_row<F>(s_src, s_luma, s_chroma, image, sf.pitch, sf.chroma_offset, sf.chroma_pitch, sf.chroma2_offset, row0 + r, Ws, q);
+  stage_bgr_row<F>(s_src, s_luma, s_chroma, s_far, image, sf.pitch, sf.chroma_offset, sf.chroma_pitch, sf.chroma2_offset,
+                   sf.chroma_rows, row0 + r, Ws, q);
   filter_row_and_store(mid + ((size_t)n * rows + r) * pitch, s_src, s_out, kx, xlo, xn, Ws, w, taps, flip, pitch);
 }
 
@@ -344,6 +478,7 @@ struct Rig { simpb_rig_camera cam[SIMPB_RIG_MAX_CAMS]; };
 // LDS is dynamic, sized by the entry point for the rig at hand (RigLds: the widest camera's (B, G, R) row, the resampled row,
 // and the widest staging planes of any camera, plane_bytes), not for the widest source the file takes: a rig of 1600-wide NV12
 // cameras holds 10 KB per workgroup where the static arrays of the surface kernel hold 26 KB, and a BGR rig has no planes.
+// A rig with a camera of interpolated 4:2:0 chroma has a third plane of that size behind the two (1.6 KB more at 1600 wide).
 struct RigLds { int src_bytes, out_bytes, plane_bytes; };   // each a multiple of 16
 
 __global__ __launch_bounds__(kThreads) void resample_rows_rig_kernel(unsigned char* __restrict__ mid,
@@ -356,6 +491,7 @@ __global__ __launch_bounds__(kThreads) void resample_rows_rig_kernel(unsigned ch
   unsigned char* s_out = s_src + lds.src_bytes;
   unsigned char* s_luma = s_out + lds.out_bytes;
   unsigned char* s_chroma = s_luma + lds.plane_bytes;
+  unsigned char* s_far = s_chroma + lds.plane_bytes;   // (there where a camera of the rig stages a far chroma row: far_plane)
   const int r = blockIdx.x, n = blockIdx.y;
   const int stream = n / num_cams;
   const simpb_rig_camera& c = rig.cam[n - stream * num_cams];
@@ -365,7 +501,8 @@ __global__ __launch_bounds__(kThreads) void resample_rows_rig_kernel(unsigned ch
   const YuvCoeffs q = {c.yoff, c.iy, c.irv, c.igu, c.igv, c.ibu};
   const int row = c.src_row0 + r, Ws = c.src_width;
   with_format<true>(c.format, [&](auto f) {
-    stage_bgr_row<decltype(f)::value>(s_src, s_luma, s_chroma, image, c.pitch, c.chroma_offset, c.chroma_pitch, c.chroma2_offset, row, Ws, q);
+    stage_bgr_row<decltype(f)::value>(s_src, s_luma, s_chroma, s_far, image, c.pitch, c.chroma_offset, c.chroma_pitch, c.chroma2_offset,
+                                      c.src_height >> 1, row, Ws, q);
   });
   filter_row_and_store(mid + ((size_t)stream * mid_rows + c.mid_row + r) * pitch, s_src, s_out, kx + c.kx_offset, xlo + c.x_offset,
                        xn + c.x_offset, Ws, w, c.taps_x, c.flip, pitch);
@@ -680,30 +817,37 @@ extern "C" int simpb_preprocess_yuv420sp_nhwc4_f16(void* out, const void* src, v
 // [lo, lo + len) of two ranges overlap
 static bool ranges_overlap(long long a, long long alen, long long b, long long blen) { return a < b + blen && b < a + alen; }
 
-static bool known_format(int format) { return (format >= kBgr && format <= kP010) || (format >= kYuv420p && format <= kRgba); }
+// a format code as the planes, roll and rig entry points take it: a format, or one with subsampled 8-bit chroma | kJpeg
+static bool known_format(int format) {
+  const int base = base_format(format);
+  if (!((base >= kBgr && base <= kP010) || (base >= kYuv420p && base <= kRgba) || base == kYuv444p)) return false;
+  return format == base || takes_jpeg_chroma(base);
+}
 
 // The layout rules of one surface of a known format, shared by every entry point that takes one: the offset one past the
 // image's last sample, or -1 for a layout that is refused. The fields a format does not look at are set to 0.
 static long long surface_extent(int format, int src_height, int src_width, long long pitch, long long& chroma_pitch,
                                 long long& chroma_offset, long long& chroma2_offset, int iy) {
   constexpr long long kMaxPitch = 1LL << 30, kMaxOffset = 1LL << 40;   // (keeps every offset below far inside 63 bits)
-  const bool planar = format == kYuv420p, semi = format == kNv12 || format == kNv21 || format == kP010;
+  format = base_format(format);   // (interpolated chroma reads the samples of its format, and no others)
+  const bool full = format == kYuv444p;   // three planes like planar 4:2:0, the chroma planes as large as the luma plane
+  const bool planar = format == kYuv420p || full, semi = format == kNv12 || format == kNv21 || format == kP010;
   const bool ycbcr = planar || semi || format == kYuyv || format == kUyvy;
   const long long pixel = format == kBgr || format == kRgb ? 3 : format == kBgra || format == kRgba ? 4
                           : format == kP010 || format == kYuyv || format == kUyvy ? 2 : 1;
   const long long row = (long long)src_width * pixel;   // sample bytes of a luma (packed) row
   if (pitch < row || pitch > kMaxPitch) return -1;
-  if (ycbcr && ((src_width & 1) || iy <= 0)) return -1;
+  if (ycbcr && ((!full && (src_width & 1)) || iy <= 0)) return -1;
   const long long luma_end = (long long)(src_height - 1) * pitch + row;
   if (!planar) chroma2_offset = 0;
   if (!planar && !semi) {
     chroma_pitch = chroma_offset = 0;
     return luma_end;
   }
-  if (src_height & 1) return -1;
-  const long long chroma_row = planar ? src_width / 2 : row;   // sample bytes of a chroma row
+  if (!full && (src_height & 1)) return -1;
+  const long long chroma_row = full ? row : planar ? src_width / 2 : row;   // sample bytes of a chroma row
   if (chroma_pitch < chroma_row || chroma_pitch > kMaxPitch) return -1;
-  const long long span = (long long)(src_height / 2 - 1) * chroma_pitch + chroma_row;
+  const long long span = (long long)((full ? src_height : src_height / 2) - 1) * chroma_pitch + chroma_row;
   if (chroma_offset < luma_end || chroma_offset > kMaxOffset) return -1;   // a chroma plane lies behind the luma plane
   if (format == kP010 && ((pitch | chroma_pitch | chroma_offset) & 1)) return -1;
   if (!planar) return chroma_offset + span;
@@ -722,6 +866,7 @@ static int preprocess_surface(void* out, Surface sf, int format, const Tables& t
   const long long end = surface_extent(format, sh.src_height, sh.src_width, sf.pitch, sf.chroma_pitch, sf.chroma_offset,
                                        sf.chroma2_offset, q.iy);
   if (end < 0) return SIMPB_EINVAL;
+  sf.chroma_rows = sh.src_height >> 1;
   if (sf.src) {
     if (sf.image_stride < end || sf.image_stride > (1LL << 40)) return SIMPB_EINVAL;
     if (format == kP010 && ((sf.image_stride | (long long)reinterpret_cast<size_t>(sf.src)) & 1)) return SIMPB_EINVAL;
@@ -740,7 +885,7 @@ extern "C" int simpb_preprocess_surface_nhwc4_f16(void* out, const void* src, co
                                                   void* stream) {
   if (format != kBgr && format != kNv12 && format != kNv21 && format != kP010) return SIMPB_EINVAL;
   const Surface sf = {static_cast<const unsigned char*>(src), static_cast<const unsigned long long*>(image_table), image_stride,
-                      chroma_offset, pitch, chroma_pitch, 0};
+                      chroma_offset, pitch, chroma_pitch, 0, 0};
   const Tables t = {mid, kx, xlo, xn, ky, ylo, yn, lut};
   const Shape sh = {num_images, src_height, src_width, out_height, out_width, taps_x, taps_y, src_row0, src_rows, flip ? 1 : 0,
                     swap_rb ? 1 : 0};
@@ -756,7 +901,7 @@ extern "C" int simpb_preprocess_planes_nhwc4_f16(void* out, const void* src, con
                                                  int igv, int ibu, void* stream) {
   if (!known_format(format)) return SIMPB_EINVAL;
   const Surface sf = {static_cast<const unsigned char*>(src), static_cast<const unsigned long long*>(image_table), image_stride,
-                      chroma_offset, pitch, chroma_pitch, chroma2_offset};
+                      chroma_offset, pitch, chroma_pitch, chroma2_offset, 0};
   const Tables t = {mid, kx, xlo, xn, ky, ylo, yn, lut};
   const Shape sh = {num_images, src_height, src_width, out_height, out_width, taps_x, taps_y, src_row0, src_rows, flip ? 1 : 0,
                     swap_rb ? 1 : 0};
@@ -782,7 +927,7 @@ extern "C" int simpb_preprocess_roll_nhwc4_f16(void* out, const void* src, const
   RollTable table;
   if (bad_roll(table, roll, roll_cams, out_height, out_width) || !known_format(format)) return SIMPB_EINVAL;
   const Surface sf = {static_cast<const unsigned char*>(src), static_cast<const unsigned long long*>(image_table), image_stride,
-                      chroma_offset, pitch, chroma_pitch, chroma2_offset};
+                      chroma_offset, pitch, chroma_pitch, chroma2_offset, 0};
   const Tables t = {mid, kx, xlo, xn, ky, ylo, yn, lut};
   const Shape sh = {num_images, src_height, src_width, out_height, out_width, taps_x, taps_y, src_row0, src_rows, flip ? 1 : 0,
                     swap_rb ? 1 : 0};
@@ -833,17 +978,19 @@ static int preprocess_rig(void* out, const void* image_table, const Tables& t, c
   const int pitch = mid_pitch(out_width);
   // LDS for the rig at hand (validated above: at most kMaxSrcW * 3 + kMaxOutW * 3 + 16 + 2 * kMaxSrcW * 2 = 34832 bytes; a 4-byte
   // row of the widest source is as long as the two P010 planes of one)
-  int src_bytes = 0, planes = 0;
+  // (behind the two planes, the far chroma row of the widest camera that stages one: at most kMaxSrcW bytes more)
+  int src_bytes = 0, planes = 0, far_bytes = 0;
   for (int i = 0; i < num_cams; ++i) {
     const int plane = plane_bytes(cams[i].format, cams[i].src_width);
     src_bytes = cams[i].src_width * 3 > src_bytes ? cams[i].src_width * 3 : src_bytes;
     planes = plane > planes ? plane : planes;
+    if (far_plane(cams[i].format) && plane > far_bytes) far_bytes = plane;
   }
   const RigLds lds = {(src_bytes + 15) / 16 * 16, pitch + 16, planes};
   hipStream_t s = static_cast<hipStream_t>(stream);
   (void)hipGetLastError();
   hipLaunchKernelGGL(resample_rows_rig_kernel, dim3(max_rows, num_images), dim3(kThreads),
-                     (size_t)(lds.src_bytes + lds.out_bytes + 2 * lds.plane_bytes), s, static_cast<unsigned char*>(t.mid), table, rig,
+                     (size_t)(lds.src_bytes + lds.out_bytes + 2 * lds.plane_bytes + far_bytes), s, static_cast<unsigned char*>(t.mid), table, rig,
                      num_cams, t.kx, t.xlo, t.xn, out_width, pitch, mid_rows, lds);
   return launch_vertical(num_images, out_height, out_width, roll, [&](dim3 grid, dim3 block, auto r) {
     hipLaunchKernelGGL(resample_cols_lut_rig_kernel<decltype(r)>, grid, block, 0, s, static_cast<_Float16*>(out),

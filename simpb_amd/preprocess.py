@@ -27,7 +27,12 @@ host-converted frames bit for bit.
 
 A camera's mount roll -- the reference function's fourth step, `img.rotate(rotate)` (augment.py:92,105) -- is `roll=` of a
 ResamplePlan or CameraSource: `roll_integers` reduces it to the six 16.16 fixed-point integers of Pillow's nearest-neighbour affine
-map, which the vertical pass applies as a gather; the aug_config's own `rotate` stays refused (0 in the reference's test mode)."""
+map, which the vertical pass applies as a gather; the aug_config's own `rotate` stays refused (0 in the reference's test mode).
+
+The reference's images are JPEG files decoded by libjpeg at its defaults. A caller who hands over the decoder's native planes gets
+libjpeg's bytes with `chroma="jpeg"` (the subsampled chroma interpolated by libjpeg's "fancy" upsampling, in integers, inside the
+horizontal pass), `colour="jpeg"` (libjpeg's own four colour constants, `YUV_INTEGERS`) and "yuv444p" (the three full planes of a
+4:4:4 file). 4:2:0, 4:4:4 and the constants are pinned to libjpeg-turbo through Pillow; the 4:2:2 rule is stated only."""
 import ctypes
 import math
 
@@ -50,6 +55,23 @@ RGB_ORDER = ("bgr", "rgb", "bgra", "rgba")  # no YCbCr conversion: the colour st
 YUV_BITS = 16         # fractional bits of the YCbCr -> BGR coefficients
 # standard -> (Kr, Kb, full range)
 YUV_STANDARDS = {"jfif": (0.299, 0.114, True), "bt601": (0.299, 0.114, False), "bt709": (0.2126, 0.0722, False)}
+# A colour given as its six integers (yoff, iy, irv, igu, igv, ibu), not derived from Kr / Kb. "jpeg": libjpeg's own YCbCr -> RGB
+# tables (jdcolor.c), FIX(1.40200) = 91881, -FIX(0.34414) = -22554, -FIX(0.71414) = -46802, FIX(1.77200) = 116130 with FIX(x) =
+# int(x * 65536 + 0.5) of the four rounded decimals. "jfif" rounds the exact 0.344136... to -22553, and G then differs by one at
+# 59 of the 65 536 (Cb, Cr) pairs; "jfif" keeps its constants and its bytes.
+YUV_INTEGERS = {"jpeg": (0, 65536, 91881, -22554, -46802, 116130)}
+COLOURS = tuple(sorted(YUV_STANDARDS)) + tuple(sorted(YUV_INTEGERS))
+# The frame formats of FRAME_FORMATS have subsampled chroma or none. "yuv444p" is the one with full-resolution chroma: three
+# planes of Hs rows of Ws bytes, what a 4:4:4 JPEG decodes to. Every place that takes a frame format takes it.
+FULL_CHROMA = ("yuv444p",)
+ALL_FORMATS = FRAME_FORMATS + FULL_CHROMA
+SURFACE_FORMAT["yuv444p"] = 16
+# chroma="replicate" | "jpeg": how the subsampled chroma of a frame becomes a Cb / Cr per pixel. "replicate": sample (i, j)
+# covers its 2 x 2 (4:2:2: 1 x 2) pixels. "jpeg": centre-sited samples, interpolated by libjpeg's "fancy" upsampling (its default
+# for a JPEG file; include/simpb_hip.h: SIMPB_SURFACE_CHROMA_JPEG has the rule).
+CHROMA_MODES = ("replicate", "jpeg")
+CHROMA_JPEG_FLAG = 0x100              # SIMPB_SURFACE_CHROMA_JPEG
+CHROMA_JPEG_FORMATS = ("nv12", "nv21", "yuv420p", "yvu420p", "yuyv", "uyvy")   # 8-bit samples, subsampled chroma
 
 
 def yuv_coefficients(standard="jfif"):
@@ -61,9 +83,12 @@ def yuv_coefficients(standard="jfif"):
         B = clip8((c + ibu * (Cb - 128)) >> 16)                      (>> arithmetic, clip8 clamps to 0..255)
 
     "jfif": full range, Kr = 0.299, Kb = 0.114 (what a JPEG holds; the default). "bt601": limited range (luma 16..235, chroma
-    16..240), the same Kr / Kb. "bt709": limited range, Kr = 0.2126, Kb = 0.0722."""
+    16..240), the same Kr / Kb. "bt709": limited range, Kr = 0.2126, Kb = 0.0722. "jpeg": full range, libjpeg's own four
+    constants as they stand (YUV_INTEGERS), for the bytes its decoder gives."""
+    if standard in YUV_INTEGERS:
+        return YUV_INTEGERS[standard]
     if standard not in YUV_STANDARDS:
-        raise ValueError(f"colour standard {standard!r}: one of {sorted(YUV_STANDARDS)}")
+        raise ValueError(f"colour standard {standard!r}: one of {list(COLOURS)}")
     kr, kb, full = YUV_STANDARDS[standard]
     kg = 1.0 - kr - kb
     ys, cs = (1.0, 1.0) if full else (255.0 / 219.0, 255.0 / 224.0)
@@ -88,8 +113,10 @@ def p010_coefficients(standard):
     An 8-bit sample stored as v << 8 (10-bit value 4 v) gives the 8-bit rule's byte, since (4 A) >> 18 == A >> 16. Limited
     range only ("bt601", "bt709"): JFIF is the 8-bit JPEG convention, and full-range 10-bit video scales by 1023, not by
     4 x 255."""
+    if standard in YUV_INTEGERS:
+        raise ValueError(f"colour {standard!r} is libjpeg's table for the 8-bit samples of a JPEG: p010 frames take 'bt601' or 'bt709'")
     if standard not in YUV_STANDARDS:
-        raise ValueError(f"colour standard {standard!r}: one of {sorted(YUV_STANDARDS)}")
+        raise ValueError(f"colour standard {standard!r}: one of {list(COLOURS)}")
     if YUV_STANDARDS[standard][2]:
         raise ValueError(f"colour standard {standard!r} is the full-range 8-bit JPEG convention: p010 frames take 'bt601' or 'bt709'")
     yoff, iy, irv, igu, igv, ibu = yuv_coefficients(standard)
@@ -100,16 +127,29 @@ def p010_coefficients(standard):
 
 
 def _unknown_format(frame_format):
-    return ValueError(f"frame format {frame_format!r}: one of {FRAME_FORMATS} (planar I420 is 'yuv420p', YV12 is 'yvu420p')")
+    return ValueError(f"frame format {frame_format!r}: one of {ALL_FORMATS} (planar I420 is 'yuv420p', YV12 is 'yvu420p')")
 
 
-def _check_format(frame_format, colour):
-    if frame_format not in FRAME_FORMATS:
+def _check_format(frame_format, colour, chroma="replicate"):
+    if frame_format not in ALL_FORMATS:
         raise _unknown_format(frame_format)
-    if colour not in YUV_STANDARDS:
-        raise ValueError(f"colour standard {colour!r}: one of {sorted(YUV_STANDARDS)}")
+    if colour not in COLOURS:
+        raise ValueError(f"colour standard {colour!r}: one of {list(COLOURS)}")
     if frame_format == "p010":
-        p010_coefficients(colour)   # (refuses "jfif")
+        p010_coefficients(colour)   # (refuses "jfif" and "jpeg")
+    if chroma not in CHROMA_MODES:
+        raise ValueError(f"chroma={chroma!r}: one of {CHROMA_MODES}")
+    if chroma == "jpeg" and frame_format not in CHROMA_JPEG_FORMATS:
+        why = ("its samples are 10-bit: libjpeg's rule is stated for the 8-bit planes of a JPEG" if frame_format == "p010"
+               else "every pixel has its own chroma sample already" if frame_format in FULL_CHROMA
+               else "it has no chroma planes")
+        raise ValueError(f"chroma='jpeg' interpolates subsampled 8-bit chroma (one of {CHROMA_JPEG_FORMATS}): a {frame_format} frame "
+                         f"does not take it, {why}")
+
+
+def format_code(frame_format, chroma="replicate"):
+    """The `format` argument of the C entry points: SIMPB_SURFACE_* of include/simpb_hip.h, | SIMPB_SURFACE_CHROMA_JPEG."""
+    return SURFACE_FORMAT[frame_format] | (CHROMA_JPEG_FLAG if chroma == "jpeg" else 0)
 
 
 def frame_shape(src_hw, frame_format="bgr"):
@@ -117,8 +157,11 @@ def frame_shape(src_hw, frame_format="bgr"):
     NV12 / NV21 (Hs luma rows, then Hs / 2 rows of interleaved chroma pairs; row pitch Ws), or (Hs * 3 / 2, Ws * 2) for P010 (the
     bytes of u16 little-endian samples in the NV12 arrangement). "yuv420p" / "yvu420p": (Hs * 3 / 2, Ws) as NV12 -- the same
     bytes count, so a caller's buffers carry over: Hs luma rows, then the Cb (yvu420p: Cr) plane of Hs / 2 rows of Ws / 2 bytes,
-    then the other one. "yuyv" / "uyvy": (Hs, Ws, 2). "rgb": (Hs, Ws, 3). "bgra" / "rgba": (Hs, Ws, 4)."""
+    then the other one. "yuyv" / "uyvy": (Hs, Ws, 2). "rgb": (Hs, Ws, 3). "bgra" / "rgba": (Hs, Ws, 4). "yuv444p": (Hs * 3, Ws), the
+    luma, Cb and Cr planes of Hs rows each, any size."""
     hs, ws = int(src_hw[0]), int(src_hw[1])
+    if frame_format in FULL_CHROMA:
+        return (hs * 3, ws)
     if frame_format in PIXEL_BYTES:
         if frame_format in PACKED_422 and ws % 2:
             raise ValueError(f"{frame_format} frames have an even width (one chroma pair per two luma samples), got {ws} x {hs}")
@@ -134,7 +177,8 @@ class SurfaceLayout:
     frame_format "bgr": one plane of Hs rows, 3 bytes per pixel. "nv12" / "nv21" / "p010": a luma plane of Hs rows, 1 byte per
     sample (2 for p010), and a chroma plane of Hs / 2 rows of interleaved pairs of the same row width. "yuv420p" / "yvu420p": a
     luma plane of Hs rows and two chroma planes of Hs / 2 rows of Ws / 2 bytes each. "yuyv" / "uyvy" (2 bytes per pixel), "rgb"
-    (3), "bgra" / "rgba" (4): one plane, like "bgr".
+    (3), "bgra" / "rgba" (4): one plane, like "bgr". "yuv444p": a luma plane of Hs rows and two chroma planes of Hs rows of Ws
+    bytes each, with the fields of "yuv420p" (chroma_pitch defaults to pitch, Cb lies first).
       pitch          bytes from one luma (packed) row to the next; at least the row's sample bytes (the default)
       luma_rows      the plane height the decoder allocated, >= Hs (default Hs)
       chroma_pitch   bytes from one chroma row to the next (default: pitch; planar: pitch // 2, shared by both chroma planes)
@@ -150,7 +194,7 @@ class SurfaceLayout:
 
     def __init__(self, src_hw, frame_format, pitch=None, luma_rows=None, chroma_pitch=None, chroma_offset=None, image_bytes=None,
                  chroma2_offset=None):
-        if frame_format not in FRAME_FORMATS:
+        if frame_format not in ALL_FORMATS:
             raise _unknown_format(frame_format)
         hs, ws = int(src_hw[0]), int(src_hw[1])
         if hs <= 0 or ws <= 0:
@@ -160,6 +204,7 @@ class SurfaceLayout:
         self.sample_bytes = 2 if frame_format == "p010" else 1
         self.row_bytes = ws * PIXEL_BYTES.get(frame_format, self.sample_bytes)   # the samples of a luma (packed) row
         self.chroma_row_bytes = 0 if frame_format in PIXEL_BYTES else ws // 2 if frame_format in PLANAR else self.row_bytes
+        self.chroma_rows = 0 if frame_format in PIXEL_BYTES else hs if frame_format in FULL_CHROMA else hs // 2
         self.pitch = self.row_bytes if pitch is None else int(pitch)
         self.chroma2_offset = 0
         if frame_format in PIXEL_BYTES:
@@ -181,19 +226,21 @@ class SurfaceLayout:
         else:
             frame_shape((hs, ws), frame_format)   # (even sizes)
             self.luma_rows = hs if luma_rows is None else int(luma_rows)
-            if chroma_pitch is None and self.pitch % 2:
+            full = frame_format in FULL_CHROMA
+            if chroma_pitch is None and self.pitch % 2 and not full:
                 raise ValueError(f"{frame_format} surface of {ws} x {hs}: the default chroma_pitch is pitch // 2 and the pitch "
                                  f"{self.pitch} is odd: give chroma_pitch")
-            self.chroma_pitch = self.pitch // 2 if chroma_pitch is None else int(chroma_pitch)
-            first, plane = self.luma_rows * self.pitch, (hs // 2) * self.chroma_pitch
-            cb, cr = (first, first + plane) if frame_format == "yuv420p" else (first + plane, first)
+            self.chroma_pitch = (self.pitch if full else self.pitch // 2) if chroma_pitch is None else int(chroma_pitch)
+            first, plane = self.luma_rows * self.pitch, self.chroma_rows * self.chroma_pitch
+            cb, cr = (first + plane, first) if frame_format == "yvu420p" else (first, first + plane)
             self.chroma_offset = cb if chroma_offset is None else int(chroma_offset)
             self.chroma2_offset = cr if chroma2_offset is None else int(chroma2_offset)
-            self.sample_end = max(self.chroma_offset, self.chroma2_offset) + (hs // 2 - 1) * self.chroma_pitch + self.chroma_row_bytes
+            self.sample_end = (max(self.chroma_offset, self.chroma2_offset) + (self.chroma_rows - 1) * self.chroma_pitch
+                               + self.chroma_row_bytes)
         self.image_bytes = self.sample_end if image_bytes is None else int(image_bytes)
         self._check()
         self.key = None if self.tight else (self.pitch, self.luma_rows, self.chroma_pitch, self.chroma_offset, self.image_bytes)
-        if self.key is not None and frame_format in PLANAR:
+        if self.key is not None and frame_format in PLANAR + FULL_CHROMA:
             self.key += (self.chroma2_offset,)
 
     def _check(self):
@@ -211,11 +258,11 @@ class SurfaceLayout:
             if self.chroma_offset < luma_end:
                 raise ValueError(f"{what}: planes overlap (the luma samples end at byte {luma_end}, the chroma plane starts at "
                                  f"{self.chroma_offset})")
-            if self.frame_format in PLANAR:
+            if self.frame_format in PLANAR + FULL_CHROMA:
                 if self.chroma2_offset < luma_end:
                     raise ValueError(f"{what}: planes overlap (the luma samples end at byte {luma_end}, the Cr plane starts at "
                                      f"{self.chroma2_offset})")
-                span = (hs // 2 - 1) * self.chroma_pitch + self.chroma_row_bytes
+                span = (self.chroma_rows - 1) * self.chroma_pitch + self.chroma_row_bytes
                 if self.chroma_offset < self.chroma2_offset + span and self.chroma2_offset < self.chroma_offset + span:
                     raise ValueError(f"{what}: planes overlap (the Cb samples span bytes {self.chroma_offset} .. "
                                      f"{self.chroma_offset + span}, the Cr samples {self.chroma2_offset} .. {self.chroma2_offset + span})")
@@ -236,17 +283,17 @@ class SurfaceLayout:
         hs, ws = self.src_hw
         if self.frame_format in PIXEL_BYTES:
             return f"{self.frame_format} surface of {ws} x {hs} ({self.PIXELS[self.frame_format]}, row pitch {self.pitch})"
-        if self.frame_format in PLANAR:
+        if self.frame_format in PLANAR + FULL_CHROMA:
             return (f"{self.frame_format} surface of {ws} x {hs} ({hs} luma rows at pitch {self.pitch} in a plane of {self.luma_rows}, "
-                    f"then two planes of {hs // 2} rows of {ws // 2} bytes at pitch {self.chroma_pitch}: Cb from byte {self.chroma_offset}, "
-                    f"Cr from byte {self.chroma2_offset})")
+                    f"then two planes of {self.chroma_rows} rows of {self.chroma_row_bytes} bytes at pitch {self.chroma_pitch}: Cb from "
+                    f"byte {self.chroma_offset}, Cr from byte {self.chroma2_offset})")
         pair = "(Cr, Cb)" if self.frame_format == "nv21" else "(Cb, Cr)"
         bits = ", u16 little-endian samples" if self.frame_format == "p010" else ""
         return (f"{self.frame_format} surface of {ws} x {hs} ({hs} luma rows at pitch {self.pitch} in a plane of {self.luma_rows}, then "
                 f"{hs // 2} rows of interleaved {pair} pairs at pitch {self.chroma_pitch} from byte {self.chroma_offset}{bits})")
 
     def __repr__(self):
-        second = f", chroma2_offset={self.chroma2_offset}" if self.frame_format in PLANAR else ""
+        second = f", chroma2_offset={self.chroma2_offset}" if self.frame_format in PLANAR + FULL_CHROMA else ""
         return (f"SurfaceLayout({self.src_hw}, {self.frame_format!r}, pitch={self.pitch}, luma_rows={self.luma_rows}, chroma_pitch="
                 f"{self.chroma_pitch}, chroma_offset={self.chroma_offset}, image_bytes={self.image_bytes}{second})")
 
@@ -458,21 +505,23 @@ def _rolls(roll):
     return (check_roll(roll),)
 
 
-def plan_key(src_hw, aug_config, frame_format="bgr", colour="jfif", layout=None, roll=0.0):
+def plan_key(src_hw, aug_config, frame_format="bgr", colour="jfif", layout=None, roll=0.0, chroma="replicate"):
     """What a ResamplePlan depends on: a frame whose key differs must not run on the plan's tables (nor a frame of another
     format or colour standard on the plan's kernel; the standard says nothing about BGR, RGB, BGRA or RGBA frames and is left
     out of their key).
     `layout` (a SurfaceLayout or a dict of its keyword arguments) adds its own key unless it is tight: a frame never runs on a
     plan, or a captured graph, made for another layout.
     `roll` (degrees; a number or one per camera) adds its own entry where a camera is rolled (roll % 360 != 0), and nothing
-    otherwise: every key of a level plan is what it was, and a frame never runs on the integers of another roll."""
-    _check_format(frame_format, colour)
+    otherwise: every key of a level plan is what it was, and a frame never runs on the integers of another roll.
+    `chroma` ("replicate" | "jpeg") adds ("chroma", "jpeg") where chroma is interpolated, and nothing otherwise."""
+    _check_format(frame_format, colour, chroma)
     dims, crop, flip = resolve_aug(src_hw, aug_config)
     key = (int(src_hw[0]), int(src_hw[1]), dims, crop, flip, frame_format, colour if frame_format not in RGB_ORDER else None)
     extra = None if layout is None else SurfaceLayout.make(layout, src_hw, frame_format).key
     key = key if extra is None else key + (extra,)
     rolls = _rolls(roll)
-    return key + (("roll",) + tuple(r % 360.0 for r in rolls),) if any(is_rolled(r) for r in rolls) else key
+    key = key + (("roll",) + tuple(r % 360.0 for r in rolls),) if any(is_rolled(r) for r in rolls) else key
+    return key + (("chroma", chroma),) if chroma != "replicate" else key
 
 
 def _device(device):
@@ -584,12 +633,22 @@ class ResamplePlan(_Resident):
     corners are normalised like any pixel. A number, or one per camera (image n takes roll[n % len]). It is a property of the
     mount and is given beside the aug_config, whose own `rotate` stays refused (0 in the reference's test mode). A plan
     without a rolled camera launches exactly what it launched before. The 2D records do not change: the reference's
-    decode_box2d (detection3d/decoder.py:36-51) does not look at rotate."""
+    decode_box2d (detection3d/decoder.py:36-51) does not look at rotate.
 
-    def __init__(self, src_hw, aug_config=None, img_norm_cfg=None, frame_format="bgr", colour="jfif", layout=None, roll=0.0):
+    "yuv444p": u8 [Hs * 3, Ws], the luma, Cb and Cr planes of Hs rows of Ws bytes, any size: what a 4:4:4 JPEG decodes to.
+    `chroma="jpeg"` (nv12, nv21, yuv420p, yvu420p, yuyv, uyvy): the chroma samples are centre-sited and every pixel gets its own
+    Cb / Cr by libjpeg's "fancy" upsampling, the triangle filter its decoder applies to a JPEG at its defaults, in integers
+    (include/simpb_hip.h has the rule). With colour="jpeg" -- libjpeg's own four constants -- the native planes of a JPEG give
+    the bytes libjpeg decodes from that file: what the reference's loader (mmcv.imread) would have handed on from the same
+    coefficients. Pinned to libjpeg-turbo through Pillow for 4:2:0, 4:4:4 and the constants (tests/test_chroma_host.py); the
+    4:2:2 rule is stated from libjpeg's published algorithm, which hands out no native 4:2:2 planes to pin it to. In every
+    layout and with `roll`; a tight nv12 / nv21 batch then takes the surface kernel. "replicate" (default): nothing changes."""
+
+    def __init__(self, src_hw, aug_config=None, img_norm_cfg=None, frame_format="bgr", colour="jfif", layout=None, roll=0.0,
+                 chroma="replicate"):
         self.src_hw = (int(src_hw[0]), int(src_hw[1]))
-        _check_format(frame_format, colour)
-        self.frame_format, self.colour = frame_format, colour
+        _check_format(frame_format, colour, chroma)
+        self.frame_format, self.colour, self.chroma = frame_format, colour, chroma
         self.surface = SurfaceLayout.make(layout, self.src_hw, frame_format)
         self.frame_shape = frame_shape(self.src_hw, frame_format) if self.surface.tight else (self.surface.image_bytes,)
         self.yuv = None if frame_format in RGB_ORDER else yuv_coefficients(colour)
@@ -597,7 +656,7 @@ class ResamplePlan(_Resident):
         self.rolls = _rolls(roll)
         self.rolled = any(is_rolled(r) for r in self.rolls)
         self.aug_config = dict(aug_config or {})
-        self.key = plan_key(self.src_hw, aug_config, frame_format, colour, self.surface, roll)
+        self.key = plan_key(self.src_hw, aug_config, frame_format, colour, self.surface, roll, chroma)
         cfg = IMG_NORM_CFG if img_norm_cfg is None else img_norm_cfg
         self.img_norm_cfg = dict(mean=list(cfg["mean"]), std=list(cfg["std"]), to_rgb=bool(cfg.get("to_rgb", True)))
         self.swap_rb = self.img_norm_cfg["to_rgb"]
@@ -632,8 +691,15 @@ class ResamplePlan(_Resident):
             source = self.src_rows * self.surface.row_bytes
         else:   # the needed luma rows and the distinct chroma rows under them (needed bytes: both luma rows of a pair stage it)
             last = self.src_row0 + self.src_rows - 1
-            chroma_rows = (last >> 1) - (self.src_row0 >> 1) + 1
-            planes = 2 if self.frame_format in PLANAR else 1
+            if self.frame_format in FULL_CHROMA:
+                chroma_rows = self.src_rows
+            elif self.chroma == "jpeg":   # the far rows as well: one above an even first row and one below an odd last row
+                hc = self.src_hw[0] // 2
+                lo = max((self.src_row0 >> 1) - (0 if self.src_row0 & 1 else 1), 0)
+                chroma_rows = min((last >> 1) + (1 if last & 1 else 0), hc - 1) - lo + 1
+            else:
+                chroma_rows = (last >> 1) - (self.src_row0 >> 1) + 1
+            planes = 2 if self.frame_format in PLANAR + FULL_CHROMA else 1
             source = self.src_rows * self.surface.row_bytes + chroma_rows * planes * self.surface.chroma_row_bytes   # (no padding)
         return dict(source=source, mid_write=mid, mid_read=mid, out=h * w * 8)
 
@@ -659,6 +725,9 @@ class ResamplePlan(_Resident):
             order = "Cb plane, then the Cr plane" if self.frame_format == "yuv420p" else "Cr plane, then the Cb plane"
             return (f"u8 [..., {hs * 3 // 2}, {ws}] {self.frame_format} frames ({hs} luma rows of {ws} bytes, then the {order}, each "
                     f"{hs // 2} rows of {ws // 2} bytes; a padded surface needs layout=)")
+        if self.frame_format in FULL_CHROMA:
+            return (f"u8 [..., {hs * 3}, {ws}] {self.frame_format} frames (the luma, Cb and Cr planes, {hs} rows of {ws} bytes each; a "
+                    f"padded surface needs layout=)")
         if self.frame_format == "p010":
             return (f"u8 [..., {hs * 3 // 2}, {ws * 2}] p010 frames (the bytes of u16 little-endian samples: {hs} luma rows, then {hs // 2} "
                     f"rows of interleaved (Cb, Cr) pairs, row pitch {ws * 2}; a padded surface needs layout=)")
@@ -703,7 +772,7 @@ class ResamplePlan(_Resident):
         import torch
         from . import _lib
         self.reserve(n, device)
-        d, sf, code = self._dev, self.surface, SURFACE_FORMAT[self.frame_format]
+        d, sf, code = self._dev, self.surface, format_code(self.frame_format, self.chroma)
         out = self._out(out, n, device)
         p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
         tables = (p(d["mid"]), p(d["kx"]), p(d["xlo"]), p(d["xn"]), p(d["ky"]), p(d["ylo"]), p(d["yn"]), p(d["lut"]))
@@ -725,11 +794,11 @@ class ResamplePlan(_Resident):
             name, head, tail = "simpb_preprocess_roll_nhwc4_f16", images(), (*layout(sf.chroma2_offset), rows, len(self.rolls))
         elif tight and self.frame_format == "bgr":   # the first forms, through their entry points
             name, head, tail = "simpb_preprocess_u8_nhwc4_f16", (p(src),), ()
-        elif tight and self.frame_format in ("nv12", "nv21"):
+        elif tight and self.frame_format in ("nv12", "nv21") and self.chroma == "replicate":
             name, head, tail = "simpb_preprocess_yuv420sp_nhwc4_f16", (p(src),), (int(self.frame_format == "nv21"), *self.yuv)
         elif code <= SURFACE_FORMAT["p010"]:
             name, head, tail = "simpb_preprocess_surface_nhwc4_f16", images(), layout()
-        else:   # planar 4:2:0, packed 4:2:2 and the RGB-order family
+        else:   # planar 4:2:0 and 4:4:4, packed 4:2:2, the RGB-order family, and every format with interpolated chroma
             name, head, tail = "simpb_preprocess_planes_nhwc4_f16", images(), layout(sf.chroma2_offset)
         _lib.check(getattr(_lib.lib(), name)(p(out), *head, *tables, *ints, *tail, stream), name)
         return out
@@ -743,29 +812,30 @@ class CameraSource:
     """One camera of a rig (RigPlan): what a ResamplePlan takes for that camera alone, with the same checks. A camera of a
     rig gives its scale as the reference's scalar `resize` (with `crop` and `flip`): the 2D boxes are mapped back to source
     pixels by that scalar (decoder.py:36-51), so an explicit, possibly anisotropic `resize_dims` is refused. `roll`: this
-    camera's mount roll in degrees (ResamplePlan has the rule)."""
+    camera's mount roll in degrees; `chroma`: "replicate" | "jpeg", this camera's chroma (ResamplePlan has both rules)."""
 
-    def __init__(self, src_hw, aug_config=None, frame_format="bgr", colour="jfif", layout=None, roll=0.0):
+    def __init__(self, src_hw, aug_config=None, frame_format="bgr", colour="jfif", layout=None, roll=0.0, chroma="replicate"):
         self.src_hw = (int(src_hw[0]), int(src_hw[1]))
         self.roll = check_roll(roll)
         self.aug_config = dict(aug_config or {})
         if self.aug_config.get("resize_dims") is not None:
             raise ValueError("a camera of a rig gives its scale as `resize` (with crop / flip): resize_dims is not taken, the 2D "
                              "boxes are mapped back to source pixels by the reference's isotropic rule")
-        _check_format(frame_format, colour)
-        self.frame_format, self.colour = frame_format, colour
+        _check_format(frame_format, colour, chroma)
+        self.frame_format, self.colour, self.chroma = frame_format, colour, chroma
         self.surface = SurfaceLayout.make(layout, self.src_hw, frame_format)
         self.resize = float(self.aug_config.get("resize", 1))
         self.resize_dims, self.crop, self.flip = resolve_aug(self.src_hw, self.aug_config)
         self.out_hw = (self.crop[3] - self.crop[1], self.crop[2] - self.crop[0])
-        self.key = plan_key(self.src_hw, self.aug_config, frame_format, colour, self.surface, self.roll) + (self.resize,)
+        self.key = plan_key(self.src_hw, self.aug_config, frame_format, colour, self.surface, self.roll, chroma) + (self.resize,)
 
     def plan(self, img_norm_cfg=None):
         """The ResamplePlan of this camera alone."""
-        return ResamplePlan(self.src_hw, self.aug_config, img_norm_cfg, self.frame_format, self.colour, self.surface, self.roll)
+        return ResamplePlan(self.src_hw, self.aug_config, img_norm_cfg, self.frame_format, self.colour, self.surface, self.roll,
+                            self.chroma)
 
     def describe(self):
-        return f"{self.frame_format} {self.src_hw[1]} x {self.src_hw[0]} -> {self.out_hw[1]} x {self.out_hw[0]}"
+        return f"{self.frame_format}{' (jpeg chroma)' if self.chroma == 'jpeg' else ''} {self.src_hw[1]} x {self.src_hw[0]} -> {self.out_hw[1]} x {self.out_hw[0]}"
 
 
 class RigPlan(_Resident):
@@ -841,7 +911,7 @@ class RigPlan(_Resident):
         cams = (_lib.RigCamera * self.num_cams)()
         for i, (p, c) in enumerate(zip(self.plans, cams)):
             sf = p.surface
-            c.format, c.src_height, c.src_width = SURFACE_FORMAT[p.frame_format], p.src_hw[0], p.src_hw[1]
+            c.format, c.src_height, c.src_width = format_code(p.frame_format, p.chroma), p.src_hw[0], p.src_hw[1]
             c.src_row0, c.src_rows, c.taps_x, c.taps_y, c.flip = p.src_row0, p.src_rows, p.taps_x, p.taps_y, int(p.flip)
             c.pitch, c.chroma_pitch, c.chroma_offset, c.chroma2_offset = sf.pitch, sf.chroma_pitch, sf.chroma_offset, sf.chroma2_offset
             c.kx_offset, c.x_offset, c.ky_offset, c.y_offset = self.kx_offset[i], self.x_offset[i], self.ky_offset[i], self.y_offset[i]

@@ -397,7 +397,8 @@ class FrameRunner:
 
     def __init__(self, model, batch_size, image_hw, capacity=1536, device=None, use_graph=True, independent_streams=False,
                  raw_input=None, img_norm_cfg=None, world_output=None, raw_format="bgr", raw_colour="jfif",
-                 raw_layout=None, raw_surfaces=False, raw_rig=None, idle_images="compute", camera_health=None, raw_roll=None):
+                 raw_layout=None, raw_surfaces=False, raw_rig=None, idle_images="compute", camera_health=None, raw_roll=None,
+                 raw_chroma=None):
         """independent_streams: the batch is a set of independent camera streams, each decoded exactly as a batch of one
         would be (`capacity` 2D slots per stream; SimPBHead.independent_streams) -- the throughput form of BASELINE config
         #3. False: the reference's batch semantics (camera groups padded to the max over the batch).
@@ -430,6 +431,12 @@ class FrameRunner:
         of the frame: the aug_config's own `rotate` stays refused. With raw_rig each CameraSource brings its own `roll`. The 2D
         records are unchanged: the reference's decode_box2d does not look at rotate. camera_health sees the rolled image, black
         corners included. None, or rolls that are all multiples of 360: nothing of this is launched.
+        raw_chroma="replicate" | "jpeg" (with raw_input only; raw_format nv12, nv21, yuv420p, yvu420p, yuyv or uyvy, in every
+        raw_layout, with raw_surfaces and with raw_roll): "jpeg" interpolates the subsampled chroma as libjpeg's decoder does at
+        its defaults, inside the ingest's first launch; with raw_colour="jpeg" (libjpeg's own colour constants, also taken by
+        "yuv444p" frames) the native planes of a JPEG give the bytes the reference's loader would have decoded from that file
+        (preprocess.ResamplePlan has the rule and says what is pinned to libjpeg). With raw_rig each CameraSource brings its own
+        `chroma`. camera_health, the 2D records and the decoder see nothing new. None or "replicate": nothing changes.
 
         world_output=dict(classes=..., tracking=bool, threshold=float | None): a second output per frame, the WORLD RECORD
         (csrc/world.hip, results.py): boxes in the global frame, threshold and class ranges applied, kept rows packed, a
@@ -472,6 +479,14 @@ class FrameRunner:
                 self.raw_roll = tuple(check_roll(r) for r in raw_roll)
             else:
                 self.raw_roll = check_roll(raw_roll)
+        self.raw_chroma = "replicate"       # raw_chroma=: how subsampled chroma becomes a Cb / Cr per pixel ("replicate" | "jpeg")
+        if raw_chroma is not None:
+            if raw_rig is not None:
+                raise ValueError("raw_rig describes every camera by itself: each CameraSource brings its own chroma=, raw_chroma must "
+                                 "not be given with it")
+            if raw_input is None:
+                raise ValueError("raw_chroma describes raw frames: it needs raw_input=(Hs, Ws)")
+            self.raw_chroma = raw_chroma    # (an unknown mode, or a format that does not take it, is refused with the format below)
         self.skipping = False               # True from the first frame with a dead image on (idle_images="skip"): the backbone reads live_dev
         self.live_pin = self.live_dev = None    # per feature slot: the live-image table, pinned host side and fixed device side
         self.live_staged = None             # per feature slot: event behind the slot's last copy out of its pinned table
@@ -526,7 +541,8 @@ class FrameRunner:
             self.img, self.raw = torch.zeros(batch_size, cams, 3, h, w, device=dev), None
         else:   # (no fp32 staging buffer in this mode)
             from .preprocess import SurfaceLayout, frame_shape, plan_key
-            plan_key(self.raw_input, None, raw_format, raw_colour, None, self.raw_roll)   # (an unknown format or standard is refused here)
+            # (an unknown format, standard or chroma mode is refused here)
+            plan_key(self.raw_input, None, raw_format, raw_colour, None, self.raw_roll, self.raw_chroma)
             self.img = None
             if raw_layout is not None:
                 self.raw_layout = SurfaceLayout.make(raw_layout, self.raw_input, raw_format)
@@ -681,9 +697,10 @@ class FrameRunner:
             return
         aug = metas["img_metas"][0]["aug_config"]
         if self.plan is not None and self.plan.key == plan_key(self.raw_input, aug, self.raw_format, self.raw_colour, self.raw_layout,
-                                                               self.raw_roll):
+                                                               self.raw_roll, self.raw_chroma):
             return
-        plan = ResamplePlan(self.raw_input, aug, self.img_norm_cfg, self.raw_format, self.raw_colour, self.raw_layout, self.raw_roll)
+        plan = ResamplePlan(self.raw_input, aug, self.img_norm_cfg, self.raw_format, self.raw_colour, self.raw_layout, self.raw_roll,
+                            self.raw_chroma)
         if plan.out_hw != self.image_hw:
             raise ValueError(f"aug_config {aug} turns {self.raw_input} frames into {plan.out_hw} images; this runner was built for "
                              f"{self.image_hw}")

@@ -39,10 +39,22 @@
       launch is the same for every format, so a difference between two lines is a difference of their horizontal launches;
       `source_bytes_per_image` (ResamplePlan.bytes_per_image) says which existing format a new one should sit with.
 
+  (g) `chroma` (--only-chroma; not part of a plain run): interpolated chroma (chroma="jpeg", libjpeg's upsampling) beside
+      replicated chroma, six 1600 x 900 NV12 -> 704 x 256. `launch`: the two ingest launches, --launches per block in --blocks
+      alternating blocks: replicated NV12 through its own tight kernel (the yardstick), through the surface kernel (the
+      address-table form) and as a six-camera rig, then the same three with interpolated chroma (a tight batch takes the
+      surface kernel), interpolated yuv420p and yuyv, and yuv444p. Every line carries a checksum of its operand (the int16
+      bits summed in int64): the replicated lines must agree with each other and with the same lines of any other commit.
+      `runner`: SplitPipelinedRunner frames/s on device-resident NV12 frames with raw_chroma off and on, in alternating blocks.
+      --replicated-only leaves out every line that needs chroma=: the same tool then times a commit without the feature,
+      for a comparison of the replicated launches in alternating processes on one box. --loop-jpeg N: nothing is timed, the
+      interpolated tight NV12 ingest and the replicated one through the same surface kernel are launched N times each (the
+      program to put behind `rocprofv3 --kernel-trace --stats --`: the trace splits each ingest into its two kernels).
+
 A run that finds no GPU fails.
 
     python tools/bench_preprocess.py [--launches 200] [--blocks 5] [--block-steps 40]
-                                     [--only-surface | --skip-surface | --only-rig | --only-planes]
+                                     [--only-surface | --skip-surface | --only-rig | --only-planes | --only-chroma]
 """
 import argparse
 import json
@@ -473,6 +485,114 @@ def planes_launch_leg(torch, args):
     return out
 
 
+def chroma_forms(torch, args):
+    """name -> (run(), out tensor): every launch form of leg (g), warmed."""
+    from simpb_amd.preprocess import CameraSource, ResamplePlan, RigPlan
+    aug = CONFIGS["r50_704x256"]
+    nv12, bgr = nv12_frames(torch, 0)
+    host = plane_frames(torch, nv12[0], bgr[0])
+    luma, pairs = nv12[0][:, :900], nv12[0][:, 900:].reshape(6, 450, 800, 2)
+    full = lambda c: c.repeat_interleave(2, 1).repeat_interleave(2, 2)   # noqa: E731
+    host["yuv444p"] = torch.cat([luma, full(pairs[..., 0]), full(pairs[..., 1])], 1).contiguous()
+    lines = [("nv12_replicated_tight", "nv12", {}, "batch"), ("nv12_replicated_surface", "nv12", {}, "table"),
+             ("nv12_replicated_rig", "nv12", {}, "rig")]
+    if not args.replicated_only:
+        jpeg = dict(chroma="jpeg")
+        lines += [("nv12_jpeg_tight", "nv12", jpeg, "batch"), ("nv12_jpeg_surface", "nv12", jpeg, "table"), ("nv12_jpeg_rig", "nv12", jpeg, "rig"),
+                  ("yuv420p_jpeg", "yuv420p", jpeg, "batch"), ("yuyv_jpeg", "yuyv", jpeg, "batch"), ("yuv444p", "yuv444p", {}, "batch")]
+    forms, keep = {}, []
+    for name, fmt, kw, form in lines:
+        frames = host[fmt].cuda()
+        dst = torch.empty(6, 256, 704, 4, dtype=torch.float16, device="cuda")
+        if form == "rig":
+            plan = RigPlan([CameraSource((900, 1600), aug, fmt, **kw)] * 6)
+            table = torch.tensor([frames[i].data_ptr() for i in range(6)], dtype=torch.int64, device="cuda")
+            run = lambda plan=plan, table=table, dst=dst: plan.run_table(table, out=dst)   # noqa: E731
+        else:
+            plan = ResamplePlan((900, 1600), aug, frame_format=fmt, **kw).reserve(6, "cuda")
+            if form == "table":
+                table = torch.tensor([frames[i].data_ptr() for i in range(6)], dtype=torch.int64, device="cuda")
+                run = lambda plan=plan, table=table, dst=dst: plan.run_table(table, out=dst)   # noqa: E731
+            else:
+                run = lambda plan=plan, frames=frames, dst=dst: plan.run(frames, out=dst)   # noqa: E731
+        keep.append(frames)
+        for _ in range(20):
+            run()
+        torch.cuda.synchronize()
+        forms[name] = (run, dst, plan)
+    return forms, keep
+
+
+def chroma_launch_leg(torch, args):
+    from simpb_amd import _lib
+    forms, keep = chroma_forms(torch, args)
+    blocks = {k: [] for k in forms}
+    for _ in range(args.blocks):
+        for name, (run, dst, plan) in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.launches):
+                run()
+            e1.record()
+            e1.synchronize()
+            blocks[name].append(e0.elapsed_time(e1) / args.launches)
+    out = {}
+    for name, v in blocks.items():
+        run, dst, plan = forms[name]
+        ms = float(np.mean(v))
+        out[name] = dict(ms=round(ms, 5), block_ms=[round(x, 5) for x in v], spread_ms=round(max(v) - min(v), 5), images=6,
+                         launches=args.launches * args.blocks, checksum=int(dst.view(torch.int16).to(torch.int64).sum()))
+        if hasattr(plan, "bytes_per_image"):
+            per_image = plan.bytes_per_image(int(_lib.lib().simpb_preprocess_mid_pitch(704)))
+            out[name].update(source_bytes_per_image=per_image["source"], bytes_per_image=sum(per_image.values()))
+    for name, v in out.items():
+        v["ms_minus_replicated_tight"] = round(v["ms"] - out["nv12_replicated_tight"]["ms"], 5)
+    same = {out[k]["checksum"] for k in out if "replicated" in k}
+    assert len(same) == 1, "the replicated forms hold one operand"
+    return out
+
+
+def chroma_runner_leg(torch, args):
+    from simpb_amd import synth
+    from simpb_amd.runner import SplitPipelinedRunner
+    ring = 4
+    frames = [nv12_frames(torch, f)[0].cuda() for f in range(ring)]
+    dev = torch.device("cuda")
+    make = lambda **kw: SplitPipelinedRunner(build_model(torch), 1, (256, 704), capacity=1536, device=dev, use_graph=True,   # noqa: E731
+                                             raw_input=(900, 1600), raw_format="nv12", **kw)
+    runners = {"raw_chroma_off": make()}
+    if not args.replicated_only:
+        runners["raw_chroma_jpeg"] = make(raw_chroma="jpeg", raw_colour="jpeg")
+    count = dict.fromkeys(runners, 0)
+
+    def run(name, steps):
+        for _ in range(steps):
+            f = count[name]
+            runners[name].step(frames[f % ring], synth.frame_metas(1, f))
+            count[name] = f + 1
+
+    for name in runners:
+        run(name, 12)
+    torch.cuda.synchronize()
+    blocks = {k: [] for k in runners}
+    for _ in range(args.blocks):
+        for name in runners:
+            run(name, 4)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(name, args.block_steps)
+            torch.cuda.synchronize()
+            blocks[name].append((time.perf_counter() - t0) / args.block_steps * 1e3)
+    out = {}
+    for name, ms in blocks.items():
+        mean = float(np.mean(ms))
+        out[name] = dict(ms_per_step=round(mean, 4), frames_per_s=round(1e3 / mean, 1), block_ms=[round(v, 4) for v in ms],
+                         spread_ms=round(max(ms) - min(ms), 4), timed_frames=args.blocks * args.block_steps, replays=runners[name].stats["replay"])
+    if "raw_chroma_jpeg" in out:
+        out["jpeg_minus_off_ms"] = round(out["raw_chroma_jpeg"]["ms_per_step"] - out["raw_chroma_off"]["ms_per_step"], 4)
+    return out
+
+
 def cpu_leg(frames=3):
     try:
         from PIL import Image
@@ -510,6 +630,9 @@ def main():
     ap.add_argument("--only-surface", action="store_true", help="the decoder-surface leg (d) alone")
     ap.add_argument("--only-rig", action="store_true", help="the rig leg (e) alone")
     ap.add_argument("--only-planes", action="store_true", help="the frame-format leg (f) alone")
+    ap.add_argument("--only-chroma", action="store_true", help="the interpolated-chroma leg (g) alone")
+    ap.add_argument("--replicated-only", action="store_true", help="leg (g) without the lines that need chroma= (times any commit)")
+    ap.add_argument("--loop-jpeg", type=int, default=0, help="leg (g): launch the interpolated tight NV12 ingest N times, time nothing")
     ap.add_argument("--profile-raw", action="store_true",
                     help="only the runner leg's raw form: the program to put behind `rocprofv3 --kernel-trace --stats --`")
     args = ap.parse_args()
@@ -522,6 +645,18 @@ def main():
         with torch.no_grad():
             rig = dict(launch=rig_launch_leg(torch, args), runner=None if args.skip_runner else rig_runner_leg(torch, args))
         print(json.dumps(dict(tool="bench_preprocess", device=torch.cuda.get_device_name(0), rig=rig)))
+        return
+    if args.only_chroma:
+        with torch.no_grad():
+            if args.loop_jpeg:
+                forms, keep = chroma_forms(torch, args)
+                for _ in range(args.loop_jpeg):
+                    forms["nv12_jpeg_tight"][0]()
+                    forms["nv12_replicated_surface"][0]()
+                torch.cuda.synchronize()
+                return
+            chroma = dict(launch=chroma_launch_leg(torch, args), runner=None if args.skip_runner else chroma_runner_leg(torch, args))
+        print(json.dumps(dict(tool="bench_preprocess", device=torch.cuda.get_device_name(0), chroma=chroma)))
         return
     if args.only_planes:
         with torch.no_grad():
